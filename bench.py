@@ -12,16 +12,30 @@ random-init on device with the real Llama-3.1-8B shapes (no network for checkpoi
 * value = B * 1000 / ((eval_ms_per_token + pred_ms_per_token) / 2), the named metric; the decode-only
   rate is reported as config.pred_tokens_per_s.
 The KV cache is f32, the reference's precision (src/llm.cpp:197-198, nn/nn-core.cpp:198-205), for
-the headline and every extra point (`--kv f32`, default); the same eval + pred with a bf16 cache is
-reported next to it (config.bf16_kv_*), never as `value`.
+the headline and every extra point (`--kv f32`, default); with `--full` the same eval + pred with a
+bf16 cache is reported next to it (config.bf16_kv_*), never as `value`.
 The engine is sized to --max-seq-len positions (default 4096, the reference run script's
 `--max-seq-len 4096`); attention launches follow the context actually reached (context buckets),
-not the capacity. Extra points in `config`: decode at position >= 4096 (long_ctx_pred_ms_per_token),
-the same short-context decode on an engine sized to the model's full 131072-position context
-(cap131072_pred_ms_per_token) and, on one GPU, the product path through
-`build/dllama inference --synthetic llama3_1_8b` (cli_*: per-token host round trips included).
+not the capacity.
+
+A plain run measures the headline only: one engine, eval, warmup, the timed decode steps, the result
+line. `--full` adds the extra points in `config`, each with an engine and timed run of its own (the
+`--no-*` / `--long-ctx 0` / `--tp-rank-compute ''` switches drop single points of a full run): the
+bf16-cache eval + pred, decode at position >= 4096 (long_ctx_pred_ms_per_token), the same
+short-context decode on an engine sized to the model's full 131072-position context
+(cap131072_pred_ms_per_token), the 4096-token prompt points, on one GPU a TP-N rank's own compute
+and the product path through `build/dllama inference --synthetic llama3_1_8b` (cli_*: per-token host
+round trips included), on several GPUs the exact f32 exchange (tp_f32_*).
+
+`--dump-outputs DIR` writes what the timed path returned to its caller, as float32 .npy files (rank
+0 writes): `pred_tokens.npy` [steps, batch], the greedy token ids of every timed decode step (the
+last row is the last step's), `eval_tokens.npy` [batch, rows], the argmax ids of the last timed
+prompt chunk, and `next_logits.npy` [batch, vocab], the logits of one further untimed forward of the
+last step's tokens at the next position, i.e. a float view of the KV cache and tokens the timed steps
+left behind. Weights (seed 1234) and prompt are fixed, so the same arguments give the same inputs.
 
     python bench.py --gpus 1 --steps 128 --warmup 16
+    python bench.py --gpus 1 --steps 128 --warmup 16 --full # every extra point as well
     python bench.py --gpus 8 --steps 128 --warmup 16        # launches its own 8 ranks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 128 --warmup 16
@@ -32,7 +46,7 @@ any rank fails - the reference's root drives its workers the same way (src/app.c
 `n_gpus` is the number of distinct devices the ranks ran on: DL_BENCH_SAME_GPU=1 rehearses N ranks on
 one GPU, labelled "same_gpu_rehearsal": true with n_gpus 1 and no vs_baseline.
 TP partial sums default to the reference's wire format, Q80 blocks (syncType = bufferFloatType,
-src/app.cpp:81, llm.cpp:150); the exact f32 exchange is reported next to it (tp_f32_*).
+src/app.cpp:81, llm.cpp:150); with `--full` the exact f32 exchange is reported next to it (tp_f32_*).
 """
 from __future__ import annotations
 
@@ -155,25 +169,43 @@ def main() -> int:
                     help="TP partial-sum exchange: q80 (the reference's ZQ wire format, default) or f32 (exact)")
     ap.add_argument("--max-seq-len", type=int, default=4096,
                     help="engine context capacity (KV cache positions) of the headline engine")
-    ap.add_argument("--no-cap128k", action="store_true", help="skip the 131072-capacity decode point")
-    ap.add_argument("--long-ctx", type=int, default=4096, help="position of the long-context decode point (0: off)")
-    ap.add_argument("--no-cli", action="store_true", help="skip the dllama CLI product-path point (1 GPU)")
+    ap.add_argument("--no-cap128k", action="store_true", help="--full: skip the 131072-capacity decode point")
+    ap.add_argument("--long-ctx", type=int, default=4096, help="--full: position of the long-context decode point (0: off)")
+    ap.add_argument("--no-cli", action="store_true", help="--full: skip the dllama CLI product-path point (1 GPU)")
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--kv", default="f32", choices=["f32", "bf16"],
                     help="KV-cache dtype of the headline and the extra points (f32: the reference's)")
     ap.add_argument("--no-altkv", action="store_true",
-                    help="skip the eval + pred point with the other KV-cache dtype (bf16 next to an f32 headline)")
+                    help="--full: skip the eval + pred point with the other KV-cache dtype (bf16 next to an f32 "
+                         "headline)")
     ap.add_argument("--no-f32kv", dest="no_altkv", action="store_true", help=argparse.SUPPRESS)  # round-5 name
-    ap.add_argument("--no-prefill4k", action="store_true", help="skip the 4096-token prompt-eval point")
+    ap.add_argument("--no-prefill4k", action="store_true", help="--full: skip the 4096-token prompt-eval point")
     ap.add_argument("--tp-rank-compute", default="2,4,8",
-                    help="1 GPU: TP degrees whose rank-0 shard is timed with the exchange removed "
+                    help="--full, 1 GPU: TP degrees whose rank-0 shard is timed with the exchange removed "
                          "(compute-only comm; '' = off)")
     ap.add_argument("--prefill-chunk", type=int, default=1024,
-                    help="rows per forward of the second 4096-token prompt point (the first uses the reference's 32)")
+                    help="--full: rows per forward of the second 4096-token prompt point (the first uses the "
+                         "reference's 32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the extra points of `config` (other KV dtype, long context, 131072 capacity, "
+                         "4096-token prompts, TP-rank compute, f32 exchange, the CLI); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write their outputs to DIR/<name>.npy (float32; see the module docstring)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return _launch_ranks(args.gpus)
+
+    if not args.full:  # a plain run: the headline's engine, eval, warmup and timed steps, nothing else
+        def given(opt):
+            return any(a == opt or a.startswith(opt + "=") for a in sys.argv[1:])
+        asked = [o for o, wanted in (("--long-ctx", args.long_ctx > 0), ("--tp-rank-compute", args.tp_rank_compute),
+                                     ("--prefill-chunk", True)) if wanted and given(o)]
+        if asked and os.environ.get("RANK", "0") == "0":
+            print(f"bench.py: {', '.join(asked)} ignored without --full; this plain run measures the "
+                  "headline alone", file=sys.stderr)
+        args.long_ctx, args.tp_rank_compute = 0, ""
+        args.no_cap128k = args.no_altkv = args.no_prefill4k = args.no_cli = True
 
     import torch
     import distributed_llama_multiusers_amd as dl
@@ -287,10 +319,10 @@ def main() -> int:
         torch.cuda.synchronize()
         barrier()
         te = time.perf_counter()
+        ev_toks = []
         for s in range(0, len(prompt), 32):
             chunk = prompt[s:s + 32]
-            for b in range(B):
-                e.forward_argmax(chunk, list(range(s, s + len(chunk))), [b] * len(chunk))
+            ev_toks = [e.forward_argmax(chunk, list(range(s, s + len(chunk))), [b] * len(chunk)) for b in range(B)]
         torch.cuda.synchronize()
         ev_s = time.perf_counter() - te
         barrier()
@@ -300,14 +332,28 @@ def main() -> int:
         barrier()
         torch.cuda.synchronize()
         t_start = time.perf_counter()
-        dms, _ = e.decode_greedy(steps, tokens, [p1] * B, list(range(B)))
+        dms, toks = e.decode_greedy(steps, tokens, [p1] * B, list(range(B)))
         torch.cuda.synchronize()
         el = time.perf_counter() - t_start
         barrier()
-        return ev_s, el, dms
+        return ev_s, el, dms, ev_toks, toks
 
-    eval_s, elapsed, dev_ms = eval_pred(eng, args.steps, args.warmup)
+    eval_s, elapsed, dev_ms, eval_toks, pred_toks = eval_pred(eng, args.steps, args.warmup)
     tp_fused = bool(eng.tp_fused) if world > 1 else None  # after the first forward's self-test
+
+    if args.dump_outputs:
+        import numpy as np
+        # decode_greedy returns its tokens sequence by sequence ([batch][steps]); the file is [steps, batch]
+        pred = np.asarray(pred_toks, dtype=np.float32).reshape(B, args.steps).T
+        # one more forward (untimed, every rank takes part) from the state the timed steps left
+        p_next = pos0 + args.warmup + args.steps
+        logits = eng.forward([int(t) for t in pred[-1]], [p_next] * B, list(range(B)))
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "pred_tokens.npy"), pred)
+            np.save(os.path.join(args.dump_outputs, "eval_tokens.npy"), np.asarray(eval_toks, dtype=np.float32))
+            np.save(os.path.join(args.dump_outputs, "next_logits.npy"), np.asarray(logits, dtype=np.float32))
+        barrier()
 
     long_ms = None
     if long_pos:  # decode at a long context, own engine sized for it (KV rows it never wrote are
@@ -341,10 +387,10 @@ def main() -> int:
     if not args.no_altkv:  # the same eval + pred with the other KV-cache dtype (never the `value`)
         del eng
         eng = make_engine(kv_bf16=not kv_bf16_main)
-        alt_eval_s, alt_pred_s, _ = eval_pred(eng, alt_steps, 4)
+        alt_eval_s, alt_pred_s = eval_pred(eng, alt_steps, 4)[:2]
 
     tpf32_ms = None
-    if world > 1 and args.sync_type != "f32":  # the exact f32 exchange next to the Q80 wire format
+    if args.full and world > 1 and args.sync_type != "f32":  # the exact f32 exchange next to the Q80 wire format
         del eng
         eng = make_engine(max(seq_len, pos0 + 48), sync="f32")
         eng.decode_greedy(4, tokens, [pos0] * B, list(range(B)))

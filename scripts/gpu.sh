@@ -3,10 +3,10 @@
 # own time limit and the first failing step ends the run. Outputs under gpurun_out/<task>/.
 #
 #   tests [pytest args]          GPU test suite (default: all of -m gpu) in one process, then smoke()
-#   bench [bench.py args]        the headline bench (default flags: the driver's)
-#   ab "<bench flags>" N a b ..  same-box A/B of bench.py: this tree (".") vs side builds ab/<name>
+#   bench [bench.py args]        the headline bench (default flags: the driver's; add --full for the extra points)
+#   ab "<bench flags>" N a b ..  same-box A/B of bench.py --full: this tree (".") vs side builds ab/<name>
 #                                (scripts/ab_build.sh), N alternating rounds -> gpurun_out/ab/runs.log
-#   env "<bench flags>" N "A=1 B=2" "A=0" ..   bench.py under each set of environment switches
+#   env "<bench flags>" N "A=1 B=2" "A=0" ..   bench.py --full under each set of environment switches
 #   prof-decode [tp list] [kv] [pos]  rocprofv3 kernel trace of batch-1 decode (TP1 / a TP-N rank in
 #                                loopback, scripts/tp_rank_compute.py) + per-kernel tables
 #   batch [B list]               batched decode steps (bench.py --batch B)
@@ -46,7 +46,7 @@ case $task in
     for i in $(seq 1 $N); do
       for name in "$@"; do
         d=$R; [ "$name" != "." ] && d=$R/ab/$name
-        (cd $d && timeout -k 10 400 python3 -u bench.py $F 2> $R/$O/$name.err | pj $name) >> $O/runs.log || exit 1
+        (cd $d && timeout -k 10 400 python3 -u bench.py --full $F 2> $R/$O/$name.err | pj $name) >> $O/runs.log || exit 1
       done
     done
     cat $O/runs.log ;;
@@ -54,7 +54,7 @@ case $task in
     F=$1; N=$2; shift 2
     for i in $(seq 1 $N); do
       for envs in "$@"; do
-        env $envs timeout -k 10 400 python3 -u bench.py $F 2>> $O/err.log | pj "[$envs]" >> $O/runs.log || exit 1
+        env $envs timeout -k 10 400 python3 -u bench.py --full $F 2>> $O/err.log | pj "[$envs]" >> $O/runs.log || exit 1
       done
     done
     cat $O/runs.log ;;
@@ -79,7 +79,7 @@ case $task in
     tail -n 1 $O/b70.json; tail -n 2 $O/api64.log $O/api16.log ;;
   tp-rehearse)
     export DL_BENCH_SAME_GPU=1
-    F="--steps 32 --warmup 8 --no-prefill4k --no-cap128k --no-altkv --long-ctx 0"
+    F="--full --steps 32 --warmup 8 --no-prefill4k --no-cap128k --no-altkv --long-ctx 0"
     timeout -k 10 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29531 \
       bench.py --gpus 2 $F > $O/tp2.log 2>&1 || exit 1
     timeout -k 10 500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29532 \

@@ -1,7 +1,7 @@
 """One TP-N rank's own decode work on one GPU: rank `--rank` of `--tp` with the exchange removed
 (ComputeOnlyComm: fused exchange in loopback, separate collectives no-ops). Prints ms per token of
 greedy decode (and of 32-row prompt chunks); run under rocprofv3 for the per-kernel split.
-bench.py reports the same points as tp{N}_rank_compute_ms_per_token."""
+`bench.py --full` reports the same points as tp{N}_rank_compute_ms_per_token."""
 import argparse
 import os
 import sys
