@@ -156,6 +156,9 @@ struct Api {
         usage.set("prompt_tokens", promptTokens);
         usage.set("completion_tokens", r->completionTokens);
         usage.set("total_tokens", promptTokens + r->completionTokens);
+        Value details = Value::object();  // OpenAI shape; 0 without --prefix-cache or without a hit
+        details.set("cached_tokens", r->cachedTokens);
+        usage.set("prompt_tokens_details", details);
         resp.set("usage", usage);
         resp.set("generated_text", text);
         conn.writeJson(200, resp.dump());
@@ -196,6 +199,13 @@ struct Api {
         metric("dllama_requests_cancelled_total", "counter", "Requests dropped after their client disconnected.",
                (double)s.cancelled);
         metric("dllama_busy_seconds_total", "counter", "Time spent in forward passes.", s.busyMs / 1000.0);
+        metric("dllama_prefix_hits_total", "counter", "Requests admitted behind a reused KV prefix.", (double)s.prefixHits);
+        metric("dllama_prefix_tokens_total", "counter", "Prompt tokens served from reused KV instead of prefill.",
+               (double)s.prefixTokens);
+        metric("dllama_prefix_copies_total", "counter", "Prefix hits that copied KV from an active slot.",
+               (double)s.prefixCopies);
+        metric("dllama_prefix_evictions_total", "counter", "Idle slots evicted to free KV pages.",
+               (double)s.prefixEvictions);
         metric("dllama_active_requests", "gauge", "Requests holding a KV slot.", (double)s.active);
         metric("dllama_queued_requests", "gauge", "Requests waiting for a KV slot.", (double)s.queued);
         metric("dllama_kv_slots", "gauge", "KV-cache slots (max concurrent sequences).", (double)sess->nSlots());
@@ -222,6 +232,10 @@ struct Api {
         v.set("cancelled", (double)s.cancelled);
         v.set("generated_tokens", (double)s.generatedTokens);
         v.set("busy_ms", s.busyMs);
+        v.set("prefix_hits", (double)s.prefixHits);
+        v.set("prefix_tokens", (double)s.prefixTokens);
+        v.set("prefix_copies", (double)s.prefixCopies);
+        v.set("prefix_evictions", (double)s.prefixEvictions);
         conn.writeJson(200, v.dump());
     }
 };
@@ -257,6 +271,7 @@ void usage() {
                  "        [--buffer-float-type {f32|f16|q40|q80}]\n"
                  "        [--max-seq-len <max>] [--slots <n>] [--max-batch <n>] [--prefill-chunk <n>]\n"
                  "        [--kv-pages <n> --kv-page-size <p>]   (GPU paged KV: slots share a page pool)\n"
+                 "        [--prefix-cache {0|1}] [--prefix-cache-min <n>]   (reuse the KV of shared prompt prefixes)\n"
                  "        [--nthreads <n>] [--gpu-index <i>]\n"
                  "        [--workers <ip:port> ...]\n"
                  "        [--temperature <temp>] [--topp <t>] [--seed <s>] [--chat-template <t>]\n"

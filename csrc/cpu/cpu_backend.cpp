@@ -165,6 +165,19 @@ class CpuBackend : public Backend {
         for (int i = 0; i < n; i++) out[i] = (int)ids[i];
     }
 
+    // rank-local: a slot's positions [0, n) are contiguous per layer ([layer][slot][pos][kv0])
+    void copyPrefix(int src, int dst, int n) override {
+        DL_CHECK(src != dst, "copyPrefix: source and destination slot are the same");
+        DL_CHECK(src >= 0 && (u32)src < cfg_.nSlots && dst >= 0 && (u32)dst < cfg_.nSlots,
+                 "copyPrefix: slot out of range");
+        DL_CHECK(n >= 1 && (u32)n < h_.seqLen, "copyPrefix: prefix length out of range");
+        const size_t bytes = (size_t)n * plan_.kv0 * sizeof(float);
+        for (u32 l = 0; l < h_.nLayers; l++) {
+            std::memcpy(kc(l, dst, 0), kc(l, src, 0), bytes);
+            std::memcpy(vc(l, dst, 0), vc(l, src, 0), bytes);
+        }
+    }
+
   private:
     int argmaxRow(const float *x) const {
         int best = 0;

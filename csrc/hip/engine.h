@@ -68,6 +68,8 @@ double benchGemmQ40(int rows, int n, int M, int epi, int copies, int iters,
 // launch.
 double benchAttention(int nHeads0, int kvMul, int hs, int seqLen, int pos, int B, int copies, int iters,
                       std::vector<unsigned long long> *trace = nullptr, bool kvBf16 = true);
+// Microseconds per device-to-device hipMemcpyAsync of `bytes` (the prefix copy's yardstick).
+double benchMemcpyD2D(size_t bytes, int iters);
 // Check a transport on the engine's separate-collective schedule (per layer Q80-rounded
 // all-reduces, root gather of logits slices, all-gather of argmax pairs), eagerly or captured in a
 // hipGraph and replayed `runs` times: returns the largest error against exact host sums (engine_bench.cpp).

@@ -402,4 +402,31 @@ double commScheduleCheck(DeviceComm &comm, int layers, int rows, int dim, int vo
     return err;
 }
 
+// Yardstick of the prefix copy (scripts/bench_prefix.py): `iters` device-to-device hipMemcpyAsync
+// copies of `bytes` between two buffers on one stream, timed by events after two warm-up copies.
+double benchMemcpyD2D(size_t bytes, int iters) {
+    void *a = nullptr, *b = nullptr;
+    hipStream_t s;
+    hipEvent_t e0, e1;
+    DL_HIP(hipMalloc(&a, bytes));
+    DL_HIP(hipMalloc(&b, bytes));
+    DL_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    DL_HIP(hipEventCreate(&e0));
+    DL_HIP(hipEventCreate(&e1));
+    DL_HIP(hipMemsetAsync(a, 1, bytes, s));
+    for (int i = 0; i < 2; i++) DL_HIP(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, s));
+    DL_HIP(hipEventRecord(e0, s));
+    for (int i = 0; i < iters; i++) DL_HIP(hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, s));
+    DL_HIP(hipEventRecord(e1, s));
+    DL_HIP(hipEventSynchronize(e1));
+    float ms = 0;
+    DL_HIP(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    (void)hipStreamDestroy(s);
+    (void)hipFree(a);
+    (void)hipFree(b);
+    return ms * 1e3 / iters;
+}
+
 }  // namespace dl

@@ -1,7 +1,7 @@
 // HipEngine implementation class, shared by the engine's translation units:
 //   engine.cpp          construction, public entry points, hipGraph cache, error checks
 //   engine_load.cpp     device buffers, weight upload (file pipeline / synthetic), capacity checks
-//   engine_kv.cpp       paged KV cache (page table per slot over per-layer pools)
+//   engine_kv.cpp       paged KV cache (page table per slot over per-layer pools), prefix copy
 //   engine_forward.cpp  the per-forward kernel schedule (GEMV / GEMM / attention / block launches)
 //   engine_bench.cpp    kernel microbenchmarks (scripts/bench_*.py)
 //
@@ -80,6 +80,7 @@ class HipEngineImpl : public HipEngine {
     int kvPagesFree() const override { return paged() ? (int)freePages_.size() : -1; }
     int kvPageSize() const override { return paged() ? (int)cfg_.kvPageSize : 0; }
     void releaseSlot(int slot) override;
+    void copyPrefix(int src, int dst, int n) override;
 
     // HipEngine
     double decodeGreedy(int steps, int token, int pos, int slot, int *outTokens) override {
@@ -200,6 +201,8 @@ class HipEngineImpl : public HipEngine {
     void setupPages();
     hipk::KvMap kvMap() const;
     void mapPages(int n, const int *positions, const int *slots, int ahead);
+    void uploadTable();
+    void setupKvCopy();
 
     // engine_forward.cpp
     void setupBuckets();
@@ -372,6 +375,7 @@ class HipEngineImpl : public HipEngine {
     int tableFlip_ = 0, pageShift_ = 0, pagesPerSlot_ = 0;
     bool tableDirty_ = false;
     std::vector<int> hostTable_, slotPages_, freePages_;
+    void **dKvBases_ = nullptr;  // copyPrefix: every layer's K and V base (hipk::KvCopyArgs::bases)
 
     // graphs
     std::map<int, hipGraphExec_t> graphs_;

@@ -80,12 +80,71 @@ void HipEngineImpl::mapPages(int n, const int *positions, const int *slots, int 
             dirty = true;
         }
     }
-    if (!dirty) return;
+    if (dirty) uploadTable();
+}
+
+// The host table to the device, stream-ordered before whatever reads it next.
+void HipEngineImpl::uploadTable() {
     // a pinned copy per upload, alternating: the previous upload may still be reading the other
     int *st = hTableStage_[tableFlip_ ^= 1];
     if (inputsInFlight_) DL_HIP(hipStreamSynchronize(stream_));
     for (size_t i = 0; i < hostTable_.size(); i++) st[i] = hostTable_[i] < 0 ? 0 : hostTable_[i];
     DL_HIP(hipMemcpyAsync(dKvTable_, st, hostTable_.size() * sizeof(int), hipMemcpyHostToDevice, stream_));
+}
+
+// ---------------------------------------------------------------- prefix copy between slots
+// copyPrefix(src, dst, n): dst's positions [0, n) become a byte copy of src's, for every layer and
+// this rank's KV heads (hipk::launchKvCopyPrefix, one launch). Launched eagerly on the engine's
+// stream: after the forwards already enqueued, before the next one. Under tensor parallelism every
+// rank copies its own shard; slots and pages follow the same deterministic rule on every rank.
+// Paged: dst gives its pages back (as a row at position 0 would) and maps ceil(n / pageSize) fresh
+// ones; a pool that cannot supply them leaves dst without pages.
+void HipEngineImpl::setupKvCopy() {
+    std::vector<void *> bases;
+    for (const DevLayer &L : layers_) {
+        bases.push_back(L.k);
+        bases.push_back(L.v);
+    }
+    dKvBases_ = dalloc<void *>(bases.size());
+    DL_HIP(hipMemcpy(dKvBases_, bases.data(), bases.size() * sizeof(void *), hipMemcpyHostToDevice));
+}
+
+void HipEngineImpl::copyPrefix(int src, int dst, int n) {
+    DL_CHECK(src != dst, "copyPrefix: source and destination slot are the same");
+    DL_CHECK(src >= 0 && (u32)src < cfg_.nSlots && dst >= 0 && (u32)dst < cfg_.nSlots, "copyPrefix: slot out of range");
+    DL_CHECK(n >= 1 && (u32)n < h_.seqLen, "copyPrefix: prefix length out of range");
+    DL_CHECK(pendingN_ == 0, "copyPrefix: a launchIds forward was not collected");
+    DL_CHECK(chainInFlight() == 0, "copyPrefix: a chained decode step is still in flight");
+    if (paged()) {
+        DL_CHECK(n <= slotPages_[src] << pageShift_, "copyPrefix: the source slot never reached that position");
+        const int need = (n + (int)cfg_.kvPageSize - 1) >> pageShift_;
+        const bool fits = (size_t)need <= freePages_.size() + (size_t)slotPages_[dst];
+        releaseSlot(dst);
+        if (!fits)
+            throw Error("KV page pool exhausted: " + std::to_string(cfg_.kvPages) + " pages of " +
+                        std::to_string(cfg_.kvPageSize) + " positions cannot hold a prefix copy of " +
+                        std::to_string(n) + " positions; raise --kv-pages or lower the concurrent context");
+        while (slotPages_[dst] < need) {
+            hostTable_[(size_t)dst * pagesPerSlot_ + slotPages_[dst]++] = freePages_.back();
+            freePages_.pop_back();
+        }
+        tableDirty_ = false;
+        uploadTable();
+        inputsInFlight_ = true;  // the upload reads pinned staging: the next one waits for it
+    }
+    hipk::KvCopyArgs a;
+    a.bases = dKvBases_;
+    a.kvMap = kvMap();
+    a.nLayers = (int)h_.nLayers;
+    a.nKv = (int)(plan_.kv0 / plan_.headSize);
+    a.hs = (int)plan_.headSize;
+    a.seqLen = (int)h_.seqLen;
+    a.elemBytes = kvBf16_ ? 2 : 4;
+    a.srcSlot = src;
+    a.dstSlot = dst;
+    a.n = n;
+    a.chunkPos = hipk::kvCopyChunkPos(a.hs, a.elemBytes, paged() ? pageShift_ : 0);
+    hipk::launchKvCopyPrefix(a, stream_);
 }
 
 }  // namespace engine_detail

@@ -218,6 +218,7 @@ void HipEngineImpl::allocBuffers() {
         DL_HIP(hipMemsetAsync(L.k, 0, kvElems * (kvBf16_ ? 2 : 4), stream_));
         DL_HIP(hipMemsetAsync(L.v, 0, kvElems * (kvBf16_ ? 2 : 4), stream_));
     }
+    setupKvCopy();
 }
 
 void HipEngineImpl::uploadRope() {

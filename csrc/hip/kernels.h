@@ -103,6 +103,20 @@ __host__ __device__ inline size_t kvOff(const KvMap &m, int seqLen, int nKv, int
     return kvOffAt(m, seqLen, nKv, hs, m.table ? kvPageOf(m, slot, pos) : (size_t)slot, pos, kvh);
 }
 
+// Prefix copy between KV slots (kv_copy.hip): positions [0, n) of srcSlot to dstSlot, K and V of
+// every layer and every local KV head, in one launch. Source and destination both go through
+// kvOff (contiguous cache or page pool; the destination's pages must be mapped). A plain byte
+// copy: elemBytes 2 (bf16) or 4 (f32).
+struct KvCopyArgs {
+    void *const *bases = nullptr;  // device array [nLayers * 2]: layer l's K base at 2l, V base at 2l + 1
+    KvMap kvMap;
+    int nLayers = 0, nKv = 0, hs = 0, seqLen = 0, elemBytes = 0;
+    int srcSlot = 0, dstSlot = 0, n = 0;
+    int chunkPos = 0;  // positions per workgroup: kvCopyChunkPos (a power of two, at most one page)
+};
+int kvCopyChunkPos(int hs, int elemBytes, int pageShift);
+void launchKvCopyPrefix(const KvCopyArgs &a, hipStream_t s);
+
 struct AttnArgs {
     const float *q = nullptr;   // [B][ldq], rotated queries
     int ldq = 0;

@@ -94,7 +94,7 @@ void exchangeAll(const std::vector<Socket *> &peers, const void *send, u64 n, co
 // ---- control protocol ------------------------------------------------------------------------
 constexpr u32 kProtoMagic = 0xD11A3355;  // "dllama MI355"
 constexpr u32 kMeshMagic = 0xD11A3356;   // worker -> worker data-plane connection
-constexpr u32 kProtoVersion = 1;
+constexpr u32 kProtoVersion = 2;         // 2: Cmd::COPY_PREFIX (a version 1 worker would ignore it)
 constexpr u32 kAck = 23571114;           // same ACK value as the reference (nn-network.cpp:23)
 
 // RELEASE: the first n ints of the payload are KV slots whose sequences ended (paged KV cache:
@@ -102,7 +102,18 @@ constexpr u32 kAck = 23571114;           // same ACK value as the reference (nn-
 // CHAIN: one step of a chained greedy decode (Backend::chainLaunch), n = 1: token (< 0: continue
 // the chain on the device), position, slot. Workers keep at most 2 steps in flight and drain them
 // before any other command.
-enum class Cmd : u32 { FORWARD = 1, FORWARD_ARGMAX = 2, STOP = 3, PING = 4, FORWARD_SAMPLE = 5, RELEASE = 6, CHAIN = 7 };
+// COPY_PREFIX: a control-only command like RELEASE (Backend::copyPrefix on every rank), n = 1:
+// tokens[0] = source slot, positions[0] = positions to copy, slots[0] = destination slot.
+enum class Cmd : u32 {
+    FORWARD = 1,
+    FORWARD_ARGMAX = 2,
+    STOP = 3,
+    PING = 4,
+    FORWARD_SAMPLE = 5,
+    RELEASE = 6,
+    CHAIN = 7,
+    COPY_PREFIX = 8
+};
 
 struct ControlHeader {
     u32 cmd;

@@ -499,7 +499,8 @@ PYBIND11_MODULE(_C, m) {
         .def("last_stats", [](const Backend &b) {
             ForwardStats s = b.lastStats();
             return py::make_tuple(s.computeMs, s.syncMs, s.sentBytes, s.recvBytes, s.xchgMs);
-        });
+        })
+        .def("copy_prefix", &Backend::copyPrefix, py::arg("src"), py::arg("dst"), py::arg("n"));
 
     m.def("cpu_backend",
           [](const std::string &model, const std::string &bufferType, int nThreads, u32 maxSeqLen, u32 maxBatch,
@@ -602,6 +603,8 @@ PYBIND11_MODULE(_C, m) {
           },
           py::arg("n_heads0"), py::arg("kv_mul"), py::arg("head_size"), py::arg("seq_len"), py::arg("pos"),
           py::arg("batch") = 1, py::arg("copies") = 32, py::arg("iters") = 200, py::arg("kv_bf16") = true,
+          py::call_guard<py::gil_scoped_release>());
+    m.def("bench_memcpy_d2d", &benchMemcpyD2D, py::arg("bytes"), py::arg("iters") = 20,
           py::call_guard<py::gil_scoped_release>());
     m.def("trace_gemm_q40",
           [](int rows, int n, int M, int epi, int copies, int iters) {
@@ -908,6 +911,8 @@ PYBIND11_MODULE(_C, m) {
         .def("profile_forward", [](PyHipEngine &e, std::vector<int> t, std::vector<int> p, std::vector<int> s) {
             e.engine->profileForward((int)t.size(), t.data(), p.data(), s.data());
         })
+        .def("copy_prefix", [](PyHipEngine &e, int src, int dst, int n) { e.engine->copyPrefix(src, dst, n); },
+             py::arg("src"), py::arg("dst"), py::arg("n"))
         .def("synchronize", [](PyHipEngine &e) { e.engine->synchronize(); });
 
 }

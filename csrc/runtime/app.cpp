@@ -71,6 +71,8 @@ AppArgs AppArgs::parse(int argc, char **argv, bool requireMode) {
         } else if (name == "--kv-pages") a.kvPages = std::atoi(value);
         else if (name == "--kv-page-size") a.kvPageSize = std::atoi(value);
         else if (name == "--batch-invariant") a.batchInvariant = std::atoi(value) != 0;
+        else if (name == "--prefix-cache") a.prefixCache = std::atoi(value) != 0;
+        else if (name == "--prefix-cache-min") a.prefixCacheMin = std::atoi(value);
         else if (name == "--graph") a.graphs = std::atoi(value) != 0;
         else if (name == "--log-level") a.logLevel = std::atoi(value);
         else if (name == "--synthetic") a.synthetic = value;
@@ -277,6 +279,11 @@ void InferenceSession::releaseSlot(int slot) {
     const int zero = 0;
     sendControl(Cmd::RELEASE, 1, &slot, &zero, &zero);
     backend_->releaseSlot(slot);
+}
+
+void InferenceSession::copyPrefix(int src, int dst, int n) {
+    sendControl(Cmd::COPY_PREFIX, 1, &src, &n, &dst);
+    backend_->copyPrefix(src, dst, n);
 }
 
 void InferenceSession::forward(int n, const int *tokens, const int *positions, const int *slots, float *logits) {
@@ -507,6 +514,8 @@ void runWorker(const AppArgs &args) {
                     while (backend->chainInFlight() > 2) backend->chainCollect();
                 } else if (cmd == Cmd::RELEASE) {
                     for (int i = 0; i < n; i++) backend->releaseSlot(buf[i]);
+                } else if (cmd == Cmd::COPY_PREFIX) {
+                    backend->copyPrefix(buf[0], buf[2 * n], buf[n]);
                 } else if (cmd == Cmd::FORWARD_SAMPLE) {
                     ids.resize(n);
                     specs.resize(n);

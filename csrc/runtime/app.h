@@ -45,6 +45,11 @@ struct AppArgs {
     int kvPages = 0;       // --kv-pages: paged KV pool pages per layer (0 = contiguous per slot)
     bool batchInvariant = false;  // --batch-invariant 1: rows take the same kernels whatever the batch
     int kvPageSize = 256;  // --kv-page-size: positions per page
+    // --prefix-cache 1 (dllama-api, dllama chat): a request starts behind the longest prefix of its
+    // prompt whose KV some slot already holds (scheduler.cpp); --prefix-cache-min: the shortest
+    // prefix worth reusing (32: one attention key tile, the smallest page; a policy default)
+    bool prefixCache = false;
+    int prefixCacheMin = 32;
     bool graphs = true;
     int logLevel = 1;
     std::string synthetic;                       // "llama3_1_8b" etc: random-init weights on device
@@ -75,6 +80,10 @@ class InferenceSession {
     // a sequence ended: its KV slot's pages return to the pool on every rank (no-op when contiguous)
     void releaseSlot(int slot);
     int kvPageSize() const { return backend_->kvPageSize(); }
+    // KV positions [0, n) of slot src copied to slot dst on every rank (Backend::copyPrefix; each
+    // rank copies its own heads, nothing crosses the data plane)
+    void copyPrefix(int src, int dst, int n);
+    const AppArgs &args() const { return args_; }
     bool isGpu() const { return gpu_; }
     int nNodes() const { return 1 + (int)workers_.size(); }
 

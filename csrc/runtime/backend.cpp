@@ -44,5 +44,6 @@ void Backend::collectIds(int *out) {
 
 void Backend::chainLaunch(int, int, int) { throw Error(name() + " backend: no chained decode"); }
 int Backend::chainCollect() { throw Error(name() + " backend: no chained decode"); }
+void Backend::copyPrefix(int, int, int) { throw Error(name() + " backend: prefix copy not supported"); }
 
 }  // namespace dl

@@ -106,6 +106,12 @@ class Backend {
     virtual int kvPageSize() const { return 0; }
     // The sequence in this slot ended: a paged cache returns its pages to the pool (no-op otherwise).
     virtual void releaseSlot(int slot) { (void)slot; }
+    // Prefix reuse (scheduler.cpp, --prefix-cache): the KV of positions [0, n) of slot src is copied
+    // to slot dst, byte for byte, for every layer and this rank's KV heads; dst's earlier contents
+    // are dropped (a paged cache returns dst's pages and maps the ones the copy needs). 1 <= n <
+    // seqLen, src != dst, no forward launched and not collected. The copy is ordered after the
+    // forwards already issued and before the next one. Default: not supported.
+    virtual void copyPrefix(int src, int dst, int n);
     virtual std::string name() const = 0;
 
   protected:

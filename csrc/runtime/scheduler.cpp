@@ -42,6 +42,11 @@ Scheduler::Scheduler(InferenceSession &sess) : sess_(sess), tok_(sess.tokenizer(
     pagesTotal_ = sess.kvPagesFree();
     pageSize_ = sess.kvPageSize();
     slotPages_.assign(sess.nSlots(), 0);
+    prefixOn_ = sess.args().prefixCache;
+    prefixMin_ = (size_t)std::max(1, sess.args().prefixCacheMin);
+    resident_.assign(sess.nSlots(), {});
+    lastUse_.assign(sess.nSlots(), 0);
+    slotReach_.assign(sess.nSlots(), 0);
     thread_ = std::thread([this] { loop(); });
 }
 
@@ -113,6 +118,12 @@ void Scheduler::loop() {
 // on every rank first: the slot waits in releasing_ until flushReleases() has sent the RELEASE
 // (network I/O, never under mu_, so submit() / stats() on the HTTP threads do not stall).
 void Scheduler::returnSlot(int slot) {
+    if (prefixOn_) {  // idle, not forgotten: the slot keeps its record and the pages that hold it
+        lastUse_[slot] = ++useStamp_;
+        if (pagesTotal_ >= 0) slotPages_[slot] = pagesFor(slotReach_[slot]);
+        freeSlots_.push_back(slot);
+        return;
+    }
     if (pagesTotal_ >= 0 && slotPages_[slot])
         releasing_.push_back(slot);
     else
@@ -169,6 +180,18 @@ void Scheduler::failAll(const std::string &what) {
         for (auto &r : draining_) returnSlot(r->slot);
         active_.clear();
         draining_.clear();
+        if (prefixOn_) {  // the device state is unknown after a failed forward: forget every record
+            for (auto &rec : resident_) rec.clear();
+            std::vector<int> keep;
+            for (int s : freeSlots_) {
+                slotReach_[s] = 0;
+                if (pagesTotal_ >= 0 && slotPages_[s])
+                    releasing_.push_back(s);
+                else
+                    keep.push_back(s);
+            }
+            freeSlots_.swap(keep);
+        }
     }
     flushReleases();
 }
@@ -178,6 +201,7 @@ void Scheduler::failAll(const std::string &what) {
 void Scheduler::finishRequest(const std::shared_ptr<GenRequest> &r, const char *reason) {
     r->finished = true;
     r->finish(reason);
+    if (prefixOn_) resident_[r->slot] = residentOf(*r);  // frozen here: rows still in flight lie beyond it
     bool inFlight = false;
     if (inflight_)
         for (auto &p : flight_.picks)
@@ -189,9 +213,162 @@ void Scheduler::finishRequest(const std::shared_ptr<GenRequest> &r, const char *
     active_.erase(std::remove(active_.begin(), active_.end(), r), active_.end());
 }
 
+// Under mu_. The request takes the slot and starts with its first `prefilled` prompt tokens' KV
+// already in place (0 without prefix reuse).
+void Scheduler::startRequest(const std::shared_ptr<GenRequest> &r, int slot, size_t prefilled) {
+    const int vocab = (int)sess_.header().vocabSize;
+    r->slot = slot;
+    r->prefilled = prefilled;
+    r->sampler.reset(new Sampler(vocab, r->params.temperature, r->params.topp, r->params.seed));
+    r->decoder.reset(new TokenDecoder(tok_));
+    ChatStops cs(tok_);
+    std::vector<std::string> stops = cs.stops;
+    size_t maxLen = cs.maxStopLength;
+    for (auto &s : r->params.stop)
+        if (!s.empty()) {
+            stops.push_back(s);
+            maxLen = std::max(maxLen, s.size());
+        }
+    std::vector<int> eosIds = tok_.eosTokenIds();
+    while (eosIds.size() < stops.size()) eosIds.push_back(-1);
+    r->eos.reset(new EosDetector(eosIds, stops, (int)maxLen, (int)maxLen));
+    active_.push_back(r);
+}
+
+// The tokens whose KV the request's slot holds: those fed as inputs of forwards already collected
+// (the last generated token has not been fed yet; rows in flight are not counted).
+std::vector<int> Scheduler::residentOf(const GenRequest &r) const {
+    std::vector<int> rec(r.prompt.begin(), r.prompt.begin() + std::min(r.prefilled, r.prompt.size()));
+    if (!r.generated.empty()) rec.insert(rec.end(), r.generated.begin(), r.generated.end() - 1);
+    return rec;
+}
+
+static size_t commonPrefix(const std::vector<int> &a, const std::vector<int> &b, size_t cap) {
+    const size_t n = std::min({a.size(), b.size(), cap});
+    size_t i = 0;
+    while (i < n && a[i] == b[i]) i++;
+    return i;
+}
+
+// Scheduler thread, between the collection of a forward and the next launch (nothing is in flight).
+// Admits the request at the head of the queue behind the longest prefix of its prompt that a slot
+// holds (capped at prompt - 1: one row must run to yield logits):
+//   the best slot is idle   -> the request takes that slot in place, no device work;
+//   the best slot is active -> copyPrefix into the least recently used idle slot;
+//   no prefix >= prefixMin_ -> the least recently used idle slot, prefilled from 0.
+// Paged cache: an idle slot's pages stay accounted; when the pool lacks unreserved pages for the
+// request, idle slots are evicted in LRU order until it fits. Only a request that the active
+// requests' reservations alone keep out waits (so an idle slot never blocks an admission). The
+// decision is taken under mu_; the device work (releases, the copy) runs after it, without mu_.
+bool Scheduler::admitWithPrefix() {
+    const u32 seqLen = sess_.header().seqLen;
+    std::vector<int> evict;
+    int target = -1, src = -1;
+    size_t L = 0;
+    bool releaseTarget = false;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        if (queue_.empty()) return false;
+        auto r = queue_.front();
+        if (r->isCancelled()) {
+            queue_.pop_front();
+            r->finish("cancelled");
+            stats_.cancelled++;
+            return true;
+        }
+        if (r->prompt.empty() || r->prompt.size() >= seqLen) {
+            queue_.pop_front();
+            r->error = r->prompt.empty() ? "empty prompt" : "prompt longer than the context";
+            r->finish("error");
+            return true;
+        }
+        if (freeSlots_.empty()) return false;
+        const size_t cap = r->prompt.size() - 1;
+        int idleBest = -1, lru = freeSlots_.back();
+        size_t idleL = 0, activeL = 0;
+        for (auto it = freeSlots_.rbegin(); it != freeSlots_.rend(); ++it) {
+            const size_t l = commonPrefix(r->prompt, resident_[*it], cap);
+            if (l > idleL) idleL = l, idleBest = *it;
+            if (lastUse_[*it] < lastUse_[lru]) lru = *it;
+        }
+        for (auto &a : active_) {
+            const size_t l = commonPrefix(r->prompt, residentOf(*a), cap);
+            if (l > activeL) activeL = l, src = a->slot;
+        }
+        bool inPlace = false;
+        if (idleL >= prefixMin_ && idleL >= activeL) {
+            inPlace = true;
+            target = idleBest;
+            L = idleL;
+            src = -1;
+        } else if (activeL >= prefixMin_) {
+            target = lru;
+            L = activeL;
+        } else {
+            target = lru;
+            src = -1;
+        }
+        if (pagesTotal_ >= 0) {
+            const u64 span = r->params.maxTokens > 0 ? (u64)r->prompt.size() + (u64)r->params.maxTokens + 1 : seqLen;
+            const int need = pagesFor(std::min<u64>(span, seqLen));
+            if (need > pagesTotal_) {
+                queue_.pop_front();
+                r->error = "request needs more KV pages than the pool holds";
+                r->finish("error");
+                return true;
+            }
+            int held = 0, idleHeld = 0;
+            for (int p : slotPages_) held += p;
+            for (int s : freeSlots_) idleHeld += slotPages_[s];
+            if (need > pagesTotal_ - (held - idleHeld)) return false;  // wait for pages (as without reuse)
+            // pages after admission: an in-place slot keeps what it has mapped; any other target
+            // gives its pages back first (copyPrefix does, a plain start is released below)
+            auto after = [&]() { return held - slotPages_[target] + (inPlace ? std::max(need, slotPages_[target]) : need); };
+            std::vector<int> order(freeSlots_);
+            std::sort(order.begin(), order.end(), [&](int a, int b) { return lastUse_[a] < lastUse_[b]; });
+            for (int s : order) {
+                if (after() <= pagesTotal_) break;
+                if (s == target || slotPages_[s] == 0) continue;
+                held -= slotPages_[s];
+                slotPages_[s] = 0;
+                slotReach_[s] = 0;
+                resident_[s].clear();
+                evict.push_back(s);
+                stats_.prefixEvictions++;
+            }
+            if (after() > pagesTotal_) {  // an in-place slot mapped beyond what the pool can spare: start it over
+                inPlace = false;
+                L = 0;
+                src = -1;
+            }
+            releaseTarget = !inPlace && src < 0 && slotPages_[target] > 0;
+            slotPages_[target] = inPlace ? std::max(need, slotPages_[target]) : need;
+        }
+        if (!inPlace) slotReach_[target] = L;  // a copy maps the pages of [0, L); a plain start none
+        resident_[target].clear();
+        queue_.pop_front();
+        freeSlots_.erase(std::find(freeSlots_.begin(), freeSlots_.end(), target));
+        startRequest(r, target, L);
+        r->cachedTokens = (int)L;
+        if (L > 0) {
+            stats_.prefixHits++;
+            stats_.prefixTokens += L;
+            if (src >= 0) stats_.prefixCopies++;
+        }
+    }
+    if (releaseTarget) evict.push_back(target);
+    for (int s : evict) {
+        try {
+            sess_.releaseSlot(s);
+        } catch (const std::exception &) {  // a lost worker surfaces on the next forward
+        }
+    }
+    if (src >= 0) sess_.copyPrefix(src, target, (int)L);  // a failure fails the step (failAll)
+    return true;
+}
+
 bool Scheduler::step() {
     const u32 seqLen = sess_.header().seqLen;
-    const int vocab = (int)sess_.header().vocabSize;
 
     // 0) collect the forward in flight: token ids and prompt progress only (cheap); the text work
     //    for these tokens runs after the next forward has been launched (step 4)
@@ -222,9 +399,12 @@ bool Scheduler::step() {
     // 1) admission: one free KV slot per request (and, with a paged KV cache, the pages its prompt +
     //    max_tokens can reach; FIFO: the head waits until enough pages are free); cancelled requests
     //    give their slot back
+    if (prefixOn_)
+        while (admitWithPrefix()) {
+        }
     {
         std::lock_guard<std::mutex> lk(mu_);
-        while (!queue_.empty() && !freeSlots_.empty()) {
+        while (!prefixOn_ && !queue_.empty() && !freeSlots_.empty()) {
             auto r = queue_.front();
             if (r->isCancelled()) {
                 queue_.pop_front();
@@ -254,23 +434,8 @@ bool Scheduler::step() {
                 slotPages_[slot] = need;
             }
             queue_.pop_front();
-            r->slot = slot;
             freeSlots_.pop_back();
-            r->prefilled = 0;
-            r->sampler.reset(new Sampler(vocab, r->params.temperature, r->params.topp, r->params.seed));
-            r->decoder.reset(new TokenDecoder(tok_));
-            ChatStops cs(tok_);
-            std::vector<std::string> stops = cs.stops;
-            size_t maxLen = cs.maxStopLength;
-            for (auto &s : r->params.stop)
-                if (!s.empty()) {
-                    stops.push_back(s);
-                    maxLen = std::max(maxLen, s.size());
-                }
-            std::vector<int> eosIds = tok_.eosTokenIds();
-            while (eosIds.size() < stops.size()) eosIds.push_back(-1);
-            r->eos.reset(new EosDetector(eosIds, stops, (int)maxLen, (int)maxLen));
-            active_.push_back(r);
+            startRequest(r, slot, 0);
         }
         // the cancel flag is read ONCE per request (cancel() runs on HTTP threads without mu_)
         std::vector<std::shared_ptr<GenRequest>> cancelled;
@@ -323,6 +488,8 @@ bool Scheduler::step() {
     //    backend (the device sampler on GPUs) with each request's own temperature / top-p and the
     //    coin its own seeded generator yields, so only token ids come back
     if (next.n > 0) {
+        if (prefixOn_)  // positions each slot's cache (and, paged, its mapped pages) reaches
+            for (int i = 0; i < next.n; i++) slotReach_[slots[i]] = std::max<size_t>(slotReach_[slots[i]], (size_t)positions[i] + 1);
         bool allGreedy = true;
         for (auto &p : next.picks)
             if (p.sample && p.r->params.temperature != 0.0f) allGreedy = false;

@@ -44,6 +44,7 @@ class GenRequest {
     std::string error;
     bool done = false;
     int completionTokens = 0;
+    int cachedTokens = 0;  // prompt tokens whose KV was reused instead of prefilled (--prefix-cache)
 
     // The client went away (e.g. a streaming connection dropped): the scheduler finishes the
     // request at its next step and frees its KV slot instead of generating to max_tokens.
@@ -73,6 +74,9 @@ struct SchedulerStats {
     u64 forwards = 0, rows = 0, prefillRows = 0, decodeRows = 0, completed = 0, generatedTokens = 0, cancelled = 0;
     double busyMs = 0;
     int active = 0, queued = 0;
+    // --prefix-cache: requests admitted behind a reused prefix, the prompt tokens that saved, the
+    // hits that needed a device copy (source slot still active), idle slots evicted for their pages
+    u64 prefixHits = 0, prefixTokens = 0, prefixCopies = 0, prefixEvictions = 0;
 };
 
 class Scheduler {
@@ -118,6 +122,24 @@ class Scheduler {
     std::vector<int> releasing_;  // freed slots whose pages are not released yet (under mu_)
     void returnSlot(int slot);
     void flushReleases();
+    void startRequest(const std::shared_ptr<GenRequest> &r, int slot, size_t prefilled);
+
+    // Prefix reuse (--prefix-cache 1; everything below is unused otherwise). resident_[slot] is the
+    // token sequence whose KV an idle slot holds: the tokens fed as inputs of collected forwards,
+    // frozen when its request finished (an active slot's record is read off its request). Freed
+    // slots stay in freeSlots_ with their record, a last-use stamp and, with a paged cache, the pages
+    // the record occupies still accounted in slotPages_ (not released). Admission starts a request
+    // behind the longest prefix of its prompt found in any record: in place when that slot is idle,
+    // through copyPrefix into the least recently used idle slot when it is active.
+    bool prefixOn_ = false;
+    size_t prefixMin_ = 32;
+    std::vector<std::vector<int>> resident_;
+    std::vector<u64> lastUse_;
+    std::vector<size_t> slotReach_;  // positions launched into each slot (its mapped pages, paged)
+    u64 useStamp_ = 0;
+    std::vector<int> residentOf(const GenRequest &r) const;
+    int pagesFor(size_t positions) const { return (int)((positions + pageSize_ - 1) / pageSize_); }
+    bool admitWithPrefix();  // one request from the head of the queue; false: nothing admitted
     Flight flight_;
     bool inflight_ = false;
     bool stop_ = false;
