@@ -2,15 +2,18 @@
 // (reference: src/dllama-api.cpp:250-410, src/api-types.hpp).
 //
 //   POST /v1/chat/completions  {"messages":[...], "max_tokens", "temperature", "top_p", "seed",
-//                               "stop", "stream"}
+//                               "stop", "stream", "logprobs", "top_logprobs"}
 //        -> {"generated_text": ...} (the reference/web-ui shape) plus the OpenAI
 //           {"id","object","created","model","choices":[...],"usage":{...}} fields;
 //           "stream": true -> server-sent events with chat.completion.chunk objects + [DONE]
+//           "logprobs": true (+ "top_logprobs": 0..20) -> choices[0].logprobs.content, one entry
+//           per generated token: log_softmax of the raw logits, whatever temperature / top_p
 //   GET  /v1/models            {"object":"list","data":[{"id":<model file name>, ...}]}
 //   GET  /health               scheduler counters (JSON)
 //   GET  /v1/metrics           the same counters in Prometheus text format
 //   GET  /, /app.js, /style.css  the chat web UI (--web-ui <dir>, default ./web-ui when present)
 // Requests run concurrently (thread per connection); the scheduler batches them into shared forwards.
+#include <cmath>
 #include <csignal>
 #include <cstdio>
 #include <ctime>
@@ -55,6 +58,71 @@ struct Api {
         return tok.encode(flat, true, false);
     }
 
+    // The vocabulary piece as a valid JSON string: every maximal invalid part of a UTF-8 sequence (a
+    // piece may be part of a character) becomes one U+FFFD; "bytes" carries the piece exactly.
+    static std::string validUtf8(const std::string &s) {
+        std::string out;
+        const size_t n = s.size();
+        for (size_t i = 0; i < n;) {
+            const unsigned char c = (unsigned char)s[i];
+            const size_t len = c < 0x80 ? 1 : (c >= 0xC2 && c <= 0xDF) ? 2 : (c >= 0xE0 && c <= 0xEF) ? 3 : (c >= 0xF0 && c <= 0xF4) ? 4 : 0;
+            size_t got = len ? 1 : 0;  // bytes of the sequence that are well-formed so far
+            for (; got >= 1 && got < len && i + got < n; got++) {
+                const unsigned char d = (unsigned char)s[i + got];
+                unsigned char lo = 0x80, hi = 0xBF;
+                if (got == 1) {  // no overlong forms, no surrogates, nothing beyond U+10FFFF
+                    if (c == 0xE0) lo = 0xA0;
+                    if (c == 0xED) hi = 0x9F;
+                    if (c == 0xF0) lo = 0x90;
+                    if (c == 0xF4) hi = 0x8F;
+                }
+                if (d < lo || d > hi) break;
+            }
+            if (len && got == len) {
+                out.append(s, i, len);
+                i += len;
+            } else {
+                out += "\xEF\xBF\xBD";
+                i += got ? got : 1;
+            }
+        }
+        return out;
+    }
+
+    Value tokenJson(const TokenLogprob &t) {
+        Tokenizer &tok = sess->tokenizer();
+        const std::string piece = t.id >= 0 && t.id < tok.vocabSize() ? tok.piece(t.id) : std::string();
+        Value v = Value::object();
+        v.set("token", validUtf8(piece));
+        v.set("token_id", t.id);
+        v.set("logprob", (double)t.logprob);
+        Value bytes = Value::array();
+        for (unsigned char c : piece) bytes.push((int)c);
+        v.set("bytes", bytes);
+        return v;
+    }
+
+    // choices[0].logprobs for the request's records [from, size): {"content": [...]}; `from` moves on
+    Value logprobsJson(GenRequest &r, size_t &from) {
+        std::vector<TokenRecord> recs;
+        {
+            std::lock_guard<std::mutex> lk(r.mu);
+            recs.assign(r.logprobs.begin() + std::min(from, r.logprobs.size()), r.logprobs.end());
+        }
+        from += recs.size();
+        Value content = Value::array();
+        for (const TokenRecord &rec : recs) {
+            Value e = tokenJson(rec.chosen);
+            Value top = Value::array();
+            for (const TokenLogprob &t : rec.top) top.push(tokenJson(t));
+            e.set("top_logprobs", top);
+            content.push(e);
+        }
+        Value lp = Value::object();
+        lp.set("content", content);
+        return lp;
+    }
+
     void complete(const HttpRequest &req, HttpConnection &conn) {
         Value body;
         try {
@@ -79,6 +147,27 @@ struct Api {
             for (const Value &s : body["stop"].items())
                 if (s.isString()) p.stop.push_back(s.asString());
         const bool stream = body["stream"].isBool() && body["stream"].asBool();
+        {
+            const Value &lp = body["logprobs"], &top = body["top_logprobs"];
+            std::string bad;
+            if (!lp.isNull() && !lp.isBool()) bad = "logprobs must be a boolean";
+            p.logprobs = lp.isBool() && lp.asBool();
+            if (bad.empty() && !top.isNull()) {
+                if (!top.isNumber() || top.asNumber() != std::floor(top.asNumber()) || top.asNumber() < 0 ||
+                    top.asNumber() > kMaxTopLogprobs)
+                    bad = "top_logprobs must be an integer from 0 to " + std::to_string(kMaxTopLogprobs);
+                else if (!p.logprobs)
+                    bad = "top_logprobs requires logprobs: true";
+                else
+                    p.topLogprobs = (int)top.asNumber();
+            }
+            if (!bad.empty()) {
+                Value err = Value::object();
+                err.set("error", "Invalid request: " + bad);
+                conn.writeJson(400, err.dump());
+                return;
+            }
+        }
         std::vector<int> prompt;
         try {
             prompt = buildPrompt(body["messages"]);
@@ -97,6 +186,7 @@ struct Api {
         } cancelGuard{r.get()};
         const std::string id = "chatcmpl-" + std::to_string(r->id);
         const long created = (long)std::time(nullptr);
+        size_t lpSent = 0;  // log-probability records already written (streaming)
         if (stream) {
             conn.beginSse();
             bool first = true;
@@ -113,6 +203,7 @@ struct Api {
                 if (first) delta.set("role", "assistant");
                 delta.set("content", d);
                 ch.set("delta", delta);
+                ch.set("logprobs", p.logprobs ? logprobsJson(*r, lpSent) : Value());
                 ch.set("finish_reason", Value());
                 chunk.set("choices", Value::array()).push(ch);
                 conn.writeSse(chunk.dump());
@@ -126,6 +217,7 @@ struct Api {
             Value ch = Value::object();
             ch.set("index", 0);
             ch.set("delta", Value::object());
+            ch.set("logprobs", p.logprobs ? logprobsJson(*r, lpSent) : Value());  // the records not sent yet
             ch.set("finish_reason", r->finishReason);
             chunk.set("choices", Value::array()).push(ch);
             conn.writeSse(chunk.dump());
@@ -150,6 +242,7 @@ struct Api {
         msg.set("role", "assistant");
         msg.set("content", text);
         choice.set("message", msg);
+        choice.set("logprobs", p.logprobs ? logprobsJson(*r, lpSent) : Value());
         choice.set("finish_reason", r->finishReason);
         resp.set("choices", Value::array()).push(choice);
         Value usage = Value::object();

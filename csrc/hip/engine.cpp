@@ -155,10 +155,12 @@ void HipEngineImpl::forwardSample(int n, const int *tokens, const int *positions
     Timer t;
     setInputs(n, tokens, positions, slots, specs);
     runGraph(n, GraphKind::SAMPLE);
+    enqueueLogprobs(n, specs);
     DL_HIP(hipMemcpyAsync(hIds_, dIds_, n * sizeof(int), hipMemcpyDeviceToHost, stream_));
     syncAndCheckComm();
     inputsInFlight_ = false;
     std::memcpy(out, hIds_, n * sizeof(int));
+    readLogprobs();
     stats_.computeMs = t.elapsedMs();
     setSyncStats(readSync(hSync_, false), stats_.computeMs);
 }
@@ -171,6 +173,7 @@ void HipEngineImpl::launchIds(int n, const int *tokens, const int *positions, co
     Timer t;
     setInputs(n, tokens, positions, slots, specs);
     runGraph(n, specs ? GraphKind::SAMPLE : GraphKind::ARGMAX);
+    enqueueLogprobs(n, specs);
     DL_HIP(hipMemcpyAsync(hIds_, dIds_, n * sizeof(int), hipMemcpyDeviceToHost, stream_));
     pendingN_ = n;
     stats_.computeMs = t.elapsedMs();  // host enqueue time; the sync is read when collected
@@ -183,7 +186,47 @@ void HipEngineImpl::collectIds(int *out) {
     syncAndCheckComm();
     inputsInFlight_ = false;
     std::memcpy(out, hIds_, n * sizeof(int));
+    readLogprobs();
     setSyncStats(readSync(hSync_, false), -1);
+}
+
+// Rows of the SAMPLE forward just enqueued ask for log-probabilities (SampleSpec::logprobs): one
+// launchLogprobs behind the graph on the same stream - not inside it, so forwards without a request
+// replay exactly the graphs they always did - over the full logits and the ids the sampler wrote,
+// and the (1 + 20) pairs per row copied to pinned memory with the ids. Root only: the other ranks
+// of a tensor-parallel forward neither hold the full logits nor draw.
+void HipEngineImpl::enqueueLogprobs(int n, const SampleSpec *specs) {
+    logprobReq_.clear();
+    if (!specs || rank() != 0) return;
+    bool any = false;
+    for (int b = 0; b < n; b++) any = any || specs[b].logprobs >= 1.f;
+    if (!any) return;
+    logprobReq_.resize(n);
+    for (int b = 0; b < n; b++) logprobReq_[b] = (int)specs[b].logprobs;
+    hipk::LogprobArgs g;
+    g.logits = plan_.nRanks > 1 ? dLogitsFull_ : dLogits_;
+    g.vocab = h_.vocabSize;
+    g.ids = dIds_;
+    g.spec = dSpec_;
+    g.scratch = logprobScratch_;
+    g.out = dLogprobs_;
+    hipk::launchLogprobs(g, n, stream_);
+    DL_HIP(hipGetLastError());
+    DL_HIP(hipMemcpyAsync(hLogprobs_, dLogprobs_, (size_t)n * hipk::kLogprobSlots * sizeof(hipk::LogprobEntry),
+                          hipMemcpyDeviceToHost, stream_));
+}
+
+// After the forward's stream sync: Backend::lastLogprobs() of the forward (rows without a request,
+// which the kernel leaves untouched, hold id -1).
+void HipEngineImpl::readLogprobs() {
+    static_assert(hipk::kLogprobSlots == kLogprobEntries && sizeof(hipk::LogprobEntry) == sizeof(TokenLogprob),
+                  "device and host logprob layouts");
+    logprobs_.assign(logprobReq_.size() * kLogprobEntries, TokenLogprob{0.f, -1});
+    for (size_t b = 0; b < logprobReq_.size(); b++)
+        if (logprobReq_[b] >= 1)
+            std::memcpy(&logprobs_[b * kLogprobEntries], hLogprobs_ + b * hipk::kLogprobSlots,
+                        kLogprobEntries * sizeof(TokenLogprob));
+    logprobReq_.clear();
 }
 
 // Chained decode for the CLI: the CHAIN graph (forward -> argmax -> tokens := ids, pos += 1 on

@@ -200,6 +200,10 @@ hipk::AttnArgs HipEngineImpl::attnArgs(const DevLayer &L, bool bat) const {
     a.ldOut = p.q0;
     a.kvBf16 = kvBf16_ ? 1 : 0;
     a.mfma = attnLong_ ? 1 : 0;
+    // batch-invariant engines: one query head per workgroup whatever the rows of the launch (the
+    // launch would group 2+ heads from 33 rows x 8 heads on, which reorders a row's sums: a prompt
+    // prefilled next to others then left other KV than the same prompt prefilled alone)
+    a.headGroup = invariant_ ? 1 : 0;
     a.counters = dAttCnt_;
     return a;
 }

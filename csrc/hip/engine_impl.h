@@ -344,6 +344,13 @@ class HipEngineImpl : public HipEngine {
     float *dArgV_ = nullptr;
     float *dArgPairs_ = nullptr, *dArgPairsAll_ = nullptr;  // separate-collective TP argmax
     hipk::SampleScratch sampleScratch_;
+    // log-probabilities (SampleSpec::logprobs): launchLogprobs after a SAMPLE forward whose rows ask
+    // for them, on the root; scratch, output and its pinned copy hold maxBatch rows
+    hipk::LogprobScratch logprobScratch_;
+    hipk::LogprobEntry *dLogprobs_ = nullptr, *hLogprobs_ = nullptr;
+    std::vector<int> logprobReq_;  // per row of the forward in flight (empty: no row asked)
+    void enqueueLogprobs(int n, const SampleSpec *specs);
+    void readLogprobs();
     // measured-sync slots (syncSlots, hipk::syncFoldWords) and their host copies: [0] the last
     // forward / chain, [1 + k] chain step k % kChainDepth (chainLaunch / chainCollect)
     unsigned *dSync_ = nullptr, *hSync_ = nullptr;

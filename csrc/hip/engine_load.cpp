@@ -184,6 +184,13 @@ void HipEngineImpl::allocBuffers() {
         DL_HIP(hipMemsetAsync(ss, 0, hipk::SampleScratch::bytes((int)MB), stream_));
         sampleScratch_.carve(ss, (int)MB);
     }
+    {
+        void *ls = dalloc<uint8_t>(hipk::LogprobScratch::bytes((int)MB));
+        DL_HIP(hipMemsetAsync(ls, 0, hipk::LogprobScratch::bytes((int)MB), stream_));
+        logprobScratch_.carve(ls, (int)MB);
+        dLogprobs_ = dalloc<hipk::LogprobEntry>((size_t)MB * hipk::kLogprobSlots);
+        hLogprobs_ = halloc<hipk::LogprobEntry>((size_t)MB * hipk::kLogprobSlots);
+    }
     dArgCnt_ = dalloc<int>(MB);
     DL_HIP(hipMemsetAsync(dArgCnt_, 0, sizeof(int) * MB, stream_));
     dLogits_ = dalloc<float>((size_t)MB * p.vocab0);

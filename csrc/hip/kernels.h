@@ -137,6 +137,8 @@ struct AttnArgs {
     int ldOut = 0;
     int kvBf16 = 1;
     int mfma = -1;              // decode kernel: 1 MFMA, 0 VALU, -1 by cache length (attnUsesMfma)
+    int headGroup = 0;          // VALU kernel: query heads per workgroup; 0 = chosen from the launch's rows
+                                // (the grouping changes a row's summation order: batch-invariant engines pin it)
     int *counters = nullptr;    // [B][nHeads0/HG] arrival counters (zero-initialised, self-resetting)
     // diagnostics (MFMA decode kernel): 8 u64 s_memrealtime stamps per workgroup, index
     // (b * splitGrid + chunk) * headGroups + group: [0] entry, [1] DMA issued, [2] first tile
@@ -500,6 +502,50 @@ struct SampleArgs {
     SampleScratch scratch;
 };
 void launchSample(const SampleArgs &a, int B, hipStream_t s);
+
+// Log-probabilities of B rows of full-vocabulary logits: log_softmax of the raw logits (whatever
+// the row's temperature / top-p). spec[b].w is the row's request (SampleSpec::logprobs): 0 = none
+// (the row's output is left untouched), 1 + k = the token ids[b] plus the k <= kLogprobTop best
+// tokens, ordered by (logit descending, id ascending) on the f32 logits. out[b] holds 1 + kLogprobTop
+// {logprob, id} pairs: slot 0 the chosen token (id -1 when ids[b] is no token), slots 1..k the best,
+// the rest id -1. One launch of logprobGroups(vocab) workgroups per row - a count that does not
+// depend on B, so a row's result is bitwise the same whatever else is in the launch: every
+// workgroup keeps the max, the sum of exp and the k best of its slice (read once, held in
+// registers), the row's last arriver combines the partials in workgroup order. The scratch must be
+// zero-initialised once; every call leaves its counters zero.
+constexpr int kLogprobTop = 20;
+constexpr int kLogprobSlots = 1 + kLogprobTop;
+constexpr int kLogprobMaxGroups = 64;
+int logprobGroups(int vocab);
+struct LogprobEntry {
+    float logprob;
+    int id;
+};
+struct LogprobScratch {
+    int *counters = nullptr;  // [B]
+    float *partM = nullptr;   // [B][kLogprobMaxGroups] slice maxima
+    float *partS = nullptr;   // [B][kLogprobMaxGroups] slice sums of exp(x - max)
+    float *candV = nullptr;   // [B][kLogprobMaxGroups][kLogprobTop] slice winners
+    int *candI = nullptr;
+    static size_t words(int B) { return (size_t)B * (1 + kLogprobMaxGroups * (2 + 2 * kLogprobTop)); }
+    static size_t bytes(int B) { return words(B) * 4; }
+    void carve(void *base, int B) {
+        counters = static_cast<int *>(base);
+        partM = reinterpret_cast<float *>(counters + B);
+        partS = partM + (size_t)B * kLogprobMaxGroups;
+        candV = partS + (size_t)B * kLogprobMaxGroups;
+        candI = reinterpret_cast<int *>(candV + (size_t)B * kLogprobMaxGroups * kLogprobTop);
+    }
+};
+struct LogprobArgs {
+    const float *logits = nullptr;  // [B][vocab]
+    int vocab = 0;
+    const int *ids = nullptr;       // [B] the tokens just written by the sampler / argmax on this stream
+    const float4 *spec = nullptr;   // [B] (temperature, topp, coin, request)
+    LogprobScratch scratch;
+    LogprobEntry *out = nullptr;    // [B][kLogprobSlots]
+};
+void launchLogprobs(const LogprobArgs &a, int B, hipStream_t s);
 
 // Round-trip f32 partial sums through Q80 blocks in place (the reference's ZQ cast before the
 // exchange) - used ahead of a plain all-reduce when the fused exchange is not available.

@@ -222,6 +222,7 @@ void launchAttentionValu(const AttnArgs &a, int B, hipStream_t s) {
     }();
     int HG = 1;
     while (HG < hgMax && (long)(a.nHeads0 / HG) * a.splitGrid * B > gridMax) HG *= 2;
+    if (a.headGroup > 0) HG = a.headGroup < hgMax ? a.headGroup : hgMax;
     if (a.hs == 128) {
         if (a.kvBf16) attnDispatchHG<128, true>(a, B, HG, s);
         else attnDispatchHG<128, false>(a, B, HG, s);

@@ -434,6 +434,82 @@ std::vector<int> sample(const std::vector<float> &logits, int B, int vocab, cons
     return sc.download(g.ids, B);
 }
 
+namespace {
+hipk::LogprobArgs logprobArgs(Scratch &sc, int B, int vocab, const std::vector<int> &requests) {
+    std::vector<float> spec((size_t)B * 4, 0.f);
+    for (int b = 0; b < B; b++) spec[(size_t)b * 4 + 3] = (float)requests[b];
+    hipk::LogprobArgs g;
+    g.vocab = vocab;
+    g.spec = reinterpret_cast<const float4 *>(sc.upload(spec));
+    g.scratch.carve(sc.alloc<uint8_t>(hipk::LogprobScratch::bytes(B)), B);  // (alloc zero-fills)
+    std::vector<hipk::LogprobEntry> fill((size_t)B * hipk::kLogprobSlots, hipk::LogprobEntry{0.f, -2});
+    g.out = sc.upload(fill);
+    return g;
+}
+}  // namespace
+
+void logprobs(const std::vector<float> &logits, int B, int vocab, const std::vector<int> &ids,
+              const std::vector<int> &requests, std::vector<float> &outLogprobs, std::vector<int> &outIds,
+              const std::vector<float> *warmLogits, const std::vector<int> *warmIds) {
+    DL_CHECK(B >= 1 && vocab >= 1 && logits.size() == (size_t)B * vocab && ids.size() == (size_t)B &&
+                 requests.size() == (size_t)B, "logprobs sizes");
+    for (int r : requests) DL_CHECK(r >= 0 && r <= hipk::kLogprobSlots, "logprobs request out of range");
+    Scratch sc;
+    hipk::LogprobArgs g = logprobArgs(sc, B, vocab, requests);
+    if (warmLogits) {
+        DL_CHECK(warmIds && warmLogits->size() == logits.size() && warmIds->size() == ids.size(), "logprobs warm sizes");
+        g.logits = sc.upload(*warmLogits);
+        g.ids = sc.upload(*warmIds);
+        hipk::launchLogprobs(g, B, sc.s);
+    }
+    g.logits = sc.upload(logits);
+    g.ids = sc.upload(ids);
+    hipk::launchLogprobs(g, B, sc.s);
+    sc.sync();
+    const std::vector<hipk::LogprobEntry> out = sc.download(g.out, (size_t)B * hipk::kLogprobSlots);
+    outLogprobs.resize(out.size());
+    outIds.resize(out.size());
+    for (size_t i = 0; i < out.size(); i++) {
+        outLogprobs[i] = out[i].logprob;
+        outIds[i] = out[i].id;
+    }
+}
+
+void benchLogprobs(const std::vector<float> &logits, int B, int vocab, int k, int iters, double &logprobsUs,
+                   double &argmaxUs) {
+    DL_CHECK(B >= 1 && vocab >= 1 && logits.size() == (size_t)B * vocab && k >= 0 && k <= hipk::kLogprobTop && iters >= 1,
+             "bench_logprobs arguments");
+    Scratch sc;
+    hipk::LogprobArgs g = logprobArgs(sc, B, vocab, std::vector<int>(B, 1 + k));
+    g.logits = sc.upload(logits);
+    hipk::ArgmaxArgs am;
+    am.logits = g.logits;
+    am.vocab = vocab;
+    am.ids = sc.alloc<int>(B);
+    am.partV = sc.alloc<float>((size_t)B * 64);
+    am.partI = sc.alloc<int>((size_t)B * 64);
+    am.counters = sc.alloc<int>(B);
+    g.ids = am.ids;
+    hipEvent_t e0, e1;
+    DL_HIP(hipEventCreate(&e0));
+    DL_HIP(hipEventCreate(&e1));
+    auto timed = [&](auto launch) {
+        for (int i = 0; i < 5; i++) launch();
+        DL_HIP(hipEventRecord(e0, sc.s));
+        for (int i = 0; i < iters; i++) launch();
+        DL_HIP(hipEventRecord(e1, sc.s));
+        DL_HIP(hipEventSynchronize(e1));
+        float ms = 0;
+        DL_HIP(hipEventElapsedTime(&ms, e0, e1));
+        return (double)ms * 1000.0 / iters;
+    };
+    argmaxUs = timed([&] { hipk::launchArgmax(am, B, sc.s); });
+    logprobsUs = timed([&] { hipk::launchLogprobs(g, B, sc.s); });
+    sc.sync();
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+}
+
 std::vector<float> embedding(const std::vector<float> &table, int vocab, int dim, const std::vector<int> &tokens) {
     const int B = (int)tokens.size();
     DL_CHECK(dim % 4 == 0 && table.size() == (size_t)vocab * dim, "embedding sizes");

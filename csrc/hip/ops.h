@@ -54,6 +54,18 @@ std::vector<int> argmax(const std::vector<float> &logits, int B, int vocab);
 // device sampler (launchSample): spec rows (temperature, topp, coin, -)
 std::vector<int> sample(const std::vector<float> &logits, int B, int vocab, const std::vector<float> &specs);
 
+// launchLogprobs over [B][vocab] logits: ids[b] the row's chosen token, requests[b] = 0 (none) or
+// 1 + k (SampleSpec::logprobs). Returns [B][21] (logprob, id) pairs as two arrays; the output is
+// pre-filled with (0, -2), which rows without a request keep. `warm` (optional): logits and ids of
+// an earlier call with the same requests, run first on the same scratch and output buffer.
+void logprobs(const std::vector<float> &logits, int B, int vocab, const std::vector<int> &ids,
+              const std::vector<int> &requests, std::vector<float> &outLogprobs, std::vector<int> &outIds,
+              const std::vector<float> *warmLogits = nullptr, const std::vector<int> *warmIds = nullptr);
+// Device microseconds per launch of launchLogprobs (request 1 + k on every row) and of launchArgmax
+// on the same [B][vocab] logits: `iters` launches of each between two events, after a warm-up.
+void benchLogprobs(const std::vector<float> &logits, int B, int vocab, int k, int iters, double &logprobsUs,
+                   double &argmaxUs);
+
 // Embedding row gather: table [vocab][dim] -> [B][dim].
 std::vector<float> embedding(const std::vector<float> &table, int vocab, int dim, const std::vector<int> &tokens);
 

@@ -135,6 +135,36 @@ std::vector<int> runSample(Backend &b, const std::vector<int> &tokens, const std
     return out;
 }
 
+// forward_sample plus per-row log-probabilities: top[i] = -1 (no request) or k in 0..20. Returns
+// (ids, float32 [n][21] logprobs, int32 [n][21] token ids); see Backend::lastLogprobs.
+py::tuple runLogprobs(Backend &b, const std::vector<int> &tokens, const std::vector<int> &positions,
+                      const std::vector<int> &slots, const std::vector<float> &temps, const std::vector<float> &topps,
+                      const std::vector<float> &coins, const std::vector<int> &top) {
+    const size_t n = tokens.size();
+    DL_CHECK(positions.size() == n && slots.size() == n && temps.size() == n && topps.size() == n &&
+                 coins.size() == n && top.size() == n, "one (temperature, topp, coin, top_logprobs) per row");
+    std::vector<SampleSpec> specs(n);
+    for (size_t i = 0; i < n; i++) {
+        DL_CHECK(top[i] >= -1 && top[i] <= kMaxTopLogprobs, "top_logprobs: -1 (none) or 0..20");
+        specs[i] = SampleSpec{temps[i], topps[i], coins[i], top[i] < 0 ? 0.f : 1.f + (float)top[i]};
+    }
+    std::vector<int> out(n);
+    std::vector<TokenLogprob> lp;
+    {
+        py::gil_scoped_release rel;
+        b.forwardSample((int)n, tokens.data(), positions.data(), slots.data(), specs.data(), out.data());
+        lp = b.lastLogprobs();
+    }
+    lp.resize(n * kLogprobEntries, TokenLogprob{0.f, -1});  // (no row asked: empty)
+    py::array_t<float> v({(py::ssize_t)n, (py::ssize_t)kLogprobEntries});
+    py::array_t<int> ids({(py::ssize_t)n, (py::ssize_t)kLogprobEntries});
+    for (size_t i = 0; i < lp.size(); i++) {
+        v.mutable_data()[i] = lp[i].logprob;
+        ids.mutable_data()[i] = lp[i].id;
+    }
+    return py::make_tuple(out, v, ids);
+}
+
 // Device communicator owned from Python (xGMI one-shot collectives); shared with engines.
 struct PyComm {
     std::shared_ptr<DeviceComm> comm;
@@ -264,6 +294,36 @@ void bindOps(py::module_ &m) {
               }
               return ids;
           });
+    o.def("logprobs",
+          [](py::object logits, std::vector<int> ids, std::vector<int> requests, py::object warmLogits,
+             py::object warmIds) {
+              const std::vector<float> l = vec<float>(logits), wl = vec<float>(warmLogits);
+              const std::vector<int> wi = vec<int>(warmIds);
+              const int B = (int)ids.size();
+              DL_CHECK(B >= 1 && l.size() % B == 0, "logprobs: one id per row");
+              std::vector<float> v;
+              std::vector<int> idx;
+              {
+                  py::gil_scoped_release rel;
+                  ops::logprobs(l, B, (int)(l.size() / B), ids, requests, v, idx, wl.empty() ? nullptr : &wl,
+                                wl.empty() ? nullptr : &wi);
+              }
+              return py::make_tuple(arr(v, {B, (py::ssize_t)kLogprobEntries}), arr(idx, {B, (py::ssize_t)kLogprobEntries}));
+          },
+          py::arg("logits"), py::arg("ids"), py::arg("requests"), py::arg("warm_logits") = py::none(),
+          py::arg("warm_ids") = py::none());
+    o.def("bench_logprobs",
+          [](py::object logits, int B, int k, int iters) {
+              const std::vector<float> l = vec<float>(logits);
+              double lp = 0, am = 0;
+              {
+                  py::gil_scoped_release rel;
+                  ops::benchLogprobs(l, B, (int)(l.size() / B), k, iters, lp, am);
+              }
+              return py::make_tuple(lp, am);
+          },
+          py::arg("logits"), py::arg("batch"), py::arg("k"), py::arg("iters") = 200,
+          "(us per launchLogprobs, us per launchArgmax) on the same logits");
     o.def("argmax",
           [](py::object logits, int B) {
               const std::vector<float> l = vec<float>(logits);
@@ -330,6 +390,17 @@ PYBIND11_MODULE(_C, m) {
         std::vector<float> l(logits.data(), logits.data() + logits.size());
         return sampleHost(l.data(), (int)l.size(), SampleSpec{temp, topp, coin, 0.f});
     });
+    co.def("logprobs_host", [](py::array_t<float, py::array::c_style | py::array::forcecast> logits, int chosen, int k) {
+        std::vector<TokenLogprob> e(kLogprobEntries);
+        logprobsHost(logits.data(), (int)logits.size(), chosen, k, e.data());
+        py::array_t<float> v((py::ssize_t)kLogprobEntries);
+        py::array_t<int> ids((py::ssize_t)kLogprobEntries);
+        for (int i = 0; i < kLogprobEntries; i++) {
+            v.mutable_data()[i] = e[i].logprob;
+            ids.mutable_data()[i] = e[i].id;
+        }
+        return py::make_tuple(v, ids);
+    }, py::arg("logits"), py::arg("chosen"), py::arg("k"));
     co.def("inv_rms", [](py::array_t<float, py::array::c_style | py::array::forcecast> x, float eps) {
         return cpu::invRms(x.data(), (u32)x.size(), eps);
     });
@@ -494,6 +565,8 @@ PYBIND11_MODULE(_C, m) {
              py::arg("tokens"), py::arg("positions"), py::arg("slots"))
         .def("forward_sample", &runSample, py::arg("tokens"), py::arg("positions"), py::arg("slots"),
              py::arg("temperatures"), py::arg("topps"), py::arg("coins"))
+        .def("forward_logprobs", &runLogprobs, py::arg("tokens"), py::arg("positions"), py::arg("slots"),
+             py::arg("temperatures"), py::arg("topps"), py::arg("coins"), py::arg("top_logprobs"))
         .def("forward_argmax", [](Backend &b, std::vector<int> t, std::vector<int> p, std::vector<int> s) { return runArgmax(b, t, p, s); },
              py::arg("tokens"), py::arg("positions"), py::arg("slots"))
         .def("last_stats", [](const Backend &b) {
@@ -889,6 +962,13 @@ PYBIND11_MODULE(_C, m) {
                 std::vector<float> topps, std::vector<float> coins) { return runSample(*e.engine, t, p, s, temps, topps, coins); },
              py::arg("tokens"), py::arg("positions"), py::arg("slots"), py::arg("temperatures"), py::arg("topps"),
              py::arg("coins"))
+        .def("forward_logprobs",
+             [](PyHipEngine &e, std::vector<int> t, std::vector<int> p, std::vector<int> s, std::vector<float> temps,
+                std::vector<float> topps, std::vector<float> coins, std::vector<int> top) {
+                 return runLogprobs(*e.engine, t, p, s, temps, topps, coins, top);
+             },
+             py::arg("tokens"), py::arg("positions"), py::arg("slots"), py::arg("temperatures"), py::arg("topps"),
+             py::arg("coins"), py::arg("top_logprobs"))
         .def("forward_argmax", [](PyHipEngine &e, std::vector<int> t, std::vector<int> p, std::vector<int> s) { return runArgmax(*e.engine, t, p, s); },
              py::arg("tokens"), py::arg("positions"), py::arg("slots"))
         .def("last_stats",

@@ -96,6 +96,9 @@ class InferenceSession {
     // Pipelined serving (Backend::launchIds / collectIds; workers run the forward in lockstep).
     void launchIds(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs);
     void collectIds(int n, int *out);
+    // log-probabilities of the forward just collected (Backend::lastLogprobs; the root draws, so
+    // workers take no part)
+    const std::vector<TokenLogprob> &lastLogprobs() const { return backend_->lastLogprobs(); }
     // Chained greedy decode of one sequence (Backend::chainLaunch; workers follow each step).
     bool chainSupported() const { return backend_->chainSupported(); }
     void chainLaunch(int token, int pos, int slot);

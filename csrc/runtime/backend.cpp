@@ -3,7 +3,8 @@
 #include "backend.h"
 
 #include <algorithm>
-
+#include <cmath>
+#include <numeric>
 #include <vector>
 
 #include "../text/tokenizer.h"
@@ -16,25 +17,58 @@ int sampleHost(float *logits, int vocab, const SampleSpec &s) {
     return smp.sampleWithCoin(logits, s.coin);
 }
 
+void logprobsHost(const float *logits, int vocab, int chosen, int k, TokenLogprob *out) {
+    // log sum exp in double: the result rounds to f32 once, at the subtraction below
+    double mx = -INFINITY, sum = 0.0;
+    for (int i = 0; i < vocab; i++) mx = std::max(mx, (double)logits[i]);
+    for (int i = 0; i < vocab; i++) sum += std::exp((double)logits[i] - mx);
+    const double lse = mx + std::log(sum);
+    for (int i = 0; i < kLogprobEntries; i++) out[i] = TokenLogprob{0.f, -1};
+    if (chosen >= 0 && chosen < vocab) out[0] = TokenLogprob{(float)((double)logits[chosen] - lse), chosen};
+    k = std::min({k, kMaxTopLogprobs, vocab});
+    if (k <= 0) return;
+    std::vector<int> order(vocab);
+    std::iota(order.begin(), order.end(), 0);
+    std::partial_sort(order.begin(), order.begin() + k, order.end(), [&](int a, int b) {
+        return logits[a] > logits[b] || (logits[a] == logits[b] && a < b);
+    });
+    for (int i = 0; i < k; i++) out[1 + i] = TokenLogprob{(float)((double)logits[order[i]] - lse), order[i]};
+}
+
 void Backend::forwardSample(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs,
                             int *out) {
     const int vocab = (int)header().vocabSize;
     if (plan().rank != 0) {  // workers take part in the forward; the root draws
         forward(n, tokens, positions, slots, nullptr);
         for (int i = 0; i < n; i++) out[i] = -1;
+        logprobs_.clear();
         return;
     }
     std::vector<float> logits((size_t)n * vocab);
     forward(n, tokens, positions, slots, logits.data());
-    for (int i = 0; i < n; i++) out[i] = sampleHost(&logits[(size_t)i * vocab], vocab, specs[i]);
+    bool anyLogprobs = false;
+    for (int i = 0; i < n; i++) anyLogprobs = anyLogprobs || specs[i].logprobs >= 1.f;
+    logprobs_.assign(anyLogprobs ? (size_t)n * kLogprobEntries : 0, TokenLogprob{0.f, -1});
+    std::vector<float> raw;
+    for (int i = 0; i < n; i++) {
+        float *row = &logits[(size_t)i * vocab];
+        const int req = (int)specs[i].logprobs;
+        if (req >= 1) raw.assign(row, row + vocab);  // the draw rewrites the row in place
+        out[i] = sampleHost(row, vocab, specs[i]);
+        if (req >= 1)
+            logprobsHost(raw.data(), vocab, out[i], std::min(req - 1, kMaxTopLogprobs),
+                         &logprobs_[(size_t)i * kLogprobEntries]);
+    }
 }
 
 void Backend::launchIds(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs) {
     pendingIds_.assign(n, -1);
     if (specs)
         forwardSample(n, tokens, positions, slots, specs, pendingIds_.data());
-    else
+    else {
+        logprobs_.clear();
         forwardArgmax(n, tokens, positions, slots, pendingIds_.data());
+    }
 }
 
 void Backend::collectIds(int *out) {

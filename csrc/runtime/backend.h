@@ -54,12 +54,27 @@ struct ForwardStats {
 // Per-row sampling request (reference Sampler::sample, tokenizer.cpp:416-502): temperature 0 =
 // greedy, < 0 = row not sampled (prefill rows), otherwise softmax(logits / temperature) then a
 // multinomial draw (topp <= 0 or >= 1) or nucleus (top-p) draw with the given coin in [0, 1).
+// logprobs is the row's log-probability request: 0 = none, 1 + k = the drawn token plus the k best
+// tokens of the row (0 <= k <= kMaxTopLogprobs); the draw itself ignores it.
 struct SampleSpec {
     float temperature = 0.f;
     float topp = 0.f;
     float coin = 0.f;
-    float pad = 0.f;
+    float logprobs = 0.f;
 };
+static_assert(sizeof(SampleSpec) == 16, "SampleSpec is part of the worker protocol");
+
+// Per-token log-probabilities: log_softmax of the row's raw logits (independent of temperature and
+// top-p). A row's result is 1 + kMaxTopLogprobs entries: [0] the drawn token (id -1 when the row drew
+// none), [1 .. k] the k best tokens ordered by (logit descending, id ascending), the rest id -1.
+constexpr int kMaxTopLogprobs = 20;
+constexpr int kLogprobEntries = 1 + kMaxTopLogprobs;
+struct TokenLogprob {
+    float logprob;
+    int id;
+};
+// Host implementation (the CPU path and the reference for the device kernel): out[kLogprobEntries].
+void logprobsHost(const float *logits, int vocab, int chosen, int k, TokenLogprob *out);
 
 // Host implementation of one row's draw (the CPU path and the reference for the device sampler).
 int sampleHost(float *logits, int vocab, const SampleSpec &s);
@@ -83,6 +98,10 @@ class Backend {
     // runs the forward synchronously inside launchIds (host backends: no overlap).
     virtual void launchIds(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs);
     virtual void collectIds(int *out);
+    // Log-probabilities of the last forwardSample / collectIds: [n][kLogprobEntries] when a row of
+    // that forward asked for them (SampleSpec::logprobs; rows that did not hold id -1 throughout),
+    // empty otherwise and on ranks other than the root. Valid until the next forward is launched.
+    virtual const std::vector<TokenLogprob> &lastLogprobs() const { return logprobs_; }
     // Chained greedy decode of one sequence (GPU engines; dllama inference): each step's input
     // token is the previous step's argmax, fed back on the device, so step k + 1 is enqueued
     // before the host has read step k (the host decodes and prints while the device runs).
@@ -117,6 +136,7 @@ class Backend {
   protected:
     ForwardStats stats_;
     std::vector<int> pendingIds_;  // default launchIds / collectIds
+    std::vector<TokenLogprob> logprobs_;
 };
 
 // Host data plane used by the CPU backend for tensor parallelism.

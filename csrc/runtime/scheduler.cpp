@@ -374,11 +374,13 @@ bool Scheduler::step() {
     //    for these tokens runs after the next forward has been launched (step 4)
     std::vector<Pick> done;
     std::vector<int> ids;
+    std::vector<TokenLogprob> doneLogprobs;
     int doneRows = 0, doneDecode = 0;
     double doneMs = 0;
     if (inflight_) {
         ids.resize(flight_.n);
         sess_.collectIds(flight_.n, ids.data());
+        doneLogprobs = sess_.lastLogprobs();  // (empty unless a row asked; the next launch overwrites them)
         doneMs = flight_.t.elapsedMs();
         doneRows = flight_.n;
         doneDecode = flight_.nDecode;
@@ -490,9 +492,11 @@ bool Scheduler::step() {
     if (next.n > 0) {
         if (prefixOn_)  // positions each slot's cache (and, paged, its mapped pages) reaches
             for (int i = 0; i < next.n; i++) slotReach_[slots[i]] = std::max<size_t>(slotReach_[slots[i]], (size_t)positions[i] + 1);
+        // (a greedy request that wants log-probabilities takes the sampler at temperature 0 - the
+        //  same lowest-index argmax - because the argmax paths keep no logits to score)
         bool allGreedy = true;
         for (auto &p : next.picks)
-            if (p.sample && p.r->params.temperature != 0.0f) allGreedy = false;
+            if (p.sample && (p.r->params.temperature != 0.0f || p.r->params.logprobs)) allGreedy = false;
         next.t.reset();
         if (allGreedy) {
             sess_.launchIds(next.n, tokens.data(), positions.data(), slots.data(), nullptr);
@@ -505,6 +509,8 @@ bool Scheduler::step() {
                 sp.temperature = p.r->params.temperature;
                 sp.topp = p.r->params.topp;
                 sp.coin = p.r->sampler->drawCoin();
+                if (p.r->params.logprobs)
+                    sp.logprobs = 1.f + (float)std::min(std::max(p.r->params.topLogprobs, 0), kMaxTopLogprobs);
             }
             sess_.launchIds(next.n, tokens.data(), positions.data(), slots.data(), specs.data());
         }
@@ -529,6 +535,14 @@ bool Scheduler::step() {
         if (!p.sample || r->finished) continue;
         const int token = ids[p.row];
         r->completionTokens = (int)r->generated.size();
+        if (r->params.logprobs && doneLogprobs.size() >= (size_t)(p.row + 1) * kLogprobEntries) {
+            const TokenLogprob *e = &doneLogprobs[(size_t)p.row * kLogprobEntries];
+            TokenRecord rec;
+            rec.chosen = e[0];
+            for (int i = 1; i < kLogprobEntries && i <= r->params.topLogprobs && e[i].id >= 0; i++) rec.top.push_back(e[i]);
+            std::lock_guard<std::mutex> rl(r->mu);
+            r->logprobs.push_back(std::move(rec));
+        }
         std::string piece, delta;
         const bool has = r->decoder->decode(token, piece);
         const EosResult er = r->eos->append(token, has ? piece.c_str() : nullptr);

@@ -27,6 +27,16 @@ struct GenParams {
     float topp = 0.9f;
     u64 seed = 0;
     std::vector<std::string> stop;  // extra stop strings
+    // per-token log-probabilities (log_softmax of the raw logits, whatever temperature / top-p):
+    // the generated token's, plus the topLogprobs (0..kMaxTopLogprobs) best tokens of its row
+    bool logprobs = false;
+    int topLogprobs = 0;
+};
+
+// One generated token's log-probability record (GenParams::logprobs).
+struct TokenRecord {
+    TokenLogprob chosen;
+    std::vector<TokenLogprob> top;  // (logit descending, id ascending)
 };
 
 class GenRequest {
@@ -44,6 +54,7 @@ class GenRequest {
     std::string error;
     bool done = false;
     int completionTokens = 0;
+    std::vector<TokenRecord> logprobs;  // one per generated token (params.logprobs), the last one included
     int cachedTokens = 0;  // prompt tokens whose KV was reused instead of prefilled (--prefix-cache)
 
     // The client went away (e.g. a streaming connection dropped): the scheduler finishes the

@@ -6,7 +6,7 @@ connection per request), and reports the aggregate completion tokens/s for tempe
 and temperature 0.8 / top_p 0.9 with per-request seeds (device sampling: only token ids come back
 to the host). One untimed round first captures the graphs.
 
-  python scripts/bench_api.py [--n 64] [--max-tokens 64] [--port 0]
+  python scripts/bench_api.py [--n 64] [--max-tokens 64] [--port 0] [--logprobs K]
 """
 import argparse
 import http.client
@@ -42,12 +42,15 @@ def _post(port, body, out, i):
         out[i] = e
 
 
+EXTRA = {}  # request fields added to every body (--logprobs)
+
+
 def _round(port, n, max_tokens, temperature, seed0):
     out = [None] * n
     th = []
     for i in range(n):
         body = {"messages": [{"role": "user", "content": f"hello world {i} the"}], "max_tokens": max_tokens,
-                "temperature": temperature, "top_p": 0.9, "seed": seed0 + i}
+                "temperature": temperature, "top_p": 0.9, "seed": seed0 + i, **EXTRA}
         th.append(threading.Thread(target=_post, args=(port, body, out, i)))
     t0 = time.perf_counter()
     for t in th:
@@ -72,7 +75,11 @@ def main():
                     help="paged KV cache: pool pages per layer (0: contiguous slots x seq_len)")
     ap.add_argument("--kv-page-size", type=int, default=64)
     ap.add_argument("--kv-dtype", default="f32", choices=["f32", "bf16"], help="KV cache (f32: the reference's, the default)")
+    ap.add_argument("--logprobs", type=int, default=-1,
+                    help="K >= 0: every request asks for logprobs with top_logprobs K (default: none)")
     args = ap.parse_args()
+    if args.logprobs >= 0:
+        EXTRA.update(logprobs=True, top_logprobs=args.logprobs)
     from distributed_llama_multiusers_amd.models.synthetic import make_tokenizer
     tmp = tempfile.mkdtemp()
     tok = os.path.join(tmp, "tok.t")
@@ -121,6 +128,7 @@ def main():
         res["kv_cache"] = args.kv_dtype
         res["max_batch"] = args.max_batch or 4 * args.n
         res["max_tokens"] = args.max_tokens
+        res["top_logprobs"] = args.logprobs if args.logprobs >= 0 else None
         print(json.dumps(res), flush=True)
     finally:
         srv.terminate()
