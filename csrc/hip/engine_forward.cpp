@@ -105,70 +105,95 @@ int HipEngineImpl::batchChunk(const DevMat &m, int pro, int epi) const {
     return bc;
 }
 
+// The exchange fields of a launch: a fused-exchange region (tpVec_ / tpArg_) and this exchange's measured-sync words.
+void HipEngineImpl::fillXchg(hipk::TpXchg &tp, const hipk::TpXchg &region) const {
+    tp = region;
+    tp.ticks = syncTicks();
+    tp.span = syncSpan();
+}
+
+// The EPI_QKV fields (RoPE, KV append into layer L's cache) of a GEMV / GEMM launch over the rows
+// from c0 on. kvMul is read by the fused attention block's qkv role only.
+void HipEngineImpl::fillLayerKv(hipk::GemvArgs &a, const DevLayer &L, int c0) const {
+    a.q0 = plan_.q0;
+    a.kv0 = plan_.kv0;
+    a.hs = plan_.headSize;
+    a.kvMul = plan_.kvMul;
+    a.seqLen = h_.seqLen;
+    a.rope = dRope_;
+    a.pos = dPos_ + c0;
+    a.slot = dSlot_ + c0;
+    a.kcache = L.k;
+    a.kvMap = kvMap();
+    a.vcache = L.v;
+    a.kvBf16 = kvBf16_ ? 1 : 0;
+}
+
 // Arguments of one GEMV launch over rows [c0, c0 + bc) of the batch (see gemv()).
-hipk::GemvArgs HipEngineImpl::gemvArgs(const DevMat &m, int c0, int bc, int epi, const float *in, int ldIn, const float *add,
-                        float *xNext, const float *normW, float *out, int ldOut, const DevLayer *L,
-                        const int8_t *aq, const float2 *as, int8_t *oq, float2 *os, bool tp) const {
+hipk::GemvArgs HipEngineImpl::gemvArgs(const DevMat &m, int c0, int bc, int epi, const MatOperands &o) const {
+    DL_CHECK(!o.xh && !o.ssIn && !o.outH && !o.rf.resIn, "GEMM operand on a GEMV launch");
     hipk::GemvArgs a;
     a.qs = m.qs;
     a.wd = m.d;
     a.wf = m.f;
     a.rows = m.rows;
     a.n = m.n;
-    a.passes = tp ? tpPasses(m, bc) : passesFor(m, epi, bc);
+    a.passes = o.tp ? tpPasses(m, bc) : passesFor(m, epi, bc);
     a.lanes = m.lanes;
-    if (tp) {
-        a.tp = tpVec_;
-        a.tp.ticks = syncTicks();
-        a.tp.span = syncSpan();
-    }
-    a.in = in ? in + (size_t)c0 * ldIn : nullptr;
-    a.aq = aq ? aq + (size_t)c0 * m.n : nullptr;
-    a.as = as ? as + (size_t)c0 * (m.n / 32) : nullptr;
-    a.oq = oq ? oq + (size_t)c0 * ldOut : nullptr;
-    a.os = os ? os + (size_t)c0 * (ldOut / 32) : nullptr;
-    a.ldIn = ldIn;
-    a.addIn = add ? add + (size_t)c0 * ldIn : nullptr;
-    a.xNext = xNext ? xNext + (size_t)c0 * ldIn : nullptr;
-    a.normW = normW;
+    if (o.tp) fillXchg(a.tp, tpVec_);
+    a.in = o.in ? o.in + (size_t)c0 * o.ldIn : nullptr;
+    a.aq = o.aq ? o.aq + (size_t)c0 * m.n : nullptr;
+    a.as = o.as ? o.as + (size_t)c0 * (m.n / 32) : nullptr;
+    a.oq = o.oq ? o.oq + (size_t)c0 * o.ldOut : nullptr;
+    a.os = o.os ? o.os + (size_t)c0 * (o.ldOut / 32) : nullptr;
+    a.ldIn = o.ldIn;
+    a.addIn = o.add ? o.add + (size_t)c0 * o.ldIn : nullptr;
+    a.xNext = o.xNext ? o.xNext + (size_t)c0 * o.ldIn : nullptr;
+    a.normW = o.normW;
     a.eps = h_.normEpsilon;
-    a.out = out ? out + (size_t)c0 * ldOut : nullptr;
-    a.ldOut = ldOut;
+    a.out = o.out ? o.out + (size_t)c0 * o.ldOut : nullptr;
+    a.ldOut = o.ldOut;
     a.act = h_.hiddenAct == HiddenAct::GELU ? 0 : 1;
-    if (L) {
-        a.q0 = plan_.q0;
-        a.kv0 = plan_.kv0;
-        a.hs = plan_.headSize;
-        a.kvMul = plan_.kvMul;
-        a.seqLen = h_.seqLen;
-        a.rope = dRope_;
-        a.pos = dPos_ + c0;
-        a.slot = dSlot_ + c0;
-        a.kcache = L->k;
-        a.kvMap = kvMap();
-        a.vcache = L->v;
-        a.kvBf16 = kvBf16_ ? 1 : 0;
-    }
+    if (o.layer) fillLayerKv(a, *o.layer, c0);
     return a;
 }
 
-// Launch a GEMV over all n rows, in batch chunks of <= 4. tp: all-reduce the EPI_STORE output
+// Launch a GEMV over all n rows, in batch chunks of <= 4. o.tp: all-reduce the EPI_STORE output
 // over the tensor-parallel ranks in the kernel tail (fused exchange).
-void HipEngineImpl::gemv(const DevMat &m, int n, int pro, int epi, const float *in, int ldIn, const float *add, float *xNext,
-          const float *normW, float *out, int ldOut, const DevLayer *L, const int8_t *aq,
-                         const float2 *as, int8_t *oq, float2 *os, bool tp) {
-    if (tp) epi = hipk::EPI_STORE_TP;
+void HipEngineImpl::gemv(const DevMat &m, int n, int pro, int epi, const MatOperands &o) {
+    if (o.tp) epi = hipk::EPI_STORE_TP;
     const int bcMax = batchChunk(m, pro, epi);
     xChunk_ = 0;  // each launch's exchange waits in a measured-sync slot of its own
     for (int c0 = 0; c0 < n; xChunk_++) {
         int bc = n - c0;
         if (bc > bcMax) bc = bcMax;
         while (bc & (bc - 1)) bc &= bc - 1;  // 1, 2 or 4 rows per launch
-        const hipk::GemvArgs a = gemvArgs(m, c0, bc, epi, in, ldIn, add, xNext, normW, out, ldOut, L, aq, as, oq, os, tp);
-        hipk::launchGemv(a, bc, pro, epi, q40_, stream_);
+        hipk::launchGemv(gemvArgs(m, c0, bc, epi, o), bc, pro, epi, q40_, stream_);
         c0 += bc;
     }
     xChunk_ = 0;
+}
+
+// The qkv launch reading the residual dX_[cur] through the norm prologue (layers > 0: plus the
+// previous layer's delta dY_, the sum kept in the other residual buffer).
+HipEngineImpl::MatOperands HipEngineImpl::qkvOperands(const DevLayer &L, int cur, bool hasDelta) const {
+    return {.in = dX_[cur], .ldIn = dim(), .add = hasDelta ? dY_ : nullptr, .xNext = hasDelta ? dX_[cur ^ 1] : nullptr,
+            .normW = L.rmsAtt, .out = dQ_, .ldOut = q0(), .layer = &L};
+}
+
+hipk::GemvArgs HipEngineImpl::woRowArgs(const DevLayer &L, int epi) const {
+    return gemvArgs(L.wo, 0, 1, epi,
+                    {.ldIn = q0(), .aq = dAttQ_, .as = dAttS_, .out = dY_, .ldOut = dim(), .tp = epi != hipk::EPI_STORE});
+}
+
+hipk::GemvArgs HipEngineImpl::w2ProducerArgs(const DevLayer &L) const {
+    return gemvArgs(L.w2, 0, 1, hipk::EPI_RESQ_TP,
+                    {.in = hQ80_ ? nullptr : dH_, .ldIn = hidden0(), .aq = hQ80_ ? dHQ_ : nullptr,
+                     .as = hQ80_ ? dHS_ : nullptr, .out = dY_, .ldOut = dim(), .tp = true});
+}
+
+hipk::GemvArgs HipEngineImpl::w13ConsumerArgs(const DevLayer &L) const {
+    return gemvArgs(L.w13, 0, 1, w13Epi(), {.ldIn = dim(), .out = dH_, .ldOut = hidden0(), .oq = dHQ_, .os = dHS_});
 }
 
 // Decode attention of this layer (rows 0..n of the forward).
@@ -211,16 +236,10 @@ hipk::AttnArgs HipEngineImpl::attnArgs(const DevLayer &L, bool bat) const {
 // The fused attention block of a single decode row (kernels.h AttnBlockArgs): qkv GEMV +
 // attention + wo GEMV in one launch. Layer l, residual input dX_[cur].
 hipk::AttnBlockArgs HipEngineImpl::attnBlockArgs(const DevLayer &L, u32 l, int cur) const {
-    const ShardPlan &p = plan_;
-    const bool hasDelta = l > 0;
     hipk::AttnBlockArgs b;
-    b.qkv = gemvArgs(L.qkv, 0, 1, hipk::EPI_QKV, dX_[cur], h_.dim, hasDelta ? dY_ : nullptr,
-                     hasDelta ? dX_[cur ^ 1] : nullptr, L.rmsAtt, dQ_, p.q0, &L, nullptr, nullptr, nullptr, nullptr,
-                     false);
+    b.qkv = gemvArgs(L.qkv, 0, 1, hipk::EPI_QKV, qkvOperands(L, cur, l > 0));
     b.at = attnArgs(L, false);
-    const bool tp = fusedTp(false);
-    b.wo = gemvArgs(L.wo, 0, 1, tp ? hipk::EPI_STORE_TP : hipk::EPI_STORE, nullptr, p.q0, nullptr, nullptr, nullptr,
-                    dY_, h_.dim, nullptr, dAttQ_, dAttS_, nullptr, nullptr, tp);
+    b.wo = woRowArgs(L, woEpi());
     b.qkv.passes *= blockPassMul_;  // same-GPU rehearsals: longer workgroups (setupAttnBlock)
     b.wo.passes *= blockPassMul_;
     b.hg = hipk::attnBlockHG(b.at);
@@ -246,7 +265,6 @@ void HipEngineImpl::setupAttnBlock() {
     // the whole wo role waits on - measured 2x the three launches (8B TP8 rank: 38 vs ~18 us per
     // layer, profiles/r5_tp_rank.md); DL_ATTN_BLOCK=1 forces it
     if (plan_.nKvHeads0 < 2 && !(e && *e == '1')) return;
-    const int share = comm_ ? std::max(1, comm_->ranksOnDevice()) : 1;
     const int keep = bucket_;
     // qkv / wo passes per workgroup: the GEMVs' own grids. A grid beyond one round of co-resident
     // workgroups keeps the three launches: longer qkv / wo workgroups measured slower on a GPU of
@@ -256,11 +274,9 @@ void HipEngineImpl::setupAttnBlock() {
     // block's exchange on one GPU) doubles the passes until the shared slots hold it.
     const bool forced = e && *e == '1';
     bucket_ = 0;
-    for (blockPassMul_ = 1; forced && share > 1 && blockPassMul_ < 8; blockPassMul_ *= 2) {
+    for (blockPassMul_ = 1; forced && ranksSharingDevice() > 1 && blockPassMul_ < 8; blockPassMul_ *= 2) {
         const hipk::AttnBlockArgs b = attnBlockArgs(layers_[0], 0, 0);
-        if (!hipk::attnBlockPlan(b, fusedTp(false)).fn) break;
-        const hipk::GemvResidency r = hipk::attnBlockResidency(b, fusedTp(false));
-        if (r.maxResident > 0 && r.grid <= r.maxResident / share) break;
+        if (!hipk::attnBlockPlan(b, fusedTp(false)).fn || fitsResident(hipk::attnBlockResidency(b, fusedTp(false)))) break;
     }
     int lastOn = -1;
     hipk::GemvResidency off;
@@ -269,7 +285,7 @@ void HipEngineImpl::setupAttnBlock() {
         const hipk::AttnBlockArgs b = attnBlockArgs(layers_[0], 0, 0);
         if (!hipk::attnBlockPlan(b, fusedTp(false)).fn) break;
         const hipk::GemvResidency r = hipk::attnBlockResidency(b, fusedTp(false));
-        if (r.maxResident <= 0 || r.grid > r.maxResident / share) {
+        if (!fitsResident(r)) {
             off = r;
             break;
         }
@@ -285,7 +301,7 @@ void HipEngineImpl::setupAttnBlock() {
     bucket_ = keep;
     if (lastOn < 0 && off.grid > 0)
         std::fprintf(stderr, "ℹ️  fused attention block off: grid %d > %d co-resident workgroups per rank\n", off.grid,
-                     off.maxResident / share);
+                     residentLimit(off));
 }
 
 // Pre-normalized hand-off between the single-row GEMVs of a tensor-parallel rank (kernels.h
@@ -302,16 +318,12 @@ void HipEngineImpl::setupPrenorm() {
     prenormOn_ = false;
     const char *e = std::getenv("DL_PRENORM");
     if ((e && *e == '0') || !q40_ || !fusedTp(false) || h_.dim % 32 || h_.dim > 16384) return;
-    const int share = comm_ ? std::max(1, comm_->ranksOnDevice()) : 1;
+    const hipk::GemvArgs producers[2] = {woRowArgs(layers_[0], hipk::EPI_RESQ_TP), w2ProducerArgs(layers_[0])};
+    const int pros[2] = {hipk::PRO_GLOBAL, w2Pro()};
     for (int w = 0; w < 2; w++) {
-        const DevMat &m = w == 0 ? layers_[0].wo : layers_[0].w2;
-        const int pro = w == 1 && !hQ80_ ? hipk::PRO_RESNORM : hipk::PRO_GLOBAL;
-        const hipk::GemvArgs a = gemvArgs(m, 0, 1, hipk::EPI_RESQ_TP, nullptr, m.n, nullptr, nullptr, nullptr, dY_,
-                                          h_.dim, nullptr, nullptr, nullptr, nullptr, nullptr, true);
-        const int R = (256 / a.lanes) * 2 * a.passes, grid = (a.rows + R - 1) / R;
-        if (R % 32 || grid > kMaxSsp) return;
-        const hipk::GemvResidency r = hipk::gemvResidency(a, 1, pro, hipk::EPI_RESQ_TP, true);
-        if (r.maxResident <= 0 || r.grid > r.maxResident / share) return;
+        const hipk::GemvArgs &a = producers[w];
+        if (rowsPerWorkgroup(a) % 32 || gemvGrid(a) > kMaxSsp) return;
+        if (!fitsResident(hipk::gemvResidency(a, 1, pros[w], hipk::EPI_RESQ_TP, true))) return;
     }
     prenormOn_ = true;
 }
@@ -337,128 +349,102 @@ void HipEngineImpl::setupFfnBlock() {
     ffnOn_ = false;
     const char *e = std::getenv("DL_FFN_BLOCK");
     if (!prenormOn_ || !(e && *e == '1')) return;
-    const DevLayer &L = layers_[0];
-    const int epi = hQ80_ ? hipk::EPI_ACT_Q80 : hipk::EPI_ACT;
-    const hipk::GemvArgs a13 = gemvArgs(L.w13, 0, 1, epi, nullptr, h_.dim, nullptr, nullptr, nullptr, dH_,
-                                        plan_.hidden0, nullptr, nullptr, nullptr, dHQ_, dHS_, false);
-    const hipk::GemvArgs a2 = gemvArgs(L.w2, 0, 1, hipk::EPI_RESQ_TP, hQ80_ ? nullptr : dH_, plan_.hidden0, nullptr,
-                                       nullptr, nullptr, dY_, h_.dim, nullptr, hQ80_ ? dHQ_ : nullptr,
-                                       hQ80_ ? dHS_ : nullptr, nullptr, nullptr, true);
-    const hipk::FfnBlockArgs f = ffnBlockArgs(a13, a2, 0);
+    const hipk::FfnBlockArgs f = ffnBlockArgs(w13ConsumerArgs(layers_[0]), w2ProducerArgs(layers_[0]), 0);
     if (!hipk::ffnBlockPlan(f).fn) return;
-    const int share = comm_ ? std::max(1, comm_->ranksOnDevice()) : 1;
     const hipk::GemvResidency r = hipk::ffnBlockResidency(f);
-    if (r.maxResident <= 0 || r.grid > r.maxResident / share) {
+    if (!fitsResident(r)) {
         std::fprintf(stderr, "ℹ️  fused FFN block off: grid %d > %d co-resident workgroups per rank\n", r.grid,
-                     r.maxResident / share);
+                     residentLimit(r));
         return;
     }
     ffnOn_ = true;
 }
 
+// The logits GEMV `a` of one greedy decode row, ending in the row's argmax (EPI_ARGMAX; under TP the
+// winners trade over the fused exchange's region; CHAIN also feeds the token back, as ArgmaxArgs).
+void HipEngineImpl::launchArgmaxTail(hipk::GemvArgs a, int pro, GraphKind kind) {
+    a.am.ids = dIds_;
+    a.am.partV = dArgV_;
+    a.am.partI = dArgI_;
+    a.am.counter = dArgCnt_;
+    a.am.vocabStart = plan_.vocabStart();
+    if (kind == GraphKind::CHAIN) {
+        a.am.tokens = dTok_;
+        a.am.pos = dPos_;
+        a.am.hist = dHist_;
+    }
+    if (plan_.nRanks > 1) fillXchg(a.tp, tpArg_);
+    hipk::launchGemv(a, 1, pro, hipk::EPI_ARGMAX, true, stream_);
+}
+
 // The layers + logits of one decode row with the pre-normalized hand-offs (setupPrenorm). The
 // residual lives in dX_[cur]; its Q80 image for the next consumer in dXQ_ / dXS_ [cur] with sspN
 // partial sums in dSSP_[cur]; each producer writes the other parity and flips cur.
-void HipEngineImpl::enqueuePrenormLayers(GraphKind kind, bool argTail) {
-    const ShardPlan &p = plan_;
-    const int dim = h_.dim;
-    const bool hQ80 = hQ80_;
-    // layer 0's qkv normalizes the embedding's row itself (norm prologue): the one-workgroup
-    // embedding kernel measured 12.8 vs 4.9 us with the pre-normalized output (PrenormOut)
+void HipEngineImpl::enqueuePrenormLayers(const FwdPath &f, GraphKind kind) {
     int cur = 0, sspN[2] = {0, 0};
-    auto consumer = [&](hipk::GemvArgs &a) {
+    auto consumer = [&](hipk::GemvArgs a) {
         a.aq = dXQ_[cur];
         a.as = dXS_[cur];
         a.sspIn = dSSP_[cur];
         a.nSsp = sspN[cur];
+        return a;
     };
-    auto producer = [&](hipk::GemvArgs &a, const float *normW) {
+    auto producer = [&](hipk::GemvArgs a, const float *normW) {
         a.rq.resIn = dX_[cur];
         a.rq.resOut = dX_[cur ^ 1];
         a.rq.resW = normW;
         a.rq.xq = dXQ_[cur ^ 1];
         a.rq.xs = dXS_[cur ^ 1];
         a.rq.ssp = dSSP_[cur ^ 1];
-        const int R = (256 / a.lanes) * 2 * a.passes;
-        sspN[cur ^ 1] = (a.rows + R - 1) / R;
+        sspN[cur ^ 1] = gemvGrid(a);
+        return a;
     };
     for (u32 l = 0; l < h_.nLayers; l++) {
         DevLayer &L = layers_[l];
         xSlot_ = 2 * (int)l;
         xChunk_ = 0;
+        // layer 0's qkv normalizes the embedding's row itself (norm prologue): the one-workgroup
+        // embedding kernel measured 12.8 vs 4.9 us with the pre-normalized output (PrenormOut)
         if (l == 0) {
-            ProfScope ps(this, "gemv_qkv");
-            gemv(L.qkv, 1, hipk::PRO_RESNORM, hipk::EPI_QKV, dX_[0], dim, nullptr, nullptr, L.rmsAtt, dQ_, p.q0, &L);
+            enqueueQkv(f, L, 0, false);
         } else {
             ProfScope ps(this, "gemv_qkv");
-            hipk::GemvArgs a = gemvArgs(L.qkv, 0, 1, hipk::EPI_QKV, nullptr, dim, nullptr, nullptr, nullptr, dQ_, p.q0, &L,
-                                        nullptr, nullptr, nullptr, nullptr, false);
-            consumer(a);
+            const hipk::GemvArgs a =
+                consumer(gemvArgs(L.qkv, 0, 1, hipk::EPI_QKV, {.ldIn = dim(), .out = dQ_, .ldOut = q0(), .layer = &L}));
             hipk::launchGemv(a, 1, hipk::PRO_PRENORM, hipk::EPI_QKV, true, stream_);
         }
-        {
-            ProfScope ps(this, "attention");
-            hipk::launchAttention(attnArgs(L, false), 1, stream_);
-        }
+        enqueueAttention(f, L);
         {
             ProfScope ps(this, "gemv_wo");
-            hipk::GemvArgs a = gemvArgs(L.wo, 0, 1, hipk::EPI_RESQ_TP, nullptr, p.q0, nullptr, nullptr, nullptr, dY_, dim,
-                                        nullptr, dAttQ_, dAttS_, nullptr, nullptr, true);
-            producer(a, L.rmsFfn);
+            const hipk::GemvArgs a = producer(woRowArgs(L, hipk::EPI_RESQ_TP), L.rmsFfn);
             hipk::launchGemv(a, 1, hipk::PRO_GLOBAL, hipk::EPI_RESQ_TP, true, stream_);
             cur ^= 1;
         }
         xSlot_ = 2 * (int)l + 1;
-        {
-            const int epi = hQ80 ? hipk::EPI_ACT_Q80 : hipk::EPI_ACT;
-            hipk::GemvArgs a13 = gemvArgs(L.w13, 0, 1, epi, nullptr, dim, nullptr, nullptr, nullptr, dH_, p.hidden0,
-                                          nullptr, nullptr, nullptr, dHQ_, dHS_, false);
-            consumer(a13);
-            const float *wNext = l + 1 < h_.nLayers ? layers_[l + 1].rmsAtt : rmsFinal_;
-            hipk::GemvArgs a2 = gemvArgs(L.w2, 0, 1, hipk::EPI_RESQ_TP, hQ80 ? nullptr : dH_, p.hidden0, nullptr, nullptr,
-                                         nullptr, dY_, dim, nullptr, hQ80 ? dHQ_ : nullptr, hQ80 ? dHS_ : nullptr, nullptr,
-                                         nullptr, true);
-            producer(a2, wNext);
-            if (ffnOn_) {  // one launch: w13 role + w2 role (weights prefetched before the hand-off wait)
-                ProfScope ps(this, "ffn_block");
-                hipk::launchFfnBlock(ffnBlockArgs(a13, a2, l), stream_);
-            } else {
-                {
-                    ProfScope ps(this, "gemv_w13");
-                    hipk::launchGemv(a13, 1, hipk::PRO_PRENORM, epi, true, stream_);
-                }
-                ProfScope ps(this, "gemv_w2");
-                hipk::launchGemv(a2, 1, hQ80 ? hipk::PRO_GLOBAL : hipk::PRO_RESNORM, hipk::EPI_RESQ_TP, true, stream_);
+        const hipk::GemvArgs a13 = consumer(w13ConsumerArgs(L));
+        const hipk::GemvArgs a2 = producer(w2ProducerArgs(L), nextNormW(l));
+        if (ffnOn_) {  // one launch: w13 role + w2 role (weights prefetched before the hand-off wait)
+            ProfScope ps(this, "ffn_block");
+            hipk::launchFfnBlock(ffnBlockArgs(a13, a2, l), stream_);
+        } else {
+            {
+                ProfScope ps(this, "gemv_w13");
+                hipk::launchGemv(a13, 1, hipk::PRO_PRENORM, w13Epi(), true, stream_);
             }
-            cur ^= 1;
+            ProfScope ps(this, "gemv_w2");
+            hipk::launchGemv(a2, 1, w2Pro(), hipk::EPI_RESQ_TP, true, stream_);
         }
+        cur ^= 1;
     }
     xSlot_ = 2 * (int)h_.nLayers;  // logits gather / argmax winners
     ProfScope ps(this, "gemv_logits");
-    if (argTail) {
-        hipk::GemvArgs a = gemvArgs(wcls_, 0, 1, hipk::EPI_ARGMAX, nullptr, dim, nullptr, nullptr, nullptr, nullptr,
-                                    p.vocab0, nullptr, nullptr, nullptr, nullptr, nullptr, false);
-        consumer(a);
-        a.am.ids = dIds_;
-        a.am.partV = dArgV_;
-        a.am.partI = dArgI_;
-        a.am.counter = dArgCnt_;
-        a.am.vocabStart = p.vocabStart();
-        if (kind == GraphKind::CHAIN) {
-            a.am.tokens = dTok_;
-            a.am.pos = dPos_;
-            a.am.hist = dHist_;
-        }
-        a.tp = tpArg_;
-        a.tp.ticks = syncTicks();
-        a.tp.span = syncSpan();
-        hipk::launchGemv(a, 1, hipk::PRO_PRENORM, hipk::EPI_ARGMAX, true, stream_);
-    } else {
-        hipk::GemvArgs a = gemvArgs(wcls_, 0, 1, hipk::EPI_STORE, nullptr, dim, nullptr, nullptr, nullptr, dLogits_,
-                                    p.vocab0, nullptr, nullptr, nullptr, nullptr, nullptr, false);
-        consumer(a);
+    const int epi = f.argTail ? hipk::EPI_ARGMAX : hipk::EPI_STORE;
+    const hipk::GemvArgs a =
+        consumer(gemvArgs(wcls_, 0, 1, epi, {.ldIn = dim(), .out = f.argTail ? nullptr : dLogits_, .ldOut = vocab0()}));
+    if (f.argTail)
+        launchArgmaxTail(a, hipk::PRO_PRENORM, kind);
+    else
         hipk::launchGemv(a, 1, hipk::PRO_PRENORM, hipk::EPI_STORE, true, stream_);
-    }
 }
 
 // The wo GEMV with the layer's attention in its prologue (PRO_ATTN, gemv_dev.h): every wo workgroup
@@ -483,17 +469,11 @@ void HipEngineImpl::setupWoAttn() {
     const int maxHeads = hm && *hm ? std::atoi(hm) : 8;
     woAttnMaxLen_ = lm && *lm ? std::atoi(lm) : 256;
     if ((int)plan_.nHeads0 > maxHeads) return;
-    const bool tp = fusedTp(false);
-    const int epi = tp ? hipk::EPI_STORE_TP : hipk::EPI_STORE;
-    const hipk::GemvArgs a = gemvArgs(layers_[0].wo, 0, 1, epi, nullptr, plan_.q0, nullptr, nullptr, nullptr, dY_,
-                                      h_.dim, nullptr, dAttQ_, dAttS_, nullptr, nullptr, tp);
+    const int epi = woEpi();
+    const hipk::GemvArgs a = woRowArgs(layers_[0], epi);
     const hipk::AttnArgs at = attnArgs(layers_[0], false);
     if (!hipk::gemvAttnSupported(a, at, epi)) return;
-    if (tp) {
-        const int share = comm_ ? std::max(1, comm_->ranksOnDevice()) : 1;
-        const hipk::GemvResidency r = hipk::gemvAttnResidency(a, at, epi);
-        if (r.maxResident <= 0 || r.grid > r.maxResident / share) return;
-    }
+    if (epi == hipk::EPI_STORE_TP && !fitsResident(hipk::gemvAttnResidency(a, at, epi))) return;
     woAttnOn_ = true;
 }
 
@@ -524,9 +504,8 @@ bool HipEngineImpl::tpBatchedOk(int n) const {
            (size_t)n * h_.dim <= (size_t)tpVec_.stride && hipk::gemmTpxFits(n, plan_.nRanks, tpVec_.q80 != 0);
 }
 
-void HipEngineImpl::gemmBatched(const DevMat &m, int n, int epi, const float *in, int ldIn, const float *add, float *xNext,
-                 const float *normW, const _Float16 *xh, float *out, int ldOut, _Float16 *outH,
-                 const DevLayer *L, const ResFuse *rf, bool ssIn) {
+void HipEngineImpl::gemmBatched(const DevMat &m, int n, int epi, const MatOperands &o) {
+    DL_CHECK(!o.aq && !o.as && !o.oq && !o.os && !o.tp, "GEMV operand on a GEMM launch");
     // tokens per launch: the wide Q40 kernel takes the whole forward in one launch (one weight
     // pass per token tile, all tiles of a row tile on one XCD), the narrow one <= 128
     // (batch-invariant engines: narrow launches only, the split count of a 16-token launch for all)
@@ -543,53 +522,39 @@ void HipEngineImpl::gemmBatched(const DevMat &m, int n, int epi, const float *in
         a.n = m.n;
         a.lanes = m.lanes;
         a.eps = h_.normEpsilon;
-        if (ssIn) {  // input = the producer's x' * normW rows; RMS scale applied per token
+        if (o.ssIn) {  // input = the producer's x' * normW rows; RMS scale applied per token
             g.x = dXh_ + (size_t)c0 * m.n;
             g.ssIn = dSS_ + c0;
             g.ssTiles = (h_.dim + 63) / 64;
             g.ldSS = (int)cfg_.maxBatch;
-        } else if (!xh) {
+        } else if (!o.xh) {
             hipk::GemvArgs nq;
             nq.n = m.n;
-            nq.in = in + (size_t)c0 * ldIn;
-            nq.ldIn = ldIn;
-            nq.addIn = add ? add + (size_t)c0 * ldIn : nullptr;
-            nq.xNext = xNext ? xNext + (size_t)c0 * ldIn : nullptr;
-            nq.normW = normW;
+            nq.in = o.in + (size_t)c0 * o.ldIn;
+            nq.ldIn = o.ldIn;
+            nq.addIn = o.add ? o.add + (size_t)c0 * o.ldIn : nullptr;
+            nq.xNext = o.xNext ? o.xNext + (size_t)c0 * o.ldIn : nullptr;
+            nq.normW = o.normW;
             nq.eps = h_.normEpsilon;
             hipk::launchNormF16(nq, dXh_, bc, stream_);
             g.x = dXh_;
         } else {
-            g.x = xh + (size_t)c0 * m.n;
+            g.x = o.xh + (size_t)c0 * m.n;
         }
-        a.out = out ? out + (size_t)c0 * ldOut : nullptr;
-        g.outH = outH ? outH + (size_t)c0 * ldOut : nullptr;
-        a.ldOut = ldOut;
+        a.out = o.out ? o.out + (size_t)c0 * o.ldOut : nullptr;
+        g.outH = o.outH ? o.outH + (size_t)c0 * o.ldOut : nullptr;
+        a.ldOut = o.ldOut;
         a.act = h_.hiddenAct == HiddenAct::GELU ? 0 : 1;
-        if (L) {
-            a.q0 = plan_.q0;
-            a.kv0 = plan_.kv0;
-            a.hs = plan_.headSize;
-            a.seqLen = h_.seqLen;
-            a.rope = dRope_;
-            a.pos = dPos_ + c0;
-            a.slot = dSlot_ + c0;
-            a.kcache = L->k;
-            a.kvMap = kvMap();
-            a.vcache = L->v;
-            a.kvBf16 = kvBf16_ ? 1 : 0;
-        }
-        if (rf && plan_.nRanks > 1) {  // the residual update needs the rank-summed tile
+        if (o.layer) fillLayerKv(a, *o.layer, c0);
+        if (o.rf.resIn && plan_.nRanks > 1) {  // the residual update needs the rank-summed tile
             g.tpx = 1;
-            a.tp = tpVec_;
-            a.tp.ticks = syncTicks();
-            a.tp.span = syncSpan();
+            fillXchg(a.tp, tpVec_);
         }
-        if (rf) {
-            g.resIn = rf->resIn + (size_t)c0 * ldOut;
-            g.resOut = rf->resOut + (size_t)c0 * ldOut;
-            g.resW = rf->w;
-            g.resX = dXh_ + (size_t)c0 * ldOut;
+        if (o.rf.resIn) {
+            g.resIn = o.rf.resIn + (size_t)c0 * o.ldOut;
+            g.resOut = o.rf.resOut + (size_t)c0 * o.ldOut;
+            g.resW = o.rf.w;
+            g.resX = dXh_ + (size_t)c0 * o.ldOut;
             g.ssOut = dSS_ + c0;
             g.ldSS = (int)cfg_.maxBatch;
         }
@@ -618,177 +583,102 @@ void HipEngineImpl::allReduce(float *buf, size_t count) {
     }
 }
 
-// The forward of n rows: embedding -> nLayers x [qkv (+RoPE, KV append) -> attention -> wo
-// (-> all-reduce) -> w13 (SwiGLU) -> w2 (-> all-reduce)] -> logits -> (gather) -> argmax / sample.
-// Single decode rows (GEMV path) run qkv + attention + wo as one fused attention-block launch when
-// the context bucket allows it; batched rows run the MFMA GEMMs with residual + norm fused into
-// their epilogues (reference step list: llm.cpp:200-434, ~840 barrier steps per forward).
-void HipEngineImpl::enqueueForward(int n, GraphKind kind) {
-    const ShardPlan &p = plan_;
-    const int dim = h_.dim;
-    int cur = 0;
-    const bool bat = batchedPath(n);                                   // MFMA GEMMs on f16 activations
-    const bool fz = bat && fuseNorm(n);                                // residual + norm in the GEMM epilogues
-    const bool blk = blockOn_ && buckets_[bucket_].block && n == 1 && !bat;  // fused attention block
-    const bool pre = prenormNow(n, bat, blk);  // pre-normalized Q80 hand-offs between the GEMVs
-    {
-        ProfScope ps(this, "embedding");
-        // the epochs count the forwards that run the fused attention block / the FFN block (their
-        // counters' targets); the two never run in the same forward (prenormNow excludes blk)
-        unsigned *ep = blk ? dEpoch_ : (pre && ffnOn_) ? dEpoch_ + 1 : nullptr;
-        hipk::launchEmbedding(emb_, dTok_, dX_[0], dim, n, stream_, ep,
-                              p.nRanks > 1 ? dSync_ : nullptr, p.nRanks > 1 ? syncSlots() : 0);
+// The per-matrix steps of a layer (enqueueForward): each picks its launch from the forward's path -
+// the fused-norm GEMM (input: the producer GEMM's rows), the GEMM behind a norm kernel, or the GEMV.
+void HipEngineImpl::enqueueQkv(const FwdPath &f, const DevLayer &L, int cur, bool hasDelta) {
+    ProfScope ps(this, "gemv_qkv");
+    if (f.fz && hasDelta)
+        gemmBatched(L.qkv, f.n, hipk::EPI_QKV, {.ssIn = true, .out = dQ_, .ldOut = q0(), .layer = &L});
+    else if (f.bat)
+        gemmBatched(L.qkv, f.n, hipk::EPI_QKV, qkvOperands(L, cur, hasDelta));
+    else
+        gemv(L.qkv, f.n, hipk::PRO_RESNORM, hipk::EPI_QKV, qkvOperands(L, cur, hasDelta));
+}
+
+void HipEngineImpl::enqueueAttention(const FwdPath &f, const DevLayer &L) {
+    ProfScope ps(this, "attention");
+    const hipk::AttnArgs a = attnArgs(L, f.bat);
+    for (int r0 = 0; r0 < f.n; r0 += attRows_) {  // one launch unless the partials cap the rows
+        const int nr = std::min(attRows_, f.n - r0);
+        hipk::AttnArgs ar = a;
+        ar.q += (size_t)r0 * a.ldq;
+        ar.pos += r0;
+        ar.slot += r0;
+        ar.out += (size_t)r0 * a.ldOut;
+        if (ar.outH) ar.outH += (size_t)r0 * a.ldOut;
+        if (ar.outQ) ar.outQ += (size_t)r0 * a.ldOut;
+        if (ar.outS) ar.outS += (size_t)r0 * (a.ldOut / 32);
+        if (f.bat && prefillOk_)
+            hipk::launchAttentionPrefill(ar, nr, stream_);
+        else
+            hipk::launchAttention(ar, nr, stream_);
     }
-    // one greedy decode row: the logits GEMV ends in the row's argmax (EPI_ARGMAX: no logits
-    // written, no argmax launch; under TP the winners trade over the fused exchange's region)
-    const bool argTail = argTailOn_ && q40_ && !bat && !fz && n == 1 &&
-                         (kind == GraphKind::ARGMAX || kind == GraphKind::CHAIN) &&
-                         (p.nRanks == 1 || (tpFused_ && tpArg_.stride >= 2));
-    if (pre) {
-        enqueuePrenormLayers(kind, argTail);
-        if (argTail) {
-            DL_HIP(hipGetLastError());
-            return;
-        }
-    }
-    // Q80 hand-off of h needs one workgroup per 32 hidden units; for skinny TP shards the w13
-    // epilogue emits f32 and w2 quantizes in its prologue instead.
-    const bool hQ80 = q40_ && hQ80_;
-    const bool woAttn = woAttnNow(n, bat, blk);  // attention inside the wo GEMV's prologue
-    for (u32 l = 0; l < h_.nLayers && !pre; l++) {
-        DevLayer &L = layers_[l];
-        const bool hasDelta = l > 0;
-        xSlot_ = 2 * (int)l;  // the wo exchange (fused in the wo kernel, or the all-reduce after it)
-        if (blk) {
-            ProfScope ps(this, "attn_block");
-            hipk::AttnBlockArgs ba = attnBlockArgs(L, l, cur);
-            if ((int)l == traceLayer_) ba.trace = traceBuf_;
-            hipk::launchAttnBlock(ba, fusedTp(false), stream_);
-            if (hasDelta) cur ^= 1;
-        } else {
-            {
-                ProfScope ps(this, "gemv_qkv");
-                if (fz && hasDelta)
-                    gemmBatched(L.qkv, n, hipk::EPI_QKV, nullptr, dim, nullptr, nullptr, nullptr, nullptr, dQ_, p.q0,
-                                nullptr, &L, nullptr, true);
-                else if (bat)
-                    gemmBatched(L.qkv, n, hipk::EPI_QKV, dX_[cur], dim, hasDelta ? dY_ : nullptr,
-                                hasDelta ? dX_[cur ^ 1] : nullptr, L.rmsAtt, nullptr, dQ_, p.q0, nullptr, &L);
-                else
-                    gemv(L.qkv, n, hipk::PRO_RESNORM, hipk::EPI_QKV, dX_[cur], dim, hasDelta ? dY_ : nullptr,
-                         hasDelta ? dX_[cur ^ 1] : nullptr, L.rmsAtt, dQ_, p.q0, &L);
-            }
-            if (hasDelta) cur ^= 1;
-            if (!woAttn) {
-                ProfScope ps(this, "attention");
-                const hipk::AttnArgs a = attnArgs(L, bat);
-                for (int r0 = 0; r0 < n; r0 += attRows_) {  // one launch unless the partials cap the rows
-                    const int nr = std::min(attRows_, n - r0);
-                    hipk::AttnArgs ar = a;
-                    ar.q += (size_t)r0 * a.ldq;
-                    ar.pos += r0;
-                    ar.slot += r0;
-                    ar.out += (size_t)r0 * a.ldOut;
-                    if (ar.outH) ar.outH += (size_t)r0 * a.ldOut;
-                    if (ar.outQ) ar.outQ += (size_t)r0 * a.ldOut;
-                    if (ar.outS) ar.outS += (size_t)r0 * (a.ldOut / 32);
-                    if (bat && prefillOk_)
-                        hipk::launchAttentionPrefill(ar, nr, stream_);
-                    else
-                        hipk::launchAttention(ar, nr, stream_);
-                }
-            }
-            {
-                ProfScope ps(this, "gemv_wo");
-                if (fz) {
-                    const ResFuse rf{dX_[cur], dX_[cur ^ 1], L.rmsFfn};
-                    gemmBatched(L.wo, n, hipk::EPI_RES, nullptr, 0, nullptr, nullptr, nullptr, dAttH_, nullptr, dim,
-                                nullptr, nullptr, &rf);
-                } else if (bat)
-                    gemmBatched(L.wo, n, hipk::EPI_STORE, nullptr, 0, nullptr, nullptr, nullptr, dAttH_, dY_, dim,
-                                nullptr, nullptr);
-                else if (woAttn) {
-                    const bool tp = fusedTp(bat);
-                    const int epi = tp ? hipk::EPI_STORE_TP : hipk::EPI_STORE;
-                    xChunk_ = 0;
-                    const hipk::GemvArgs a = gemvArgs(L.wo, 0, 1, epi, nullptr, p.q0, nullptr, nullptr, nullptr, dY_, dim,
-                                                      nullptr, dAttQ_, dAttS_, nullptr, nullptr, tp);
-                    hipk::launchGemvAttn(a, attnArgs(L, false), epi, stream_);
-                } else
-                    gemv(L.wo, n, hipk::PRO_GLOBAL, hipk::EPI_STORE, q40_ ? nullptr : dAtt_, p.q0, nullptr, nullptr,
-                         nullptr, dY_, dim, nullptr, dAttQ_, dAttS_, nullptr, nullptr, fusedTp(bat));
-            }
-        }
-        if (!fusedTp(bat) && !fz) allReduce(dY_, (size_t)n * dim);
-        xSlot_ = 2 * (int)l + 1;  // the w2 exchange
-        {
-            ProfScope ps(this, "gemv_w13");
-            if (fz)
-                gemmBatched(L.w13, n, hipk::EPI_ACT_F16, nullptr, dim, nullptr, nullptr, nullptr, nullptr, nullptr,
-                            p.hidden0, dHh_, nullptr, nullptr, true);
-            else if (bat)
-                gemmBatched(L.w13, n, hipk::EPI_ACT_F16, dX_[cur], dim, dY_, dX_[cur ^ 1], L.rmsFfn, nullptr, nullptr,
-                            p.hidden0, dHh_, nullptr);
-            else
-                gemv(L.w13, n, hipk::PRO_RESNORM, hQ80 ? hipk::EPI_ACT_Q80 : hipk::EPI_ACT, dX_[cur], dim, dY_,
-                     dX_[cur ^ 1], L.rmsFfn, dH_, p.hidden0, nullptr, nullptr, nullptr, dHQ_, dHS_);
-        }
-        cur ^= 1;
-        {
-            ProfScope ps(this, "gemv_w2");
-            if (fz) {
-                const float *wNext = l + 1 < h_.nLayers ? layers_[l + 1].rmsAtt : rmsFinal_;
-                const ResFuse rf{dX_[cur], dX_[cur ^ 1], wNext};
-                gemmBatched(L.w2, n, hipk::EPI_RES, nullptr, 0, nullptr, nullptr, nullptr, dHh_, nullptr, dim, nullptr,
-                            nullptr, &rf);
-            } else if (bat)
-                gemmBatched(L.w2, n, hipk::EPI_STORE, nullptr, 0, nullptr, nullptr, nullptr, dHh_, dY_, dim, nullptr,
-                            nullptr);
-            else if (hQ80 || !q40_)
-                gemv(L.w2, n, hipk::PRO_GLOBAL, hipk::EPI_STORE, q40_ ? nullptr : dH_, p.hidden0, nullptr, nullptr,
-                     nullptr, dY_, dim, nullptr, dHQ_, dHS_, nullptr, nullptr, fusedTp(bat));
-            else
-                gemv(L.w2, n, hipk::PRO_RESNORM, hipk::EPI_STORE, dH_, p.hidden0, nullptr, nullptr, nullptr, dY_, dim,
-                     nullptr, nullptr, nullptr, nullptr, nullptr, fusedTp(bat));
-        }
-        if (!fusedTp(bat) && !fz) allReduce(dY_, (size_t)n * dim);
-    }
+}
+
+void HipEngineImpl::enqueueWo(const FwdPath &f, const DevLayer &L, int cur) {
+    ProfScope ps(this, "gemv_wo");
+    if (f.fz)
+        gemmBatched(L.wo, f.n, hipk::EPI_RES, {.xh = dAttH_, .ldOut = dim(), .rf = {dX_[cur], dX_[cur ^ 1], L.rmsFfn}});
+    else if (f.bat)
+        gemmBatched(L.wo, f.n, hipk::EPI_STORE, {.xh = dAttH_, .out = dY_, .ldOut = dim()});
+    else if (f.woAttn) {
+        xChunk_ = 0;
+        hipk::launchGemvAttn(woRowArgs(L, woEpi()), attnArgs(L, false), woEpi(), stream_);
+    } else
+        gemv(L.wo, f.n, hipk::PRO_GLOBAL, hipk::EPI_STORE,
+             {.in = q40_ ? nullptr : dAtt_, .ldIn = q0(), .aq = dAttQ_, .as = dAttS_, .out = dY_, .ldOut = dim(),
+              .tp = fusedTp(false)});
+}
+
+void HipEngineImpl::enqueueW13(const FwdPath &f, const DevLayer &L, int cur) {
+    ProfScope ps(this, "gemv_w13");
+    if (f.fz)
+        gemmBatched(L.w13, f.n, hipk::EPI_ACT_F16, {.ssIn = true, .ldOut = hidden0(), .outH = dHh_});
+    else if (f.bat)
+        gemmBatched(L.w13, f.n, hipk::EPI_ACT_F16,
+                    {.in = dX_[cur], .ldIn = dim(), .add = dY_, .xNext = dX_[cur ^ 1], .normW = L.rmsFfn,
+                     .ldOut = hidden0(), .outH = dHh_});
+    else
+        gemv(L.w13, f.n, hipk::PRO_RESNORM, w13Epi(),
+             {.in = dX_[cur], .ldIn = dim(), .add = dY_, .xNext = dX_[cur ^ 1], .normW = L.rmsFfn, .out = dH_,
+              .ldOut = hidden0(), .oq = dHQ_, .os = dHS_});
+}
+
+void HipEngineImpl::enqueueW2(const FwdPath &f, u32 l, int cur) {
+    ProfScope ps(this, "gemv_w2");
+    const DevLayer &L = layers_[l];
+    if (f.fz)
+        gemmBatched(L.w2, f.n, hipk::EPI_RES, {.xh = dHh_, .ldOut = dim(), .rf = {dX_[cur], dX_[cur ^ 1], nextNormW(l)}});
+    else if (f.bat)
+        gemmBatched(L.w2, f.n, hipk::EPI_STORE, {.xh = dHh_, .out = dY_, .ldOut = dim()});
+    else if (!q40_ || hQ80_)
+        gemv(L.w2, f.n, hipk::PRO_GLOBAL, hipk::EPI_STORE,
+             {.in = q40_ ? nullptr : dH_, .ldIn = hidden0(), .aq = dHQ_, .as = dHS_, .out = dY_, .ldOut = dim(),
+              .tp = fusedTp(false)});
+    else
+        gemv(L.w2, f.n, hipk::PRO_RESNORM, hipk::EPI_STORE,
+             {.in = dH_, .ldIn = hidden0(), .out = dY_, .ldOut = dim(), .tp = fusedTp(false)});
+}
+
+// The logits of the forward's rows from the residual dX_[cur] + dY_ (argTail: the row's argmax).
+void HipEngineImpl::enqueueLogits(const FwdPath &f, GraphKind kind, int cur) {
     xSlot_ = 2 * (int)h_.nLayers;  // logits gather / argmax winners
-    if (!pre) {
-        ProfScope ps(this, "gemv_logits");
-        if (fz)
-            gemmBatched(wcls_, n, hipk::EPI_STORE, nullptr, dim, nullptr, nullptr, nullptr, nullptr, dLogits_, p.vocab0,
-                        nullptr, nullptr, nullptr, true);
-        else if (bat)
-            gemmBatched(wcls_, n, hipk::EPI_STORE, dX_[cur], dim, dY_, nullptr, rmsFinal_, nullptr, dLogits_, p.vocab0,
-                        nullptr, nullptr);
-        else if (argTail) {
-            hipk::GemvArgs a = gemvArgs(wcls_, 0, 1, hipk::EPI_ARGMAX, dX_[cur], dim, dY_, nullptr, rmsFinal_, nullptr,
-                                        p.vocab0, nullptr, nullptr, nullptr, nullptr, nullptr, false);
-            a.am.ids = dIds_;
-            a.am.partV = dArgV_;
-            a.am.partI = dArgI_;
-            a.am.counter = dArgCnt_;
-            a.am.vocabStart = p.vocabStart();
-            if (kind == GraphKind::CHAIN) {
-                a.am.tokens = dTok_;
-                a.am.pos = dPos_;
-                a.am.hist = dHist_;
-            }
-            if (p.nRanks > 1) {
-                a.tp = tpArg_;
-                a.tp.ticks = syncTicks();
-                a.tp.span = syncSpan();
-            }
-            hipk::launchGemv(a, 1, hipk::PRO_RESNORM, hipk::EPI_ARGMAX, true, stream_);
-        } else
-            gemv(wcls_, n, hipk::PRO_RESNORM, hipk::EPI_STORE, dX_[cur], dim, dY_, nullptr, rmsFinal_, dLogits_,
-                 p.vocab0, nullptr);
-    }
-    if (argTail) {
-        DL_HIP(hipGetLastError());
-        return;
-    }
+    ProfScope ps(this, "gemv_logits");
+    const MatOperands o{.in = dX_[cur], .ldIn = dim(), .add = dY_, .normW = rmsFinal_,
+                        .out = f.argTail ? nullptr : dLogits_, .ldOut = vocab0()};
+    if (f.fz)
+        gemmBatched(wcls_, f.n, hipk::EPI_STORE, {.ssIn = true, .out = dLogits_, .ldOut = vocab0()});
+    else if (f.bat)
+        gemmBatched(wcls_, f.n, hipk::EPI_STORE, o);
+    else if (f.argTail)
+        launchArgmaxTail(gemvArgs(wcls_, 0, 1, hipk::EPI_ARGMAX, o), hipk::PRO_RESNORM, kind);
+    else
+        gemv(wcls_, f.n, hipk::PRO_RESNORM, hipk::EPI_STORE, o);
+}
+
+// From the logits of n rows to their token ids: (gather) -> argmax / sample.
+void HipEngineImpl::enqueueTokenPick(int n, GraphKind kind) {
+    const ShardPlan &p = plan_;
     const float *full = dLogits_;
     // greedy rows under tensor parallelism: each rank reduces its own vocab slice and only the
     // (value, index) winners cross the links (reference: logits gathered to the root,
@@ -831,13 +721,10 @@ void HipEngineImpl::enqueueForward(int n, GraphKind kind) {
             g.vocab = p.vocab0;
             g.vocabStart = p.vocabStart();
             // fused winners exchange up to its region's rows (2 words per row), else one all-gather
-            if (tpFused_ && (size_t)2 * n <= (size_t)tpArg_.stride) {
-                g.tp = tpArg_;
-                g.tp.ticks = syncTicks();
-                g.tp.span = syncSpan();
-            } else {
+            if (tpFused_ && (size_t)2 * n <= (size_t)tpArg_.stride)
+                fillXchg(g.tp, tpArg_);
+            else
                 g.pairs = dArgPairs_;
-            }
         }
         g.ids = dIds_;
         g.partV = dArgV_;
@@ -856,6 +743,63 @@ void HipEngineImpl::enqueueForward(int n, GraphKind kind) {
             hipk::launchArgmaxPick(g, dArgPairsAll_, n, p.nRanks, stream_);
         }
     }
+}
+
+// The forward of n rows: embedding -> nLayers x [qkv (+RoPE, KV append) -> attention -> wo
+// (-> all-reduce) -> w13 (SwiGLU) -> w2 (-> all-reduce)] -> logits -> (gather) -> argmax / sample.
+// Single decode rows (GEMV path) run qkv + attention + wo as one fused attention-block launch when
+// the context bucket allows it; batched rows run the MFMA GEMMs with residual + norm fused into
+// their epilogues (reference step list: llm.cpp:200-434, ~840 barrier steps per forward).
+void HipEngineImpl::enqueueForward(int n, GraphKind kind) {
+    FwdPath f{.n = n, .bat = batchedPath(n)};
+    f.fz = f.bat && fuseNorm(n);
+    f.blk = blockOn_ && buckets_[bucket_].block && n == 1 && !f.bat;
+    const bool row = n == 1 && !f.bat && !f.blk;  // a single decode row outside the block
+    f.pre = prenormOn_ && row;
+    f.woAttn = woAttnOn_ && row && buckets_[bucket_].maxLen <= woAttnMaxLen_;
+    // one greedy decode row: the logits GEMV ends in the row's argmax (EPI_ARGMAX: no logits
+    // written, no argmax launch; under TP the winners trade over the fused exchange's region)
+    f.argTail = argTailOn_ && q40_ && !f.bat && !f.fz && n == 1 &&
+                (kind == GraphKind::ARGMAX || kind == GraphKind::CHAIN) &&
+                (plan_.nRanks == 1 || (tpFused_ && tpArg_.stride >= 2));
+    {
+        ProfScope ps(this, "embedding");
+        // the epochs count the forwards that run the fused attention block / the FFN block (their
+        // counters' targets); the two never run in the same forward (FwdPath::pre excludes blk)
+        unsigned *ep = f.blk ? dEpoch_ : (f.pre && ffnOn_) ? dEpoch_ + 1 : nullptr;
+        hipk::launchEmbedding(emb_, dTok_, dX_[0], dim(), n, stream_, ep,
+                              plan_.nRanks > 1 ? dSync_ : nullptr, plan_.nRanks > 1 ? syncSlots() : 0);
+    }
+    const bool sepReduce = !fusedTp(f.bat) && !f.fz;  // wo / w2 partial sums: a separate all-reduce
+    int cur = 0;
+    for (u32 l = 0; l < h_.nLayers && !f.pre; l++) {
+        DevLayer &L = layers_[l];
+        const bool hasDelta = l > 0;
+        xSlot_ = 2 * (int)l;  // the wo exchange (fused in the wo kernel, or the all-reduce after it)
+        if (f.blk) {
+            ProfScope ps(this, "attn_block");
+            hipk::AttnBlockArgs ba = attnBlockArgs(L, l, cur);
+            if ((int)l == traceLayer_) ba.trace = traceBuf_;
+            hipk::launchAttnBlock(ba, fusedTp(false), stream_);
+            if (hasDelta) cur ^= 1;
+        } else {
+            enqueueQkv(f, L, cur, hasDelta);
+            if (hasDelta) cur ^= 1;
+            if (!f.woAttn) enqueueAttention(f, L);
+            enqueueWo(f, L, cur);
+        }
+        if (sepReduce) allReduce(dY_, (size_t)n * dim());
+        xSlot_ = 2 * (int)l + 1;  // the w2 exchange
+        enqueueW13(f, L, cur);
+        cur ^= 1;
+        enqueueW2(f, l, cur);
+        if (sepReduce) allReduce(dY_, (size_t)n * dim());
+    }
+    if (f.pre)
+        enqueuePrenormLayers(f, kind);
+    else
+        enqueueLogits(f, kind, cur);
+    if (!f.argTail) enqueueTokenPick(n, kind);
     DL_HIP(hipGetLastError());
 }
 

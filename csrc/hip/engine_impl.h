@@ -214,46 +214,104 @@ class HipEngineImpl : public HipEngine {
     int passesFor(const DevMat &m, int epi, int B) const {
         return hipk::gemvDefaultPasses(m.n, m.rows, B, q40_, epi, q40_ ? m.lanes : 0);
     }
-    hipk::GemvArgs gemvArgs(const DevMat &m, int c0, int bc, int epi, const float *in, int ldIn, const float *add,
-                            float *xNext, const float *normW, float *out, int ldOut, const DevLayer *L,
-                            const int8_t *aq, const float2 *as, int8_t *oq, float2 *os, bool tp) const;
-    void gemv(const DevMat &m, int n, int pro, int epi, const float *in, int ldIn, const float *add, float *xNext,
-              const float *normW, float *out, int ldOut, const DevLayer *L, const int8_t *aq = nullptr,
-              const float2 *as = nullptr, int8_t *oq = nullptr, float2 *os = nullptr, bool tp = false);
+    // rows one workgroup of a Q40 GEMV launch covers, and the launch's grid
+    static int rowsPerWorkgroup(int lanes, int passes) { return (256 / lanes) * 2 * passes; }
+    static int rowsPerWorkgroup(const hipk::GemvArgs &a) { return rowsPerWorkgroup(a.lanes, a.passes); }
+    static int gemvGrid(const hipk::GemvArgs &a) { return (a.rows + rowsPerWorkgroup(a) - 1) / rowsPerWorkgroup(a); }
+    // Co-residency of a launch whose workgroups spin on peers: the ranks sharing this GPU (same-GPU
+    // rehearsals) share its resident slots, so the whole grid must fit this rank's part of them.
+    int ranksSharingDevice() const { return comm_ ? std::max(1, comm_->ranksOnDevice()) : 1; }
+    int residentLimit(const hipk::GemvResidency &r) const { return r.maxResident / ranksSharingDevice(); }
+    static bool fitsResident(const hipk::GemvResidency &r, int limit) { return limit > 0 && r.grid <= limit; }
+    bool fitsResident(const hipk::GemvResidency &r) const { return fitsResident(r, residentLimit(r)); }
+    struct ResFuse {
+        const float *resIn = nullptr;
+        float *resOut = nullptr;
+        const float *w = nullptr;
+    };
+    // Operands of one GEMV (gemv, gemvArgs) or batched GEMM (gemmBatched) launch over the rows of a
+    // forward; a call site names the ones it uses. The input comes in one of three forms.
+    struct MatOperands {
+        // f32 rows [ldIn]: in + add (-> xNext when set) through the RMS norm, times normW
+        const float *in = nullptr;
+        int ldIn = 0;
+        const float *add = nullptr;
+        float *xNext = nullptr;
+        const float *normW = nullptr;
+        const int8_t *aq = nullptr;     // Q80 rows (GEMV, PRO_GLOBAL on Q40 weights): blocks ...
+        const float2 *as = nullptr;     //   ... and (d, sum of q) per block
+        const _Float16 *xh = nullptr;   // f16 rows (GEMM): xh ...
+        bool ssIn = false;              //   ... or the producer GEMM's x' * normW rows (dXh_) and its sums of squares
+        // output rows [ldOut]: f32, Q80 (GEMV, EPI_ACT_Q80) or f16 (GEMM, EPI_ACT_F16)
+        float *out = nullptr;
+        int ldOut = 0;
+        int8_t *oq = nullptr;
+        float2 *os = nullptr;
+        _Float16 *outH = nullptr;
+        const DevLayer *layer = nullptr;  // EPI_QKV: the layer whose KV cache takes the rows
+        bool tp = false;                  // GEMV: all-reduce the output over the ranks in the kernel tail
+        ResFuse rf;                       // GEMM, EPI_RES: residual update + the next norm's weights
+    };
+    int dim() const { return (int)h_.dim; }  // the shard's widths as the launches' leading dimensions
+    int q0() const { return (int)plan_.q0; }
+    int hidden0() const { return (int)plan_.hidden0; }
+    int vocab0() const { return (int)plan_.vocab0; }
+    void fillXchg(hipk::TpXchg &tp, const hipk::TpXchg &region) const;
+    void fillLayerKv(hipk::GemvArgs &a, const DevLayer &L, int c0) const;
+    hipk::GemvArgs gemvArgs(const DevMat &m, int c0, int bc, int epi, const MatOperands &o) const;
+    void gemv(const DevMat &m, int n, int pro, int epi, const MatOperands &o);
+    MatOperands qkvOperands(const DevLayer &L, int cur, bool hasDelta) const;
+    // single decode rows: the wo / w2 / w13 argument sets that a setup probe and the forward share
+    int woEpi() const { return fusedTp(false) ? hipk::EPI_STORE_TP : hipk::EPI_STORE; }
+    hipk::GemvArgs woRowArgs(const DevLayer &L, int epi) const;  // fused exchange unless epi is EPI_STORE
+    hipk::GemvArgs w2ProducerArgs(const DevLayer &L) const;
+    hipk::GemvArgs w13ConsumerArgs(const DevLayer &L) const;
+    // Q80 hand-off of h needs one workgroup per 32 hidden units; for skinny TP shards the w13
+    // epilogue emits f32 and w2 quantizes in its prologue instead.
+    int w13Epi() const { return q40_ && hQ80_ ? hipk::EPI_ACT_Q80 : hipk::EPI_ACT; }
+    int w2Pro() const { return hQ80_ ? hipk::PRO_GLOBAL : hipk::PRO_RESNORM; }
+    const float *nextNormW(u32 l) const { return l + 1 < h_.nLayers ? layers_[l + 1].rmsAtt : rmsFinal_; }
     hipk::AttnArgs attnArgs(const DevLayer &L, bool bat) const;
     hipk::AttnBlockArgs attnBlockArgs(const DevLayer &L, u32 l, int cur) const;
     void setupAttnBlock();
     void resetAttnBlockState();
     // the wo GEMV with the attention in its prologue (PRO_ATTN) for single decode rows of short
-    // contexts when a rank holds few heads: decided once (setupWoAttn), taken per forward (woAttnNow)
+    // contexts when a rank holds few heads: decided once (setupWoAttn), taken per forward (FwdPath::woAttn)
     void setupWoAttn();
     // pre-normalized hand-off for single decode rows (EPI_RESQ_TP producers -> PRO_PRENORM
-    // consumers): decided once (setupPrenorm), taken per forward (prenormNow)
+    // consumers): decided once (setupPrenorm), taken per forward (FwdPath::pre)
     void setupPrenorm();
-    bool prenormNow(int n, bool bat, bool blk) const { return prenormOn_ && n == 1 && !bat && !blk; }
     // fused FFN block (w13 + w2 roles in one launch) inside the pre-normalized layers: setupFfnBlock
     void setupFfnBlock();
     hipk::FfnBlockArgs ffnBlockArgs(const hipk::GemvArgs &w13, const hipk::GemvArgs &w2, u32 l);
-    void enqueuePrenormLayers(GraphKind kind, bool argTail);
-    bool woAttnNow(int n, bool bat, bool blk) const {
-        return woAttnOn_ && n == 1 && !bat && !blk && buckets_[bucket_].maxLen <= woAttnMaxLen_;
-    }
     bool batchedPath(int n) const {
         return n >= gemmMin_ && hipk::gemmSupported(h_.dim) && hipk::gemmSupported(plan_.q0) &&
                hipk::gemmSupported(plan_.hidden0);
     }
-    struct ResFuse {
-        const float *resIn;
-        float *resOut;
-        const float *w;
-    };
     bool tpBatchedOk(int n) const;
     bool fuseNorm(int n) const { return fuseNormEnv_ && (plan_.nRanks == 1 || tpBatchedOk(n)); }
-    void gemmBatched(const DevMat &m, int n, int epi, const float *in, int ldIn, const float *add, float *xNext,
-                     const float *normW, const _Float16 *xh, float *out, int ldOut, _Float16 *outH,
-                     const DevLayer *L, const ResFuse *rf = nullptr, bool ssIn = false);
+    void gemmBatched(const DevMat &m, int n, int epi, const MatOperands &o);
     void allReduce(float *buf, size_t count);
     bool fusedTp(bool bat) const { return tpFused_ && !bat && q40_; }
+    // The path a forward of n rows takes (enqueueForward): the per-matrix steps pick their launch from it.
+    struct FwdPath {
+        int n;
+        bool bat;      // MFMA GEMMs on f16 activations (else GEMVs in batch chunks)
+        bool fz;       // batched: residual + norm in the GEMM epilogues
+        bool blk;      // single row: qkv + attention + wo as the fused attention block
+        bool pre;      // single row: pre-normalized Q80 hand-offs between the GEMVs
+        bool woAttn;   // single row: attention inside the wo GEMV's prologue
+        bool argTail;  // single greedy row: the logits GEMV ends in the argmax
+    };
+    void enqueueQkv(const FwdPath &f, const DevLayer &L, int cur, bool hasDelta);
+    void enqueueAttention(const FwdPath &f, const DevLayer &L);
+    void enqueueWo(const FwdPath &f, const DevLayer &L, int cur);
+    void enqueueW13(const FwdPath &f, const DevLayer &L, int cur);
+    void enqueueW2(const FwdPath &f, u32 l, int cur);
+    void enqueuePrenormLayers(const FwdPath &f, GraphKind kind);
+    void enqueueLogits(const FwdPath &f, GraphKind kind, int cur);
+    void launchArgmaxTail(hipk::GemvArgs a, int pro, GraphKind kind);
+    void enqueueTokenPick(int n, GraphKind kind);
     void enqueueForward(int n, GraphKind kind);
 
     // timing hook for profileForward (eager only)

@@ -50,16 +50,12 @@ void HipEngineImpl::checkFits() {
 // (hipOccupancyMaxActiveBlocksPerMultiprocessor x CUs at the launch's LDS size); if any would
 // not fit, fall back to the separate all-reduce kernels, whose grids are a few workgroups.
 void HipEngineImpl::checkFusedResidency() {
-    const ShardPlan &p = plan_;
     // ranks sharing this GPU (same-GPU rehearsals) share its resident slots; DL_FUSED_RESIDENT
     // overrides the limit (diagnostics / tests of the fallback)
-    const int share = std::max(1, comm_->ranksOnDevice());
     const char *ov = std::getenv("DL_FUSED_RESIDENT");
-    const bool hQ80 = hQ80_;
     struct Shape {
         int rows, n, pro;
-    } shapes[2] = {{(int)h_.dim, (int)p.q0, hipk::PRO_GLOBAL},
-                   {(int)h_.dim, (int)p.hidden0, hQ80 ? hipk::PRO_GLOBAL : hipk::PRO_RESNORM}};
+    } shapes[2] = {{dim(), q0(), hipk::PRO_GLOBAL}, {dim(), hidden0(), w2Pro()}};
     for (const Shape &sh : shapes) {
         DevMat m;
         m.rows = sh.rows;
@@ -74,14 +70,14 @@ void HipEngineImpl::checkFusedResidency() {
             a.passes = tpPasses(m, bc);
             a.tp = tpVec_;
             const hipk::GemvResidency r = hipk::gemvResidency(a, bc, sh.pro, hipk::EPI_STORE_TP, true);
-            const int limit = ov && *ov ? std::atoi(ov) : r.maxResident / share;
+            const int limit = ov && *ov ? std::atoi(ov) : residentLimit(r);
             fusedGridMax_ = std::max(fusedGridMax_, r.grid);
-            if (limit <= 0 || r.grid > limit) {
+            if (!fitsResident(r, limit)) {
                 std::fprintf(stderr,
                              "⚠️  fused TP exchange disabled: a %dx%d GEMV at batch %d needs %d co-resident "
                              "workgroups, this rank may hold %d (%d per device, %d rank(s) on it); using "
                              "separate all-reduce kernels\n",
-                             sh.rows, sh.n, bc, r.grid, limit, r.maxResident, share);
+                             sh.rows, sh.n, bc, r.grid, limit, r.maxResident, ranksSharingDevice());
                 tpFused_ = false;
                 return;
             }
@@ -92,7 +88,7 @@ void HipEngineImpl::checkFusedResidency() {
 int HipEngineImpl::tpPasses(const DevMat &m, int bc) const {
     int passes = passesFor(m, hipk::EPI_STORE_TP, bc);
     if (tpVec_.q80)  // whole Q80 blocks of 32 rows per workgroup
-        while ((256 / m.lanes * 2 * passes) % 32) passes++;
+        while (rowsPerWorkgroup(m.lanes, passes) % 32) passes++;
     return passes;
 }
 
