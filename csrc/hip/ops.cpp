@@ -51,10 +51,50 @@ class Scratch {
         DL_HIP(hipGetLastError());
         DL_HIP(hipStreamSynchronize(s));
     }
+    // Output buffer of `rows` rows of `ld` elements of which the first `valid` are results and the
+    // rest (ld - valid >= one workgroup's rows) guard, every byte preset to kGuardByte (a result
+    // the launch never wrote reads back as NaN). checkGuards() throws when a launch changed a
+    // guard byte: a store past the last valid row of an op is an error, not silent corruption.
+    static constexpr uint8_t kGuardByte = 0xFF;
+    template <typename T>
+    T *allocGuarded(size_t rows, size_t valid, size_t ld, const char *what) {
+        DL_CHECK(ld > valid && rows > 0, "guarded buffer needs a guard region");
+        void *p = nullptr;
+        const size_t bytes = rows * ld * sizeof(T);
+        DL_HIP(hipMalloc(&p, bytes));
+        mem_.push_back(p);
+        DL_HIP(hipMemsetAsync(p, kGuardByte, bytes, s));
+        guards_.push_back({static_cast<uint8_t *>(p), rows, valid * sizeof(T), ld * sizeof(T), what});
+        return static_cast<T *>(p);
+    }
+    void checkGuards() {
+        for (const Guard &g : guards_) {
+            const std::vector<uint8_t> v = download(g.p, g.rows * g.ld);
+            for (size_t r = 0; r < g.rows; r++)
+                for (size_t i = g.valid; i < g.ld; i++)
+                    DL_CHECK(v[r * g.ld + i] == kGuardByte,
+                             std::string("ops: the launch wrote past the valid part of ") + g.what + " (row " +
+                                 std::to_string(r) + ", byte " + std::to_string(i - g.valid) + " of its guard)");
+        }
+    }
+    // the valid part of a guarded buffer, rows packed
+    template <typename T>
+    std::vector<T> downloadRows(const T *p, size_t rows, size_t valid, size_t ld) {
+        const std::vector<T> all = download(p, rows * ld);
+        std::vector<T> v(rows * valid);
+        for (size_t r = 0; r < rows; r++) std::copy(all.begin() + r * ld, all.begin() + r * ld + valid, v.begin() + r * valid);
+        return v;
+    }
     hipStream_t s = nullptr;
 
   private:
+    struct Guard {
+        uint8_t *p;
+        size_t rows, valid, ld;  // bytes
+        const char *what;
+    };
     std::vector<void *> mem_;
+    std::vector<Guard> guards_;
 };
 
 // File-layout Q40 blocks -> the engine's tiled device layout (csrc/hip/kernels.h Q40Tiling).
@@ -64,8 +104,35 @@ struct DevQ40 {
     int lanes = 0;
 };
 
-DevQ40 uploadQ40(Scratch &sc, const std::vector<uint8_t> &blocks, int rows, int n) {
+constexpr size_t kLdsLimit = 160 * 1024;  // LDS of a gfx950 CU
+
+void checkLanes(int lanes) {
+    DL_CHECK(lanes == 0 || lanes == 16 || lanes == 32 || lanes == 64, "gemv lanes must be 0 (auto), 16, 32 or 64");
+}
+
+// Launch geometry of a Q40 ring GEMV op: the forced (or default) lanes per row and passes, the
+// rows one workgroup covers, and the refusal of a launch the kernel cannot run.
+struct Q40Geom {
+    int lanes = 0, passes = 0, wgRows = 0;
+};
+Q40Geom q40Geom(int rows, int n, int B, int epi, int lanes, int passes) {
+    checkLanes(lanes);
+    DL_CHECK(rows > 0 && n > 0 && n % 32 == 0, "Q40 shape");
+    DL_CHECK(passes >= 0, "gemv passes must be 0 (default) or >= 1");
+    Q40Geom g;
+    g.lanes = lanes > 0 ? lanes : hipk::gemvLanesPerRow(n, rows, 1, true);
+    g.passes = passes > 0 ? passes : hipk::gemvDefaultPasses(n, rows, B, true, epi, g.lanes);
+    g.wgRows = 256 / g.lanes * hipk::gemvRowGroup(B, true) * g.passes;
+    DL_CHECK(hipk::gemvLdsBytes(n, B, true, g.wgRows, hipk::PRO_RESNORM) <= kLdsLimit,
+             "gemv LDS footprint beyond the device limit");
+    DL_CHECK(epi != hipk::EPI_ACT_Q80 || g.wgRows % 64 == 0,
+             "gemv SwiGLU -> Q80: rows per workgroup must be a multiple of 64 (whole Q80 blocks)");
+    return g;
+}
+
+DevQ40 uploadQ40(Scratch &sc, const std::vector<uint8_t> &blocks, int rows, int n, int lanes = 0) {
     DL_CHECK(n % 32 == 0 && rows > 0, "Q40 shape");
+    checkLanes(lanes);
     const size_t nb = (size_t)rows * (n / 32);
     DL_CHECK(blocks.size() == nb * sizeof(BlockQ40), "Q40 blocks size");
     std::vector<uint8_t> qs(nb * 16);
@@ -76,7 +143,7 @@ DevQ40 uploadQ40(Scratch &sc, const std::vector<uint8_t> &blocks, int rows, int 
         d[i] = b[i].d;
     }
     DevQ40 m;
-    m.lanes = hipk::gemvLanesPerRow(n, rows, 1, true);
+    m.lanes = lanes > 0 ? lanes : hipk::gemvLanesPerRow(n, rows, 1, true);
     const hipk::Q40Tiling t = hipk::q40Tiling(rows, n, m.lanes);
     std::vector<uint8_t> qt(t.qsBytes);
     std::vector<uint32_t> dt(t.dBytes / 4);
@@ -90,51 +157,108 @@ void checkRows(const std::vector<float> &v, size_t want, const char *what) {
     DL_CHECK(v.empty() || v.size() == want, std::string("ops: bad size of ") + what);
 }
 
-}  // namespace
-
-std::vector<float> gemvQ40(const std::vector<uint8_t> &blocks, int rows, int n, const std::vector<float> &in,
-                           const std::vector<float> &residual, const std::vector<float> &normW, float eps, int B,
-                           int epi, std::vector<float> *xNext) {
+// PRO_RESNORM operands shared by the Q40 ops with a norm prologue: weights tiled at the geometry's
+// L, in / residual / norm weights uploaded, xNext (guarded) when there is a residual.
+hipk::GemvArgs resnormArgs(Scratch &sc, const std::vector<uint8_t> &blocks, int rows, int n,
+                           const std::vector<float> &in, const std::vector<float> &residual,
+                           const std::vector<float> &normW, float eps, int B, const Q40Geom &g) {
     DL_CHECK(B == 1 || B == 2 || B == 4, "gemv batch must be 1, 2 or 4");
-    DL_CHECK(epi == 0 || (epi == 1 && rows % 2 == 0), "gemv epilogue");
-    DL_CHECK(in.size() == (size_t)B * n, "gemv input size");
+    DL_CHECK(n % 32 == 0 && in.size() == (size_t)B * n, "gemv input size");
     checkRows(residual, (size_t)B * n, "residual");
     checkRows(normW, (size_t)n, "norm weights");
-    Scratch sc;
-    const DevQ40 w = uploadQ40(sc, blocks, rows, n);
-    const int outRows = epi == 1 ? rows / 2 : rows;
+    const DevQ40 w = uploadQ40(sc, blocks, rows, n, g.lanes);
     hipk::GemvArgs a;
     a.qs = w.qs;
     a.wd = w.d;
     a.rows = rows;
     a.n = n;
-    a.lanes = w.lanes;
-    const int ep = epi == 1 ? hipk::EPI_ACT : hipk::EPI_STORE;
-    a.passes = hipk::gemvDefaultPasses(n, rows, B, true, ep);
+    a.lanes = g.lanes;
+    a.passes = g.passes;
     a.in = sc.upload(in);
     a.ldIn = n;
     a.addIn = sc.upload(residual);
-    a.xNext = residual.empty() ? nullptr : sc.alloc<float>((size_t)B * n);
+    // rows of ldIn = n floats back to back: one guard after the last
+    a.xNext = residual.empty() ? nullptr : sc.allocGuarded<float>(1, (size_t)B * n, (size_t)B * n + 256, "xNext");
     a.normW = sc.upload(normW);
     a.eps = eps;
-    a.out = sc.alloc<float>((size_t)B * outRows);
-    a.ldOut = outRows;
     a.act = 1;
-    const size_t lds = hipk::gemvLdsBytes(n, B, true, hipk::gemvRowsPerPass(n, rows, B, true) * a.passes,
-                                          hipk::PRO_RESNORM);
-    DL_CHECK(B == 1 || lds <= 64 * 1024, "gemv LDS footprint too large for this batch");
+    return a;
+}
+
+}  // namespace
+
+std::vector<float> gemvQ40(const std::vector<uint8_t> &blocks, int rows, int n, const std::vector<float> &in,
+                           const std::vector<float> &residual, const std::vector<float> &normW, float eps, int B,
+                           int epi, std::vector<float> *xNext, int lanes, int passes) {
+    DL_CHECK(B == 1 || B == 2 || B == 4, "gemv batch must be 1, 2 or 4");
+    DL_CHECK(epi == 0 || (epi == 1 && rows % 2 == 0), "gemv epilogue");
+    const int ep = epi == 1 ? hipk::EPI_ACT : hipk::EPI_STORE;
+    const Q40Geom g = q40Geom(rows, n, B, ep, lanes, passes);
+    DL_CHECK(B == 1 || hipk::gemvLdsBytes(n, B, true, g.wgRows, hipk::PRO_RESNORM) <= 64 * 1024,
+             "gemv LDS footprint too large for this batch");
+    Scratch sc;
+    hipk::GemvArgs a = resnormArgs(sc, blocks, rows, n, in, residual, normW, eps, B, g);
+    const int outRows = epi == 1 ? rows / 2 : rows;
+    a.ldOut = outRows + g.wgRows;
+    a.out = sc.allocGuarded<float>(B, outRows, a.ldOut, "the GEMV output");
     hipk::launchGemv(a, B, hipk::PRO_RESNORM, ep, true, sc.s);
     sc.sync();
+    sc.checkGuards();
     if (xNext && a.xNext) *xNext = sc.download(a.xNext, (size_t)B * n);
-    return sc.download(a.out, (size_t)B * outRows);
+    return sc.downloadRows(a.out, B, outRows, a.ldOut);
+}
+
+void gemvQ40SwigluQ80(const std::vector<uint8_t> &blocks, int rows, int n, const std::vector<float> &in,
+                      const std::vector<float> &residual, const std::vector<float> &normW, float eps, int B,
+                      int lanes, int passes, std::vector<int8_t> &codes, std::vector<float> &scales) {
+    DL_CHECK(rows > 0 && rows % 64 == 0, "gemv SwiGLU -> Q80: rows must be whole 64-row (32 hidden unit) blocks");
+    const Q40Geom g = q40Geom(rows, n, B, hipk::EPI_ACT_Q80, lanes, passes);
+    Scratch sc;
+    hipk::GemvArgs a = resnormArgs(sc, blocks, rows, n, in, residual, normW, eps, B, g);
+    const int hidden = rows / 2;
+    a.ldOut = hidden + g.wgRows;  // a multiple of 32: the scale pairs are [B][ldOut / 32]
+    a.oq = sc.allocGuarded<int8_t>(B, hidden, a.ldOut, "the Q80 codes");
+    float *os = sc.allocGuarded<float>(B, (size_t)hidden / 32 * 2, (size_t)a.ldOut / 32 * 2, "the Q80 scales");
+    a.os = reinterpret_cast<float2 *>(os);
+    hipk::launchGemv(a, B, hipk::PRO_RESNORM, hipk::EPI_ACT_Q80, true, sc.s);
+    sc.sync();
+    sc.checkGuards();
+    codes = sc.downloadRows(a.oq, B, hidden, a.ldOut);
+    scales = sc.downloadRows(os, B, (size_t)hidden / 32 * 2, (size_t)a.ldOut / 32 * 2);
+}
+
+int gemvQ40Argmax(const std::vector<uint8_t> &blocks, int rows, int n, const std::vector<float> &in,
+                  const std::vector<float> &residual, const std::vector<float> &normW, float eps, int vocabStart,
+                  int lanes, int passes, int repeat) {
+    DL_CHECK(repeat >= 1 && repeat <= 8, "gemv argmax: 1..8 launches");
+    const Q40Geom g = q40Geom(rows, n, 1, hipk::EPI_ARGMAX, lanes, passes);
+    Scratch sc;
+    hipk::GemvArgs a = resnormArgs(sc, blocks, rows, n, in, residual, normW, eps, 1, g);
+    const int grid = (rows + g.wgRows - 1) / g.wgRows;
+    a.am.partV = sc.allocGuarded<float>(1, grid, grid + 64, "the argmax partial values");
+    a.am.partI = sc.allocGuarded<int>(1, grid, grid + 64, "the argmax partial rows");
+    int *ids = sc.allocGuarded<int>(1, repeat, repeat + 16, "the argmax ids");
+    a.am.counter = sc.alloc<int>(1);  // zeroed
+    a.am.vocabStart = vocabStart;
+    for (int i = 0; i < repeat; i++) {
+        a.am.ids = ids + i;
+        hipk::launchGemv(a, 1, hipk::PRO_RESNORM, hipk::EPI_ARGMAX, true, sc.s);
+    }
+    sc.sync();
+    sc.checkGuards();
+    DL_CHECK(sc.download(a.am.counter, 1)[0] == 0, "gemv argmax: the arrival counter did not return to zero");
+    const std::vector<int> got = sc.download(ids, repeat);
+    for (int i = 1; i < repeat; i++) DL_CHECK(got[i] == got[0], "gemv argmax: repeated launches on the same scratch disagree");
+    return got[0];
 }
 
 std::vector<float> gemvQ40Q80In(const std::vector<uint8_t> &blocks, int rows, int n, const std::vector<float> &in,
-                                int B) {
+                                int B, int lanes, int passes) {
     DL_CHECK(B == 1 || B == 2 || B == 4, "gemv batch must be 1, 2 or 4");
-    DL_CHECK(in.size() == (size_t)B * n, "gemv input size");
+    DL_CHECK(n % 32 == 0 && in.size() == (size_t)B * n, "gemv input size");
+    const Q40Geom g = q40Geom(rows, n, B, hipk::EPI_STORE, lanes, passes);
     Scratch sc;
-    const DevQ40 w = uploadQ40(sc, blocks, rows, n);
+    const DevQ40 w = uploadQ40(sc, blocks, rows, n, g.lanes);
     // host Q80 (the reference quantizer) -> int8 codes + (d, sum of codes) per block, as the
     // attention / SwiGLU epilogues hand them to this kernel
     const int nb = n / 32;
@@ -156,15 +280,96 @@ std::vector<float> gemvQ40Q80In(const std::vector<uint8_t> &blocks, int rows, in
     a.wd = w.d;
     a.rows = rows;
     a.n = n;
-    a.lanes = w.lanes;
-    a.passes = hipk::gemvDefaultPasses(n, rows, B, true, hipk::EPI_STORE);
+    a.lanes = g.lanes;
+    a.passes = g.passes;
     a.aq = sc.upload(codes);
     a.as = reinterpret_cast<const float2 *>(sc.upload(scales));
-    a.out = sc.alloc<float>((size_t)B * rows);
-    a.ldOut = rows;
+    a.ldOut = rows + g.wgRows;
+    a.out = sc.allocGuarded<float>(B, rows, a.ldOut, "the GEMV output");
     hipk::launchGemv(a, B, hipk::PRO_GLOBAL, hipk::EPI_STORE, true, sc.s);
     sc.sync();
-    return sc.download(a.out, (size_t)B * rows);
+    sc.checkGuards();
+    return sc.downloadRows(a.out, B, rows, a.ldOut);
+}
+
+std::vector<float> gemvF32(const std::vector<float> &w, int rows, int n, const std::vector<float> &in,
+                           const std::vector<float> &residual, const std::vector<float> &normW, float eps, int B,
+                           int pro, int epi, int lanes, int passes, std::vector<float> *xNext) {
+    DL_CHECK(B == 1 || B == 2 || B == 4, "gemv batch must be 1, 2 or 4");
+    DL_CHECK(pro == 0 || pro == 1, "gemv_f32 prologue: 0 global, 1 residual + norm");
+    DL_CHECK(epi == 0 || (epi == 1 && rows % 2 == 0), "gemv_f32 epilogue: 0 store, 1 SwiGLU (even rows)");
+    DL_CHECK(rows > 0 && n > 0 && n % 8 == 0, "gemv_f32: input width must be a multiple of 8");
+    DL_CHECK(w.size() == (size_t)rows * n && in.size() == (size_t)B * n, "gemv_f32 operand sizes");
+    DL_CHECK(pro == 1 || (residual.empty() && normW.empty()), "gemv_f32: the global prologue takes no residual or norm");
+    // no engine launch pairs them (the F32 w13 GEMV always normalizes), so no instance is compiled
+    DL_CHECK(pro == 1 || epi == 0, "gemv_f32: the global prologue has no SwiGLU instance");
+    checkRows(residual, (size_t)B * n, "residual");
+    checkRows(normW, (size_t)n, "norm weights");
+    checkLanes(lanes);
+    DL_CHECK(passes >= 0, "gemv passes must be 0 (default) or >= 1");
+    const int pr = pro == 1 ? hipk::PRO_RESNORM : hipk::PRO_GLOBAL, ep = epi == 1 ? hipk::EPI_ACT : hipk::EPI_STORE;
+    const int L = lanes > 0 ? lanes : hipk::gemvLanesPerRow(n, rows, B, false);
+    const int rp = 256 / L * hipk::gemvRowGroup(B, false);
+    // the default of the shape's own lane count; a forced one keeps its rule (1..4, grid / 1024)
+    const int grid0 = (rows + rp - 1) / rp;
+    const int P = passes > 0 ? passes
+                             : (lanes > 0 ? std::max(1, std::min(4, grid0 / 1024))
+                                          : hipk::gemvDefaultPasses(n, rows, B, false, ep));
+    const int wgRows = rp * P;
+    DL_CHECK(hipk::gemvLdsBytes(n, B, false, wgRows, pr) <= kLdsLimit, "gemv LDS footprint beyond the device limit");
+    Scratch sc;
+    hipk::GemvArgs a;
+    a.wf = sc.upload(w);
+    a.rows = rows;
+    a.n = n;
+    a.lanes = L;
+    a.passes = P;
+    a.in = sc.upload(in);
+    a.ldIn = n;
+    a.addIn = sc.upload(residual);
+    a.xNext = residual.empty() ? nullptr : sc.allocGuarded<float>(1, (size_t)B * n, (size_t)B * n + 256, "xNext");
+    a.normW = sc.upload(normW);
+    a.eps = eps;
+    a.act = 1;
+    const int outRows = epi == 1 ? rows / 2 : rows;
+    a.ldOut = outRows + wgRows;
+    a.out = sc.allocGuarded<float>(B, outRows, a.ldOut, "the GEMV output");
+    hipk::launchGemv(a, B, pr, ep, false, sc.s);
+    sc.sync();
+    sc.checkGuards();
+    if (xNext && a.xNext) *xNext = sc.download(a.xNext, (size_t)B * n);
+    return sc.downloadRows(a.out, B, outRows, a.ldOut);
+}
+
+void gemvDefaults(int rows, int n, int B, bool q40, int epi, int &lanes, int &passes) {
+    lanes = hipk::gemvLanesPerRow(n, rows, q40 ? 1 : B, q40);
+    passes = hipk::gemvDefaultPasses(n, rows, B, q40, epi, q40 ? lanes : 0);
+}
+
+void tileQ40Host(const std::vector<uint8_t> &blocks, int rows, int n, int lanes, bool aos, std::vector<uint8_t> &qs,
+                 std::vector<uint32_t> &d) {
+    DL_CHECK(n > 0 && n % 32 == 0 && rows > 0, "Q40 shape");
+    DL_CHECK(lanes == 16 || lanes == 32 || lanes == 64, "tiling lanes must be 16, 32 or 64");
+    const size_t nb = (size_t)n / 32;
+    DL_CHECK(blocks.size() == (size_t)rows * nb * sizeof(BlockQ40), "Q40 blocks size");
+    const hipk::Q40Tiling t = hipk::q40Tiling(rows, n, lanes);
+    // preset to a pattern neither writer produces as padding: every byte of the image must be written
+    qs.assign(t.qsBytes, 0xEE);
+    d.assign(t.dBytes / 4, 0xEEEEEEEEu);
+    if (aos) {
+        std::vector<const uint8_t *> rowPtr(rows);
+        for (int r = 0; r < rows; r++) rowPtr[r] = blocks.data() + (size_t)r * nb * sizeof(BlockQ40);
+        hipk::tileQ40AoS(rowPtr.data(), rows, n, lanes, qs.data(), d.data());
+        return;
+    }
+    std::vector<uint8_t> nib((size_t)rows * nb * 16);
+    std::vector<uint16_t> sc((size_t)rows * nb);
+    const BlockQ40 *b = reinterpret_cast<const BlockQ40 *>(blocks.data());
+    for (size_t i = 0; i < (size_t)rows * nb; i++) {
+        std::memcpy(&nib[i * 16], b[i].qs, 16);
+        sc[i] = b[i].d;
+    }
+    hipk::tileQ40(nib.data(), sc.data(), rows, n, lanes, qs.data(), d.data());
 }
 
 std::vector<float> gemmQ40(const std::vector<uint8_t> &blocks, int rows, int n, const std::vector<float> &in,
@@ -261,33 +466,37 @@ std::vector<float> gemmF32(const std::vector<float> &w, int rows, int n, const s
 std::vector<float> qkvRope(const std::vector<uint8_t> &blocks, int q0, int kv0, int hs, int n,
                            const std::vector<float> &in, const std::vector<float> &normW, float eps,
                            const std::vector<float> &rope, int seqLen, const std::vector<int> &pos, bool kvBf16,
-                           std::vector<float> *kOut, std::vector<float> *vOut) {
+                           std::vector<float> *kOut, std::vector<float> *vOut, int lanes, int passes) {
     const int B = (int)pos.size(), rows = q0 + 2 * kv0;
     DL_CHECK(B == 1 || B == 2 || B == 4, "qkv batch must be 1, 2 or 4");
     DL_CHECK(hs % 2 == 0 && hs <= 128 && q0 % hs == 0 && kv0 % hs == 0, "qkv head layout");
     DL_CHECK(in.size() == (size_t)B * n && rope.size() == (size_t)seqLen * hs, "qkv operand sizes");
     checkRows(normW, (size_t)n, "norm weights");
     for (int p : pos) DL_CHECK(p >= 0 && p < seqLen, "qkv position out of range");
+    const Q40Geom g = q40Geom(rows, n, B, hipk::EPI_QKV, lanes, passes);
     Scratch sc;
-    const DevQ40 w = uploadQ40(sc, blocks, rows, n);
+    const DevQ40 w = uploadQ40(sc, blocks, rows, n, g.lanes);
     std::vector<int> slots(B);
     for (int b = 0; b < B; b++) slots[b] = b;
-    const size_t cacheElems = (size_t)B * seqLen * kv0;
-    void *kc = kvBf16 ? (void *)sc.alloc<uint16_t>(cacheElems) : (void *)sc.alloc<float>(cacheElems);
-    void *vc = kvBf16 ? (void *)sc.alloc<uint16_t>(cacheElems) : (void *)sc.alloc<float>(cacheElems);
+    // the caches are preset to the guard pattern as a whole (plus a guard after the last slot):
+    // only the B appended rows may change
+    const size_t cacheElems = (size_t)B * seqLen * kv0, cacheGuard = (size_t)g.wgRows * seqLen;
+    const size_t eb = kvBf16 ? 2 : 4;
+    uint8_t *kc = sc.allocGuarded<uint8_t>(1, cacheElems * eb, (cacheElems + cacheGuard) * eb, "the K cache");
+    uint8_t *vc = sc.allocGuarded<uint8_t>(1, cacheElems * eb, (cacheElems + cacheGuard) * eb, "the V cache");
     hipk::GemvArgs a;
     a.qs = w.qs;
     a.wd = w.d;
     a.rows = rows;
     a.n = n;
-    a.lanes = w.lanes;
-    a.passes = hipk::gemvDefaultPasses(n, rows, B, true, hipk::EPI_QKV);
+    a.lanes = g.lanes;
+    a.passes = g.passes;
     a.in = sc.upload(in);
     a.ldIn = n;
     a.normW = sc.upload(normW);
     a.eps = eps;
-    a.out = sc.alloc<float>((size_t)B * q0);
-    a.ldOut = q0;
+    a.ldOut = q0 + g.wgRows;
+    a.out = sc.allocGuarded<float>(B, q0, a.ldOut, "the rotated queries");
     a.q0 = q0;
     a.kv0 = kv0;
     a.hs = hs;
@@ -300,36 +509,36 @@ std::vector<float> qkvRope(const std::vector<uint8_t> &blocks, int q0, int kv0, 
     a.kvBf16 = kvBf16 ? 1 : 0;
     hipk::launchGemv(a, B, hipk::PRO_RESNORM, hipk::EPI_QKV, true, sc.s);
     sc.sync();
-    auto row = [&](void *cache, int b) {  // the [kv0] row of (slot b, pos[b]) from the head-major cache
-        std::vector<float> r(kv0);
-        for (int kh = 0; kh < kv0 / hs; kh++) {
-            const size_t off = hipk::kvOff(hipk::KvMap{}, seqLen, kv0 / hs, hs, b, pos[b], kh);
-            if (kvBf16) {
-                const std::vector<uint16_t> h = sc.download(static_cast<uint16_t *>(cache) + off, hs);
+    sc.checkGuards();
+    // the [kv0] row of (slot b, pos[b]) from each head-major cache; every other element untouched
+    auto rowsOf = [&](const uint8_t *cache, const char *what, std::vector<float> *out) {
+        std::vector<uint8_t> all = sc.download(cache, cacheElems * eb);
+        out->assign((size_t)B * kv0, 0.f);
+        for (int b = 0; b < B; b++)
+            for (int kh = 0; kh < kv0 / hs; kh++) {
+                const size_t off = hipk::kvOff(hipk::KvMap{}, seqLen, kv0 / hs, hs, b, pos[b], kh);
                 for (int i = 0; i < hs; i++) {
-                    const uint32_t u = (uint32_t)h[i] << 16;
-                    std::memcpy(&r[kh * hs + i], &u, 4);
+                    uint32_t u = 0;
+                    if (kvBf16) {
+                        uint16_t h;
+                        std::memcpy(&h, &all[(off + i) * 2], 2);
+                        u = (uint32_t)h << 16;
+                    } else {
+                        std::memcpy(&u, &all[(off + i) * 4], 4);
+                    }
+                    std::memcpy(&(*out)[(size_t)b * kv0 + (size_t)kh * hs + i], &u, 4);
                 }
-            } else {
-                const std::vector<float> f = sc.download(static_cast<float *>(cache) + off, hs);
-                std::copy(f.begin(), f.end(), r.begin() + (size_t)kh * hs);
+                std::memset(&all[off * eb], Scratch::kGuardByte, (size_t)hs * eb);
             }
-        }
-        return r;
+        for (size_t i = 0; i < all.size(); i++)
+            DL_CHECK(all[i] == Scratch::kGuardByte, std::string("ops: the launch wrote outside the appended rows of ") + what);
     };
-    if (kOut) kOut->clear();
-    if (vOut) vOut->clear();
-    for (int b = 0; b < B; b++) {
-        if (kOut) {
-            const std::vector<float> r = row(kc, b);
-            kOut->insert(kOut->end(), r.begin(), r.end());
-        }
-        if (vOut) {
-            const std::vector<float> r = row(vc, b);
-            vOut->insert(vOut->end(), r.begin(), r.end());
-        }
-    }
-    return sc.download(a.out, (size_t)B * q0);
+    std::vector<float> k, v;
+    rowsOf(kc, "the K cache", &k);
+    rowsOf(vc, "the V cache", &v);
+    if (kOut) *kOut = k;
+    if (vOut) *vOut = v;
+    return sc.downloadRows(a.out, B, q0, a.ldOut);
 }
 
 std::vector<float> attention(const std::vector<float> &q, const std::vector<float> &k, const std::vector<float> &v,

@@ -16,14 +16,56 @@ namespace ops {
 // (18 bytes: f16 d + 16 nibble bytes). Prologue: in (+ residual) -> RMS norm with normW (if given,
 // else plain) -> Q80 in LDS. epi 0: out[b][r] = W[r] . xq; epi 1: rows interleaved (w1, w3) pairs,
 // out[b][r/2] = silu(W[2i] . xq) * (W[2i+1] . xq). Returns out; xNext (if residual) = in + residual.
+//
+// Launch geometry of the Q40 ring GEMV ops (gemvQ40, gemvQ40Q80In, qkvRope and the ones below):
+// `lanes` = lanes per row L of the weight tiling and the launch (0: the GEMV's own choice for the
+// shape, else 16, 32 or 64), `passes` = row passes per workgroup (0: the default for the shape,
+// else >= 1). A launch the kernel cannot run is refused (a lane count that has no instance, an
+// LDS footprint beyond the CU's 160 KB, SwiGLU -> Q80 with workgroups of other than whole 64-row
+// blocks). Every output buffer carries a guard region of a fixed bit pattern after each batch
+// row's last valid element (at least one workgroup's rows); the op throws when a launch changed it.
 std::vector<float> gemvQ40(const std::vector<uint8_t> &blocks, int rows, int n, const std::vector<float> &in,
                            const std::vector<float> &residual, const std::vector<float> &normW, float eps, int B,
-                           int epi, std::vector<float> *xNext);
+                           int epi, std::vector<float> *xNext, int lanes = 0, int passes = 0);
 
 // Same weights, activations already Q80 (the wo / w2 path: prologue-free, Q80 blocks read from
 // global): `in` is quantized on the host with the reference Q80 quantizer first.
 std::vector<float> gemvQ40Q80In(const std::vector<uint8_t> &blocks, int rows, int n, const std::vector<float> &in,
-                                int B);
+                                int B, int lanes = 0, int passes = 0);
+
+// The w13 hand-off of a decode step (PRO_RESNORM + EPI_ACT_Q80): rows are interleaved (w1, w3)
+// pairs, rows % 64 == 0; the SwiGLU row is quantized to Q80 blocks of 32 hidden units. codes =
+// [B][rows/2] int8, scales = [B][rows/64] (d, sum of codes) pairs as [B][rows/64][2] floats.
+void gemvQ40SwigluQ80(const std::vector<uint8_t> &blocks, int rows, int n, const std::vector<float> &in,
+                      const std::vector<float> &residual, const std::vector<float> &normW, float eps, int B,
+                      int lanes, int passes, std::vector<int8_t> &codes, std::vector<float> &scales);
+
+// The fused greedy logits GEMV (PRO_RESNORM + EPI_ARGMAX, one row, one rank): returns
+// vocabStart + the argmax row (ties -> lowest). The partials are sized to the launch's grid and the
+// arrival counter starts at zero; `repeat` launches run on the same scratch (the counter resets
+// itself) and must all give the same id; the op throws if they do not or if the counter is not
+// back to zero.
+int gemvQ40Argmax(const std::vector<uint8_t> &blocks, int rows, int n, const std::vector<float> &in,
+                  const std::vector<float> &residual, const std::vector<float> &normW, float eps, int vocabStart,
+                  int lanes, int passes, int repeat);
+
+// F32-weight GEMV (gemvKernel; w = [rows][n] row-major), B = 1, 2 or 4. pro 0: PRO_GLOBAL (f32
+// rows read straight from global; no residual, no norm), 1: PRO_RESNORM (in (+ residual) -> RMS norm
+// with normW if given -> f32 in LDS). epi 0: EPI_STORE, 1: EPI_ACT (interleaved (w1, w3) rows;
+// PRO_RESNORM only: the engine never launches PRO_GLOBAL + EPI_ACT and no instance exists, refused).
+// lanes / passes as above (one row per lane group: 256 / L rows per pass).
+std::vector<float> gemvF32(const std::vector<float> &w, int rows, int n, const std::vector<float> &in,
+                           const std::vector<float> &residual, const std::vector<float> &normW, float eps, int B,
+                           int pro, int epi, int lanes, int passes, std::vector<float> *xNext);
+
+// Host side of the launches above, no device needed. gemvDefaults: the (lanes, passes) the engine
+// takes for a matrix of this shape (gemvLanesPerRow at one row, gemvDefaultPasses with that tiling;
+// epi: 0 store, 1 SwiGLU, 2 QKV, 3 SwiGLU -> Q80, 7 argmax). tileQ40Host: the tiled device image
+// (Q40Tiling, kernels.h) of `blocks` written by tileQ40 (aos false: from split nibble / scale
+// arrays) or tileQ40AoS (from the file's 18-byte blocks).
+void gemvDefaults(int rows, int n, int B, bool q40, int epi, int &lanes, int &passes);
+void tileQ40Host(const std::vector<uint8_t> &blocks, int rows, int n, int lanes, bool aos, std::vector<uint8_t> &qs,
+                 std::vector<uint32_t> &d);
 
 // Batched F32 matmul on MFMA: norm kernel -> f16 -> gemmF32Kernel (store epilogue).
 std::vector<float> gemmF32(const std::vector<float> &w, int rows, int n, const std::vector<float> &in,
@@ -39,7 +81,7 @@ std::vector<float> gemmQ40(const std::vector<uint8_t> &blocks, int rows, int n, 
 std::vector<float> qkvRope(const std::vector<uint8_t> &blocks, int q0, int kv0, int hs, int n,
                            const std::vector<float> &in, const std::vector<float> &normW, float eps,
                            const std::vector<float> &rope, int seqLen, const std::vector<int> &pos, bool kvBf16,
-                           std::vector<float> *kOut, std::vector<float> *vOut);
+                           std::vector<float> *kOut, std::vector<float> *vOut, int lanes = 0, int passes = 0);
 
 // Decode attention over caches k/v [nSlots][seqLen][kv0] (f32 values, stored bf16 when kvBf16),
 // q [B][nHeads0*hs] (already rotated), row b at position pos[b] in slot slot[b]. Returns f32 [B][q0].

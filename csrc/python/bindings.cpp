@@ -199,34 +199,103 @@ void bindOps(py::module_ &m) {
     // runs with it released
     py::module_ o = m.def_submodule("ops", "single-kernel entry points (csrc/hip/ops.h) for numerics tests");
     o.def("gemv_q40",
-          [](py::object blocks, int rows, int n, py::object x, py::object residual, py::object normW, float eps, int epi) {
+          [](py::object blocks, int rows, int n, py::object x, py::object residual, py::object normW, float eps, int epi,
+             int lanes, int passes) {
               const std::vector<uint8_t> w = vec<uint8_t>(blocks);
               const std::vector<float> in = vec<float>(x), res = vec<float>(residual), nw = vec<float>(normW);
               const int B = (int)(in.size() / n);
               std::vector<float> out, xn;
               {
                   py::gil_scoped_release rel;
-                  out = ops::gemvQ40(w, rows, n, in, res, nw, eps, B, epi, &xn);
+                  out = ops::gemvQ40(w, rows, n, in, res, nw, eps, B, epi, &xn, lanes, passes);
               }
               py::object xo = py::none();
               if (!xn.empty()) xo = arr(xn, {B, n});
               return py::make_tuple(arr(out, {B, (py::ssize_t)(out.size() / B)}), xo);
           },
           py::arg("blocks"), py::arg("rows"), py::arg("n"), py::arg("x"), py::arg("residual") = py::none(),
-          py::arg("norm_w") = py::none(), py::arg("eps") = 1e-5f, py::arg("epi") = 0);
+          py::arg("norm_w") = py::none(), py::arg("eps") = 1e-5f, py::arg("epi") = 0, py::arg("lanes") = 0,
+          py::arg("passes") = 0);
     o.def("gemv_q40_q80_in",
-          [](py::object blocks, int rows, int n, py::object x) {
+          [](py::object blocks, int rows, int n, py::object x, int lanes, int passes) {
               const std::vector<uint8_t> w = vec<uint8_t>(blocks);
               const std::vector<float> in = vec<float>(x);
               const int B = (int)(in.size() / n);
               std::vector<float> out;
               {
                   py::gil_scoped_release rel;
-                  out = ops::gemvQ40Q80In(w, rows, n, in, B);
+                  out = ops::gemvQ40Q80In(w, rows, n, in, B, lanes, passes);
               }
               return arr(out, {B, rows});
           },
-          py::arg("blocks"), py::arg("rows"), py::arg("n"), py::arg("x"));
+          py::arg("blocks"), py::arg("rows"), py::arg("n"), py::arg("x"), py::arg("lanes") = 0, py::arg("passes") = 0);
+    o.def("gemv_q40_swiglu_q80",
+          [](py::object blocks, int rows, int n, py::object x, py::object residual, py::object normW, float eps, int lanes,
+             int passes) {
+              const std::vector<uint8_t> w = vec<uint8_t>(blocks);
+              const std::vector<float> in = vec<float>(x), res = vec<float>(residual), nw = vec<float>(normW);
+              const int B = (int)(in.size() / n);
+              std::vector<int8_t> codes;
+              std::vector<float> scales;
+              {
+                  py::gil_scoped_release rel;
+                  ops::gemvQ40SwigluQ80(w, rows, n, in, res, nw, eps, B, lanes, passes, codes, scales);
+              }
+              return py::make_tuple(arr(codes, {B, (py::ssize_t)rows / 2}), arr(scales, {B, (py::ssize_t)rows / 64, 2}));
+          },
+          py::arg("blocks"), py::arg("rows"), py::arg("n"), py::arg("x"), py::arg("residual") = py::none(),
+          py::arg("norm_w") = py::none(), py::arg("eps") = 1e-5f, py::arg("lanes") = 0, py::arg("passes") = 0);
+    o.def("gemv_q40_argmax",
+          [](py::object blocks, int rows, int n, py::object x, py::object residual, py::object normW, float eps,
+             int vocabStart, int lanes, int passes, int repeat) {
+              const std::vector<uint8_t> w = vec<uint8_t>(blocks);
+              const std::vector<float> in = vec<float>(x), res = vec<float>(residual), nw = vec<float>(normW);
+              int id;
+              {
+                  py::gil_scoped_release rel;
+                  id = ops::gemvQ40Argmax(w, rows, n, in, res, nw, eps, vocabStart, lanes, passes, repeat);
+              }
+              return id;
+          },
+          py::arg("blocks"), py::arg("rows"), py::arg("n"), py::arg("x"), py::arg("residual") = py::none(),
+          py::arg("norm_w") = py::none(), py::arg("eps") = 1e-5f, py::arg("vocab_start") = 0, py::arg("lanes") = 0,
+          py::arg("passes") = 0, py::arg("repeat") = 1);
+    o.def("gemv_f32",
+          [](py::object wts, int rows, int n, py::object x, py::object residual, py::object normW, float eps, int pro,
+             int epi, int lanes, int passes) {
+              const std::vector<float> w = vec<float>(wts), in = vec<float>(x), res = vec<float>(residual),
+                                       nw = vec<float>(normW);
+              const int B = (int)(in.size() / n);
+              std::vector<float> out, xn;
+              {
+                  py::gil_scoped_release rel;
+                  out = ops::gemvF32(w, rows, n, in, res, nw, eps, B, pro, epi, lanes, passes, &xn);
+              }
+              py::object xo = py::none();
+              if (!xn.empty()) xo = arr(xn, {B, n});
+              return py::make_tuple(arr(out, {B, (py::ssize_t)(out.size() / B)}), xo);
+          },
+          py::arg("w"), py::arg("rows"), py::arg("n"), py::arg("x"), py::arg("residual") = py::none(),
+          py::arg("norm_w") = py::none(), py::arg("eps") = 1e-5f, py::arg("pro") = 1, py::arg("epi") = 0,
+          py::arg("lanes") = 0, py::arg("passes") = 0);
+    o.def("gemv_defaults",
+          [](int rows, int n, int B, bool q40, int epi) {
+              int lanes = 0, passes = 0;
+              ops::gemvDefaults(rows, n, B, q40, epi, lanes, passes);
+              return py::make_tuple(lanes, passes);
+          },
+          py::arg("rows"), py::arg("n"), py::arg("batch") = 1, py::arg("q40") = true, py::arg("epi") = 0,
+          "(lanes per row, passes) the engine takes for a matrix of this shape; no device needed");
+    o.def("tile_q40",
+          [](py::object blocks, int rows, int n, int lanes, bool aos) {
+              const std::vector<uint8_t> w = vec<uint8_t>(blocks);
+              std::vector<uint8_t> qs;
+              std::vector<uint32_t> d;
+              ops::tileQ40Host(w, rows, n, lanes, aos, qs, d);
+              return py::make_tuple(arr(qs, {(py::ssize_t)qs.size()}), arr(d, {(py::ssize_t)d.size()}));
+          },
+          py::arg("blocks"), py::arg("rows"), py::arg("n"), py::arg("lanes"), py::arg("aos") = false,
+          "the tiled device image (nibble bytes, u32 scale pairs) written by tileQ40 / tileQ40AoS; no device needed");
     o.def("gemm_q40",
           [](py::object blocks, int rows, int n, py::object x, py::object residual, py::object normW, float eps,
              int splits) {
@@ -257,19 +326,20 @@ void bindOps(py::module_ &m) {
           py::arg("eps") = 1e-5f);
     o.def("qkv_rope",
           [](py::object blocks, int q0, int kv0, int hs, int n, py::object x, py::object normW, float eps, py::object rope,
-             int seqLen, std::vector<int> pos, bool kvBf16) {
+             int seqLen, std::vector<int> pos, bool kvBf16, int lanes, int passes) {
               const std::vector<uint8_t> w = vec<uint8_t>(blocks);
               const std::vector<float> in = vec<float>(x), nw = vec<float>(normW), rp = vec<float>(rope);
               std::vector<float> k, v, q;
               {
                   py::gil_scoped_release rel;
-                  q = ops::qkvRope(w, q0, kv0, hs, n, in, nw, eps, rp, seqLen, pos, kvBf16, &k, &v);
+                  q = ops::qkvRope(w, q0, kv0, hs, n, in, nw, eps, rp, seqLen, pos, kvBf16, &k, &v, lanes, passes);
               }
               const py::ssize_t B = (py::ssize_t)pos.size();
               return py::make_tuple(arr(q, {B, q0}), arr(k, {B, kv0}), arr(v, {B, kv0}));
           },
           py::arg("blocks"), py::arg("q0"), py::arg("kv0"), py::arg("head_size"), py::arg("n"), py::arg("x"),
-          py::arg("norm_w"), py::arg("eps"), py::arg("rope"), py::arg("seq_len"), py::arg("pos"), py::arg("kv_bf16") = true);
+          py::arg("norm_w"), py::arg("eps"), py::arg("rope"), py::arg("seq_len"), py::arg("pos"), py::arg("kv_bf16") = true,
+          py::arg("lanes") = 0, py::arg("passes") = 0);
     o.def("attention",
           [](py::object q, py::object k, py::object v, int nSlots, int seqLen, int nHeads0, int kvMul, int hs,
              std::vector<int> pos, std::vector<int> slot, bool kvBf16, int impl) {

@@ -43,18 +43,59 @@ def dequantize_q80(x: torch.Tensor) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------- HIP kernels
-def gemv_q40(blocks, rows: int, n: int, x, residual=None, norm_w=None, eps: float = 1e-5, swiglu: bool = False):
+def gemv_q40(blocks, rows: int, n: int, x, residual=None, norm_w=None, eps: float = 1e-5, swiglu: bool = False,
+             epilogue: str | None = None, lanes: int = 0, passes: int = 0):
     """Decode GEMV (1, 2 or 4 rows): (x + residual) -> RMS norm (norm_w) -> Q80 -> W.x.
-    swiglu: rows are interleaved (w1, w3) pairs and the result is silu(w1.x) * (w3.x).
-    Returns (out [B, rows or rows/2], x + residual or None)."""
+    swiglu (or epilogue="swiglu"): rows are interleaved (w1, w3) pairs and the result is
+    silu(w1.x) * (w3.x). Returns (out [B, rows or rows/2], x + residual or None).
+    epilogue="swiglu_q80": the SwiGLU row quantized to Q80 as the w13 hand-off of a decode step
+    stores it; returns (int8 codes [B, rows/2], (d, sum of codes) pairs [B, rows/64, 2]).
+    lanes (0, 16, 32, 64) / passes (0, >= 1) force the launch geometry (0: the engine's choice);
+    every output buffer is guarded, a store past its valid part raises."""
+    epilogue = epilogue or ("swiglu" if swiglu else "store")
+    if epilogue == "swiglu_q80":
+        codes, scales = native().ops.gemv_q40_swiglu_q80(_np(blocks, np.uint8), rows, n, _np(x), _np(residual),
+                                                         _np(norm_w), eps, lanes, passes)
+        return torch.from_numpy(codes), torch.from_numpy(scales)
     out, xn = native().ops.gemv_q40(_np(blocks, np.uint8), rows, n, _np(x), _np(residual), _np(norm_w), eps,
-                                    1 if swiglu else 0)
+                                    {"store": 0, "swiglu": 1}[epilogue], lanes, passes)
     return torch.from_numpy(out), (torch.from_numpy(xn) if xn is not None else None)
 
 
-def gemv_q40_q80_in(blocks, rows: int, n: int, x) -> torch.Tensor:
+def gemv_q40_q80_in(blocks, rows: int, n: int, x, lanes: int = 0, passes: int = 0) -> torch.Tensor:
     """Decode GEMV on activations handed over as Q80 blocks (the wo / w2 path)."""
-    return torch.from_numpy(native().ops.gemv_q40_q80_in(_np(blocks, np.uint8), rows, n, _np(x)))
+    return torch.from_numpy(native().ops.gemv_q40_q80_in(_np(blocks, np.uint8), rows, n, _np(x), lanes, passes))
+
+
+def gemv_q40_argmax(blocks, rows: int, n: int, x, residual=None, norm_w=None, eps: float = 1e-5,
+                    vocab_start: int = 0, lanes: int = 0, passes: int = 0, repeat: int = 1) -> int:
+    """Fused greedy logits GEMV (one row): vocab_start + argmax of W.x without storing the logits,
+    ties to the lowest row. repeat > 1 launches again on the same scratch; all ids must agree."""
+    return native().ops.gemv_q40_argmax(_np(blocks, np.uint8), rows, n, _np(x), _np(residual), _np(norm_w), eps,
+                                        vocab_start, lanes, passes, repeat)
+
+
+def gemv_f32(w, x, residual=None, norm_w=None, eps: float = 1e-5, prologue: str = "resnorm", swiglu: bool = False,
+             lanes: int = 0, passes: int = 0):
+    """F32-weight decode GEMV (1, 2 or 4 rows), w [rows, n]. prologue "resnorm": (x + residual) ->
+    RMS norm (norm_w) staged in LDS; "global": x read straight from global memory. Returns
+    (out [B, rows or rows/2], x + residual or None)."""
+    rows, n = w.shape
+    out, xn = native().ops.gemv_f32(_np(w), rows, n, _np(x), _np(residual), _np(norm_w), eps,
+                                    {"global": 0, "resnorm": 1}[prologue], 1 if swiglu else 0, lanes, passes)
+    return torch.from_numpy(out), (torch.from_numpy(xn) if xn is not None else None)
+
+
+def gemv_defaults(rows: int, n: int, batch: int = 1, q40: bool = True, epilogue: str = "store"):
+    """(lanes per row, passes) the engine takes for a matrix of this shape (host only)."""
+    epi = {"store": 0, "swiglu": 1, "qkv": 2, "swiglu_q80": 3, "argmax": 7}[epilogue]
+    return native().ops.gemv_defaults(rows, n, batch, q40, epi)
+
+
+def tile_q40(blocks, rows: int, n: int, lanes: int, aos: bool = False):
+    """Tiled device image of file-layout Q40 blocks (host only): (uint8 nibble bytes, uint32 scale
+    pairs), written by tileQ40 (aos=False) or tileQ40AoS (aos=True)."""
+    return native().ops.tile_q40(_np(blocks, np.uint8), rows, n, lanes, aos)
 
 
 def gemm_q40(blocks, rows: int, n: int, x, residual=None, norm_w=None, eps: float = 1e-5,
@@ -74,10 +115,10 @@ def gemm_f32(w, x, norm_w=None, eps: float = 1e-5) -> torch.Tensor:
 
 
 def qkv_rope(blocks, q0: int, kv0: int, head_size: int, n: int, x, norm_w, eps: float, rope, seq_len: int,
-             pos, kv_bf16: bool = True):
+             pos, kv_bf16: bool = True, lanes: int = 0, passes: int = 0):
     """QKV GEMV with the RoPE + KV-cache-append epilogue. Returns (q rotated, k row, v row)."""
     q, k, v = native().ops.qkv_rope(_np(blocks, np.uint8), q0, kv0, head_size, n, _np(x), _np(norm_w), eps,
-                                    _np(rope), seq_len, [int(p) for p in pos], kv_bf16)
+                                    _np(rope), seq_len, [int(p) for p in pos], kv_bf16, lanes, passes)
     return torch.from_numpy(q), torch.from_numpy(k), torch.from_numpy(v)
 
 
