@@ -509,7 +509,8 @@ void HipEngineImpl::gemmBatched(const DevMat &m, int n, int epi, const MatOperan
     // tokens per launch: the wide Q40 kernel takes the whole forward in one launch (one weight
     // pass per token tile, all tiles of a row tile on one XCD), the narrow one <= 128
     // (batch-invariant engines: narrow launches only, the split count of a 16-token launch for all)
-    const int chunk = q40_ ? (hipk::gemmUsesWide(n) && !invariant_ ? n : kGemmMaxTokens) : hipk::kGemmF32MaxTokens;
+    // (a width the wide kernel cannot split into its two-block stages: narrow launches too)
+    const int chunk = hipk::gemmChunkTokens(m.n, n, q40_, invariant_);
     for (int c0 = 0; c0 < n; c0 += chunk) {
         const int bc = std::min(chunk, n - c0);
         xChunk_ = c0 / chunk;  // each launch's tile exchange waits in a measured-sync slot of its own

@@ -431,8 +431,21 @@ bool gemmTpxFits(int M, int world, bool q80) {
     return need <= (size_t)stg * gemmStageBytes(MT, gemmRowTiles(M));
 }
 
+GemmKernel gemmKernelFor(int n, int M, int lanes, int splits, bool fixed) {
+    if (fixed) return GEMM_NARROW;
+    if (gemmUsesWide(M)) return GEMM_WIDE;
+    return gemmL16Eligible(n, M, lanes) && splits > 0 && (n / 32 / kG16Ch) % splits == 0 ? GEMM_L16 : GEMM_NARROW;
+}
+
+int gemmChunkTokens(int n, int M, bool q40, bool fixed) {
+    if (!q40) return kGemmF32MaxTokens;
+    if (!gemmUsesWide(M) || fixed) return kGemmMaxTokens;
+    return gemmWideAccepts(n, 1) ? M : std::min(kGemmMaxTokens, gemmWideMin() - 1);
+}
+
 void launchGemmQ40(const GemmArgs &ga, int epi, hipStream_t s) {
-    if (gemmUsesWide(ga.M) && !ga.fixed) {
+    const GemmKernel kernel = gemmKernelFor(ga.e.n, ga.M, ga.e.lanes, ga.splits, ga.fixed != 0);
+    if (kernel == GEMM_WIDE) {
         launchGemmWide(ga, epi, s);
         return;
     }
@@ -445,7 +458,7 @@ void launchGemmQ40(const GemmArgs &ga, int epi, hipStream_t s) {
     const int tiles = (ga.e.rows + kGemmRows - 1) / kGemmRows;
     const int MT = gemmTokenPad(ga.M) / 16;
     const dim3 grid(tiles, ga.splits);
-    if (!ga.fixed && gemmL16Eligible(ga.e.n, ga.M, ga.e.lanes) && (ga.e.n / 32 / kG16Ch) % ga.splits == 0) {
+    if (kernel == GEMM_L16) {
         const size_t lds = 2 * (size_t)gemm16StageBytes(MT) + 16 + kGemmScaleFloats * 4;
 #define DL_G16_CASE(M_, E)                                                                         \
     if (MT == M_ && epi == E) {                                                                    \

@@ -64,6 +64,9 @@ int gemmWideSplits(int rows, int n, int M) {
     return S;
 }
 
+// a stage is two Q40 blocks: every split must be a whole number of stages
+bool gemmWideAccepts(int n, int splits) { return splits >= 1 && n % 64 == 0 && (n / 32) % (kWKB * splits) == 0; }
+
 size_t gemmWidePartFloats(int rows, int n, int maxTokens) {
     const int rowTiles = (rows + kWRows - 1) / kWRows;
     size_t best = 0;
@@ -207,7 +210,7 @@ const void *gemmWideModuleKernel() { return (const void *)gemmWideKernel<EPI_STO
 
 void launchGemmWide(const GemmArgs &ga, int epi, hipStream_t s) {
     const int rowTiles = (ga.e.rows + kWRows - 1) / kWRows, tokTiles = (ga.M + kWTok - 1) / kWTok;
-    if (ga.e.n % 64 != 0 || (ga.e.n / 32) % (kWKB * ga.splits) != 0) throw Error("launchGemmWide: bad K split");
+    if (!gemmWideAccepts(ga.e.n, ga.splits)) throw Error("launchGemmWide: bad K split");
     if (ga.splits > 1 && (!ga.part || !ga.counters)) throw Error("launchGemmWide: split-K without buffers");
     const dim3 grid(rowTiles * tokTiles * ga.splits);
 #define DL_GEMMW_CASE(E)                                                                              \

@@ -270,6 +270,16 @@ struct GemmArgs {
     int fixed = 0;
 };
 void launchGemmQ40(const GemmArgs &a, int epi, hipStream_t s);
+// The kernel launchGemmQ40 runs for a launch of M tokens on a matrix of input width n tiled at
+// `lanes`, with `splits` K splits (host query, no device needed): the wide 128 x 128 tiles, the
+// 16-block-chunk kernel of 16-lane tilings, or the narrow 64-row tiles.
+enum GemmKernel : int { GEMM_NARROW = 0, GEMM_L16 = 1, GEMM_WIDE = 2 };
+GemmKernel gemmKernelFor(int n, int M, int lanes, int splits, bool fixed);
+// Tokens per launch of a forward of M tokens over a matrix of input width n: the whole forward in
+// one wide launch where the wide kernel takes it, else <= 128 (Q40) / <= 64 (F32) per narrow launch.
+// The wide kernel streams two Q40 blocks per stage, so a width that is no multiple of 64 stays on
+// narrow launches below its token threshold.
+int gemmChunkTokens(int n, int M, bool q40, bool fixed);
 // Same contract for F32 weights (`e.wf` [rows][n] row-major; EPI_ACT_Q80 not supported).
 void launchGemmF32(const GemmArgs &a, int epi, hipStream_t s);
 // Tile / split-K plan of one matrix (rt = 16-row tiles per wave: 64 * rt rows per workgroup).
@@ -286,6 +296,7 @@ bool gemmUsesWide(int M);
 int gemmWideSplits(int rows, int n, int M);
 size_t gemmWidePartFloats(int rows, int n, int maxTokens);
 int gemmWideCounters(int rows, int maxTokens);
+bool gemmWideAccepts(int n, int splits);  // whole two-block stages per split (else launchGemmWide throws)
 void launchGemmWide(const GemmArgs &a, int epi, hipStream_t s);
 // whether a narrow launch of M tokens can run the tensor-parallel tile exchange (GemmArgs::tpx)
 bool gemmTpxFits(int M, int world, bool q80);

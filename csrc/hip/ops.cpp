@@ -67,6 +67,20 @@ class Scratch {
         guards_.push_back({static_cast<uint8_t *>(p), rows, valid * sizeof(T), ld * sizeof(T), what});
         return static_cast<T *>(p);
     }
+    // ... followed by `tail` whole guard rows (a store to a row past the last valid one); here the
+    // rows may be all valid (ld == valid: no room for a guard inside the row)
+    template <typename T>
+    T *allocGuardedTail(size_t rows, size_t valid, size_t ld, size_t tail, const char *what) {
+        DL_CHECK(ld >= valid && rows > 0 && tail > 0, "guarded buffer needs a guard region");
+        void *p = nullptr;
+        const size_t bytes = (rows + tail) * ld * sizeof(T);
+        DL_HIP(hipMalloc(&p, bytes));
+        mem_.push_back(p);
+        DL_HIP(hipMemsetAsync(p, kGuardByte, bytes, s));
+        guards_.push_back({static_cast<uint8_t *>(p), rows, valid * sizeof(T), ld * sizeof(T), what});
+        guards_.push_back({static_cast<uint8_t *>(p) + rows * ld * sizeof(T), tail, 0, ld * sizeof(T), what});
+        return static_cast<T *>(p);
+    }
     void checkGuards() {
         for (const Guard &g : guards_) {
             const std::vector<uint8_t> v = download(g.p, g.rows * g.ld);
@@ -151,6 +165,38 @@ DevQ40 uploadQ40(Scratch &sc, const std::vector<uint8_t> &blocks, int rows, int 
     m.qs = sc.upload(qt);
     m.d = reinterpret_cast<uint16_t *>(sc.upload(dt));
     return m;
+}
+
+// The [kv0] cache row of (slot[b], pos[b]) for every b from a head-major cache preset to the guard
+// pattern as a whole (f32 view of the bf16 or f32 elements); throws when any other element changed.
+void appendedRows(Scratch &sc, const uint8_t *cache, size_t cacheElems, int seqLen, int kv0, int hs,
+                  const std::vector<int> &pos, const std::vector<int> &slot, bool kvBf16, const char *what,
+                  std::vector<float> *out) {
+    const size_t eb = kvBf16 ? 2 : 4;
+    const int B = (int)pos.size();
+    std::vector<uint8_t> all = sc.download(cache, cacheElems * eb);
+    out->assign((size_t)B * kv0, 0.f);
+    for (int b = 0; b < B; b++)
+        for (int kh = 0; kh < kv0 / hs; kh++) {
+            const size_t off = hipk::kvOff(hipk::KvMap{}, seqLen, kv0 / hs, hs, slot[b], pos[b], kh);
+            for (int i = 0; i < hs; i++) {
+                uint32_t u = 0;
+                if (kvBf16) {
+                    uint16_t h;
+                    std::memcpy(&h, &all[(off + i) * 2], 2);
+                    u = (uint32_t)h << 16;
+                } else {
+                    std::memcpy(&u, &all[(off + i) * 4], 4);
+                }
+                std::memcpy(&(*out)[(size_t)b * kv0 + (size_t)kh * hs + i], &u, 4);
+            }
+        }
+    for (int b = 0; b < B; b++)
+        for (int kh = 0; kh < kv0 / hs; kh++)
+            std::memset(&all[hipk::kvOff(hipk::KvMap{}, seqLen, kv0 / hs, hs, slot[b], pos[b], kh) * eb],
+                        Scratch::kGuardByte, (size_t)hs * eb);
+    for (size_t i = 0; i < all.size(); i++)
+        DL_CHECK(all[i] == Scratch::kGuardByte, std::string("ops: the launch wrote outside the appended rows of ") + what);
 }
 
 void checkRows(const std::vector<float> &v, size_t want, const char *what) {
@@ -463,6 +509,241 @@ std::vector<float> gemmF32(const std::vector<float> &w, int rows, int n, const s
     return sc.download(out, (size_t)M * rows);
 }
 
+std::vector<GemmLaunch> gemmBatchedPlan(const GemmBatchedArgs &a) {
+    const bool q40 = a.wf.empty();
+    const int rows = a.rows, n = a.n, M = a.M;
+    DL_CHECK(rows > 0 && n > 0 && hipk::gemmSupported(n), "gemm input width must be a multiple of 32");
+    DL_CHECK(M >= 1 && M <= 2048, "gemm tokens must be 1..2048");
+    if (q40) {
+        checkLanes(a.lanes);
+        DL_CHECK(a.blocks.size() == (size_t)rows * (n / 32) * sizeof(BlockQ40), "Q40 blocks size");
+    } else {
+        DL_CHECK(a.blocks.empty() && a.wf.size() == (size_t)rows * n, "gemm F32 weights size");
+    }
+    DL_CHECK(a.in.size() == (size_t)M * n, "gemm input size");
+    if (a.input == GEMM_IN_NORM) {
+        checkRows(a.residual, (size_t)M * n, "residual");
+        checkRows(a.normW, (size_t)n, "norm weights");
+    } else {
+        DL_CHECK(a.input == GEMM_IN_F16 || a.input == GEMM_IN_PRENORM, "gemm input mode");
+        DL_CHECK(a.residual.empty() && a.normW.empty(), "gemm: f16 / prenorm rows take no residual or norm weights");
+    }
+    const bool ssUsed = a.input == GEMM_IN_PRENORM || a.epi == hipk::EPI_RES;
+    DL_CHECK(!ssUsed || a.ldSS >= M, "gemm ldSS must be at least the token count");
+    if (a.input == GEMM_IN_PRENORM)
+        DL_CHECK(a.ssTiles >= 1 && a.ss.size() == (size_t)a.ssTiles * a.ldSS, "gemm prenorm sums of squares: [ssTiles][ldSS]");
+    switch (a.epi) {
+        case hipk::EPI_STORE: break;
+        case hipk::EPI_ACT_F16: DL_CHECK(rows % 2 == 0, "gemm SwiGLU: rows are (w1, w3) pairs"); break;
+        case hipk::EPI_RES:
+            DL_CHECK(rows % 2 == 0, "gemm EPI_RES: the epilogue stores whole row pairs (even rows)");
+            DL_CHECK(a.resIn.size() == (size_t)M * rows && a.resW.size() == (size_t)rows, "gemm EPI_RES operand sizes");
+            break;
+        case hipk::EPI_QKV:
+            DL_CHECK((a.hs == 64 || a.hs == 128) && a.q0 > 0 && a.kv0 > 0 && a.q0 % a.hs == 0 && a.kv0 % a.hs == 0 &&
+                         rows == a.q0 + 2 * a.kv0, "qkv head layout");
+            DL_CHECK(a.seqLen > 0 && a.nSlots > 0 && a.rope.size() == (size_t)a.seqLen * a.hs &&
+                         a.pos.size() == (size_t)M && a.slot.size() == (size_t)M, "qkv operand sizes");
+            for (int t = 0; t < M; t++)
+                DL_CHECK(a.pos[t] >= 0 && a.pos[t] < a.seqLen && a.slot[t] >= 0 && a.slot[t] < a.nSlots,
+                         "qkv position / slot out of range");
+            break;
+        default: throw Error("gemm epilogue: the engine launches only store, SwiGLU -> f16, residual and QKV on a GEMM");
+    }
+    DL_CHECK(a.splits >= 0 && a.chunk >= 0 && (a.fixed == 0 || a.fixed == 1), "gemm launch controls");
+    const int L = q40 ? (a.lanes > 0 ? a.lanes : hipk::gemvLanesPerRow(n, rows, 1, true)) : 0;
+    const int chunk = a.chunk > 0 ? a.chunk : hipk::gemmChunkTokens(n, M, q40, a.fixed != 0);
+    const int tiles = (rows + 63) / 64;
+    std::vector<GemmLaunch> plan;
+    for (int c0 = 0; c0 < M; c0 += chunk) {
+        GemmLaunch l;
+        l.c0 = c0;
+        l.M = std::min(chunk, M - c0);
+        l.splits = a.splits > 0 ? a.splits : a.fixed ? hipk::gemmSplits(rows, n, 16, 0) : hipk::gemmSplits(rows, n, l.M, L);
+        DL_CHECK((n / 32) % l.splits == 0, "gemm splits must divide n / 32");
+        l.grid = tiles * l.splits;
+        if (q40) {
+            l.kernel = hipk::gemmKernelFor(n, l.M, L, l.splits, a.fixed != 0);
+            if (l.kernel == hipk::GEMM_WIDE) {
+                DL_CHECK(hipk::gemmWideAccepts(n, l.splits), "wide gemm: bad K split (whole two-block stages per split)");
+                l.grid = (rows + 127) / 128 * ((l.M + 127) / 128) * l.splits;
+            } else {
+                DL_CHECK(l.M <= hipk::kGemmMaxTokens, "gemm: more than 128 tokens per narrow launch");
+            }
+        } else {
+            l.kernel = 3;
+            DL_CHECK(l.M <= hipk::kGemmF32MaxTokens, "gemm: more than 64 tokens per F32 launch");
+        }
+        plan.push_back(l);
+    }
+    return plan;
+}
+
+int gemmSplitsFor(int rows, int n, int M, int lanes) {
+    DL_CHECK(rows > 0 && n > 0 && n % 32 == 0 && M >= 1, "gemm shape");
+    return hipk::gemmSplits(rows, n, M, lanes);
+}
+
+GemmBatchedResult gemmBatched(const GemmBatchedArgs &a) {
+    const std::vector<GemmLaunch> plan = gemmBatchedPlan(a);  // refusals: before any device work
+    const bool q40 = a.wf.empty();
+    const int rows = a.rows, n = a.n, M = a.M, epi = a.epi;
+    Scratch sc;
+    DevQ40 w;
+    const float *wf = nullptr;
+    if (q40)
+        w = uploadQ40(sc, a.blocks, rows, n, a.lanes);
+    else
+        wf = sc.upload(a.wf);
+    // activations: rows past a launch's tokens are read by design (token tiles of 16..128), zeroed here
+    _Float16 *xh = sc.alloc<_Float16>((size_t)(M + 128) * n);
+    hipk::GemvArgs nq;
+    if (a.input == GEMM_IN_NORM) {
+        nq.n = n;
+        nq.in = sc.upload(a.in);
+        nq.ldIn = n;
+        nq.addIn = sc.upload(a.residual);
+        nq.normW = sc.upload(a.normW);
+        nq.eps = a.eps;
+    } else {
+        std::vector<uint16_t> h(a.in.size());
+        for (size_t i = 0; i < h.size(); i++) h[i] = f32ToF16(a.in[i]);
+        DL_HIP(hipMemcpyAsync(xh, h.data(), h.size() * 2, hipMemcpyHostToDevice, sc.s));
+        DL_HIP(hipStreamSynchronize(sc.s));
+    }
+    const float *ssIn = a.input == GEMM_IN_PRENORM ? sc.upload(a.ss) : nullptr;
+    // outputs: a guard after each token row's valid columns and whole guard rows after the last token
+    // (as many as the last token tile's padding, so a store of any dropped token lands in one)
+    const int outCols = epi == hipk::EPI_ACT_F16 ? rows / 2 : epi == hipk::EPI_QKV ? a.q0 : rows;
+    const int ldOut = outCols + 128;
+    const size_t tail = (size_t)(M + 127) / 128 * 128 - M + 16;
+    float *out = nullptr, *ssOut = nullptr;
+    uint16_t *outH = nullptr, *resX = nullptr;
+    const float *resIn = nullptr, *resW = nullptr;
+    const int ssRows = (rows + 63) / 64;
+    if (epi == hipk::EPI_ACT_F16)
+        outH = sc.allocGuardedTail<uint16_t>(M, outCols, ldOut, tail, "the f16 SwiGLU rows");
+    else
+        out = sc.allocGuardedTail<float>(M, outCols, ldOut, tail, epi == hipk::EPI_RES ? "resOut" : "the GEMM output");
+    if (epi == hipk::EPI_RES) {
+        resX = sc.allocGuardedTail<uint16_t>(M, rows, ldOut, tail, "resX");
+        ssOut = sc.allocGuardedTail<float>(ssRows, M, a.ldSS, 2, "ssOut");
+        std::vector<float> padded((size_t)M * ldOut, 0.f);  // resIn shares the outputs' row stride
+        for (int t = 0; t < M; t++) std::copy(a.resIn.begin() + (size_t)t * rows, a.resIn.begin() + (size_t)(t + 1) * rows, padded.begin() + (size_t)t * ldOut);
+        resIn = sc.upload(padded);
+        resW = sc.upload(a.resW);
+    }
+    size_t cacheElems = 0;
+    uint8_t *kc = nullptr, *vc = nullptr;
+    const float2 *rope = nullptr;
+    const int *pos = nullptr, *slot = nullptr;
+    if (epi == hipk::EPI_QKV) {
+        // the caches are preset to the guard pattern as a whole (plus a guard after the last slot):
+        // only the appended rows may change
+        cacheElems = (size_t)a.nSlots * a.seqLen * a.kv0;
+        const size_t eb = a.kvBf16 ? 2 : 4, cacheGuard = (size_t)128 * a.seqLen;
+        kc = sc.allocGuarded<uint8_t>(1, cacheElems * eb, (cacheElems + cacheGuard) * eb, "the K cache");
+        vc = sc.allocGuarded<uint8_t>(1, cacheElems * eb, (cacheElems + cacheGuard) * eb, "the V cache");
+        rope = reinterpret_cast<const float2 *>(sc.upload(a.rope));
+        pos = sc.upload(a.pos);
+        slot = sc.upload(a.slot);
+    }
+    size_t part = 0, counters = (size_t)ssRows;
+    for (const GemmLaunch &l : plan) {
+        if (l.kernel == hipk::GEMM_WIDE) {
+            const size_t wt = (size_t)((rows + 127) / 128) * ((l.M + 127) / 128);
+            part = std::max(part, l.splits * wt * 128 * 128);
+            counters = std::max(counters, wt);
+        } else {
+            part = std::max(part, (size_t)l.splits * ssRows * hipk::gemmTokenPad(l.M) * 64);
+        }
+    }
+    float *partBuf = sc.alloc<float>(part + 4);
+    int *cnt = sc.alloc<int>(counters + 1);  // zeroed
+    for (const GemmLaunch &l : plan) {
+        const int c0 = l.c0;
+        hipk::GemmArgs g;
+        hipk::GemvArgs &e = g.e;
+        e.qs = w.qs;
+        e.wd = w.d;
+        e.wf = wf;
+        e.rows = rows;
+        e.n = n;
+        e.lanes = w.lanes;
+        e.eps = a.eps;
+        if (a.input == GEMM_IN_NORM) {  // the engine normalizes each chunk into the head of its f16 buffer
+            hipk::GemvArgs nc = nq;
+            nc.in = nq.in + (size_t)c0 * n;
+            nc.addIn = nq.addIn ? nq.addIn + (size_t)c0 * n : nullptr;
+            hipk::launchNormF16(nc, xh, l.M, sc.s);
+            g.x = xh;
+        } else {
+            g.x = xh + (size_t)c0 * n;
+        }
+        if (ssIn) {
+            g.ssIn = ssIn + c0;
+            g.ssTiles = a.ssTiles;
+            g.ldSS = a.ldSS;
+        }
+        e.out = out ? out + (size_t)c0 * ldOut : nullptr;
+        g.outH = outH ? reinterpret_cast<_Float16 *>(outH) + (size_t)c0 * ldOut : nullptr;
+        e.ldOut = ldOut;
+        e.act = 1;
+        if (epi == hipk::EPI_QKV) {
+            e.q0 = a.q0;
+            e.kv0 = a.kv0;
+            e.hs = a.hs;
+            e.seqLen = a.seqLen;
+            e.rope = rope;
+            e.pos = pos + c0;
+            e.slot = slot + c0;
+            e.kcache = kc;
+            e.vcache = vc;
+            e.kvBf16 = a.kvBf16 ? 1 : 0;
+        }
+        if (epi == hipk::EPI_RES) {
+            g.resIn = resIn + (size_t)c0 * ldOut;
+            g.resOut = out + (size_t)c0 * ldOut;
+            e.out = nullptr;
+            g.resW = resW;
+            g.resX = reinterpret_cast<_Float16 *>(resX) + (size_t)c0 * ldOut;
+            g.ssOut = ssOut + c0;
+            g.ldSS = a.ldSS;
+        }
+        g.M = l.M;
+        g.splits = l.splits;
+        g.fixed = a.fixed;
+        g.part = partBuf;
+        g.counters = cnt;
+        if (q40)
+            hipk::launchGemmQ40(g, epi, sc.s);
+        else
+            hipk::launchGemmF32(g, epi, sc.s);
+    }
+    sc.sync();
+    sc.checkGuards();
+    GemmBatchedResult r;
+    r.launches = plan;
+    auto widen = [](const std::vector<uint16_t> &h) {
+        std::vector<float> f(h.size());
+        for (size_t i = 0; i < h.size(); i++) f[i] = f16ToF32(h[i]);
+        return f;
+    };
+    if (outH)
+        r.out = widen(sc.downloadRows(outH, M, outCols, ldOut));
+    else
+        r.out = sc.downloadRows(out, M, outCols, ldOut);
+    if (epi == hipk::EPI_RES) {
+        r.resX = widen(sc.downloadRows(resX, M, rows, ldOut));
+        r.ssOut = sc.download(ssOut, (size_t)ssRows * a.ldSS);
+    }
+    if (epi == hipk::EPI_QKV) {
+        appendedRows(sc, kc, cacheElems, a.seqLen, a.kv0, a.hs, a.pos, a.slot, a.kvBf16, "the K cache", &r.k);
+        appendedRows(sc, vc, cacheElems, a.seqLen, a.kv0, a.hs, a.pos, a.slot, a.kvBf16, "the V cache", &r.v);
+    }
+    return r;
+}
+
 std::vector<float> qkvRope(const std::vector<uint8_t> &blocks, int q0, int kv0, int hs, int n,
                            const std::vector<float> &in, const std::vector<float> &normW, float eps,
                            const std::vector<float> &rope, int seqLen, const std::vector<int> &pos, bool kvBf16,
@@ -510,32 +791,9 @@ std::vector<float> qkvRope(const std::vector<uint8_t> &blocks, int q0, int kv0, 
     hipk::launchGemv(a, B, hipk::PRO_RESNORM, hipk::EPI_QKV, true, sc.s);
     sc.sync();
     sc.checkGuards();
-    // the [kv0] row of (slot b, pos[b]) from each head-major cache; every other element untouched
-    auto rowsOf = [&](const uint8_t *cache, const char *what, std::vector<float> *out) {
-        std::vector<uint8_t> all = sc.download(cache, cacheElems * eb);
-        out->assign((size_t)B * kv0, 0.f);
-        for (int b = 0; b < B; b++)
-            for (int kh = 0; kh < kv0 / hs; kh++) {
-                const size_t off = hipk::kvOff(hipk::KvMap{}, seqLen, kv0 / hs, hs, b, pos[b], kh);
-                for (int i = 0; i < hs; i++) {
-                    uint32_t u = 0;
-                    if (kvBf16) {
-                        uint16_t h;
-                        std::memcpy(&h, &all[(off + i) * 2], 2);
-                        u = (uint32_t)h << 16;
-                    } else {
-                        std::memcpy(&u, &all[(off + i) * 4], 4);
-                    }
-                    std::memcpy(&(*out)[(size_t)b * kv0 + (size_t)kh * hs + i], &u, 4);
-                }
-                std::memset(&all[off * eb], Scratch::kGuardByte, (size_t)hs * eb);
-            }
-        for (size_t i = 0; i < all.size(); i++)
-            DL_CHECK(all[i] == Scratch::kGuardByte, std::string("ops: the launch wrote outside the appended rows of ") + what);
-    };
     std::vector<float> k, v;
-    rowsOf(kc, "the K cache", &k);
-    rowsOf(vc, "the V cache", &v);
+    appendedRows(sc, kc, cacheElems, seqLen, kv0, hs, pos, slots, kvBf16, "the K cache", &k);
+    appendedRows(sc, vc, cacheElems, seqLen, kv0, hs, pos, slots, kvBf16, "the V cache", &v);
     if (kOut) *kOut = k;
     if (vOut) *vOut = v;
     return sc.downloadRows(a.out, B, q0, a.ldOut);

@@ -75,6 +75,61 @@ std::vector<float> gemmQ40(const std::vector<uint8_t> &blocks, int rows, int n, 
                            int splits = 0);  // Batched Q40 matmul on MFMA (narrow <= 64 tokens, wide above);
                                              // splits > 0 forces the K split (must divide n / 32)
 
+// One batched GEMM of the forward schedule, launched as the engine's gemmBatched launches it: Q40
+// (`blocks`, tiled at `lanes`: 0 = the GEMV's choice for the shape, else 16 / 32 / 64) or F32 (`wf`
+// [rows][n]) weights, one of three input modes, one of the four epilogues the engine fuses into a
+// GEMM, the engine's chunking (gemmChunkTokens: one wide launch, or <= 128 (Q40) / <= 64 (F32) tokens
+// per narrow launch, every operand pointer advanced by the chunk's first token, ldSS held fixed).
+//   input  GEMM_IN_NORM:    in (+ residual) -> launchNormF16 (normW empty: no norm) per chunk
+//          GEMM_IN_F16:     `in` rounded to f16 on the host (the wo / w2 operand)
+//          GEMM_IN_PRENORM: `in` = x' * w * 2^-5 rows (rounded to f16) and `ss` = [ssTiles][ldSS]
+//                           partial sums of squares of x' (the EPI_RES producer's outputs)
+//   epi    EPI_STORE:   out [M][rows]
+//          EPI_ACT_F16: interleaved (w1, w3) rows, SiLU; out [M][rows / 2] (the f16 values)
+//          EPI_RES:     resIn [M][rows], resW [rows] -> out = resOut [M][rows], resX [M][rows] (the
+//                       f16 values), ssOut [ceil(rows / 64)][ldSS] (unwritten slots read back NaN)
+//          EPI_QKV:     rows = q0 + 2 kv0; rope / pos / slot as ops::qkvRope, nSlots caches slots;
+//                       out = q [M][q0], kOut / vOut the appended rows [M][kv0]
+// splits: 0 = the launcher's gemmSplits with the tiling's L per launch, as the engine passes it;
+// fixed: the batch-invariant narrow launch (the caller sets splits as such an engine does). chunk:
+// 0 = the engine's rule, else the tokens per launch forced.
+// Every output carries guard regions of a fixed bit pattern (after each token row's last valid
+// element, after the last token, for ssOut after column M of every tile row and after the last tile
+// row, for the caches everywhere but the appended rows); the op throws when a launch changed one.
+// A launch the launchers refuse (or whose operands do not fit their contract) throws before any
+// device work. The report names the kernel of every launch by the launcher's own predicates.
+enum GemmInput : int { GEMM_IN_NORM = 0, GEMM_IN_F16 = 1, GEMM_IN_PRENORM = 2 };
+struct GemmBatchedArgs {
+    std::vector<uint8_t> blocks;
+    std::vector<float> wf;
+    int rows = 0, n = 0, lanes = 0;
+    int input = GEMM_IN_NORM;
+    std::vector<float> in, residual, normW;
+    float eps = 1e-5f;
+    int M = 0;
+    std::vector<float> ss;
+    int ssTiles = 0, ldSS = 0;
+    int epi = 0;
+    std::vector<float> resIn, resW;
+    int q0 = 0, kv0 = 0, hs = 0, seqLen = 0, nSlots = 0;
+    std::vector<float> rope;
+    std::vector<int> pos, slot;
+    bool kvBf16 = true;
+    int splits = 0, fixed = 0, chunk = 0;
+};
+struct GemmLaunch {
+    int c0 = 0, M = 0, kernel = 0 /* GemmKernel, 3 = F32 */, splits = 1, grid = 0 /* workgroups */;
+};
+struct GemmBatchedResult {
+    std::vector<float> out, resX, ssOut, k, v;
+    std::vector<GemmLaunch> launches;
+};
+// the launches of the call (kernels, splits, grids) and its refusals; no device needed
+std::vector<GemmLaunch> gemmBatchedPlan(const GemmBatchedArgs &a);
+GemmBatchedResult gemmBatched(const GemmBatchedArgs &a);
+// hipk::gemmSplits: the K splits the launcher takes for M tokens on a matrix tiled at `lanes`
+int gemmSplitsFor(int rows, int n, int M, int lanes);
+
 // QKV GEMV with the RoPE + KV-append epilogue (rows = q0 + 2*kv0, head size hs): returns rotated q
 // [B][q0]; kOut/vOut receive the appended cache rows [B][kv0] (f32 view of the bf16 or f32 cache).
 // rope = [seqLen][hs/2] (cos, sin) pairs; pos[b] < seqLen; each row b writes cache slot b.

@@ -324,6 +324,85 @@ void bindOps(py::module_ &m) {
           },
           py::arg("w"), py::arg("rows"), py::arg("n"), py::arg("x"), py::arg("norm_w") = py::none(),
           py::arg("eps") = 1e-5f);
+    // ops::gemmBatched: `plan_only` returns the launches (and raises the refusals) without a device
+    o.def("gemm",
+          [](py::object blocks, py::object wf, int rows, int n, int lanes, int input, py::object x, py::object residual,
+             py::object normW, float eps, py::object ss, int ssTiles, int ldSS, int epi, py::object resIn,
+             py::object resW, int q0, int kv0, int hs, py::object rope, int seqLen, int nSlots, std::vector<int> pos,
+             std::vector<int> slot, bool kvBf16, int splits, int fixed, int chunk, bool planOnly) {
+              ops::GemmBatchedArgs a;
+              a.blocks = vec<uint8_t>(blocks);
+              a.wf = vec<float>(wf);
+              a.rows = rows;
+              a.n = n;
+              a.lanes = lanes;
+              a.input = input;
+              a.in = vec<float>(x);
+              a.residual = vec<float>(residual);
+              a.normW = vec<float>(normW);
+              a.eps = eps;
+              a.M = n > 0 ? (int)(a.in.size() / n) : 0;
+              a.ss = vec<float>(ss);
+              a.ssTiles = ssTiles;
+              a.ldSS = ldSS;
+              a.epi = epi;
+              a.resIn = vec<float>(resIn);
+              a.resW = vec<float>(resW);
+              a.q0 = q0;
+              a.kv0 = kv0;
+              a.hs = hs;
+              a.rope = vec<float>(rope);
+              a.seqLen = seqLen;
+              a.nSlots = nSlots;
+              a.pos = pos;
+              a.slot = slot;
+              a.kvBf16 = kvBf16;
+              a.splits = splits;
+              a.fixed = fixed;
+              a.chunk = chunk;
+              ops::GemmBatchedResult r;
+              {
+                  py::gil_scoped_release rel;
+                  if (planOnly)
+                      r.launches = ops::gemmBatchedPlan(a);
+                  else
+                      r = ops::gemmBatched(a);
+              }
+              static const char *const names[] = {"narrow", "l16", "wide", "f32"};
+              py::list launches;
+              for (const ops::GemmLaunch &l : r.launches) {
+                  py::dict d;
+                  d["c0"] = l.c0;
+                  d["tokens"] = l.M;
+                  d["kernel"] = names[l.kernel];
+                  d["splits"] = l.splits;
+                  d["grid"] = l.grid;
+                  launches.append(d);
+              }
+              py::dict res;
+              res["launches"] = launches;
+              if (planOnly) return res;
+              const py::ssize_t M = a.M;
+              res["out"] = arr(r.out, {M, (py::ssize_t)(r.out.size() / M)});
+              if (!r.resX.empty()) {
+                  res["res_x"] = arr(r.resX, {M, (py::ssize_t)rows});
+                  res["ss_out"] = arr(r.ssOut, {(py::ssize_t)(rows + 63) / 64, (py::ssize_t)ldSS});
+              }
+              if (!r.k.empty()) {
+                  res["k"] = arr(r.k, {M, (py::ssize_t)kv0});
+                  res["v"] = arr(r.v, {M, (py::ssize_t)kv0});
+              }
+              return res;
+          },
+          py::arg("blocks"), py::arg("wf"), py::arg("rows"), py::arg("n"), py::arg("lanes"), py::arg("input"), py::arg("x"),
+          py::arg("residual") = py::none(), py::arg("norm_w") = py::none(), py::arg("eps") = 1e-5f,
+          py::arg("ss") = py::none(), py::arg("ss_tiles") = 0, py::arg("ld_ss") = 0, py::arg("epi") = 0,
+          py::arg("res_in") = py::none(), py::arg("res_w") = py::none(), py::arg("q0") = 0, py::arg("kv0") = 0,
+          py::arg("head_size") = 0, py::arg("rope") = py::none(), py::arg("seq_len") = 0, py::arg("n_slots") = 0,
+          py::arg("pos") = std::vector<int>(), py::arg("slot") = std::vector<int>(), py::arg("kv_bf16") = true,
+          py::arg("splits") = 0, py::arg("fixed") = 0, py::arg("chunk") = 0, py::arg("plan_only") = false);
+    o.def("gemm_splits", &ops::gemmSplitsFor, py::arg("rows"), py::arg("n"), py::arg("tokens"), py::arg("lanes") = 0,
+          "K splits the GEMM launcher takes for a launch of `tokens`; no device needed");
     o.def("qkv_rope",
           [](py::object blocks, int q0, int kv0, int hs, int n, py::object x, py::object normW, float eps, py::object rope,
              int seqLen, std::vector<int> pos, bool kvBf16, int lanes, int passes) {

@@ -114,6 +114,43 @@ def gemm_f32(w, x, norm_w=None, eps: float = 1e-5) -> torch.Tensor:
     return torch.from_numpy(native().ops.gemm_f32(_np(w), rows, n, _np(x), _np(norm_w), eps))
 
 
+GEMM_INPUTS = {"norm": 0, "f16": 1, "prenorm": 2}
+GEMM_EPILOGUES = {"store": 0, "qkv": 2, "swiglu_f16": 4, "res": 6}
+
+
+def gemm(x, blocks=None, w=None, rows: int = 0, n: int = 0, lanes: int = 0, input: str = "norm", residual=None,
+         norm_w=None, eps: float = 1e-5, ss=None, ld_ss: int = 0, epilogue: str = "store", res_in=None, res_w=None,
+         q0: int = 0, kv0: int = 0, head_size: int = 0, rope=None, n_slots: int = 0, pos=(), slot=(),
+         kv_bf16: bool = True, splits: int = 0, fixed: bool = False, chunk: int = 0, plan_only: bool = False) -> dict:
+    """One batched GEMM of the forward schedule, launched as the engine launches it (ops::gemmBatched,
+    csrc/hip/ops.h): Q40 `blocks` [rows][n/32] tiled at `lanes` (0: the GEMV's choice; 16 / 32 / 64) or
+    F32 `w` [rows, n]; x [M, n].
+    input "norm": (x + residual) -> RMS norm (norm_w) -> f16 by the norm kernel; "f16": x rounded to
+    f16 on the host; "prenorm": x = x' * w / 32 rows and ss = [ss_tiles, ld_ss] partial sums of squares.
+    epilogue "store" -> out [M, rows]; "swiglu_f16" -> out [M, rows/2] (f16 values); "res" (res_in
+    [M, rows], res_w [rows], ld_ss) -> out (= resOut), res_x (f16 values), ss_out [ceil(rows/64), ld_ss];
+    "qkv" (q0, kv0, head_size, rope [seq_len, hs/2, 2], pos, slot, n_slots) -> out (= q [M, q0]), k, v.
+    splits 0: the launcher's choice; fixed: the batch-invariant narrow launch; chunk: tokens per launch
+    (0: the engine's rule). Outputs are guarded: a store outside their valid part raises. Returns a
+    dict with the outputs and "launches": [{c0, tokens, kernel, splits, grid}] ("narrow", "l16",
+    "wide", "f32"). plan_only: just the launches and the refusals, no device needed."""
+    if w is not None:
+        rows, n = w.shape
+    ss_np = _np(ss)
+    rope_np = _np(rope)
+    r = native().ops.gemm(_np(blocks, np.uint8), _np(w), rows, n, lanes, GEMM_INPUTS[input], _np(x), _np(residual),
+                          _np(norm_w), eps, ss_np, 0 if ss_np is None else ss_np.shape[0], ld_ss,
+                          GEMM_EPILOGUES[epilogue], _np(res_in), _np(res_w), q0, kv0, head_size, rope_np,
+                          0 if rope_np is None else rope_np.shape[0], n_slots, [int(p) for p in pos],
+                          [int(s) for s in slot], kv_bf16, splits, 1 if fixed else 0, chunk, plan_only)
+    return {k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()}
+
+
+def gemm_splits(rows: int, n: int, tokens: int, lanes: int = 0) -> int:
+    """K splits the launcher takes for a launch of `tokens` on a matrix tiled at `lanes` (host only)."""
+    return native().ops.gemm_splits(rows, n, tokens, lanes)
+
+
 def qkv_rope(blocks, q0: int, kv0: int, head_size: int, n: int, x, norm_w, eps: float, rope, seq_len: int,
              pos, kv_bf16: bool = True, lanes: int = 0, passes: int = 0):
     """QKV GEMV with the RoPE + KV-cache-append epilogue. Returns (q rotated, k row, v row)."""
