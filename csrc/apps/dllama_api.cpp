@@ -168,6 +168,48 @@ struct Api {
                 return;
             }
         }
+        {
+            std::string bad;
+            auto penalty = [&](const char *name, float &dst) {
+                const Value &v = body[name];
+                if (v.isNull() || !bad.empty()) return;
+                if (!v.isNumber() || !(v.asNumber() >= -2.0 && v.asNumber() <= 2.0))
+                    bad = std::string(name) + " must be a number from -2 to 2";
+                else
+                    dst = (float)v.asNumber();
+            };
+            penalty("frequency_penalty", p.frequencyPenalty);
+            penalty("presence_penalty", p.presencePenalty);
+            const Value &lb = body["logit_bias"];
+            if (bad.empty() && !lb.isNull()) {
+                const int vocab = (int)sess->header().vocabSize;
+                if (!lb.isObject())
+                    bad = "logit_bias must be an object of token id: bias";
+                else if (lb.size() > (size_t)kMaxLogitBias)
+                    bad = "logit_bias holds at most " + std::to_string(kMaxLogitBias) + " entries";
+                for (size_t e = 0; bad.empty() && e < lb.size(); e++) {
+                    const auto &kv = lb.members()[e];
+                    const std::string &k = kv.first;
+                    const bool digits = !k.empty() && k.size() <= 9 && k.find_first_not_of("0123456789") == std::string::npos;
+                    const int id = digits ? std::atoi(k.c_str()) : -1;
+                    if (!digits || id >= vocab)
+                        bad = "logit_bias keys must be token ids from 0 to " + std::to_string(vocab - 1);
+                    else if (!kv.second.isNumber() || !(kv.second.asNumber() >= -100.0 && kv.second.asNumber() <= 100.0))
+                        bad = "logit_bias values must be numbers from -100 to 100";
+                    else {
+                        for (const LogitBias &e : p.logitBias)
+                            if (e.id == id) bad = "logit_bias names token " + std::to_string(id) + " twice";
+                        p.logitBias.push_back(LogitBias{id, (float)kv.second.asNumber()});
+                    }
+                }
+            }
+            if (!bad.empty()) {
+                Value err = Value::object();
+                err.set("error", "Invalid request: " + bad);
+                conn.writeJson(400, err.dump());
+                return;
+            }
+        }
         std::vector<int> prompt;
         try {
             prompt = buildPrompt(body["messages"]);
@@ -299,6 +341,8 @@ struct Api {
                (double)s.prefixCopies);
         metric("dllama_prefix_evictions_total", "counter", "Idle slots evicted to free KV pages.",
                (double)s.prefixEvictions);
+        metric("dllama_logit_proc_requests_total", "counter", "Finished requests that used penalties or a logit bias.",
+               (double)s.logitProcRequests);
         metric("dllama_active_requests", "gauge", "Requests holding a KV slot.", (double)s.active);
         metric("dllama_queued_requests", "gauge", "Requests waiting for a KV slot.", (double)s.queued);
         metric("dllama_kv_slots", "gauge", "KV-cache slots (max concurrent sequences).", (double)sess->nSlots());
@@ -329,6 +373,7 @@ struct Api {
         v.set("prefix_tokens", (double)s.prefixTokens);
         v.set("prefix_copies", (double)s.prefixCopies);
         v.set("prefix_evictions", (double)s.prefixEvictions);
+        v.set("logit_proc_requests", (double)s.logitProcRequests);
         conn.writeJson(200, v.dump());
     }
 };

@@ -2,6 +2,7 @@
 // lists the other translation units of the engine).
 #include "engine_impl.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -153,8 +154,11 @@ void HipEngineImpl::forwardArgmax(int n, const int *tokens, const int *positions
 void HipEngineImpl::forwardSample(int n, const int *tokens, const int *positions, const int *slots,
                                   const SampleSpec *specs, int *out) {
     Timer t;
-    setInputs(n, tokens, positions, slots, specs);
-    runGraph(n, GraphKind::SAMPLE);
+    std::vector<LogitProc> procs;
+    const bool proc = beginProcs(n, slots, specs, procs);
+    setInputs(n, tokens, positions, slots, specs, 0, proc ? procRows_.data() : nullptr);
+    if (proc) enqueueProcState(n, slots, procs);
+    runGraph(n, proc ? GraphKind::SAMPLE_PROC : GraphKind::SAMPLE);
     enqueueLogprobs(n, specs);
     DL_HIP(hipMemcpyAsync(hIds_, dIds_, n * sizeof(int), hipMemcpyDeviceToHost, stream_));
     syncAndCheckComm();
@@ -171,8 +175,11 @@ void HipEngineImpl::launchIds(int n, const int *tokens, const int *positions, co
                               const SampleSpec *specs) {
     DL_CHECK(pendingN_ == 0, "launchIds: the previous forward was not collected");
     Timer t;
-    setInputs(n, tokens, positions, slots, specs);
-    runGraph(n, specs ? GraphKind::SAMPLE : GraphKind::ARGMAX);
+    std::vector<LogitProc> procs;
+    const bool proc = beginProcs(n, slots, specs, procs);
+    setInputs(n, tokens, positions, slots, specs, 0, proc ? procRows_.data() : nullptr);
+    if (proc) enqueueProcState(n, slots, procs);
+    runGraph(n, proc ? GraphKind::SAMPLE_PROC : specs ? GraphKind::SAMPLE : GraphKind::ARGMAX);
     enqueueLogprobs(n, specs);
     DL_HIP(hipMemcpyAsync(hIds_, dIds_, n * sizeof(int), hipMemcpyDeviceToHost, stream_));
     pendingN_ = n;
@@ -188,6 +195,70 @@ void HipEngineImpl::collectIds(int *out) {
     std::memcpy(out, hIds_, n * sizeof(int));
     readLogprobs();
     setSyncStats(readSync(hSync_, false), -1);
+}
+
+// The logit processors handed over for this forward (Backend::setLogitProcs). Ranks other than the
+// root drop them: they neither hold the full logits nor draw, and run their SAMPLE schedule with
+// the same collectives in the same order. Returns whether a row is active, with procRows_ filled.
+bool HipEngineImpl::beginProcs(int n, const int *slots, const SampleSpec *specs, std::vector<LogitProc> &procs) {
+    if (pendingProcs_.empty()) return false;
+    if (!specs) {
+        pendingProcs_.clear();
+        throw Error("launchIds: logit processors need a sampled forward (specs)");
+    }
+    procs = takeLogitProcs(n);
+    if (procs.empty() || rank() != 0) return false;
+    std::vector<int> seen;
+    procRows_.assign((size_t)n * 4, 0.f);
+    bool any = false;
+    for (int b = 0; b < n; b++) {
+        const LogitProc &p = procs[b];
+        if (!p.active || specs[b].temperature < 0.f) continue;
+        DL_CHECK(slots[b] >= 0 && (u32)slots[b] < cfg_.nSlots, "slot out of range");
+        seen.push_back(slots[b]);
+        procRows_[(size_t)b * 4] = p.presence;
+        procRows_[(size_t)b * 4 + 1] = p.frequency;
+        procRows_[(size_t)b * 4 + 2] = 1.f;
+        any = true;
+    }
+    std::sort(seen.begin(), seen.end());
+    DL_CHECK(std::adjacent_find(seen.begin(), seen.end()) == seen.end(),
+             "logit processors: two drawn rows of one forward share a slot");
+    return any;
+}
+
+// Before the forward, in stream order: a fresh slot's counts are zeroed and its bias entries and
+// their number uploaded from the pinned staging (free: the previous forward was collected).
+void HipEngineImpl::enqueueProcState(int n, const int *slots, const std::vector<LogitProc> &procs) {
+    static_assert(sizeof(hipk::LogitBiasEntry) == sizeof(LogitBias) && hipk::kMaxLogitBias == kMaxLogitBias,
+                  "device and host bias layouts");
+    for (int b = 0; b < n; b++) {
+        const LogitProc &p = procs[b];
+        if (procRows_[(size_t)b * 4 + 2] == 0.f || !p.fresh) continue;
+        const size_t s = (size_t)slots[b], nb = p.bias.size();
+        DL_HIP(hipMemsetAsync(dProcCounts_ + s * h_.vocabSize, 0, (size_t)h_.vocabSize * sizeof(uint32_t), stream_));
+        hProcNBias_[s] = (int)nb;
+        DL_HIP(hipMemcpyAsync(dProcNBias_ + s, hProcNBias_ + s, sizeof(int), hipMemcpyHostToDevice, stream_));
+        if (nb == 0) continue;
+        std::memcpy(hProcBias_ + s * kMaxLogitBias, p.bias.data(), nb * sizeof(LogitBias));
+        DL_HIP(hipMemcpyAsync(dProcBias_ + s * kMaxLogitBias, hProcBias_ + s * kMaxLogitBias, nb * sizeof(LogitBias),
+                              hipMemcpyHostToDevice, stream_));
+    }
+}
+
+hipk::LogitProcArgs HipEngineImpl::logitProcArgs(const float *raw) const {
+    hipk::LogitProcArgs g;
+    g.logits = raw;
+    g.out = dProcLogits_;
+    g.vocab = h_.vocabSize;
+    g.spec = dSpec_;
+    g.proc = dProc_;
+    g.slots = dSlot_;
+    g.counts = dProcCounts_;
+    g.bias = dProcBias_;
+    g.nBias = dProcNBias_;
+    g.ids = dIds_;
+    return g;
 }
 
 // Rows of the SAMPLE forward just enqueued ask for log-probabilities (SampleSpec::logprobs): one
@@ -540,7 +611,7 @@ void HipEngineImpl::runGraph(int n, GraphKind kind, unsigned *syncDst) {
         copySync();
         return;
     }
-    const int key = ((((n * 4 + (int)kind) * 2 + (prefillOk_ ? 1 : 0)) * 2 + (attnLong_ ? 1 : 0)) << 4) + bucket_;
+    const int key = ((((n * 8 + (int)kind) * 2 + (prefillOk_ ? 1 : 0)) * 2 + (attnLong_ ? 1 : 0)) << 4) + bucket_;
     auto it = graphs_.find(key);
     if (it == graphs_.end()) {
         // capture on the second use of a shape: a one-off row count (the tail chunk of a prompt,

@@ -40,7 +40,7 @@ const CtxBucket &HipEngineImpl::bucketFor(int maxPos) const {
 }
 
 void HipEngineImpl::setInputs(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs,
-                              int ahead) {
+                              int ahead, const float *procRows) {
     DL_CHECK(n >= 1 && (u32)n <= cfg_.maxBatch, "batch size out of range");
     DL_CHECK(chainHead_ == chainTail_, "a chained decode step is still in flight");
     for (int b = 0; b < n; b++) {
@@ -86,6 +86,10 @@ void HipEngineImpl::setInputs(int n, const int *tokens, const int *positions, co
         static_assert(sizeof(SampleSpec) == 4 * sizeof(float), "spec layout");
         std::memcpy(hIn_ + 3 * MB, specs, n * sizeof(SampleSpec));
         words = 3 * (size_t)MB + 4 * (size_t)n;
+    }
+    if (procRows) {  // the rows' logit processors, behind the specs
+        std::memcpy(hIn_ + 7 * MB, procRows, (size_t)n * 4 * sizeof(float));
+        words = 7 * (size_t)MB + 4 * (size_t)n;
     }
     // one copy of the row arrays (the unused tail of each is never read)
     DL_HIP(hipMemcpyAsync(dTok_, hIn_, words * sizeof(int), hipMemcpyHostToDevice, stream_));
@@ -690,7 +694,8 @@ void HipEngineImpl::enqueueTokenPick(int n, GraphKind kind) {
     // logits for the host (LOGITS) and sampled rows (SAMPLE) are needed on the root only: the
     // vocab slices are gathered to rank 0 (the reference's SYNC_NODE_SLICES_EXCEPT_ROOT), the
     // other ranks publish theirs and skip the unshard and the draw (the root's ids are used)
-    const bool rootOnly = kind == GraphKind::LOGITS || kind == GraphKind::SAMPLE;
+    const bool sampled = kind == GraphKind::SAMPLE || kind == GraphKind::SAMPLE_PROC;
+    const bool rootOnly = kind == GraphKind::LOGITS || sampled;
     if (p.nRanks > 1 && !distArgmax) {
         ProfScope ps(this, "allgather");
         stamped([&] {
@@ -702,16 +707,30 @@ void HipEngineImpl::enqueueTokenPick(int n, GraphKind kind) {
         if (!rootOnly || rank() == 0) hipk::launchUnshardLogits(dLogitsAll_, dLogitsFull_, p.nRanks, n, p.vocab0, stream_);
         full = dLogitsFull_;
     }
-    if (kind == GraphKind::SAMPLE) {
+    if (sampled) {
         if (p.nRanks == 1 || rank() == 0) {  // the other ranks' ids are not used (no draw, no argmax)
-            ProfScope ps(this, "sample");
-            hipk::SampleArgs g;
-            g.logits = full;
-            g.vocab = h_.vocabSize;
-            g.spec = dSpec_;
-            g.ids = dIds_;
-            g.scratch = sampleScratch_;
-            hipk::launchSample(g, n, stream_);
+            // SAMPLE_PROC (root only): the drawn rows' penalties and bias into the processed buffer,
+            // which the sampler reads instead; the raw logits stay for the log-probabilities; the
+            // drawn tokens are counted behind the draw
+            const bool proc = kind == GraphKind::SAMPLE_PROC;
+            if (proc) {
+                ProfScope ps(this, "logit_proc");
+                hipk::launchLogitProc(logitProcArgs(full), n, stream_);
+            }
+            {
+                ProfScope ps(this, "sample");
+                hipk::SampleArgs g;
+                g.logits = proc ? dProcLogits_ : full;
+                g.vocab = h_.vocabSize;
+                g.spec = dSpec_;
+                g.ids = dIds_;
+                g.scratch = sampleScratch_;
+                hipk::launchSample(g, n, stream_);
+            }
+            if (proc) {
+                ProfScope ps(this, "logit_proc");
+                hipk::launchLogitProcCount(logitProcArgs(full), n, stream_);
+            }
         }
     } else if (kind != GraphKind::LOGITS) {
         ProfScope ps(this, "argmax");

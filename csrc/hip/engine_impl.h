@@ -101,7 +101,9 @@ class HipEngineImpl : public HipEngine {
     bool tpBatchedFused(int n) const override { return plan_.nRanks > 1 && batchedPath(n) && fuseNorm(n); }
 
     // ------------------------------------------------------------------ internals
-    enum class GraphKind { LOGITS = 0, ARGMAX = 1, CHAIN = 2, SAMPLE = 3 };
+    // SAMPLE_PROC: SAMPLE with the logit processors between the logits and the draw (root rank of a
+    // forward with an active LogitProc row; every other forward takes the kinds it always took)
+    enum class GraphKind { LOGITS = 0, ARGMAX = 1, CHAIN = 2, SAMPLE = 3, SAMPLE_PROC = 4 };
 
     // engine.cpp
     void syncAndCheckComm();
@@ -207,8 +209,9 @@ class HipEngineImpl : public HipEngine {
     // engine_forward.cpp
     void setupBuckets();
     const CtxBucket &bucketFor(int maxPos) const;
+    // procRows: [n][4] (presence, frequency, active, -) of a SAMPLE_PROC forward, else null
     void setInputs(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs = nullptr,
-                   int ahead = 0);
+                   int ahead = 0, const float *procRows = nullptr);
     int tpPasses(const DevMat &m, int bc) const;
     int batchChunk(const DevMat &m, int pro, int epi) const;
     int passesFor(const DevMat &m, int epi, int B) const {
@@ -409,6 +412,21 @@ class HipEngineImpl : public HipEngine {
     std::vector<int> logprobReq_;  // per row of the forward in flight (empty: no row asked)
     void enqueueLogprobs(int n, const SampleSpec *specs);
     void readLogprobs();
+    // logit processors (Backend::setLogitProcs), root rank only: per slot the dense token counts and
+    // the bias entries, the processed logits the sampler of a SAMPLE_PROC forward reads, and pinned
+    // staging of the bias entries | counts per slot (free once the previous forward was collected)
+    uint32_t *dProcCounts_ = nullptr;              // [nSlots][vocab]
+    hipk::LogitBiasEntry *dProcBias_ = nullptr, *hProcBias_ = nullptr;  // [nSlots][kMaxLogitBias]
+    int *dProcNBias_ = nullptr, *hProcNBias_ = nullptr;                 // [nSlots]
+    float *dProcLogits_ = nullptr;                 // [maxBatch][vocab]
+    float4 *dProc_ = nullptr;                      // [maxBatch] per row, behind dSpec_ in the input block
+    std::vector<float> procRows_;                  // host copy of the forward being set up
+    size_t procBytes() const;
+    hipk::LogitProcArgs logitProcArgs(const float *raw) const;
+    // takes the pending processors of a sampled forward: true when a row is active (the forward then
+    // runs as SAMPLE_PROC); beginProcs fills procRows_, enqueueProcState resets / uploads fresh slots
+    bool beginProcs(int n, const int *slots, const SampleSpec *specs, std::vector<LogitProc> &procs);
+    void enqueueProcState(int n, const int *slots, const std::vector<LogitProc> &procs);
     // measured-sync slots (syncSlots, hipk::syncFoldWords) and their host copies: [0] the last
     // forward / chain, [1 + k] chain step k % kChainDepth (chainLaunch / chainCollect)
     unsigned *dSync_ = nullptr, *hSync_ = nullptr;

@@ -22,7 +22,7 @@ void HipEngineImpl::checkFits() {
     size_t w = (size_t)h_.nLayers * (matStageBytes(p.q0 + 2 * p.kv0, h_.dim) + matStageBytes(h_.dim, p.q0) +
                                      matStageBytes(2 * p.hidden0, h_.dim) + matStageBytes(h_.dim, p.hidden0));
     w += matStageBytes(p.vocab0, h_.dim) + (size_t)h_.vocabSize * h_.dim * 4;
-    const size_t act = (size_t)cfg_.maxBatch * h_.vocabSize * 4 * 3 + ((size_t)256 << 20);
+    const size_t act = (size_t)cfg_.maxBatch * h_.vocabSize * 4 * 3 + ((size_t)256 << 20) + procBytes();
     if (kv + w + act > freeB) {
         // the page pool that would fit (positions shared by all slots), as a hint
         const size_t perPos = (size_t)h_.nLayers * 2 * p.kv0 * (kvBf16_ ? 2 : 4);
@@ -85,6 +85,14 @@ void HipEngineImpl::checkFusedResidency() {
     }
 }
 
+// Device state of the logit processors (root rank): token counts and bias entries per slot, and the
+// processed logits of a forward's rows.
+size_t HipEngineImpl::procBytes() const {
+    if (rank() != 0) return 0;
+    return (size_t)cfg_.nSlots * ((size_t)h_.vocabSize * sizeof(uint32_t) + kMaxLogitBias * sizeof(hipk::LogitBiasEntry) + sizeof(int)) +
+           (size_t)cfg_.maxBatch * h_.vocabSize * sizeof(float);
+}
+
 int HipEngineImpl::tpPasses(const DevMat &m, int bc) const {
     int passes = passesFor(m, hipk::EPI_STORE_TP, bc);
     if (tpVec_.q80)  // whole Q80 blocks of 32 rows per workgroup
@@ -95,14 +103,27 @@ int HipEngineImpl::tpPasses(const DevMat &m, int bc) const {
 void HipEngineImpl::allocBuffers() {
     const u32 MB = cfg_.maxBatch;
     const ShardPlan &p = plan_;
-    // [tokens | positions | slots | sample specs (4 floats per row)]: one H2D copy per forward
-    dTok_ = dalloc<int>(7 * (size_t)MB);
+    // [tokens | positions | slots | sample specs (4 floats per row) | logit processors (4 floats per
+    // row)]: one H2D copy per forward, up to the last array the forward uses
+    dTok_ = dalloc<int>(11 * (size_t)MB);
     dPos_ = dTok_ + MB;
     dSlot_ = dTok_ + 2 * MB;
     dSpec_ = reinterpret_cast<float4 *>(dTok_ + 3 * MB);
+    dProc_ = reinterpret_cast<float4 *>(dTok_ + 7 * MB);
     dIds_ = dalloc<int>(MB);
     dHist_ = dalloc<int>((size_t)decodeRows_ * h_.seqLen);  // greedy chains only (decode rows)
-    hIn_ = halloc<int>(7 * MB);
+    hIn_ = halloc<int>(11 * MB);
+    if (rank() == 0) {  // logit processors: the root draws
+        const size_t S = cfg_.nSlots, V = h_.vocabSize;
+        dProcCounts_ = dalloc<uint32_t>(S * V);
+        dProcBias_ = dalloc<hipk::LogitBiasEntry>(S * kMaxLogitBias);
+        dProcNBias_ = dalloc<int>(S);
+        dProcLogits_ = dalloc<float>((size_t)MB * V);
+        hProcBias_ = halloc<hipk::LogitBiasEntry>(S * kMaxLogitBias);
+        hProcNBias_ = halloc<int>(S);
+        DL_HIP(hipMemsetAsync(dProcCounts_, 0, S * V * sizeof(uint32_t), stream_));
+        DL_HIP(hipMemsetAsync(dProcNBias_, 0, S * sizeof(int), stream_));
+    }
     hIds_ = halloc<int>(MB);
     hErr_ = halloc<int>(2);
     hErr_[0] = hErr_[1] = 0;

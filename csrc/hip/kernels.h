@@ -558,6 +558,41 @@ struct LogprobArgs {
 };
 void launchLogprobs(const LogprobArgs &a, int B, hipStream_t s);
 
+// Logit processors of B rows of full-vocabulary logits, between the logits and the sampler:
+// frequency / presence penalties over the tokens a sequence generated so far and a per-sequence
+// logit bias (OpenAI's formula). For a row b with proc[b].z != 0 (active), slot s = slots[b]:
+//   x = logits[b][t];  c = counts[s][t]
+//   if c > 0:  x = x - proc[b].y * float(c);  x = x - proc[b].x      (frequency, then presence)
+//   if t is one of bias[s][0 .. nBias[s]):  x = x + its value
+// every step one f32 operation rounded to nearest, nothing contracted; elements with c == 0 and no
+// bias are copied bit for bit. Rows the sampler draws (spec[b].x >= 0) that are not active are
+// copied; rows with spec[b].x < 0 are neither read nor written. One streaming pass in 16-byte loads
+// and stores (scalar for the vocab % 4 tail) over dense counts: no sort, no atomics, no dependence
+// of a row's result on B. grid (logitProcGroups(vocab), B); the bias entries are applied by the
+// workgroup that owns their element, after its dense pass (ids must be distinct within a slot).
+constexpr int kMaxLogitBias = 300;
+struct LogitBiasEntry {
+    int id;
+    float v;
+};
+int logitProcGroups(int vocab);
+struct LogitProcArgs {
+    const float *logits = nullptr;       // [B][vocab] raw
+    float *out = nullptr;                // [B][vocab] processed
+    int vocab = 0;
+    const float4 *spec = nullptr;        // [B] (temperature, -, -, -)
+    const float4 *proc = nullptr;        // [B] (presence, frequency, active, -)
+    const int *slots = nullptr;          // [B]
+    uint32_t *counts = nullptr;          // [nSlots][vocab] times the slot's sequence generated each token
+    const LogitBiasEntry *bias = nullptr;  // [nSlots][kMaxLogitBias]
+    const int *nBias = nullptr;          // [nSlots]
+    const int *ids = nullptr;            // [B] launchLogitProcCount: the tokens just drawn on this stream
+};
+void launchLogitProc(const LogitProcArgs &a, int B, hipStream_t s);
+// counts[slots[b]][ids[b]] += 1 for the active rows with 0 <= ids[b] < vocab (plain stores: a
+// forward holds at most one row per slot).
+void launchLogitProcCount(const LogitProcArgs &a, int B, hipStream_t s);
+
 // Round-trip f32 partial sums through Q80 blocks in place (the reference's ZQ cast before the
 // exchange) - used ahead of a plain all-reduce when the fused exchange is not available.
 void launchQ80Roundtrip(float *x, size_t n, hipStream_t s);

@@ -977,6 +977,142 @@ void benchLogprobs(const std::vector<float> &logits, int B, int vocab, int k, in
     (void)hipEventDestroy(e1);
 }
 
+namespace {
+// spec / proc rows and the per-slot state of a LogitProcArgs
+hipk::LogitProcArgs logitProcArgs(Scratch &sc, int B, int vocab, const std::vector<float> &temps,
+                                  const std::vector<int> &slots, const std::vector<int> &active,
+                                  const std::vector<float> &presence, const std::vector<float> &frequency,
+                                  const std::vector<uint32_t> &counts, int nSlots, const std::vector<int> &biasIds,
+                                  const std::vector<float> &biasVals, const std::vector<int> &nBias) {
+    DL_CHECK(B >= 1 && vocab >= 1 && nSlots >= 1, "logit_proc sizes");
+    DL_CHECK(temps.size() == (size_t)B && slots.size() == (size_t)B && active.size() == (size_t)B &&
+                 presence.size() == (size_t)B && frequency.size() == (size_t)B, "logit_proc: one entry per row");
+    DL_CHECK(counts.size() == (size_t)nSlots * vocab, "logit_proc: counts is [slots][vocab]");
+    DL_CHECK(biasIds.size() == (size_t)nSlots * hipk::kMaxLogitBias && biasVals.size() == biasIds.size() &&
+                 nBias.size() == (size_t)nSlots, "logit_proc: bias is [slots][300]");
+    for (int v : slots) DL_CHECK(v >= 0 && v < nSlots, "logit_proc: slot out of range");
+    std::vector<hipk::LogitBiasEntry> bias(biasIds.size());
+    for (int s = 0; s < nSlots; s++) {
+        DL_CHECK(nBias[s] >= 0 && nBias[s] <= hipk::kMaxLogitBias, "logit_proc: at most 300 bias entries per slot");
+        for (int j = 0; j < hipk::kMaxLogitBias; j++) {
+            const size_t i = (size_t)s * hipk::kMaxLogitBias + j;
+            DL_CHECK(j >= nBias[s] || (biasIds[i] >= 0 && biasIds[i] < vocab), "logit_proc: bias id out of range");
+            bias[i] = hipk::LogitBiasEntry{biasIds[i], biasVals[i]};
+        }
+    }
+    std::vector<float> spec((size_t)B * 4, 0.f), proc((size_t)B * 4, 0.f);
+    for (int b = 0; b < B; b++) {
+        spec[(size_t)b * 4] = temps[b];
+        proc[(size_t)b * 4] = presence[b];
+        proc[(size_t)b * 4 + 1] = frequency[b];
+        proc[(size_t)b * 4 + 2] = active[b] ? 1.f : 0.f;
+    }
+    hipk::LogitProcArgs g;
+    g.vocab = vocab;
+    g.spec = reinterpret_cast<const float4 *>(sc.upload(spec));
+    g.proc = reinterpret_cast<const float4 *>(sc.upload(proc));
+    g.slots = sc.upload(slots);
+    g.counts = sc.upload(counts);
+    g.bias = sc.upload(bias);
+    g.nBias = sc.upload(nBias);
+    return g;
+}
+}  // namespace
+
+std::vector<float> logitProc(const std::vector<float> &logits, int B, int vocab, const std::vector<float> &temps,
+                             const std::vector<int> &slots, const std::vector<int> &active,
+                             const std::vector<float> &presence, const std::vector<float> &frequency,
+                             const std::vector<uint32_t> &counts, int nSlots, const std::vector<int> &biasIds,
+                             const std::vector<float> &biasVals, const std::vector<int> &nBias, float fill) {
+    DL_CHECK(B >= 1 && vocab >= 1 && logits.size() == (size_t)B * vocab, "logit_proc: logits is [B][vocab]");
+    Scratch sc;
+    hipk::LogitProcArgs g =
+        logitProcArgs(sc, B, vocab, temps, slots, active, presence, frequency, counts, nSlots, biasIds, biasVals, nBias);
+    g.logits = sc.upload(logits);
+    constexpr size_t kPad = 256;  // guard elements behind the last row
+    const std::vector<float> filled((size_t)B * vocab + kPad, fill);
+    g.out = sc.upload(filled);
+    hipk::launchLogitProc(g, B, sc.s);
+    sc.sync();
+    std::vector<float> out = sc.download(g.out, filled.size());
+    for (size_t i = (size_t)B * vocab; i < out.size(); i++)
+        DL_CHECK(std::memcmp(&out[i], &fill, sizeof(float)) == 0, "logit_proc: the launch wrote past the last row");
+    out.resize((size_t)B * vocab);
+    return out;
+}
+
+std::vector<uint32_t> logitProcCount(const std::vector<uint32_t> &counts, int nSlots, int vocab,
+                                     const std::vector<int> &ids, const std::vector<int> &slots,
+                                     const std::vector<int> &active) {
+    const int B = (int)ids.size();
+    DL_CHECK(B >= 1 && vocab >= 1 && nSlots >= 1 && counts.size() == (size_t)nSlots * vocab &&
+                 slots.size() == (size_t)B && active.size() == (size_t)B, "logit_proc_count sizes");
+    std::vector<int> seen;
+    for (int b = 0; b < B; b++) {
+        DL_CHECK(slots[b] >= 0 && slots[b] < nSlots, "logit_proc_count: slot out of range");
+        if (active[b]) seen.push_back(slots[b]);
+    }
+    std::sort(seen.begin(), seen.end());
+    DL_CHECK(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "logit_proc_count: one active row per slot");
+    Scratch sc;
+    std::vector<float> proc((size_t)B * 4, 0.f);
+    for (int b = 0; b < B; b++) proc[(size_t)b * 4 + 2] = active[b] ? 1.f : 0.f;
+    hipk::LogitProcArgs g;
+    g.vocab = vocab;
+    g.proc = reinterpret_cast<const float4 *>(sc.upload(proc));
+    g.slots = sc.upload(slots);
+    g.counts = sc.upload(counts);
+    g.ids = sc.upload(ids);
+    hipk::launchLogitProcCount(g, B, sc.s);
+    sc.sync();
+    return sc.download(g.counts, counts.size());
+}
+
+void benchLogitProc(int B, int vocab, int nBias, int iters, double &procUs, double &countUs) {
+    DL_CHECK(B >= 1 && vocab >= 1 && nBias >= 0 && nBias <= hipk::kMaxLogitBias && nBias <= vocab && iters >= 1,
+             "bench_logit_proc arguments");
+    Scratch sc;
+    std::vector<float> logits((size_t)B * vocab);
+    for (size_t i = 0; i < logits.size(); i++) logits[i] = (float)((i * 2654435761u) % 4096) * (1.f / 256.f) - 8.f;
+    std::vector<uint32_t> counts((size_t)B * vocab);
+    for (size_t i = 0; i < counts.size(); i++) counts[i] = i % 3 == 0 ? (uint32_t)(1 + i % 5) : 0u;
+    std::vector<int> slots(B), active(B, 1), ids(B), nb(B, nBias);
+    std::vector<int> biasIds((size_t)B * hipk::kMaxLogitBias, 0);
+    std::vector<float> biasVals(biasIds.size(), 0.f);
+    for (int b = 0; b < B; b++) {
+        slots[b] = b;
+        ids[b] = (int)(((size_t)b * 7919) % vocab);
+        for (int j = 0; j < nBias; j++) {  // distinct ids spread over the row
+            biasIds[(size_t)b * hipk::kMaxLogitBias + j] = (int)((size_t)j * vocab / nBias);
+            biasVals[(size_t)b * hipk::kMaxLogitBias + j] = (float)(j % 9) - 4.f;
+        }
+    }
+    hipk::LogitProcArgs g = logitProcArgs(sc, B, vocab, std::vector<float>(B, 0.8f), slots, active,
+                                          std::vector<float>(B, 0.5f), std::vector<float>(B, 1.5f), counts, B, biasIds,
+                                          biasVals, nb);
+    g.logits = sc.upload(logits);
+    g.out = sc.alloc<float>((size_t)B * vocab);
+    g.ids = sc.upload(ids);
+    hipEvent_t e0, e1;
+    DL_HIP(hipEventCreate(&e0));
+    DL_HIP(hipEventCreate(&e1));
+    auto timed = [&](auto launch) {
+        for (int i = 0; i < 5; i++) launch();
+        DL_HIP(hipEventRecord(e0, sc.s));
+        for (int i = 0; i < iters; i++) launch();
+        DL_HIP(hipEventRecord(e1, sc.s));
+        DL_HIP(hipEventSynchronize(e1));
+        float ms = 0;
+        DL_HIP(hipEventElapsedTime(&ms, e0, e1));
+        return (double)ms * 1000.0 / iters;
+    };
+    procUs = timed([&] { hipk::launchLogitProc(g, B, sc.s); });
+    countUs = timed([&] { hipk::launchLogitProcCount(g, B, sc.s); });
+    sc.sync();
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+}
+
 std::vector<float> embedding(const std::vector<float> &table, int vocab, int dim, const std::vector<int> &tokens) {
     const int B = (int)tokens.size();
     DL_CHECK(dim % 4 == 0 && table.size() == (size_t)vocab * dim, "embedding sizes");

@@ -163,6 +163,25 @@ void logprobs(const std::vector<float> &logits, int B, int vocab, const std::vec
 void benchLogprobs(const std::vector<float> &logits, int B, int vocab, int k, int iters, double &logprobsUs,
                    double &argmaxUs);
 
+// launchLogitProc over [B][vocab] logits. Row b: temps[b] (< 0: the row is not drawn and its output
+// keeps `fill`), slots[b] in [0, nSlots), active[b], presence[b], frequency[b]. counts is the
+// [nSlots][vocab] table, biasIds / biasVals [nSlots][300] with nBias[s] entries used per slot.
+// Returns the [B][vocab] output, which is pre-filled with `fill`; a write behind its last row is
+// an error.
+std::vector<float> logitProc(const std::vector<float> &logits, int B, int vocab, const std::vector<float> &temps,
+                             const std::vector<int> &slots, const std::vector<int> &active,
+                             const std::vector<float> &presence, const std::vector<float> &frequency,
+                             const std::vector<uint32_t> &counts, int nSlots, const std::vector<int> &biasIds,
+                             const std::vector<float> &biasVals, const std::vector<int> &nBias, float fill);
+// launchLogitProcCount on a [nSlots][vocab] table: returns the table after the launch.
+std::vector<uint32_t> logitProcCount(const std::vector<uint32_t> &counts, int nSlots, int vocab,
+                                     const std::vector<int> &ids, const std::vector<int> &slots,
+                                     const std::vector<int> &active);
+// Device microseconds per launch of launchLogitProc (B active rows, row b on slot b, a third of the
+// counts positive, nBias entries per slot) and of launchLogitProcCount: `iters` launches of each
+// between two events, after a warm-up.
+void benchLogitProc(int B, int vocab, int nBias, int iters, double &procUs, double &countUs);
+
 // Embedding row gather: table [vocab][dim] -> [B][dim].
 std::vector<float> embedding(const std::vector<float> &table, int vocab, int dim, const std::vector<int> &tokens);
 

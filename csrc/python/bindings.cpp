@@ -121,16 +121,43 @@ std::vector<int> runArgmax(Backend &b, const std::vector<int> &tokens, const std
     return out;
 }
 
+// Per-row logit processors (Backend LogitProc) from Python: None (no row has one) or a sequence
+// of n entries, each None (the row has none) or a dict with the optional keys "presence",
+// "frequency", "fresh" and "bias" (a dict token id -> value, read when fresh).
+std::vector<LogitProc> parseProcs(const py::object &o, size_t n) {
+    std::vector<LogitProc> procs;
+    if (o.is_none()) return procs;
+    const py::sequence seq = o.cast<py::sequence>();
+    DL_CHECK(seq.size() == n, "logit_procs: one entry (or None) per row");
+    procs.resize(n);
+    for (size_t i = 0; i < n; i++) {
+        const py::object e = seq[i];
+        if (e.is_none()) continue;
+        const py::dict d = e.cast<py::dict>();
+        LogitProc &p = procs[i];
+        p.active = true;
+        if (d.contains("presence")) p.presence = d["presence"].cast<float>();
+        if (d.contains("frequency")) p.frequency = d["frequency"].cast<float>();
+        if (d.contains("fresh")) p.fresh = d["fresh"].cast<bool>();
+        if (d.contains("bias") && !d["bias"].is_none())
+            for (auto kv : d["bias"].cast<py::dict>()) p.bias.push_back(LogitBias{kv.first.cast<int>(), kv.second.cast<float>()});
+    }
+    return procs;
+}
+
 // Per-row draws: specs from (temperature, topp, coin) lists.
 std::vector<int> runSample(Backend &b, const std::vector<int> &tokens, const std::vector<int> &positions,
                            const std::vector<int> &slots, const std::vector<float> &temps,
-                           const std::vector<float> &topps, const std::vector<float> &coins) {
+                           const std::vector<float> &topps, const std::vector<float> &coins,
+                           const py::object &logitProcs = py::none()) {
     const size_t n = tokens.size();
     DL_CHECK(temps.size() == n && topps.size() == n && coins.size() == n, "one (temperature, topp, coin) per row");
     std::vector<SampleSpec> specs(n);
     for (size_t i = 0; i < n; i++) specs[i] = SampleSpec{temps[i], topps[i], coins[i], 0.f};
     std::vector<int> out(n);
+    const std::vector<LogitProc> procs = parseProcs(logitProcs, n);
     py::gil_scoped_release rel;
+    if (!procs.empty()) b.setLogitProcs((int)n, procs.data());
     b.forwardSample((int)n, tokens.data(), positions.data(), slots.data(), specs.data(), out.data());
     return out;
 }
@@ -139,7 +166,8 @@ std::vector<int> runSample(Backend &b, const std::vector<int> &tokens, const std
 // (ids, float32 [n][21] logprobs, int32 [n][21] token ids); see Backend::lastLogprobs.
 py::tuple runLogprobs(Backend &b, const std::vector<int> &tokens, const std::vector<int> &positions,
                       const std::vector<int> &slots, const std::vector<float> &temps, const std::vector<float> &topps,
-                      const std::vector<float> &coins, const std::vector<int> &top) {
+                      const std::vector<float> &coins, const std::vector<int> &top,
+                      const py::object &logitProcs = py::none()) {
     const size_t n = tokens.size();
     DL_CHECK(positions.size() == n && slots.size() == n && temps.size() == n && topps.size() == n &&
                  coins.size() == n && top.size() == n, "one (temperature, topp, coin, top_logprobs) per row");
@@ -150,8 +178,10 @@ py::tuple runLogprobs(Backend &b, const std::vector<int> &tokens, const std::vec
     }
     std::vector<int> out(n);
     std::vector<TokenLogprob> lp;
+    const std::vector<LogitProc> procs = parseProcs(logitProcs, n);
     {
         py::gil_scoped_release rel;
+        if (!procs.empty()) b.setLogitProcs((int)n, procs.data());
         b.forwardSample((int)n, tokens.data(), positions.data(), slots.data(), specs.data(), out.data());
         lp = b.lastLogprobs();
     }
@@ -461,6 +491,50 @@ void bindOps(py::module_ &m) {
           },
           py::arg("logits"), py::arg("ids"), py::arg("requests"), py::arg("warm_logits") = py::none(),
           py::arg("warm_ids") = py::none());
+    o.def("logit_proc",
+          [](py::object logits, std::vector<float> temps, std::vector<int> slots, std::vector<int> active,
+             std::vector<float> presence, std::vector<float> frequency, py::object counts, py::object biasIds,
+             py::object biasVals, std::vector<int> nBias, float fill) {
+              const std::vector<float> l = vec<float>(logits), bv = vec<float>(biasVals);
+              const std::vector<uint32_t> c = vec<uint32_t>(counts);
+              const std::vector<int> bi = vec<int>(biasIds);
+              const int B = (int)temps.size(), S = (int)nBias.size();
+              DL_CHECK(B >= 1 && S >= 1 && l.size() % B == 0, "logit_proc: one temperature per row, one count per slot");
+              const int vocab = (int)(l.size() / B);
+              std::vector<float> out;
+              {
+                  py::gil_scoped_release rel;
+                  out = ops::logitProc(l, B, vocab, temps, slots, active, presence, frequency, c, S, bi, bv, nBias, fill);
+              }
+              return arr(out, {B, vocab});
+          },
+          py::arg("logits"), py::arg("temperatures"), py::arg("slots"), py::arg("active"), py::arg("presence"),
+          py::arg("frequency"), py::arg("counts"), py::arg("bias_ids"), py::arg("bias_values"), py::arg("n_bias"),
+          py::arg("fill"));
+    o.def("logit_proc_count",
+          [](py::object counts, int nSlots, std::vector<int> ids, std::vector<int> slots, std::vector<int> active) {
+              const std::vector<uint32_t> c = vec<uint32_t>(counts);
+              DL_CHECK(nSlots >= 1 && c.size() % nSlots == 0, "logit_proc_count: counts is [slots][vocab]");
+              const int vocab = (int)(c.size() / nSlots);
+              std::vector<uint32_t> out;
+              {
+                  py::gil_scoped_release rel;
+                  out = ops::logitProcCount(c, nSlots, vocab, ids, slots, active);
+              }
+              return arr(out, {nSlots, vocab});
+          },
+          py::arg("counts"), py::arg("n_slots"), py::arg("ids"), py::arg("slots"), py::arg("active"));
+    o.def("bench_logit_proc",
+          [](int B, int vocab, int nBias, int iters) {
+              double pu = 0, cu = 0;
+              {
+                  py::gil_scoped_release rel;
+                  ops::benchLogitProc(B, vocab, nBias, iters, pu, cu);
+              }
+              return py::make_tuple(pu, cu);
+          },
+          py::arg("batch"), py::arg("vocab"), py::arg("n_bias"), py::arg("iters") = 200,
+          "(us per launchLogitProc, us per launchLogitProcCount) on batch x vocab logits");
     o.def("bench_logprobs",
           [](py::object logits, int B, int k, int iters) {
               const std::vector<float> l = vec<float>(logits);
@@ -539,6 +613,20 @@ PYBIND11_MODULE(_C, m) {
         std::vector<float> l(logits.data(), logits.data() + logits.size());
         return sampleHost(l.data(), (int)l.size(), SampleSpec{temp, topp, coin, 0.f});
     });
+    co.def("logit_proc_host",
+           [](py::array_t<float, py::array::c_style | py::array::forcecast> logits,
+              py::array_t<uint32_t, py::array::c_style | py::array::forcecast> counts, float presence, float frequency,
+              std::vector<int> biasIds, std::vector<float> biasVals) {
+               DL_CHECK(counts.size() == logits.size() && biasIds.size() == biasVals.size(), "logit_proc_host sizes");
+               std::vector<LogitBias> bias(biasIds.size());
+               for (size_t i = 0; i < bias.size(); i++) bias[i] = LogitBias{biasIds[i], biasVals[i]};
+               py::array_t<float> out((py::ssize_t)logits.size());
+               logitProcHost(logits.data(), (int)logits.size(), counts.data(), presence, frequency, bias.data(),
+                             (int)bias.size(), out.mutable_data());
+               return out;
+           },
+           py::arg("logits"), py::arg("counts"), py::arg("presence"), py::arg("frequency"), py::arg("bias_ids"),
+           py::arg("bias_values"));
     co.def("logprobs_host", [](py::array_t<float, py::array::c_style | py::array::forcecast> logits, int chosen, int k) {
         std::vector<TokenLogprob> e(kLogprobEntries);
         logprobsHost(logits.data(), (int)logits.size(), chosen, k, e.data());
@@ -713,9 +801,10 @@ PYBIND11_MODULE(_C, m) {
         .def("forward", [](Backend &b, std::vector<int> t, std::vector<int> p, std::vector<int> s) { return runForward(b, t, p, s); },
              py::arg("tokens"), py::arg("positions"), py::arg("slots"))
         .def("forward_sample", &runSample, py::arg("tokens"), py::arg("positions"), py::arg("slots"),
-             py::arg("temperatures"), py::arg("topps"), py::arg("coins"))
+             py::arg("temperatures"), py::arg("topps"), py::arg("coins"), py::arg("logit_procs") = py::none())
         .def("forward_logprobs", &runLogprobs, py::arg("tokens"), py::arg("positions"), py::arg("slots"),
-             py::arg("temperatures"), py::arg("topps"), py::arg("coins"), py::arg("top_logprobs"))
+             py::arg("temperatures"), py::arg("topps"), py::arg("coins"), py::arg("top_logprobs"),
+             py::arg("logit_procs") = py::none())
         .def("forward_argmax", [](Backend &b, std::vector<int> t, std::vector<int> p, std::vector<int> s) { return runArgmax(b, t, p, s); },
              py::arg("tokens"), py::arg("positions"), py::arg("slots"))
         .def("last_stats", [](const Backend &b) {
@@ -1108,16 +1197,18 @@ PYBIND11_MODULE(_C, m) {
              py::arg("tokens"), py::arg("positions"), py::arg("slots"))
         .def("forward_sample",
              [](PyHipEngine &e, std::vector<int> t, std::vector<int> p, std::vector<int> s, std::vector<float> temps,
-                std::vector<float> topps, std::vector<float> coins) { return runSample(*e.engine, t, p, s, temps, topps, coins); },
-             py::arg("tokens"), py::arg("positions"), py::arg("slots"), py::arg("temperatures"), py::arg("topps"),
-             py::arg("coins"))
-        .def("forward_logprobs",
-             [](PyHipEngine &e, std::vector<int> t, std::vector<int> p, std::vector<int> s, std::vector<float> temps,
-                std::vector<float> topps, std::vector<float> coins, std::vector<int> top) {
-                 return runLogprobs(*e.engine, t, p, s, temps, topps, coins, top);
+                std::vector<float> topps, std::vector<float> coins, py::object procs) {
+                 return runSample(*e.engine, t, p, s, temps, topps, coins, procs);
              },
              py::arg("tokens"), py::arg("positions"), py::arg("slots"), py::arg("temperatures"), py::arg("topps"),
-             py::arg("coins"), py::arg("top_logprobs"))
+             py::arg("coins"), py::arg("logit_procs") = py::none())
+        .def("forward_logprobs",
+             [](PyHipEngine &e, std::vector<int> t, std::vector<int> p, std::vector<int> s, std::vector<float> temps,
+                std::vector<float> topps, std::vector<float> coins, std::vector<int> top, py::object procs) {
+                 return runLogprobs(*e.engine, t, p, s, temps, topps, coins, top, procs);
+             },
+             py::arg("tokens"), py::arg("positions"), py::arg("slots"), py::arg("temperatures"), py::arg("topps"),
+             py::arg("coins"), py::arg("top_logprobs"), py::arg("logit_procs") = py::none())
         .def("forward_argmax", [](PyHipEngine &e, std::vector<int> t, std::vector<int> p, std::vector<int> s) { return runArgmax(*e.engine, t, p, s); },
              py::arg("tokens"), py::arg("positions"), py::arg("slots"))
         .def("last_stats",

@@ -99,6 +99,9 @@ class InferenceSession {
     // log-probabilities of the forward just collected (Backend::lastLogprobs; the root draws, so
     // workers take no part)
     const std::vector<TokenLogprob> &lastLogprobs() const { return backend_->lastLogprobs(); }
+    // logit processors of the next forwardSample / launchIds (Backend::setLogitProcs; the root
+    // draws, so nothing goes to the workers)
+    void setLogitProcs(int n, const LogitProc *procs) { backend_->setLogitProcs(n, procs); }
     // Chained greedy decode of one sequence (Backend::chainLaunch; workers follow each step).
     bool chainSupported() const { return backend_->chainSupported(); }
     void chainLaunch(int token, int pos, int slot);

@@ -35,9 +35,57 @@ void logprobsHost(const float *logits, int vocab, int chosen, int k, TokenLogpro
     for (int i = 0; i < k; i++) out[1 + i] = TokenLogprob{(float)((double)logits[order[i]] - lse), order[i]};
 }
 
+// volatile intermediates: every step is rounded to f32 on its own whatever the compiler's
+// contraction setting (g++ fuses a * b - c into an FMA by default where the target has one)
+void logitProcHost(const float *logits, int vocab, const u32 *counts, float presence, float frequency,
+                   const LogitBias *bias, int nBias, float *out) {
+    for (int t = 0; t < vocab; t++) {
+        float x = logits[t];
+        if (counts[t] > 0) {
+            volatile float fc = frequency * (float)counts[t];
+            volatile float y = x - fc;
+            volatile float z = y - presence;
+            x = z;
+        }
+        out[t] = x;
+    }
+    for (int j = 0; j < nBias; j++) {
+        if (bias[j].id < 0 || bias[j].id >= vocab) continue;
+        volatile float y = out[bias[j].id] + bias[j].value;
+        out[bias[j].id] = y;
+    }
+}
+
+void Backend::setLogitProcs(int n, const LogitProc *procs) { pendingProcs_.assign(procs, procs + n); }
+
+std::vector<LogitProc> Backend::takeLogitProcs(int n) {
+    std::vector<LogitProc> procs;
+    procs.swap(pendingProcs_);
+    if (procs.empty()) return procs;
+    if ((int)procs.size() != n) throw Error("setLogitProcs: one processor per row of the forward");
+    const int vocab = (int)header().vocabSize;
+    bool any = false;
+    for (const LogitProc &p : procs) {
+        if (!p.active) continue;
+        any = true;
+        if (!p.fresh) continue;
+        if (p.bias.size() > (size_t)kMaxLogitBias) throw Error("logit_bias: at most 300 entries");
+        std::vector<int> seen;
+        for (const LogitBias &e : p.bias) {
+            if (e.id < 0 || e.id >= vocab) throw Error("logit_bias: token id out of range");
+            seen.push_back(e.id);
+        }
+        std::sort(seen.begin(), seen.end());
+        if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) throw Error("logit_bias: duplicate token id");
+    }
+    if (!any) procs.clear();  // no active row: the forward is the plain one
+    return procs;
+}
+
 void Backend::forwardSample(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs,
                             int *out) {
     const int vocab = (int)header().vocabSize;
+    const std::vector<LogitProc> procs = takeLogitProcs(n);
     if (plan().rank != 0) {  // workers take part in the forward; the root draws
         forward(n, tokens, positions, slots, nullptr);
         for (int i = 0; i < n; i++) out[i] = -1;
@@ -54,7 +102,21 @@ void Backend::forwardSample(int n, const int *tokens, const int *positions, cons
         float *row = &logits[(size_t)i * vocab];
         const int req = (int)specs[i].logprobs;
         if (req >= 1) raw.assign(row, row + vocab);  // the draw rewrites the row in place
+        const bool proc = !procs.empty() && procs[i].active && specs[i].temperature >= 0.f;
+        if (proc) {  // penalties and bias ahead of the draw; the log-probabilities score the raw row
+            const LogitProc &p = procs[i];
+            const size_t s = (size_t)slots[i];
+            if (procCounts_.size() <= s) {
+                procCounts_.resize(s + 1);
+                procBias_.resize(s + 1);
+            }
+            if (p.fresh || procCounts_[s].empty()) procCounts_[s].assign(vocab, 0);
+            if (p.fresh) procBias_[s] = p.bias;
+            logitProcHost(row, vocab, procCounts_[s].data(), p.presence, p.frequency, procBias_[s].data(),
+                          (int)procBias_[s].size(), row);
+        }
         out[i] = sampleHost(row, vocab, specs[i]);
+        if (proc && out[i] >= 0 && out[i] < vocab) procCounts_[(size_t)slots[i]][out[i]]++;
         if (req >= 1)
             logprobsHost(raw.data(), vocab, out[i], std::min(req - 1, kMaxTopLogprobs),
                          &logprobs_[(size_t)i * kLogprobEntries]);
@@ -66,6 +128,10 @@ void Backend::launchIds(int n, const int *tokens, const int *positions, const in
     if (specs)
         forwardSample(n, tokens, positions, slots, specs, pendingIds_.data());
     else {
+        if (!pendingProcs_.empty()) {
+            pendingProcs_.clear();
+            throw Error("launchIds: logit processors need a sampled forward (specs)");
+        }
         logprobs_.clear();
         forwardArgmax(n, tokens, positions, slots, pendingIds_.data());
     }

@@ -79,6 +79,29 @@ void logprobsHost(const float *logits, int vocab, int chosen, int k, TokenLogpro
 // Host implementation of one row's draw (the CPU path and the reference for the device sampler).
 int sampleHost(float *logits, int vocab, const SampleSpec &s);
 
+// Logit processors of a sampled row (OpenAI's frequency_penalty / presence_penalty / logit_bias),
+// applied to the row's logits before the draw; counts[t] is how often the row's sequence has
+// generated token t so far (prompt tokens are not counted):
+//   x = logits[t];  if counts[t] > 0: x = x - frequency * float(counts[t]);  x = x - presence
+//   if t has a bias entry: x = x + its value
+// every step one f32 operation rounded to nearest (nothing contracted to an FMA); elements with a
+// zero count and no bias are copied bit for bit. Log-probabilities keep scoring the raw logits.
+constexpr int kMaxLogitBias = 300;  // OpenAI's limit on logit_bias entries
+struct LogitBias {
+    int id;
+    float value;
+};
+struct LogitProc {
+    bool active = false;     // the row's request uses a processor (a row that does not ignores the rest)
+    float presence = 0.f;
+    float frequency = 0.f;
+    bool fresh = false;      // the row's slot starts a generation: zero its counts, take `bias`
+    std::vector<LogitBias> bias;  // read when fresh: distinct ids in [0, vocab), at most kMaxLogitBias
+};
+// Host implementation (the CPU path and the reference for the device kernel); out may be logits.
+void logitProcHost(const float *logits, int vocab, const u32 *counts, float presence, float frequency,
+                   const LogitBias *bias, int nBias, float *out);
+
 class Backend {
   public:
     virtual ~Backend() = default;
@@ -98,6 +121,11 @@ class Backend {
     // runs the forward synchronously inside launchIds (host backends: no overlap).
     virtual void launchIds(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs);
     virtual void collectIds(int *out);
+    // Logit processors of the next forwardSample / launchIds (with specs) of n rows, which consumes
+    // them: procs[i] belongs to row i and acts when that row is drawn. The backend keeps per KV slot
+    // the counts of the tokens drawn by active rows since the slot's last `fresh` row, and the bias
+    // that row brought. Root only (the root draws); without a call, forwards run as they always did.
+    virtual void setLogitProcs(int n, const LogitProc *procs);
     // Log-probabilities of the last forwardSample / collectIds: [n][kLogprobEntries] when a row of
     // that forward asked for them (SampleSpec::logprobs; rows that did not hold id -1 throughout),
     // empty otherwise and on ranks other than the root. Valid until the next forward is launched.
@@ -137,6 +165,12 @@ class Backend {
     ForwardStats stats_;
     std::vector<int> pendingIds_;  // default launchIds / collectIds
     std::vector<TokenLogprob> logprobs_;
+    std::vector<LogitProc> pendingProcs_;  // setLogitProcs, until the next sampled forward takes them
+    // takes pendingProcs_ for a forward of n rows (empty: none set); checks sizes, bias ids and counts
+    std::vector<LogitProc> takeLogitProcs(int n);
+    // host state of the default forwardSample, per slot (allocated at a slot's first fresh row)
+    std::vector<std::vector<u32>> procCounts_;
+    std::vector<std::vector<LogitBias>> procBias_;
 };
 
 // Host data plane used by the CPU backend for tensor parallelism.

@@ -493,10 +493,14 @@ bool Scheduler::step() {
         if (prefixOn_)  // positions each slot's cache (and, paged, its mapped pages) reaches
             for (int i = 0; i < next.n; i++) slotReach_[slots[i]] = std::max<size_t>(slotReach_[slots[i]], (size_t)positions[i] + 1);
         // (a greedy request that wants log-probabilities takes the sampler at temperature 0 - the
-        //  same lowest-index argmax - because the argmax paths keep no logits to score)
-        bool allGreedy = true;
-        for (auto &p : next.picks)
-            if (p.sample && (p.r->params.temperature != 0.0f || p.r->params.logprobs)) allGreedy = false;
+        //  same lowest-index argmax - because the argmax paths keep no logits to score; so does one
+        //  with penalties or a logit bias, which act between the logits and the draw)
+        bool allGreedy = true, anyProc = false;
+        for (auto &p : next.picks) {
+            if (!p.sample) continue;
+            if (p.r->params.temperature != 0.0f || p.r->params.logprobs || p.r->params.logitProc()) allGreedy = false;
+            anyProc = anyProc || p.r->params.logitProc();
+        }
         next.t.reset();
         if (allGreedy) {
             sess_.launchIds(next.n, tokens.data(), positions.data(), slots.data(), nullptr);
@@ -511,6 +515,20 @@ bool Scheduler::step() {
                 sp.coin = p.r->sampler->drawCoin();
                 if (p.r->params.logprobs)
                     sp.logprobs = 1.f + (float)std::min(std::max(p.r->params.topLogprobs, 0), kMaxTopLogprobs);
+            }
+            if (anyProc) {  // the rows' logit processors; a request's first drawn row resets its slot's state
+                std::vector<LogitProc> procs(next.n);
+                for (auto &p : next.picks) {
+                    const GenParams &gp = p.r->params;
+                    if (!p.sample || !gp.logitProc()) continue;
+                    LogitProc &lp = procs[p.row];
+                    lp.active = true;
+                    lp.presence = gp.presencePenalty;
+                    lp.frequency = gp.frequencyPenalty;
+                    lp.fresh = p.r->generated.empty();
+                    if (lp.fresh) lp.bias = gp.logitBias;
+                }
+                sess_.setLogitProcs(next.n, procs.data());
             }
             sess_.launchIds(next.n, tokens.data(), positions.data(), slots.data(), specs.data());
         }
@@ -558,6 +576,7 @@ bool Scheduler::step() {
             reason = "length";
         if (reason) {
             stats_.completed++;
+            if (r->params.logitProc()) stats_.logitProcRequests++;
             stats_.generatedTokens += r->generated.size();
             finishRequest(rp, reason);
         }

@@ -31,6 +31,12 @@ struct GenParams {
     // the generated token's, plus the topLogprobs (0..kMaxTopLogprobs) best tokens of its row
     bool logprobs = false;
     int topLogprobs = 0;
+    // logit processors (Backend LogitProc): OpenAI's penalties over the tokens generated so far and a
+    // per-token bias, applied before the draw; all three at their defaults: none
+    float presencePenalty = 0.f;
+    float frequencyPenalty = 0.f;
+    std::vector<LogitBias> logitBias;  // distinct token ids, at most kMaxLogitBias
+    bool logitProc() const { return presencePenalty != 0.f || frequencyPenalty != 0.f || !logitBias.empty(); }
 };
 
 // One generated token's log-probability record (GenParams::logprobs).
@@ -88,6 +94,7 @@ struct SchedulerStats {
     // --prefix-cache: requests admitted behind a reused prefix, the prompt tokens that saved, the
     // hits that needed a device copy (source slot still active), idle slots evicted for their pages
     u64 prefixHits = 0, prefixTokens = 0, prefixCopies = 0, prefixEvictions = 0;
+    u64 logitProcRequests = 0;  // finished requests that used penalties or a logit bias
 };
 
 class Scheduler {

@@ -195,6 +195,50 @@ def logprobs(logits, ids, top_logprobs, warm=None):
     return native().ops.logprobs(x, [int(i) for i in ids], req, wl, wi)
 
 
+MAX_LOGIT_BIAS = 300
+
+
+def _bias_tables(bias, n_slots):
+    """bias: None or one {token id: value} dict (or None) per slot -> ([S, 300] ids, [S, 300] values, [S] counts)."""
+    ids = np.zeros((n_slots, MAX_LOGIT_BIAS), np.int32)
+    vals = np.zeros((n_slots, MAX_LOGIT_BIAS), np.float32)
+    nb = [0] * n_slots
+    for s, d in enumerate(bias or []):
+        items = list((d or {}).items())
+        if len(items) > MAX_LOGIT_BIAS:
+            raise ValueError("at most 300 logit_bias entries per slot")
+        nb[s] = len(items)
+        for j, (t, v) in enumerate(items):
+            ids[s, j], vals[s, j] = int(t), float(v)
+    return ids, vals, nb
+
+
+def logit_proc(logits, temperatures, slots, active, presence, frequency, counts, bias=None, fill=float("nan")):
+    """Device logit processors (launchLogitProc) of [B, vocab] logits, OpenAI's formula in separate f32
+    steps: for an active row b on slot s = slots[b], x[t] = logits[b, t]; where counts[s, t] > 0,
+    x[t] -= frequency[b] * float(counts[s, t]) and then x[t] -= presence[b]; where t is a key of
+    bias[s], x[t] += bias[s][t]. Rows with temperatures[b] >= 0 that are not active are copied; rows
+    with temperatures[b] < 0 are not written and keep `fill`. counts is uint32 [slots, vocab], bias
+    None or one {token id: value} dict (or None) per slot. Returns float32 [B, vocab]."""
+    x = _np(logits)
+    x = x.reshape(1, -1) if x.ndim == 1 else x
+    c = np.ascontiguousarray(np.asarray(counts, np.uint32))
+    c = c.reshape(1, -1) if c.ndim == 1 else c
+    ids, vals, nb = _bias_tables(bias, c.shape[0])
+    return native().ops.logit_proc(x, [float(t) for t in temperatures], [int(s) for s in slots],
+                                   [int(bool(a)) for a in active], [float(p) for p in presence],
+                                   [float(f) for f in frequency], c, ids, vals, nb, float(fill))
+
+
+def logit_proc_count(counts, ids, slots, active):
+    """Device count update (launchLogitProcCount): counts[slots[b], ids[b]] += 1 for the active rows
+    with ids[b] >= 0 (at most one active row per slot). Returns the uint32 [slots, vocab] table after."""
+    c = np.ascontiguousarray(np.asarray(counts, np.uint32))
+    c = c.reshape(1, -1) if c.ndim == 1 else c
+    return native().ops.logit_proc_count(c, c.shape[0], [int(i) for i in ids], [int(s) for s in slots],
+                                         [int(bool(a)) for a in active])
+
+
 def argmax(logits) -> list:
     x = _np(logits)
     return native().ops.argmax(x, x.shape[0] if x.ndim == 2 else 1)

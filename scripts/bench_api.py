@@ -6,7 +6,7 @@ connection per request), and reports the aggregate completion tokens/s for tempe
 and temperature 0.8 / top_p 0.9 with per-request seeds (device sampling: only token ids come back
 to the host). One untimed round first captures the graphs.
 
-  python scripts/bench_api.py [--n 64] [--max-tokens 64] [--port 0] [--logprobs K]
+  python scripts/bench_api.py [--n 64] [--max-tokens 64] [--port 0] [--logprobs K] [--penalties]
 """
 import argparse
 import http.client
@@ -42,7 +42,7 @@ def _post(port, body, out, i):
         out[i] = e
 
 
-EXTRA = {}  # request fields added to every body (--logprobs)
+EXTRA = {}  # request fields added to every body (--logprobs, --penalties)
 
 
 def _round(port, n, max_tokens, temperature, seed0):
@@ -77,7 +77,11 @@ def main():
     ap.add_argument("--kv-dtype", default="f32", choices=["f32", "bf16"], help="KV cache (f32: the reference's, the default)")
     ap.add_argument("--logprobs", type=int, default=-1,
                     help="K >= 0: every request asks for logprobs with top_logprobs K (default: none)")
+    ap.add_argument("--penalties", action="store_true",
+                    help="every request sends frequency_penalty 0.5, presence_penalty 0.5 and a 16-entry logit_bias")
     args = ap.parse_args()
+    if args.penalties:
+        EXTRA.update(frequency_penalty=0.5, presence_penalty=0.5, logit_bias={str(1000 + 37 * i): (i % 5) - 2 for i in range(16)})
     if args.logprobs >= 0:
         EXTRA.update(logprobs=True, top_logprobs=args.logprobs)
     from distributed_llama_multiusers_amd.models.synthetic import make_tokenizer
@@ -129,6 +133,7 @@ def main():
         res["max_batch"] = args.max_batch or 4 * args.n
         res["max_tokens"] = args.max_tokens
         res["top_logprobs"] = args.logprobs if args.logprobs >= 0 else None
+        res["penalties"] = bool(args.penalties)
         print(json.dumps(res), flush=True)
     finally:
         srv.terminate()
