@@ -180,6 +180,19 @@ struct Api {
             };
             penalty("frequency_penalty", p.frequencyPenalty);
             penalty("presence_penalty", p.presencePenalty);
+            const Value &tk = body["top_k"], &mp = body["min_p"];
+            if (bad.empty() && !tk.isNull()) {
+                if (!tk.isNumber() || tk.asNumber() != std::floor(tk.asNumber()) || tk.asNumber() < 0)
+                    bad = "top_k must be an integer >= 0";
+                else  // the whole vocabulary or more: off
+                    p.topK = tk.asNumber() >= (double)sess->header().vocabSize ? 0 : (int)tk.asNumber();
+            }
+            if (bad.empty() && !mp.isNull()) {
+                if (!mp.isNumber() || !(mp.asNumber() >= 0.0 && mp.asNumber() <= 1.0))
+                    bad = "min_p must be a number from 0 to 1";
+                else
+                    p.minP = (float)mp.asNumber();
+            }
             const Value &lb = body["logit_bias"];
             if (bad.empty() && !lb.isNull()) {
                 const int vocab = (int)sess->header().vocabSize;
@@ -343,6 +356,8 @@ struct Api {
                (double)s.prefixEvictions);
         metric("dllama_logit_proc_requests_total", "counter", "Finished requests that used penalties or a logit bias.",
                (double)s.logitProcRequests);
+        metric("dllama_logit_filter_requests_total", "counter", "Finished requests with top_k or min_p on.",
+               (double)s.logitFilterRequests);
         metric("dllama_active_requests", "gauge", "Requests holding a KV slot.", (double)s.active);
         metric("dllama_queued_requests", "gauge", "Requests waiting for a KV slot.", (double)s.queued);
         metric("dllama_kv_slots", "gauge", "KV-cache slots (max concurrent sequences).", (double)sess->nSlots());
@@ -374,6 +389,7 @@ struct Api {
         v.set("prefix_copies", (double)s.prefixCopies);
         v.set("prefix_evictions", (double)s.prefixEvictions);
         v.set("logit_proc_requests", (double)s.logitProcRequests);
+        v.set("logit_filter_requests", (double)s.logitFilterRequests);
         conn.writeJson(200, v.dump());
     }
 };

@@ -155,10 +155,12 @@ void HipEngineImpl::forwardSample(int n, const int *tokens, const int *positions
                                   const SampleSpec *specs, int *out) {
     Timer t;
     std::vector<LogitProc> procs;
-    const bool proc = beginProcs(n, slots, specs, procs);
-    setInputs(n, tokens, positions, slots, specs, 0, proc ? procRows_.data() : nullptr);
+    const GraphKind kind = beginProcs(n, slots, specs, procs);
+    const bool proc = kind != GraphKind::SAMPLE;
+    setInputs(n, tokens, positions, slots, specs, 0, proc ? procRows_.data() : nullptr,
+              kind == GraphKind::SAMPLE_PROC_FILTER ? filterRows_.data() : nullptr);
     if (proc) enqueueProcState(n, slots, procs);
-    runGraph(n, proc ? GraphKind::SAMPLE_PROC : GraphKind::SAMPLE);
+    runGraph(n, kind);
     enqueueLogprobs(n, specs);
     DL_HIP(hipMemcpyAsync(hIds_, dIds_, n * sizeof(int), hipMemcpyDeviceToHost, stream_));
     syncAndCheckComm();
@@ -176,10 +178,12 @@ void HipEngineImpl::launchIds(int n, const int *tokens, const int *positions, co
     DL_CHECK(pendingN_ == 0, "launchIds: the previous forward was not collected");
     Timer t;
     std::vector<LogitProc> procs;
-    const bool proc = beginProcs(n, slots, specs, procs);
-    setInputs(n, tokens, positions, slots, specs, 0, proc ? procRows_.data() : nullptr);
+    const GraphKind kind = beginProcs(n, slots, specs, procs);
+    const bool proc = kind != GraphKind::SAMPLE;
+    setInputs(n, tokens, positions, slots, specs, 0, proc ? procRows_.data() : nullptr,
+              kind == GraphKind::SAMPLE_PROC_FILTER ? filterRows_.data() : nullptr);
     if (proc) enqueueProcState(n, slots, procs);
-    runGraph(n, proc ? GraphKind::SAMPLE_PROC : specs ? GraphKind::SAMPLE : GraphKind::ARGMAX);
+    runGraph(n, specs ? kind : GraphKind::ARGMAX);
     enqueueLogprobs(n, specs);
     DL_HIP(hipMemcpyAsync(hIds_, dIds_, n * sizeof(int), hipMemcpyDeviceToHost, stream_));
     pendingN_ = n;
@@ -199,18 +203,22 @@ void HipEngineImpl::collectIds(int *out) {
 
 // The logit processors handed over for this forward (Backend::setLogitProcs). Ranks other than the
 // root drop them: they neither hold the full logits nor draw, and run their SAMPLE schedule with
-// the same collectives in the same order. Returns whether a row is active, with procRows_ filled.
-bool HipEngineImpl::beginProcs(int n, const int *slots, const SampleSpec *specs, std::vector<LogitProc> &procs) {
-    if (pendingProcs_.empty()) return false;
+// the same collectives in the same order. Returns the sampled forward's graph kind: SAMPLE without an
+// active row, else SAMPLE_PROC with procRows_ filled, or SAMPLE_PROC_FILTER with filterRows_ filled
+// too when one of the active rows has top_k or min_p on.
+HipEngineImpl::GraphKind HipEngineImpl::beginProcs(int n, const int *slots, const SampleSpec *specs,
+                                                   std::vector<LogitProc> &procs) {
+    if (pendingProcs_.empty()) return GraphKind::SAMPLE;
     if (!specs) {
         pendingProcs_.clear();
         throw Error("launchIds: logit processors need a sampled forward (specs)");
     }
     procs = takeLogitProcs(n);
-    if (procs.empty() || rank() != 0) return false;
+    if (procs.empty() || rank() != 0) return GraphKind::SAMPLE;
     std::vector<int> seen;
     procRows_.assign((size_t)n * 4, 0.f);
-    bool any = false;
+    filterRows_.assign((size_t)n, hipk::LogitFilterRow{0, -INFINITY, 0, 0});
+    bool any = false, anyFilter = false;
     for (int b = 0; b < n; b++) {
         const LogitProc &p = procs[b];
         if (!p.active || specs[b].temperature < 0.f) continue;
@@ -220,11 +228,15 @@ bool HipEngineImpl::beginProcs(int n, const int *slots, const SampleSpec *specs,
         procRows_[(size_t)b * 4 + 1] = p.frequency;
         procRows_[(size_t)b * 4 + 2] = 1.f;
         any = true;
+        if (p.filter(specs[b].temperature, (int)h_.vocabSize)) {
+            filterRows_[b] = hipk::LogitFilterRow{p.topK, minPDelta(specs[b].temperature, p.minP), 1, 0};
+            anyFilter = true;
+        }
     }
     std::sort(seen.begin(), seen.end());
     DL_CHECK(std::adjacent_find(seen.begin(), seen.end()) == seen.end(),
              "logit processors: two drawn rows of one forward share a slot");
-    return any;
+    return !any ? GraphKind::SAMPLE : anyFilter ? GraphKind::SAMPLE_PROC_FILTER : GraphKind::SAMPLE_PROC;
 }
 
 // Before the forward, in stream order: a fresh slot's counts are zeroed and its bias entries and

@@ -40,7 +40,7 @@ const CtxBucket &HipEngineImpl::bucketFor(int maxPos) const {
 }
 
 void HipEngineImpl::setInputs(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs,
-                              int ahead, const float *procRows) {
+                              int ahead, const float *procRows, const hipk::LogitFilterRow *filterRows) {
     DL_CHECK(n >= 1 && (u32)n <= cfg_.maxBatch, "batch size out of range");
     DL_CHECK(chainHead_ == chainTail_, "a chained decode step is still in flight");
     for (int b = 0; b < n; b++) {
@@ -90,6 +90,11 @@ void HipEngineImpl::setInputs(int n, const int *tokens, const int *positions, co
     if (procRows) {  // the rows' logit processors, behind the specs
         std::memcpy(hIn_ + 7 * MB, procRows, (size_t)n * 4 * sizeof(float));
         words = 7 * (size_t)MB + 4 * (size_t)n;
+    }
+    if (filterRows) {  // the rows' candidate filters, behind the processors
+        static_assert(sizeof(hipk::LogitFilterRow) == 4 * sizeof(int), "filter row layout");
+        std::memcpy(hIn_ + 11 * MB, filterRows, (size_t)n * sizeof(hipk::LogitFilterRow));
+        words = 11 * (size_t)MB + 4 * (size_t)n;
     }
     // one copy of the row arrays (the unused tail of each is never read)
     DL_HIP(hipMemcpyAsync(dTok_, hIn_, words * sizeof(int), hipMemcpyHostToDevice, stream_));
@@ -694,7 +699,8 @@ void HipEngineImpl::enqueueTokenPick(int n, GraphKind kind) {
     // logits for the host (LOGITS) and sampled rows (SAMPLE) are needed on the root only: the
     // vocab slices are gathered to rank 0 (the reference's SYNC_NODE_SLICES_EXCEPT_ROOT), the
     // other ranks publish theirs and skip the unshard and the draw (the root's ids are used)
-    const bool sampled = kind == GraphKind::SAMPLE || kind == GraphKind::SAMPLE_PROC;
+    const bool filtered = kind == GraphKind::SAMPLE_PROC_FILTER;
+    const bool sampled = kind == GraphKind::SAMPLE || kind == GraphKind::SAMPLE_PROC || filtered;
     const bool rootOnly = kind == GraphKind::LOGITS || sampled;
     if (p.nRanks > 1 && !distArgmax) {
         ProfScope ps(this, "allgather");
@@ -712,10 +718,25 @@ void HipEngineImpl::enqueueTokenPick(int n, GraphKind kind) {
             // SAMPLE_PROC (root only): the drawn rows' penalties and bias into the processed buffer,
             // which the sampler reads instead; the raw logits stay for the log-probabilities; the
             // drawn tokens are counted behind the draw
-            const bool proc = kind == GraphKind::SAMPLE_PROC;
+            // SAMPLE_PROC_FILTER: top_k / min_p then mask the processed rows in place; the filter's
+            // partial histograms and maxima live in the sampler's scratch, which the sampler rewrites
+            // before it reads it
+            const bool proc = kind == GraphKind::SAMPLE_PROC || filtered;
             if (proc) {
                 ProfScope ps(this, "logit_proc");
                 hipk::launchLogitProc(logitProcArgs(full), n, stream_);
+            }
+            if (filtered) {
+                ProfScope ps(this, "logit_filter");
+                hipk::LogitFilterArgs f;
+                f.logits = dProcLogits_;
+                f.vocab = h_.vocabSize;
+                f.spec = dSpec_;
+                f.rows = dFilter_;
+                f.hist = reinterpret_cast<uint32_t *>(sampleScratch_.hist);
+                f.part = sampleScratch_.part;
+                f.state = dFilterState_;
+                hipk::launchLogitFilter(f, n, stream_);
             }
             {
                 ProfScope ps(this, "sample");

@@ -103,7 +103,9 @@ class HipEngineImpl : public HipEngine {
     // ------------------------------------------------------------------ internals
     // SAMPLE_PROC: SAMPLE with the logit processors between the logits and the draw (root rank of a
     // forward with an active LogitProc row; every other forward takes the kinds it always took)
-    enum class GraphKind { LOGITS = 0, ARGMAX = 1, CHAIN = 2, SAMPLE = 3, SAMPLE_PROC = 4 };
+    // SAMPLE_PROC_FILTER: SAMPLE_PROC with the candidate filter (top_k / min_p) between the processors
+    // and the draw (a forward with a row whose filter is on)
+    enum class GraphKind { LOGITS = 0, ARGMAX = 1, CHAIN = 2, SAMPLE = 3, SAMPLE_PROC = 4, SAMPLE_PROC_FILTER = 5 };
 
     // engine.cpp
     void syncAndCheckComm();
@@ -209,9 +211,10 @@ class HipEngineImpl : public HipEngine {
     // engine_forward.cpp
     void setupBuckets();
     const CtxBucket &bucketFor(int maxPos) const;
-    // procRows: [n][4] (presence, frequency, active, -) of a SAMPLE_PROC forward, else null
+    // procRows: [n][4] (presence, frequency, active, -) of a SAMPLE_PROC / SAMPLE_PROC_FILTER forward,
+    // else null; filterRows: [n] of a SAMPLE_PROC_FILTER forward, else null
     void setInputs(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs = nullptr,
-                   int ahead = 0, const float *procRows = nullptr);
+                   int ahead = 0, const float *procRows = nullptr, const hipk::LogitFilterRow *filterRows = nullptr);
     int tpPasses(const DevMat &m, int bc) const;
     int batchChunk(const DevMat &m, int pro, int epi) const;
     int passesFor(const DevMat &m, int epi, int B) const {
@@ -421,11 +424,17 @@ class HipEngineImpl : public HipEngine {
     float *dProcLogits_ = nullptr;                 // [maxBatch][vocab]
     float4 *dProc_ = nullptr;                      // [maxBatch] per row, behind dSpec_ in the input block
     std::vector<float> procRows_;                  // host copy of the forward being set up
+    // candidate filter (top_k / min_p) of a SAMPLE_PROC_FILTER forward: per row (topK, delta, on, -)
+    // behind dProc_ in the input block, and the filter's per-row state (its partial histograms and
+    // maxima use the sampler's scratch, which the sampler rewrites before it reads it)
+    hipk::LogitFilterRow *dFilter_ = nullptr;      // [maxBatch]
+    std::vector<hipk::LogitFilterRow> filterRows_;
+    uint32_t *dFilterState_ = nullptr;             // [maxBatch][kLogitFilterStateWords], zero between launches
     size_t procBytes() const;
     hipk::LogitProcArgs logitProcArgs(const float *raw) const;
-    // takes the pending processors of a sampled forward: true when a row is active (the forward then
-    // runs as SAMPLE_PROC); beginProcs fills procRows_, enqueueProcState resets / uploads fresh slots
-    bool beginProcs(int n, const int *slots, const SampleSpec *specs, std::vector<LogitProc> &procs);
+    // takes the pending processors of a sampled forward and returns its graph kind (SAMPLE: no row is
+    // active); beginProcs fills procRows_ / filterRows_, enqueueProcState resets / uploads fresh slots
+    GraphKind beginProcs(int n, const int *slots, const SampleSpec *specs, std::vector<LogitProc> &procs);
     void enqueueProcState(int n, const int *slots, const std::vector<LogitProc> &procs);
     // measured-sync slots (syncSlots, hipk::syncFoldWords) and their host copies: [0] the last
     // forward / chain, [1 + k] chain step k % kChainDepth (chainLaunch / chainCollect)

@@ -90,7 +90,7 @@ void HipEngineImpl::checkFusedResidency() {
 size_t HipEngineImpl::procBytes() const {
     if (rank() != 0) return 0;
     return (size_t)cfg_.nSlots * ((size_t)h_.vocabSize * sizeof(uint32_t) + kMaxLogitBias * sizeof(hipk::LogitBiasEntry) + sizeof(int)) +
-           (size_t)cfg_.maxBatch * h_.vocabSize * sizeof(float);
+           (size_t)cfg_.maxBatch * (h_.vocabSize * sizeof(float) + hipk::kLogitFilterStateWords * sizeof(uint32_t));
 }
 
 int HipEngineImpl::tpPasses(const DevMat &m, int bc) const {
@@ -104,15 +104,17 @@ void HipEngineImpl::allocBuffers() {
     const u32 MB = cfg_.maxBatch;
     const ShardPlan &p = plan_;
     // [tokens | positions | slots | sample specs (4 floats per row) | logit processors (4 floats per
-    // row)]: one H2D copy per forward, up to the last array the forward uses
-    dTok_ = dalloc<int>(11 * (size_t)MB);
+    // row) | candidate filters (4 words per row)]: one H2D copy per forward, up to the last array the
+    // forward uses
+    dTok_ = dalloc<int>(15 * (size_t)MB);
     dPos_ = dTok_ + MB;
     dSlot_ = dTok_ + 2 * MB;
     dSpec_ = reinterpret_cast<float4 *>(dTok_ + 3 * MB);
     dProc_ = reinterpret_cast<float4 *>(dTok_ + 7 * MB);
+    dFilter_ = reinterpret_cast<hipk::LogitFilterRow *>(dTok_ + 11 * MB);
     dIds_ = dalloc<int>(MB);
     dHist_ = dalloc<int>((size_t)decodeRows_ * h_.seqLen);  // greedy chains only (decode rows)
-    hIn_ = halloc<int>(11 * MB);
+    hIn_ = halloc<int>(15 * MB);
     if (rank() == 0) {  // logit processors: the root draws
         const size_t S = cfg_.nSlots, V = h_.vocabSize;
         dProcCounts_ = dalloc<uint32_t>(S * V);
@@ -123,6 +125,8 @@ void HipEngineImpl::allocBuffers() {
         hProcNBias_ = halloc<int>(S);
         DL_HIP(hipMemsetAsync(dProcCounts_, 0, S * V * sizeof(uint32_t), stream_));
         DL_HIP(hipMemsetAsync(dProcNBias_, 0, S * sizeof(int), stream_));
+        dFilterState_ = dalloc<uint32_t>((size_t)MB * hipk::kLogitFilterStateWords);
+        DL_HIP(hipMemsetAsync(dFilterState_, 0, (size_t)MB * hipk::kLogitFilterStateWords * sizeof(uint32_t), stream_));
     }
     hIds_ = halloc<int>(MB);
     hErr_ = halloc<int>(2);

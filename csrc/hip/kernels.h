@@ -593,6 +593,39 @@ void launchLogitProc(const LogitProcArgs &a, int B, hipStream_t s);
 // forward holds at most one row per slot).
 void launchLogitProcCount(const LogitProcArgs &a, int B, hipStream_t s);
 
+// Candidate filter (top_k / min_p) of B rows of full-vocabulary logits, in place, between the logit
+// processors and the sampler. For a row b with rows[b].active != 0 and spec[b].x > 0:
+//   thr_k = the topK-th largest value of the row, with multiplicity   (1 <= topK < vocab, else -inf)
+//   thr_p = max of the row + delta                                    (delta == -inf: off)
+//   x[t]  = x[t] >= max(thr_k, thr_p) ? x[t] : -inf                   (f32 comparison)
+// survivors keep their bits, ties at the threshold all survive, -0.0 and +0.0 are one value. Every
+// other row is neither read nor written. Four launches of sampleGroups(B) workgroups per row: three
+// 11/11/10-bit radix passes over the order-preserving key of x that count candidates in integer
+// histograms (per-wave copies in LDS, partial histograms to `hist`, the row's last arriver sums
+// them and picks the digit; the first pass also reduces the row maximum), then the mask pass in
+// 16-byte loads and stores. Counts are integers, so a row's result does not depend on B, on the
+// arrival order or on the call. Rows without top-k skip the histograms. `state` must be
+// zero-initialised once; every call leaves its counters zero. `hist` and `part` need no
+// initialisation and may be the sampler's (SampleScratch::hist / part: same shapes) when the
+// sampler runs behind the filter on the same stream.
+struct LogitFilterRow {
+    int topK;
+    float delta;  // minPDelta(temperature, min_p), -inf: off
+    int active;
+    int pad;
+};
+constexpr int kLogitFilterStateWords = 4;
+struct LogitFilterArgs {
+    float *logits = nullptr;               // [B][vocab], filtered in place
+    int vocab = 0;
+    const float4 *spec = nullptr;          // [B] (temperature, -, -, -)
+    const LogitFilterRow *rows = nullptr;  // [B]
+    uint32_t *hist = nullptr;              // [B][sampleGroups(B)][2048]
+    float *part = nullptr;                 // [B][kSampleMaxGroups]
+    uint32_t *state = nullptr;             // [B][kLogitFilterStateWords]
+};
+void launchLogitFilter(const LogitFilterArgs &a, int B, hipStream_t s);
+
 // Round-trip f32 partial sums through Q80 blocks in place (the reference's ZQ cast before the
 // exchange) - used ahead of a plain all-reduce when the fused exchange is not available.
 void launchQ80Roundtrip(float *x, size_t n, hipStream_t s);

@@ -1113,6 +1113,110 @@ void benchLogitProc(int B, int vocab, int nBias, int iters, double &procUs, doub
     (void)hipEventDestroy(e1);
 }
 
+namespace {
+// spec / filter rows and the scratch of a LogitFilterArgs
+hipk::LogitFilterArgs logitFilterArgs(Scratch &sc, int B, int vocab, const std::vector<float> &temps,
+                                      const std::vector<int> &topK, const std::vector<float> &delta,
+                                      const std::vector<int> &active) {
+    DL_CHECK(B >= 1 && vocab >= 1, "logit_filter sizes");
+    DL_CHECK(temps.size() == (size_t)B && topK.size() == (size_t)B && delta.size() == (size_t)B &&
+                 active.size() == (size_t)B, "logit_filter: one entry per row");
+    std::vector<float> spec((size_t)B * 4, 0.f);
+    std::vector<hipk::LogitFilterRow> rows(B);
+    for (int b = 0; b < B; b++) {
+        spec[(size_t)b * 4] = temps[b];
+        rows[b] = hipk::LogitFilterRow{topK[b], delta[b], active[b] ? 1 : 0, 0};
+    }
+    hipk::LogitFilterArgs g;
+    g.vocab = vocab;
+    g.spec = reinterpret_cast<const float4 *>(sc.upload(spec));
+    g.rows = sc.upload(rows);
+    g.hist = sc.alloc<uint32_t>(hipk::SampleScratch::histFloats(B));
+    g.part = sc.alloc<float>((size_t)B * hipk::kSampleMaxGroups);
+    g.state = sc.alloc<uint32_t>((size_t)B * hipk::kLogitFilterStateWords);  // (alloc zero-fills)
+    return g;
+}
+}  // namespace
+
+std::vector<float> logitFilter(const std::vector<float> &logits, int B, int vocab, const std::vector<float> &temps,
+                               const std::vector<int> &topK, const std::vector<float> &delta,
+                               const std::vector<int> &active) {
+    DL_CHECK(B >= 1 && vocab >= 1 && logits.size() == (size_t)B * vocab, "logit_filter: logits is [B][vocab]");
+    Scratch sc;
+    hipk::LogitFilterArgs g = logitFilterArgs(sc, B, vocab, temps, topK, delta, active);
+    constexpr size_t kPad = 256;  // guard elements behind the last row
+    const float guard = -7.5f;
+    std::vector<float> padded(logits);
+    padded.resize(logits.size() + kPad, guard);
+    g.logits = sc.upload(padded);
+    hipk::launchLogitFilter(g, B, sc.s);
+    sc.sync();
+    std::vector<float> out = sc.download(g.logits, padded.size());
+    for (size_t i = logits.size(); i < out.size(); i++)
+        DL_CHECK(std::memcmp(&out[i], &guard, sizeof(float)) == 0, "logit_filter: the launch wrote past the last row");
+    const std::vector<uint32_t> state = sc.download(g.state, (size_t)B * hipk::kLogitFilterStateWords);
+    for (int b = 0; b < B; b++)
+        DL_CHECK(state[(size_t)b * hipk::kLogitFilterStateWords + 3] == 0, "logit_filter: a row's counter is not back to zero");
+    out.resize(logits.size());
+    return out;
+}
+
+void benchLogitFilter(int B, int vocab, int topK, float delta, int iters, double &copyUs, double &copyFilterUs,
+                      double &sampleUs) {
+    DL_CHECK(B >= 1 && vocab >= 2 && iters >= 1, "bench_logit_filter arguments");
+    Scratch sc;
+    std::vector<float> logits((size_t)B * vocab);
+    uint32_t r = 12345u;  // sums of 4 uniform draws: a bell shape over about [-8, 8]
+    for (size_t i = 0; i < logits.size(); i++) {
+        float v = 0.f;
+        for (int j = 0; j < 4; j++) {
+            r = r * 1664525u + 1013904223u;
+            v += (float)(r >> 8) * (1.f / 16777216.f);
+        }
+        logits[i] = (v - 2.f) * 4.f;
+    }
+    hipk::LogitFilterArgs g = logitFilterArgs(sc, B, vocab, std::vector<float>(B, 0.8f), std::vector<int>(B, topK),
+                                              std::vector<float>(B, delta), std::vector<int>(B, 1));
+    const float *src = sc.upload(logits);
+    g.logits = sc.alloc<float>(logits.size());
+    const size_t bytes = logits.size() * sizeof(float);
+    hipk::SampleArgs sa;
+    sa.logits = g.logits;
+    sa.vocab = vocab;
+    std::vector<float> sspec((size_t)B * 4, 0.f);
+    for (int b = 0; b < B; b++) {
+        sspec[(size_t)b * 4] = 0.8f;
+        sspec[(size_t)b * 4 + 1] = 0.9f;
+        sspec[(size_t)b * 4 + 2] = (float)((b * 37 + 11) % 100) * 0.01f;
+    }
+    sa.spec = reinterpret_cast<const float4 *>(sc.upload(sspec));
+    sa.ids = sc.alloc<int>(B);
+    sa.scratch.carve(sc.alloc<uint8_t>(hipk::SampleScratch::bytes(B)), B);  // (alloc zero-fills)
+    hipEvent_t e0, e1;
+    DL_HIP(hipEventCreate(&e0));
+    DL_HIP(hipEventCreate(&e1));
+    auto timed = [&](auto launch) {
+        for (int i = 0; i < 5; i++) launch();
+        DL_HIP(hipEventRecord(e0, sc.s));
+        for (int i = 0; i < iters; i++) launch();
+        DL_HIP(hipEventRecord(e1, sc.s));
+        DL_HIP(hipEventSynchronize(e1));
+        float ms = 0;
+        DL_HIP(hipEventElapsedTime(&ms, e0, e1));
+        return (double)ms * 1000.0 / iters;
+    };
+    auto copy = [&] { DL_HIP(hipMemcpyAsync(g.logits, src, bytes, hipMemcpyDeviceToDevice, sc.s)); };
+    copyUs = timed(copy);
+    copyFilterUs = timed([&] {
+        copy();
+        hipk::launchLogitFilter(g, B, sc.s);
+    });
+    sampleUs = timed([&] { hipk::launchSample(sa, B, sc.s); });  // on the filtered rows
+    sc.sync();
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+}
+
 std::vector<float> embedding(const std::vector<float> &table, int vocab, int dim, const std::vector<int> &tokens) {
     const int B = (int)tokens.size();
     DL_CHECK(dim % 4 == 0 && table.size() == (size_t)vocab * dim, "embedding sizes");

@@ -182,6 +182,19 @@ std::vector<uint32_t> logitProcCount(const std::vector<uint32_t> &counts, int nS
 // between two events, after a warm-up.
 void benchLogitProc(int B, int vocab, int nBias, int iters, double &procUs, double &countUs);
 
+// launchLogitFilter over a copy of [B][vocab] logits. Row b: temps[b], topK[b], delta[b] (-inf: min_p
+// off), active[b]. Returns the [B][vocab] buffer after the launch; a write behind its last row, or a
+// row counter left non-zero, is an error.
+std::vector<float> logitFilter(const std::vector<float> &logits, int B, int vocab, const std::vector<float> &temps,
+                               const std::vector<int> &topK, const std::vector<float> &delta,
+                               const std::vector<int> &active);
+// Device microseconds, each over `iters` back-to-back repeats between two events after a warm-up, on
+// B active rows of bell-shaped logits at temperature 0.8: a device copy of the logits; that copy
+// followed by launchLogitFilter(topK, delta) on the copy (the filter works in place, so every launch
+// gets fresh rows); launchSample (top-p 0.9) on the filtered rows.
+void benchLogitFilter(int B, int vocab, int topK, float delta, int iters, double &copyUs, double &copyFilterUs,
+                      double &sampleUs);
+
 // Embedding row gather: table [vocab][dim] -> [B][dim].
 std::vector<float> embedding(const std::vector<float> &table, int vocab, int dim, const std::vector<int> &tokens);
 

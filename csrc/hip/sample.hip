@@ -426,7 +426,7 @@ __global__ __launch_bounds__(kSampleWg) void samplePhaseKernel(SampleArgs a) {
             if (x > mx) {
                 sm = sm * __expf(mx - x) + 1.f;
                 mx = x;
-            } else {
+            } else if (x != -INFINITY) {  // a masked candidate (launchLogitFilter): -inf - -inf is NaN
                 sm += __expf(x - mx);
             }
         });

@@ -139,6 +139,8 @@ std::vector<LogitProc> parseProcs(const py::object &o, size_t n) {
         if (d.contains("presence")) p.presence = d["presence"].cast<float>();
         if (d.contains("frequency")) p.frequency = d["frequency"].cast<float>();
         if (d.contains("fresh")) p.fresh = d["fresh"].cast<bool>();
+        if (d.contains("top_k") && !d["top_k"].is_none()) p.topK = d["top_k"].cast<int>();
+        if (d.contains("min_p") && !d["min_p"].is_none()) p.minP = d["min_p"].cast<float>();
         if (d.contains("bias") && !d["bias"].is_none())
             for (auto kv : d["bias"].cast<py::dict>()) p.bias.push_back(LogitBias{kv.first.cast<int>(), kv.second.cast<float>()});
     }
@@ -535,6 +537,32 @@ void bindOps(py::module_ &m) {
           },
           py::arg("batch"), py::arg("vocab"), py::arg("n_bias"), py::arg("iters") = 200,
           "(us per launchLogitProc, us per launchLogitProcCount) on batch x vocab logits");
+    o.def("logit_filter",
+          [](py::object logits, std::vector<float> temps, std::vector<int> topK, std::vector<float> delta,
+             std::vector<int> active) {
+              const std::vector<float> l = vec<float>(logits);
+              const int B = (int)temps.size();
+              DL_CHECK(B >= 1 && l.size() % B == 0, "logit_filter: one temperature per row");
+              const int vocab = (int)(l.size() / B);
+              std::vector<float> out;
+              {
+                  py::gil_scoped_release rel;
+                  out = ops::logitFilter(l, B, vocab, temps, topK, delta, active);
+              }
+              return arr(out, {B, vocab});
+          },
+          py::arg("logits"), py::arg("temperatures"), py::arg("top_k"), py::arg("delta"), py::arg("active"));
+    o.def("bench_logit_filter",
+          [](int B, int vocab, int topK, float delta, int iters) {
+              double cu = 0, fu = 0, su = 0;
+              {
+                  py::gil_scoped_release rel;
+                  ops::benchLogitFilter(B, vocab, topK, delta, iters, cu, fu, su);
+              }
+              return py::make_tuple(cu, fu, su);
+          },
+          py::arg("batch"), py::arg("vocab"), py::arg("top_k"), py::arg("delta"), py::arg("iters") = 200,
+          "(us per device copy of the logits, us per copy + launchLogitFilter, us per launchSample on the filtered rows)");
     o.def("bench_logprobs",
           [](py::object logits, int B, int k, int iters) {
               const std::vector<float> l = vec<float>(logits);
@@ -627,6 +655,17 @@ PYBIND11_MODULE(_C, m) {
            },
            py::arg("logits"), py::arg("counts"), py::arg("presence"), py::arg("frequency"), py::arg("bias_ids"),
            py::arg("bias_values"));
+    co.def("logit_filter_host",
+           [](py::array_t<float, py::array::c_style | py::array::forcecast> logits, int topK, float delta) {
+               py::array_t<float> out((py::ssize_t)logits.size());
+               std::copy(logits.data(), logits.data() + logits.size(), out.mutable_data());
+               logitFilterHost(out.mutable_data(), (int)logits.size(), topK, delta);
+               return out;
+           },
+           py::arg("logits"), py::arg("top_k"), py::arg("delta"),
+           "One row through logitFilterHost: top_k (0 or >= vocab: off), delta = min_p_delta(T, min_p) (-inf: off).");
+    co.def("min_p_delta", &minPDelta, py::arg("temperature"), py::arg("min_p"),
+           "T * log(min_p) as float32 (-inf for min_p <= 0): the distance below the row maximum that min_p keeps.");
     co.def("logprobs_host", [](py::array_t<float, py::array::c_style | py::array::forcecast> logits, int chosen, int k) {
         std::vector<TokenLogprob> e(kLogprobEntries);
         logprobsHost(logits.data(), (int)logits.size(), chosen, k, e.data());

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <functional>
 #include <numeric>
 #include <vector>
 
@@ -56,6 +57,27 @@ void logitProcHost(const float *logits, int vocab, const u32 *counts, float pres
     }
 }
 
+float minPDelta(float T, float minP) {
+    if (!(minP > 0.f)) return -INFINITY;
+    volatile float l = std::log(minP);  // (f32 overload; the product is rounded on its own)
+    return T * l;
+}
+
+void logitFilterHost(float *x, int vocab, int topK, float delta) {
+    float thr = -INFINITY;
+    if (topK >= 1 && topK < vocab) {
+        std::vector<float> v(x, x + vocab);
+        std::nth_element(v.begin(), v.begin() + (topK - 1), v.end(), std::greater<float>());
+        thr = v[topK - 1];
+    }
+    if (delta > -INFINITY) {
+        volatile float tp = *std::max_element(x, x + vocab) + delta;
+        thr = std::max(thr, (float)tp);
+    }
+    for (int t = 0; t < vocab; t++)
+        if (!(x[t] >= thr)) x[t] = -INFINITY;
+}
+
 void Backend::setLogitProcs(int n, const LogitProc *procs) { pendingProcs_.assign(procs, procs + n); }
 
 std::vector<LogitProc> Backend::takeLogitProcs(int n) {
@@ -68,6 +90,8 @@ std::vector<LogitProc> Backend::takeLogitProcs(int n) {
     for (const LogitProc &p : procs) {
         if (!p.active) continue;
         any = true;
+        if (p.topK < 0) throw Error("top_k: a count >= 0");
+        if (!(p.minP >= 0.f && p.minP <= 1.f)) throw Error("min_p: a number from 0 to 1");
         if (!p.fresh) continue;
         if (p.bias.size() > (size_t)kMaxLogitBias) throw Error("logit_bias: at most 300 entries");
         std::vector<int> seen;
@@ -114,6 +138,8 @@ void Backend::forwardSample(int n, const int *tokens, const int *positions, cons
             if (p.fresh) procBias_[s] = p.bias;
             logitProcHost(row, vocab, procCounts_[s].data(), p.presence, p.frequency, procBias_[s].data(),
                           (int)procBias_[s].size(), row);
+            if (p.filter(specs[i].temperature, vocab))
+                logitFilterHost(row, vocab, p.topK, minPDelta(specs[i].temperature, p.minP));
         }
         out[i] = sampleHost(row, vocab, specs[i]);
         if (proc && out[i] >= 0 && out[i] < vocab) procCounts_[(size_t)slots[i]][out[i]]++;

@@ -97,10 +97,29 @@ struct LogitProc {
     float frequency = 0.f;
     bool fresh = false;      // the row's slot starts a generation: zero its counts, take `bias`
     std::vector<LogitBias> bias;  // read when fresh: distinct ids in [0, vocab), at most kMaxLogitBias
+    // candidate filter behind the penalties and the bias (logitFilterHost), re-sent every row like the
+    // penalties; acts on rows drawn at a temperature > 0
+    int topK = 0;     // 0 or >= vocab: off
+    float minP = 0.f;  // 0: off
+    bool filter(float temperature, int vocab) const {
+        return active && temperature > 0.f && ((topK >= 1 && topK < vocab) || minP > 0.f);
+    }
 };
 // Host implementation (the CPU path and the reference for the device kernel); out may be logits.
 void logitProcHost(const float *logits, int vocab, const u32 *counts, float presence, float frequency,
                    const LogitBias *bias, int nBias, float *out);
+
+// Candidate filter of a sampled row (top_k / min_p), in place on the row's logits after the
+// penalties and the bias, ahead of the draw at temperature T > 0:
+//   thr_k = the topK-th largest value of x, counted with multiplicity  (1 <= topK < vocab, else -inf)
+//   thr_p = max(x) + delta, delta = minPDelta(T, min_p)                (delta == -inf: off)
+//   x[t]  = x[t] >= max(thr_k, thr_p) ? x[t] : -inf                    (f32 comparison)
+// so ties at the k-th value all survive (top_k keeps at least k tokens), survivors keep their bits and
+// the maximum always survives. min_p keeps t iff p[t] >= min_p * p_max under softmax(x / T), which is
+// x[t] >= max(x) + T * log(min_p): minPDelta is that one f32 product (-inf for min_p <= 0), the only
+// place a logarithm is taken.
+float minPDelta(float T, float minP);
+void logitFilterHost(float *x, int vocab, int topK, float delta);
 
 class Backend {
   public:

@@ -527,6 +527,8 @@ bool Scheduler::step() {
                     lp.frequency = gp.frequencyPenalty;
                     lp.fresh = p.r->generated.empty();
                     if (lp.fresh) lp.bias = gp.logitBias;
+                    lp.topK = gp.topK;
+                    lp.minP = gp.minP;
                 }
                 sess_.setLogitProcs(next.n, procs.data());
             }
@@ -576,7 +578,8 @@ bool Scheduler::step() {
             reason = "length";
         if (reason) {
             stats_.completed++;
-            if (r->params.logitProc()) stats_.logitProcRequests++;
+            if (r->params.penalized()) stats_.logitProcRequests++;
+            if (r->params.logitFilter()) stats_.logitFilterRequests++;
             stats_.generatedTokens += r->generated.size();
             finishRequest(rp, reason);
         }

@@ -36,7 +36,15 @@ struct GenParams {
     float presencePenalty = 0.f;
     float frequencyPenalty = 0.f;
     std::vector<LogitBias> logitBias;  // distinct token ids, at most kMaxLogitBias
-    bool logitProc() const { return presencePenalty != 0.f || frequencyPenalty != 0.f || !logitBias.empty(); }
+    // candidate filter (logitFilterHost) behind them: the topK best logits (ties kept) and / or the
+    // tokens with at least minP times the best token's probability; 0: off (a topK >= the vocabulary
+    // size is off too: callers pass 0). A greedy request ignores both: the argmax always survives.
+    int topK = 0;
+    float minP = 0.f;
+    bool penalized() const { return presencePenalty != 0.f || frequencyPenalty != 0.f || !logitBias.empty(); }
+    bool logitFilter() const { return temperature != 0.f && (topK > 0 || minP > 0.f); }
+    // the request's drawn rows carry a LogitProc
+    bool logitProc() const { return penalized() || logitFilter(); }
 };
 
 // One generated token's log-probability record (GenParams::logprobs).
@@ -95,6 +103,7 @@ struct SchedulerStats {
     // hits that needed a device copy (source slot still active), idle slots evicted for their pages
     u64 prefixHits = 0, prefixTokens = 0, prefixCopies = 0, prefixEvictions = 0;
     u64 logitProcRequests = 0;  // finished requests that used penalties or a logit bias
+    u64 logitFilterRequests = 0;  // finished requests with top_k or min_p on
 };
 
 class Scheduler {

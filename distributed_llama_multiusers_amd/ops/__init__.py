@@ -239,6 +239,25 @@ def logit_proc_count(counts, ids, slots, active):
                                          [int(bool(a)) for a in active])
 
 
+def logit_filter(logits, temperatures, top_k, delta, active, fill=None):
+    """Device candidate filter (launchLogitFilter) of [B, vocab] logits. For an active row b with
+    temperatures[b] > 0: thr = max(the top_k[b]-th largest value of the row (1 <= top_k[b] < vocab,
+    else -inf), max of the row + delta[b] (delta = cpu_ops.min_p_delta(T, min_p); -inf: off)), and
+    every element below thr (float32 comparison) becomes -inf; survivors keep their bits. The kernel
+    works in place and neither reads nor writes any other row: with `fill`, those rows hold `fill`
+    instead of their logits when the kernel runs, and must hold it afterwards. Returns float32
+    [B, vocab], the buffer after the launch."""
+    x = _np(logits)
+    x = (x.reshape(1, -1) if x.ndim == 1 else x).copy()
+    temps = [float(t) for t in temperatures]
+    act = [int(bool(a)) for a in active]
+    if fill is not None:
+        for b in range(x.shape[0]):
+            if not (act[b] and temps[b] > 0):
+                x[b] = fill
+    return native().ops.logit_filter(x, temps, [int(k) for k in top_k], [float(d) for d in delta], act)
+
+
 def argmax(logits) -> list:
     x = _np(logits)
     return native().ops.argmax(x, x.shape[0] if x.ndim == 2 else 1)

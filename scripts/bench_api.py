@@ -6,7 +6,7 @@ connection per request), and reports the aggregate completion tokens/s for tempe
 and temperature 0.8 / top_p 0.9 with per-request seeds (device sampling: only token ids come back
 to the host). One untimed round first captures the graphs.
 
-  python scripts/bench_api.py [--n 64] [--max-tokens 64] [--port 0] [--logprobs K] [--penalties]
+  python scripts/bench_api.py [--n 64] [--max-tokens 64] [--port 0] [--logprobs K] [--penalties] [--filters]
 """
 import argparse
 import http.client
@@ -42,7 +42,7 @@ def _post(port, body, out, i):
         out[i] = e
 
 
-EXTRA = {}  # request fields added to every body (--logprobs, --penalties)
+EXTRA = {}  # request fields added to every body (--logprobs, --penalties, --filters)
 
 
 def _round(port, n, max_tokens, temperature, seed0):
@@ -79,7 +79,12 @@ def main():
                     help="K >= 0: every request asks for logprobs with top_logprobs K (default: none)")
     ap.add_argument("--penalties", action="store_true",
                     help="every request sends frequency_penalty 0.5, presence_penalty 0.5 and a 16-entry logit_bias")
+    ap.add_argument("--filters", action="store_true",
+                    help="every request sends top_k 40 and min_p 0.05: they act in the sampled round "
+                         "(temperature 0.8), the greedy round ignores them")
     args = ap.parse_args()
+    if args.filters:
+        EXTRA.update(top_k=40, min_p=0.05)
     if args.penalties:
         EXTRA.update(frequency_penalty=0.5, presence_penalty=0.5, logit_bias={str(1000 + 37 * i): (i % 5) - 2 for i in range(16)})
     if args.logprobs >= 0:
@@ -134,6 +139,7 @@ def main():
         res["max_tokens"] = args.max_tokens
         res["top_logprobs"] = args.logprobs if args.logprobs >= 0 else None
         res["penalties"] = bool(args.penalties)
+        res["filters"] = bool(args.filters)
         print(json.dumps(res), flush=True)
     finally:
         srv.terminate()
