@@ -121,18 +121,16 @@ __device__ __forceinline__ bool attnFinish(const AttnArgs &a, int b, int hgIdx, 
     }
     const int G = a.splitGrid;
     const size_t pbase = ((size_t)b * a.nHeads0 + head0) * G;  // [HG][G] chunks of this head group
-    // fence-free hand-off (as gemmFinish): partials stored and read back with agent-scope atomic
-    // accesses (sc1, performed at the coherence point), vmcnt(0) before the arrival count; an
-    // agent-scope fence would write back / invalidate this XCD's whole L2
-    auto st = [](float *q, float v) { __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    // fence-free hand-off (splitArrive, decode_common.h); the combine's loads are sc1 like wtLoad
     for (int i = tid; i < HG * HS; i += AT) {
         const int h = i / HS, d = i % HS;
-        st(a.partO + ((pbase + (size_t)h * G) + c) * HS + d, redL[i]);
+        wtStore(a.partO + ((pbase + (size_t)h * G) + c) * HS + d, redL[i]);
     }
     if (tid < HG) {
-        st(a.partML + ((pbase + (size_t)tid * G) + c) * 2, mlL[tid * 2]);
-        st(a.partML + ((pbase + (size_t)tid * G) + c) * 2 + 1, mlL[tid * 2 + 1]);
+        wtStore(a.partML + ((pbase + (size_t)tid * G) + c) * 2, mlL[tid * 2]);
+        wtStore(a.partML + ((pbase + (size_t)tid * G) + c) * 2 + 1, mlL[tid * 2 + 1]);
     }
+    // splitArrive (decode_common.h), open-coded: the call compiles to other code in these kernels
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     int *cnt = a.counters + (size_t)b * (a.nHeads0 / HG) + hgIdx;

@@ -456,8 +456,8 @@ __global__ __launch_bounds__(kAmThreads) void attnPrefillDmaKernel(AttnArgs a, i
         }
         return;
     }
-    // several chunks: publish (fence-free, gemm_dev.h pattern: write-through stores, drained, then
-    // the arrival count), the last arriver combines in chunk order
+    // several chunks: publish (fence-free hand-off, splitArrive in decode_common.h), the last
+    // arriver combines in chunk order
     const int G = a.splitGrid;
     if (rowOk) {
         const size_t pb = ((size_t)row * a.nHeads0 + head) * G + c;
@@ -465,13 +465,13 @@ __global__ __launch_bounds__(kAmThreads) void attnPrefillDmaKernel(AttnArgs a, i
         for (int n = 0; n < NT; n++)
 #pragma unroll
             for (int e = 0; e < 4; e++)
-                __hip_atomic_store(a.partO + pb * HS + 16 * n + 4 * h + e, o[n][e], __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
+                wtStore(a.partO + pb * HS + 16 * n + 4 * h + e, o[n][e]);
         if (h == 0) {
-            __hip_atomic_store(a.partML + pb * 2, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(a.partML + pb * 2 + 1, lsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            wtStore(a.partML + pb * 2, m);
+            wtStore(a.partML + pb * 2 + 1, lsum);
         }
     }
+    // splitArrive (decode_common.h), open-coded: the call compiles to other code in this kernel
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     int *flagL = reinterpret_cast<int *>(smem + 2 * kApRound * 2 * kAmTileBytes);
@@ -480,7 +480,6 @@ __global__ __launch_bounds__(kAmThreads) void attnPrefillDmaKernel(AttnArgs a, i
     __syncthreads();
     if (!flagL[0]) return;
     if (tid == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    auto ld = [](const float *q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
     constexpr int nCol = RPB * KM;  // 64 columns
     float *wts = reinterpret_cast<float *>(smem);  // [nCol][nSplit] (the tiles are free)
     float *tot = wts + nCol * (HS / 2);            // [nCol]
@@ -489,12 +488,12 @@ __global__ __launch_bounds__(kAmThreads) void attnPrefillDmaKernel(AttnArgs a, i
         float M = -INFINITY, L = 0.f;
         if (rw < nRows) {
             const float *ml = a.partML + ((size_t)rw * a.nHeads0 + hd) * G * 2;
-            for (int cc = 0; cc < nSplit; cc++) M = fmaxf(M, ld(ml + 2 * cc));
+            for (int cc = 0; cc < nSplit; cc++) M = fmaxf(M, wtLoad(ml + 2 * cc));
             for (int cc = 0; cc < nSplit; cc++) {
-                const float mc = ld(ml + 2 * cc);
+                const float mc = wtLoad(ml + 2 * cc);
                 const float w = (M == -INFINITY || mc == -INFINITY) ? 0.f : __expf(mc - M);
                 wts[tid * nSplit + cc] = w;
-                L += w * ld(ml + 2 * cc + 1);
+                L += w * wtLoad(ml + 2 * cc + 1);
             }
         }
         tot[tid] = L;
@@ -509,7 +508,7 @@ __global__ __launch_bounds__(kAmThreads) void attnPrefillDmaKernel(AttnArgs a, i
         for (int cc = 0; cc < nSplit; cc++) {
             const float w = wts[cl * nSplit + cc];
             const float *x = po + (size_t)cc * HS;
-            acc[0] += w * ld(x); acc[1] += w * ld(x + 1); acc[2] += w * ld(x + 2); acc[3] += w * ld(x + 3);
+            acc[0] += w * wtLoad(x); acc[1] += w * wtLoad(x + 1); acc[2] += w * wtLoad(x + 2); acc[3] += w * wtLoad(x + 3);
         }
         const float il = tot[cl] > 0.f ? 1.0f / tot[cl] : 0.f;
         const float v[4] = {acc[0] * il, acc[1] * il, acc[2] * il, acc[3] * il};

@@ -93,20 +93,19 @@ __device__ __forceinline__ void pfFinish(const AttnArgs &a, int nRows, const f32
     // several chunks: publish (every column of the block, masked ones as (-inf, 0, 0)), count in,
     // the last arriver combines
     const int G = a.splitGrid;
-    // fence-free hand-off (see gemmFinish): agent-scope atomic stores here, atomic loads below
-    auto st = [](float *q, float v) { __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    auto ld = [](const float *q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    // fence-free hand-off (splitArrive, decode_common.h)
     if (rowOk) {
         const size_t pb = ((size_t)row * a.nHeads0 + head) * G + c;
 #pragma unroll
         for (int n = 0; n < NT; n++)
 #pragma unroll
-            for (int e = 0; e < 4; e++) st(a.partO + pb * HS + 16 * n + 4 * h + e, o[n][e]);
+            for (int e = 0; e < 4; e++) wtStore(a.partO + pb * HS + 16 * n + 4 * h + e, o[n][e]);
         if (h == 0) {
-            st(a.partML + pb * 2, m);
-            st(a.partML + pb * 2 + 1, lsum);
+            wtStore(a.partML + pb * 2, m);
+            wtStore(a.partML + pb * 2 + 1, lsum);
         }
     }
+    // splitArrive (decode_common.h), open-coded: the call compiles to other code in this kernel
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     int *cnt = a.counters + (size_t)rb * nKv + g;
@@ -121,12 +120,12 @@ __device__ __forceinline__ void pfFinish(const AttnArgs &a, int nRows, const f32
         float M = -INFINITY, L = 0.f;
         if (r < nRows) {
             const float *ml = a.partML + ((size_t)r * a.nHeads0 + hd) * G * 2;
-            for (int cc = 0; cc < nSplit; cc++) M = fmaxf(M, ld(ml + 2 * cc));
+            for (int cc = 0; cc < nSplit; cc++) M = fmaxf(M, wtLoad(ml + 2 * cc));
             for (int cc = 0; cc < nSplit; cc++) {
-                const float mc = ld(ml + 2 * cc);
+                const float mc = wtLoad(ml + 2 * cc);
                 const float w = (M == -INFINITY || mc == -INFINITY) ? 0.f : __expf(mc - M);
                 wts[tid * nSplit + cc] = w;
-                L += w * ld(ml + 2 * cc + 1);
+                L += w * wtLoad(ml + 2 * cc + 1);
             }
         }
         tot[tid] = L;
@@ -141,7 +140,7 @@ __device__ __forceinline__ void pfFinish(const AttnArgs &a, int nRows, const f32
         for (int cc = 0; cc < nSplit; cc++) {
             const float w = wts[cl * nSplit + cc];
             const float *x = po + (size_t)cc * HS;
-            acc[0] += w * ld(x); acc[1] += w * ld(x + 1); acc[2] += w * ld(x + 2); acc[3] += w * ld(x + 3);
+            acc[0] += w * wtLoad(x); acc[1] += w * wtLoad(x + 1); acc[2] += w * wtLoad(x + 2); acc[3] += w * wtLoad(x + 3);
         }
         const float il = tot[cl] > 0.f ? 1.0f / tot[cl] : 0.f;
         const float v[4] = {acc[0] * il, acc[1] * il, acc[2] * il, acc[3] * il};

@@ -259,6 +259,46 @@ __device__ __forceinline__ uint64_t ldWT64(const void *p) {
     return __hip_atomic_load(reinterpret_cast<const uint64_t *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Fence-free cross-workgroup hand-off (split-K partials, attention chunks, the row kernels'
+// partials), the one place for the pattern:
+// * producer: every handed-off value stored with wtStore (agent-scope relaxed atomic store =
+//   global_store ... sc1, performed at the device coherence point, never left dirty in one XCD's
+//   L2), then splitArrive: s_waitcnt vmcnt(0) (all of this wave's stores performed), a workgroup
+//   barrier, one relaxed agent-scope fetch_add on the tile counter;
+// * consumer (the last arriver): loads with wtLoad (global_load ... sc1, served from the coherence
+//   point, never from a stale L1/L2 line).
+// This is the "Valid forms" alternative to a release/acquire pair in MI355X_MICROARCH.md
+// (Correctness boundaries: inter-workgroup visibility). The release/acquire fences compile to a
+// whole-L2 writeback / invalidate (buffer_wbl2 sc1 / buffer_inv sc1) on gfx950, ~28 us per split
+// level on w13 (profiles/r2_splitk_fences.md). The asm vmcnt(0) carries a "memory" clobber so the
+// compiler cannot move the stores below it; tests/test_gpu_ops.py::test_gemm_split_determinism
+// pins the result of many splits across XCDs bitwise against one split.
+// Two sites keep a cheaper form of their own on purpose, argmaxKernel (sample.hip) and the argmax
+// tail of the logits GEMV (gemv_dev.h): only thread 0 stores there, so only thread 0 waits and
+// there is no first barrier. The counters of the attention block / FFN block are other protocols.
+template <typename T>
+__device__ __forceinline__ void wtStore(T *p, T v) {  // T: float, int, uint32_t
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <typename T>
+__device__ __forceinline__ T wtLoad(const T *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// All S workgroups of a tile call this after their wtStores; true in the last arriver only (which
+// also re-arms the counter for the next launch). flag: one int of LDS.
+__device__ __forceinline__ bool splitArrive(int *counter, int S, int *flag) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int old = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        flag[0] = old == S - 1;
+    }
+    __syncthreads();
+    const bool last = flag[0] != 0;
+    if (last && threadIdx.x == 0) __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return last;
+}
+
 // Rows [0, q0) are Q, [q0, q0+kv0) K, then V. Q and K pairs are rotated (RoPE at this row's
 // position); K and V are appended to the KV cache at [slot][pos]. WT: write-through (the fused
 // attention block's attention workgroups read them in the same launch).

@@ -56,39 +56,7 @@ __device__ __forceinline__ void glds4(const void *g, void *lds) {
 static constexpr float kResXScale = 1.0f / 32.0f;
 __device__ __forceinline__ _Float16 satF16(float v) { return (_Float16)fminf(fmaxf(v, -65504.f), 65504.f); }
 
-// Fence-free cross-workgroup hand-off (split-K partials), one place for the pattern:
-// * producer: every handed-off value stored with wtStore (agent-scope relaxed atomic store =
-//   global_store ... sc1, performed at the device coherence point, never left dirty in one XCD's
-//   L2), then splitArrive: s_waitcnt vmcnt(0) (all of this wave's stores performed), a workgroup
-//   barrier, one relaxed agent-scope fetch_add on the tile counter;
-// * consumer (the last arriver): loads with wtLoad (global_load ... sc1, served from the coherence
-//   point, never from a stale L1/L2 line).
-// This is the "Valid forms" alternative to a release/acquire pair in MI355X_MICROARCH.md
-// (Correctness boundaries: inter-workgroup visibility). The release/acquire fences compile to a
-// whole-L2 writeback / invalidate (buffer_wbl2 sc1 / buffer_inv sc1) on gfx950, ~28 us per split
-// level on w13 (profiles/r2_splitk_fences.md). The asm vmcnt(0) carries a "memory" clobber so the
-// compiler cannot move the stores below it; tests/test_gpu_ops.py::test_gemm_split_determinism
-// pins the result of many splits across XCDs bitwise against one split.
-__device__ __forceinline__ void wtStore(float *p, float v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float wtLoad(const float *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// All S workgroups of a tile call this after their wtStores; true in the last arriver only (which
-// also re-arms the counter for the next launch). flag: one int of LDS.
-__device__ __forceinline__ bool splitArrive(int *counter, int S, int *flag) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int old = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        flag[0] = old == S - 1;
-    }
-    __syncthreads();
-    const bool last = flag[0] != 0;
-    if (last && threadIdx.x == 0) __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return last;
-}
+// (The fence-free split hand-off wtStore / wtLoad / splitArrive: decode_common.h.)
 // Sum S partials (P + s * stride, f32x4 units [0, n4)) in split order into dst (LDS; unit i lands
 // at dst[(i / rowU) * ldU + i % rowU], a padded row stride): the loads of 4 splits are in flight
 // before their adds. Register-lean on purpose: an 8-deep fully unrolled form set the whole

@@ -21,8 +21,8 @@
 // The grid is mapped XCD-aware: consecutive logical workgroups (the token tiles and K splits of one
 // row tile, which share weights) are dispatched to the same XCD (its L2).
 // Split-K (thin matrices: wo, w2, qkv) stores partials with write-through stores; the last arriving
-// split sums them in split order (deterministic, gemm_dev.h splitArrive / splitCombine). The
-// output tile goes through LDS (padded rows) into the shared fused epilogues (gemm_dev.h).
+// split sums them in split order (deterministic; splitArrive in decode_common.h, splitCombine in
+// gemm_dev.h). The output tile goes through LDS (padded rows) into the shared fused epilogues (gemm_dev.h).
 #include "gemm_dev.h"
 
 #include <cstdlib>

@@ -11,41 +11,35 @@
 //     nothing is sorted and the held elements are never changed. A further tile competes against
 //     the list of the tiles before it (one list entry per thread as an extra element).
 // The partials go to the row's scratch with agent-scope stores; the row's last-arriving workgroup
-// (argmaxKernel's fence-free hand-off, sample.hip) combines the (max, sum) pairs in workgroup
+// (the fence-free hand-off, splitArrive in decode_common.h) combines the (max, sum) pairs in workgroup
 // order, runs the same k rounds over the groups x k candidates and writes the row's output. No
 // float atomics in memory and no dependence on B or on the arrival order: a row's output is
 // bitwise reproducible.
-#include "decode_common.h"
+#include "row_dev.h"
 
 namespace dl {
 namespace hipk {
 
-static constexpr int kLpWg = 256;
-static constexpr int kLpVals = 32;  // logits per thread per tile
-static constexpr int kLpTile = kLpWg * kLpVals;
-static constexpr int kLpNone = 0x7fffffff;
-static constexpr int kLpCands = kLogprobMaxGroups * kLogprobTop / kLpWg;  // candidates per thread, last arriver
-static_assert(kLogprobMaxGroups * kLogprobTop % kLpWg == 0, "candidates per thread");
-static_assert(kLogprobTop <= kLpWg && kLogprobSlots <= kLpWg, "one thread per list entry / output slot");
+static constexpr int kLgpVals = 32;  // logits per thread per tile
+static constexpr int kLgpTile = kRowWg * kLgpVals;
+static constexpr int kLgpNone = 0x7fffffff;
+static constexpr int kLgpCands = kLogprobMaxGroups * kLogprobTop / kRowWg;  // candidates per thread, last arriver
+static_assert(kLogprobMaxGroups * kLogprobTop % kRowWg == 0, "candidates per thread");
+static_assert(kLogprobTop <= kRowWg && kLogprobSlots <= kRowWg, "one thread per list entry / output slot");
 static_assert(sizeof(LogprobEntry) == 8, "LogprobEntry layout");
 
 int logprobGroups(int vocab) {
-    const int G = (vocab + kLpTile - 1) / kLpTile;
+    const int G = (vocab + kLgpTile - 1) / kLgpTile;
     return G < 1 ? 1 : (G > kLogprobMaxGroups ? kLogprobMaxGroups : G);
 }
 
-__device__ __forceinline__ void lpStore(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void lpStore(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float lpLoad(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int lpLoad(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
 // (v, i) comes strictly after (pv, pi) in the (value descending, index ascending) order
-__device__ __forceinline__ bool lpAfter(float v, int i, float pv, int pi) { return v < pv || (v == pv && i > pi); }
+__device__ __forceinline__ bool lgpAfter(float v, int i, float pv, int pi) { return v < pv || (v == pv && i > pi); }
 
 // The workgroup's winner, in every thread. sv / si: two sets of one word per wave; consecutive
 // calls alternate `par`, so one barrier per call is enough (a thread two calls ahead has passed the
 // barrier of the call in between, which every thread reaches after its reads of this one).
-__device__ __forceinline__ void lpBlockBest(float &bv, int &bi, float (*sv)[kLpWg / 64], int (*si)[kLpWg / 64], int par) {
+__device__ __forceinline__ void lgpBlockBest(float &bv, int &bi, float (*sv)[kRowWaves], int (*si)[kRowWaves], int par) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) argBetter(bv, bi, __shfl_xor(bv, off), __shfl_xor(bi, off));
     if ((threadIdx.x & 63) == 0) {
@@ -56,29 +50,15 @@ __device__ __forceinline__ void lpBlockBest(float &bv, int &bi, float (*sv)[kLpW
     bv = sv[par][0];
     bi = si[par][0];
 #pragma unroll
-    for (int w = 1; w < kLpWg / 64; w++) argBetter(bv, bi, sv[par][w], si[par][w]);
+    for (int w = 1; w < kRowWaves; w++) argBetter(bv, bi, sv[par][w], si[par][w]);
 }
 
-// Workgroup reduction in a fixed order (wave butterfly, then the waves in wave order).
-template <typename F>
-__device__ __forceinline__ float lpReduce(float v, float *red, F op) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = op(v, __shfl_xor(v, off));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = red[0];
-#pragma unroll
-    for (int w = 1; w < kLpWg / 64; w++) r = op(r, red[w]);
-    return r;
-}
-
-__global__ __launch_bounds__(kLpWg) void logprobsKernel(LogprobArgs a) {
-    __shared__ float sv[2][kLpWg / 64];
-    __shared__ int si[2][kLpWg / 64];
+__global__ __launch_bounds__(kRowWg) void logprobsKernel(LogprobArgs a) {
+    __shared__ float sv[2][kRowWaves];
+    __shared__ int si[2][kRowWaves];
     __shared__ float listV[2][kLogprobTop];  // the slice's best so far (double-buffered over tiles)
     __shared__ int listI[2][kLogprobTop];
-    __shared__ float red[kLpWg / 64];
+    __shared__ float red[kRowWaves];
     __shared__ float lse[2];
     __shared__ int last;
     const int g = blockIdx.x, b = blockIdx.y, G = gridDim.x, tid = threadIdx.x, V = a.vocab;
@@ -90,25 +70,25 @@ __global__ __launch_bounds__(kLpWg) void logprobsKernel(LogprobArgs a) {
     const int c0 = min(g * C, V), c1 = min(c0 + C, V);
     if (tid < kLogprobTop) {
         listV[0][tid] = listV[1][tid] = -INFINITY;
-        listI[0][tid] = listI[1][tid] = kLpNone;
+        listI[0][tid] = listI[1][tid] = kLgpNone;
     }
     __syncthreads();
     float m = -INFINITY, s = 0.f;  // this thread's elements: max, sum of exp(x - max)
     int cur = 0, par = 0;
-    for (int r0 = c0; r0 < c1; r0 += kLpTile) {
-        float v[kLpVals];
+    for (int r0 = c0; r0 < c1; r0 += kLgpTile) {
+        float v[kLgpVals];
 #pragma unroll
-        for (int j = 0; j < kLpVals; j++) v[j] = x[min(r0 + j * kLpWg + tid, c1 - 1)];
+        for (int j = 0; j < kLgpVals; j++) v[j] = x[min(r0 + j * kRowWg + tid, c1 - 1)];
         __builtin_amdgcn_sched_barrier(0);  // all loads issued before the first use
         float tm = -INFINITY;
 #pragma unroll
-        for (int j = 0; j < kLpVals; j++)
-            if (r0 + j * kLpWg + tid < c1) tm = fmaxf(tm, v[j]);
+        for (int j = 0; j < kLgpVals; j++)
+            if (r0 + j * kRowWg + tid < c1) tm = fmaxf(tm, v[j]);
         if (tm > -INFINITY) {
             float ts = 0.f;
 #pragma unroll
-            for (int j = 0; j < kLpVals; j++)
-                if (r0 + j * kLpWg + tid < c1) ts += __expf(v[j] - tm);
+            for (int j = 0; j < kLgpVals; j++)
+                if (r0 + j * kRowWg + tid < c1) ts += __expf(v[j] - tm);
             if (tm > m) {
                 s = s * __expf(m - tm) + ts;
                 m = tm;
@@ -119,19 +99,19 @@ __global__ __launch_bounds__(kLpWg) void logprobsKernel(LogprobArgs a) {
         if (k == 0) continue;
         // the list of the tiles before this one: entry tid is this thread's extra element
         const float ov = tid < kLogprobTop ? listV[cur][tid] : -INFINITY;
-        const int oi = tid < kLogprobTop ? listI[cur][tid] : kLpNone;
+        const int oi = tid < kLogprobTop ? listI[cur][tid] : kLgpNone;
         float pv = INFINITY;
         int pi = -1;
         for (int r = 0; r < k; r++) {
             float bv = -INFINITY;
-            int bi = kLpNone;
+            int bi = kLgpNone;
 #pragma unroll
-            for (int j = 0; j < kLpVals; j++) {
-                const int i = r0 + j * kLpWg + tid;
-                if (i < c1 && lpAfter(v[j], i, pv, pi)) argBetter(bv, bi, v[j], i);
+            for (int j = 0; j < kLgpVals; j++) {
+                const int i = r0 + j * kRowWg + tid;
+                if (i < c1 && lgpAfter(v[j], i, pv, pi)) argBetter(bv, bi, v[j], i);
             }
-            if (oi != kLpNone && lpAfter(ov, oi, pv, pi)) argBetter(bv, bi, ov, oi);
-            lpBlockBest(bv, bi, sv, si, par);
+            if (oi != kLgpNone && lgpAfter(ov, oi, pv, pi)) argBetter(bv, bi, ov, oi);
+            lgpBlockBest(bv, bi, sv, si, par);
             par ^= 1;
             if (tid == 0) {  // (nothing left: the (-inf, none) pair, after which nothing comes)
                 listV[cur ^ 1][r] = bv;
@@ -143,37 +123,29 @@ __global__ __launch_bounds__(kLpWg) void logprobsKernel(LogprobArgs a) {
         cur ^= 1;
         __syncthreads();
     }
-    const float M = lpReduce(m, red, [](float p, float q) { return fmaxf(p, q); });
-    const float S = lpReduce(m == -INFINITY ? 0.f : s * __expf(m - M), red, [](float p, float q) { return p + q; });
+    const float M = wgReduce(m, red, [](float p, float q) { return fmaxf(p, q); });
+    const float S = wgReduce(m == -INFINITY ? 0.f : s * __expf(m - M), red, [](float p, float q) { return p + q; });
     const size_t slot = (size_t)b * kLogprobMaxGroups + g;
     if (tid == 0) {
-        lpStore(a.scratch.partM + slot, M);
-        lpStore(a.scratch.partS + slot, S);
+        wtStore(a.scratch.partM + slot, M);
+        wtStore(a.scratch.partS + slot, S);
     }
     if (tid < k) {
-        lpStore(a.scratch.candV + slot * kLogprobTop + tid, listV[cur][tid]);
-        lpStore(a.scratch.candI + slot * kLogprobTop + tid, listI[cur][tid]);
+        wtStore(a.scratch.candV + slot * kLogprobTop + tid, listV[cur][tid]);
+        wtStore(a.scratch.candI + slot * kLogprobTop + tid, listI[cur][tid]);
     }
-    // fence-free hand-off (argmaxKernel, sample.hip): the partials are agent-scope stores, every
-    // storing wave waits for its own, then one thread counts the workgroup in
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0)
-        last = __hip_atomic_fetch_add(a.scratch.counters + b, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == G - 1;
-    __syncthreads();
-    if (!last) return;
-    if (tid == 0) __hip_atomic_store(a.scratch.counters + b, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!splitArrive(a.scratch.counters + b, G, &last)) return;
 
     // ---- the row's last arriver
     const size_t row = (size_t)b * kLogprobMaxGroups;
     LogprobEntry *out = a.out + (size_t)b * kLogprobSlots;
     if (tid == 0) {
         float gm = -INFINITY;
-        for (int j = 0; j < G; j++) gm = fmaxf(gm, lpLoad(a.scratch.partM + row + j));
+        for (int j = 0; j < G; j++) gm = fmaxf(gm, wtLoad(a.scratch.partM + row + j));
         float z = 0.f;
         for (int j = 0; j < G; j++) {
-            const float pm = lpLoad(a.scratch.partM + row + j);
-            if (pm != -INFINITY) z += lpLoad(a.scratch.partS + row + j) * expf(pm - gm);
+            const float pm = wtLoad(a.scratch.partM + row + j);
+            if (pm != -INFINITY) z += wtLoad(a.scratch.partS + row + j) * expf(pm - gm);
         }
         const float lz = logf(z);
         lse[0] = gm;
@@ -187,29 +159,29 @@ __global__ __launch_bounds__(kLpWg) void logprobsKernel(LogprobArgs a) {
     }
     __syncthreads();
     const float gm = lse[0], lz = lse[1];
-    float cv[kLpCands];
-    int ci[kLpCands];
+    float cv[kLgpCands];
+    int ci[kLgpCands];
 #pragma unroll
-    for (int q = 0; q < kLpCands; q++) {
-        const int c = q * kLpWg + tid;  // group c / kLogprobTop, its entry c % kLogprobTop
+    for (int q = 0; q < kLgpCands; q++) {
+        const int c = q * kRowWg + tid;  // group c / kLogprobTop, its entry c % kLogprobTop
         const bool ok = c < G * kLogprobTop && c % kLogprobTop < k;
-        cv[q] = ok ? lpLoad(a.scratch.candV + row * kLogprobTop + c) : -INFINITY;
-        ci[q] = ok ? lpLoad(a.scratch.candI + row * kLogprobTop + c) : kLpNone;
+        cv[q] = ok ? wtLoad(a.scratch.candV + row * kLogprobTop + c) : -INFINITY;
+        ci[q] = ok ? wtLoad(a.scratch.candI + row * kLogprobTop + c) : kLgpNone;
     }
     float pv = INFINITY;
     int pi = -1;
     for (int r = 0; r < k; r++) {
         float bv = -INFINITY;
-        int bi = kLpNone;
+        int bi = kLgpNone;
 #pragma unroll
-        for (int q = 0; q < kLpCands; q++)
-            if (ci[q] != kLpNone && lpAfter(cv[q], ci[q], pv, pi)) argBetter(bv, bi, cv[q], ci[q]);
-        lpBlockBest(bv, bi, sv, si, par);
+        for (int q = 0; q < kLgpCands; q++)
+            if (ci[q] != kLgpNone && lgpAfter(cv[q], ci[q], pv, pi)) argBetter(bv, bi, cv[q], ci[q]);
+        lgpBlockBest(bv, bi, sv, si, par);
         par ^= 1;
         if (tid == 0) {
             LogprobEntry e;
-            e.logprob = bi == kLpNone ? 0.f : (bv - gm) - lz;
-            e.id = bi == kLpNone ? -1 : bi;  // fewer than k tokens in the vocabulary
+            e.logprob = bi == kLgpNone ? 0.f : (bv - gm) - lz;
+            e.id = bi == kLgpNone ? -1 : bi;  // fewer than k tokens in the vocabulary
             out[1 + r] = e;
         }
         pv = bv;
@@ -224,7 +196,7 @@ __global__ __launch_bounds__(kLpWg) void logprobsKernel(LogprobArgs a) {
 }
 
 void launchLogprobs(const LogprobArgs &a, int B, hipStream_t s) {
-    hipLaunchKernelGGL(logprobsKernel, dim3(logprobGroups(a.vocab), B), dim3(kLpWg), 0, s, a);
+    hipLaunchKernelGGL(logprobsKernel, dim3(logprobGroups(a.vocab), B), dim3(kRowWg), 0, s, a);
 }
 
 }  // namespace hipk

@@ -1,7 +1,9 @@
 // Argmax and device sampling of the logits rows (ArgmaxArgs / SampleArgs in kernels.h).
 #include "decode_dev.h"
+#include "row_dev.h"
 
 #include <cstdlib>
+#include <utility>
 
 namespace dl {
 namespace hipk {
@@ -113,9 +115,6 @@ void launchArgmaxPick(const ArgmaxArgs &a, const float *all, int B, int W, hipSt
 // Round 2's first version ran one 1024-thread workgroup per row through 11 passes over the
 // vocabulary (607 us for 64 x 128256 logits, flat distribution; profiles/r2_sampler.md).
 // ------------------------------------------------------------------------------------------------
-static constexpr int kSampleWg = 256;
-static constexpr int kSampleBins = 2048;
-
 struct SampleRow {  // per-row state (SampleScratch::state, kSampleStateWords u32)
     float m, invZ, above, nucleus;
     uint32_t prefix, cutKey;
@@ -128,74 +127,15 @@ struct SampleRow {  // per-row state (SampleScratch::state, kSampleStateWords u3
 };
 static_assert(sizeof(SampleRow) == kSampleStateWords * 4, "SampleRow size");
 
-__device__ __forceinline__ uint32_t orderKey(float x) {
-    const uint32_t u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-template <typename F>
-__device__ __forceinline__ float wgReduce(float v, float *red, F op) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = op(v, __shfl_xor(v, off));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = red[0];
-#pragma unroll
-    for (int w = 1; w < kSampleWg / 64; w++) r = op(r, red[w]);
-    __syncthreads();
-    return r;
-}
-
-// Lanes that share the first active lane's bin are summed and added once (three times), the rest
-// add directly: a flat distribution puts nearly every element of the top-digit pass in one bin,
-// where per-lane LDS atomics would serialise 64-fold.
-__device__ __forceinline__ void histAddWave(float *h, bool act, uint32_t bin, float p) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int rep = 0; rep < 3; rep++) {
-        const unsigned long long am = __ballot(act);
-        if (am == 0ull) return;
-        const int leader = __builtin_ctzll(am);
-        const uint32_t b0 = __shfl(bin, leader);
-        const bool mine = act && bin == b0;
-        float v = mine ? p : 0.f;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-        if (lane == leader) atomicAdd(&h[b0], v);
-        act = act && !mine;
-    }
-    if (act) atomicAdd(&h[bin], p);
-}
-
 struct SamplePhaseCtx {
     const float *l;
     int V, g, G, c0, c1;
     float T, P, coin;
     SampleRow *st;
-    float *gh;    // the row's partial histograms [G][kSampleBins] (every slot rewritten each pass)
+    float *gh;    // the row's partial histograms [G][kRowBins] (every slot rewritten each pass)
     float *part;  // the row's per-chunk values [G]
     int *partI;
 };
-
-// Last-arriver handshake. Every cross-workgroup value of a phase is written with agent-scope
-// atomics (histogram adds, partial stores) and read back with agent-scope atomic loads, so no
-// cache maintenance is needed: each thread waits until its own writes have been performed, then
-// one thread counts the workgroup in. (A __threadfence() per thread here - an L2 writeback plus
-// invalidate per wave, 4096 per phase at 64 rows - cost ~80 us per phase.)
-__device__ __forceinline__ bool lastArrival(SampleRow *st, int G, int *flag) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0)
-        flag[0] = __hip_atomic_fetch_add(&st->counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == G - 1;
-    __syncthreads();
-    if (!flag[0]) return false;
-    if (threadIdx.x == 0) __hip_atomic_store(&st->counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return true;
-}
-
-__device__ __forceinline__ void gstore(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void gstore(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // Visit the workgroup's chunk: per round every thread loads kSampleVals elements (coalesced,
 // index clamped so the loads are unconditional) before using any, so a phase costs about one
@@ -204,14 +144,14 @@ __device__ __forceinline__ void gstore(int *p, int v) { __hip_atomic_store(p, v,
 static constexpr int kSampleVals = 32;
 template <typename F>
 __device__ __forceinline__ void forChunk(const SamplePhaseCtx &c, F f) {
-    for (int r0 = c.c0; r0 < c.c1; r0 += kSampleVals * kSampleWg) {
+    for (int r0 = c.c0; r0 < c.c1; r0 += kSampleVals * kRowWg) {
         float v[kSampleVals];
 #pragma unroll
-        for (int j = 0; j < kSampleVals; j++) v[j] = c.l[min(r0 + j * kSampleWg + (int)threadIdx.x, c.c1 - 1)];
+        for (int j = 0; j < kSampleVals; j++) v[j] = c.l[min(r0 + j * kRowWg + (int)threadIdx.x, c.c1 - 1)];
         __builtin_amdgcn_sched_barrier(0);  // all loads issued before the first use
 #pragma unroll
         for (int j = 0; j < kSampleVals; j++) {
-            const int i = r0 + j * kSampleWg + (int)threadIdx.x;
+            const int i = r0 + j * kRowWg + (int)threadIdx.x;
             f(i, v[j], i < c.c1);
         }
     }
@@ -229,8 +169,8 @@ __device__ void sampleRadixPass(const SamplePhaseCtx &c, int pass, bool draw, fl
     const uint32_t minKey = draw ? st->cutKey : 0u;
     const uint32_t prefix = pass == 0 ? 0u : st->prefix;
     const int hiShift = shift + (int)width;  // bits above this digit (32 for pass 0)
-    float *hw = h + (tid >> 6) * kSampleBins;  // this wave's histogram
-    for (int i = tid; i < kSampleBins * (kSampleWg / 64); i += kSampleWg) h[i] = 0.f;
+    float *hw = h + (tid >> 6) * kRowBins;  // this wave's histogram
+    for (int i = tid; i < kRowBins * kRowWaves; i += kRowWg) h[i] = 0.f;
     __syncthreads();
     forChunk(c, [&](int, float lv, bool act) {
         const float x = lv * invT;
@@ -241,61 +181,14 @@ __device__ void sampleRadixPass(const SamplePhaseCtx &c, int pass, bool draw, fl
         histAddWave(hw, act, (k >> shift) & mask, p);
     });
     __syncthreads();
-    // this workgroup's histogram (the waves' copies summed in wave order) -> its partial slot
-    constexpr int PER = kSampleBins / kSampleWg;  // 8 consecutive bins per thread
-    float *mine = c.gh + (size_t)c.g * kSampleBins;
-#pragma unroll
-    for (int j = 0; j < PER; j++) {  // lane-consecutive bins: every store instruction is one 1 KB line run
-        const int bin = j * kSampleWg + tid;
-        float v = 0.f;
-#pragma unroll
-        for (int w = 0; w < kSampleWg / 64; w++) v += h[w * kSampleBins + bin];
-        gstore(&mine[bin], v);
-    }
-    if (!lastArrival(st, c.G, flag)) return;
-    // ---- last arriver: sum the G partial histograms in workgroup order (deterministic) into LDS,
-    // then pick the bin where the descending cumulative mass crosses the target
-    {
-        float acc8[PER];
-#pragma unroll
-        for (int j = 0; j < PER; j++) acc8[j] = 0.f;
-        for (int g0 = 0; g0 < c.G; g0 += 4) {
-            float t4[4][PER];
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-#pragma unroll
-                for (int j = 0; j < PER; j++)
-                    t4[q][j] = __hip_atomic_load(&c.gh[(size_t)min(g0 + q, c.G - 1) * kSampleBins + j * kSampleWg + tid],
-                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-                if (g0 + q < c.G)
-#pragma unroll
-                    for (int j = 0; j < PER; j++) acc8[j] += t4[q][j];
-        }
-#pragma unroll
-        for (int j = 0; j < PER; j++) h[j * kSampleWg + tid] = acc8[j];
-    }
-    __syncthreads();
+    histStorePartial(h, c.gh + (size_t)c.g * kRowBins);
+    if (!splitArrive(&st->counter, c.G, flag)) return;
+    // ---- last arriver: the G partial histograms summed in workgroup order, then the bin where
+    // the descending cumulative mass crosses the target
+    constexpr int PER = kRowBinsPer;
+    histSumPartials(c.gh, c.G, h);
     float v[PER];
-    float tot = 0.f;
-#pragma unroll
-    for (int j = 0; j < PER; j++) {
-        v[j] = h[tid * PER + j];
-        tot += v[j];
-    }
-    // mass of the bins of higher threads (exclusive suffix over threads)
-    float inc = tot;  // inclusive suffix within the wave (lanes >= this lane)
-    const int lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const float y = __shfl_down(inc, off);
-        if (lane + off < 64) inc += y;
-    }
-    if (lane == 0) red[wv] = inc;  // wave totals
-    __syncthreads();
-    float higher = inc - tot;
-    for (int w = wv + 1; w < kSampleWg / 64; w++) higher += red[w];
+    const float higher = suffixAbove(h, red, v);  // mass of the bins of higher threads
     const float above0 = pass == 0 ? 0.f : st->above;
     const float target = draw ? st->nucleus * c.coin : c.P;
     const float t = target - above0;
@@ -356,9 +249,9 @@ __device__ void sampleRadixPass(const SamplePhaseCtx &c, int pass, bool draw, fl
 }
 
 template <int PHASE>
-__global__ __launch_bounds__(kSampleWg) void samplePhaseKernel(SampleArgs a) {
-    __shared__ float h[kSampleBins * (kSampleWg / 64)];  // one histogram per wave (32 KB)
-    __shared__ float red[kSampleWg / 64 + 2];
+__global__ __launch_bounds__(kRowWg) void samplePhaseKernel(SampleArgs a) {
+    __shared__ float h[kRowBins * kRowWaves];  // one histogram per wave (32 KB)
+    __shared__ float red[kRowWaves + 2];
     __shared__ int flag[1];
     const int g = blockIdx.x, b = blockIdx.y, G = gridDim.x, tid = threadIdx.x, V = a.vocab;
     SampleRow *st = reinterpret_cast<SampleRow *>(a.scratch.state) + b;
@@ -375,7 +268,7 @@ __global__ __launch_bounds__(kSampleWg) void samplePhaseKernel(SampleArgs a) {
     c.P = sp.y;
     c.coin = sp.z;
     c.st = st;
-    c.gh = a.scratch.hist + (size_t)b * G * kSampleBins;
+    c.gh = a.scratch.hist + (size_t)b * G * kRowBins;
     c.part = a.scratch.part + (size_t)b * G;
     c.partI = a.scratch.partI + (size_t)b * G;
     const bool multinomial = c.P <= 0.f || c.P >= 1.f;
@@ -400,16 +293,16 @@ __global__ __launch_bounds__(kSampleWg) void samplePhaseKernel(SampleArgs a) {
             if (bv == mv && bi != 0x7fffffff) atomicMin(&flag[0], bi);
             __syncthreads();
             if (tid == 0) {
-                gstore(&c.part[g], mv);
-                gstore(&c.partI[g], flag[0]);
+                wtStore(&c.part[g], mv);
+                wtStore(&c.partI[g], flag[0]);
             }
-            if (!lastArrival(st, G, flag)) return;
+            if (!splitArrive(&st->counter, G, flag)) return;
             if (tid == 0) {
                 float best = -INFINITY;
                 int bestI = 0x7fffffff;
                 for (int j = 0; j < G; j++) {
-                    const float pv = __hip_atomic_load(&c.part[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const int pi = __hip_atomic_load(&c.partI[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const float pv = wtLoad(&c.part[j]);
+                    const int pi = wtLoad(&c.partI[j]);
                     if (pi != 0x7fffffff) argBetter(best, bestI, pv, pi);
                 }
                 a.ids[b] = bestI == 0x7fffffff ? 0 : bestI;
@@ -433,17 +326,17 @@ __global__ __launch_bounds__(kSampleWg) void samplePhaseKernel(SampleArgs a) {
         const float M = wgReduce(mx, red, [](float x, float y) { return fmaxf(x, y); });
         const float S = wgReduce(mx == -INFINITY ? 0.f : sm * __expf(mx - M), red, [](float x, float y) { return x + y; });
         if (tid == 0) {
-            gstore(&c.part[g], M);
-            gstore(&c.partI[g], __float_as_int(S));
+            wtStore(&c.part[g], M);
+            wtStore(&c.partI[g], __float_as_int(S));
         }
-        if (!lastArrival(st, G, flag)) return;
+        if (!splitArrive(&st->counter, G, flag)) return;
         if (tid == 0) {
             float gm = -INFINITY;
-            for (int j = 0; j < G; j++) gm = fmaxf(gm, __hip_atomic_load(&c.part[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            for (int j = 0; j < G; j++) gm = fmaxf(gm, wtLoad(&c.part[j]));
             float z = 0.f;
             for (int j = 0; j < G; j++) {
-                const float pm = __hip_atomic_load(&c.part[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const float ps = __int_as_float(__hip_atomic_load(&c.partI[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                const float pm = wtLoad(&c.part[j]);
+                const float ps = __int_as_float(wtLoad(&c.partI[j]));
                 if (pm != -INFINITY) z += ps * __expf(pm - gm);
             }
             st->m = gm;
@@ -462,13 +355,13 @@ __global__ __launch_bounds__(kSampleWg) void samplePhaseKernel(SampleArgs a) {
                     if (ok) s += __expf(lv * invT - m) * invZ;
                 });
                 s = wgReduce(s, red, [](float x, float y) { return x + y; });
-                if (tid == 0) gstore(&c.part[g], s);
-                if (!lastArrival(st, G, flag)) return;
+                if (tid == 0) wtStore(&c.part[g], s);
+                if (!splitArrive(&st->counter, G, flag)) return;
                 if (tid == 0) {
                     float base = 0.f;
                     int ch = -1;
                     for (int j = 0; j < G; j++) {
-                        const float pj = __hip_atomic_load(&c.part[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        const float pj = wtLoad(&c.part[j]);
                         if (ch < 0 && c.coin >= base && c.coin < base + pj) {
                             ch = j;
                             break;
@@ -485,7 +378,7 @@ __global__ __launch_bounds__(kSampleWg) void samplePhaseKernel(SampleArgs a) {
             } else if constexpr (PHASE == 2) {
                 if (g != st->chunk) return;
                 // thread t owns a contiguous sub-range of the chunk (index order)
-                const int n = c.c1 - c.c0, per = (n + kSampleWg - 1) / kSampleWg;
+                const int n = c.c1 - c.c0, per = (n + kRowWg - 1) / kRowWg;
                 const int i0 = c.c0 + min(tid * per, n), i1 = c.c0 + min(tid * per + per, n);
                 // the thread's run, loaded at once (per <= kSampleVals for the chunk sizes used)
                 float pv[kSampleVals];
@@ -548,9 +441,9 @@ __global__ __launch_bounds__(kSampleWg) void samplePhaseKernel(SampleArgs a) {
             if (mine != 0x7fffffff) atomicMin(&flag[0], mine);
             __syncthreads();
             if (tid == 0 && flag[0] != 0x7fffffff) atomicMin(&st->result, flag[0]);
-            if (!lastArrival(st, G, flag)) return;
+            if (!splitArrive(&st->counter, G, flag)) return;
             if (tid == 0) {
-                const int r = __hip_atomic_load(&st->result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const int r = wtLoad(&st->result);
                 a.ids[b] = r == 0x7fffffff ? 0 : r;
                 st->mode = 0;
             }
@@ -563,16 +456,13 @@ int sampleGroups(int B) {
     return G < 8 ? 8 : (G > kSampleMaxGroups ? kSampleMaxGroups : G);
 }
 
+template <int... PHASE>
+static void launchSamplePhases(const SampleArgs &a, dim3 grid, hipStream_t s, std::integer_sequence<int, PHASE...>) {
+    ([&] { hipLaunchKernelGGL(samplePhaseKernel<PHASE>, grid, dim3(kRowWg), 0, s, a); }(), ...);
+}
+
 void launchSample(const SampleArgs &a, int B, hipStream_t s) {
-    const dim3 grid(sampleGroups(B), B);
-    hipLaunchKernelGGL(samplePhaseKernel<0>, grid, dim3(kSampleWg), 0, s, a);
-    hipLaunchKernelGGL(samplePhaseKernel<1>, grid, dim3(kSampleWg), 0, s, a);
-    hipLaunchKernelGGL(samplePhaseKernel<2>, grid, dim3(kSampleWg), 0, s, a);
-    hipLaunchKernelGGL(samplePhaseKernel<3>, grid, dim3(kSampleWg), 0, s, a);
-    hipLaunchKernelGGL(samplePhaseKernel<4>, grid, dim3(kSampleWg), 0, s, a);
-    hipLaunchKernelGGL(samplePhaseKernel<5>, grid, dim3(kSampleWg), 0, s, a);
-    hipLaunchKernelGGL(samplePhaseKernel<6>, grid, dim3(kSampleWg), 0, s, a);
-    hipLaunchKernelGGL(samplePhaseKernel<7>, grid, dim3(kSampleWg), 0, s, a);
+    launchSamplePhases(a, dim3(sampleGroups(B), B), s, std::make_integer_sequence<int, 8>{});  // phases 0..7 in order
 }
 
 // (preloadModules: any kernel of this code object)
