@@ -305,9 +305,8 @@ __global__ __launch_bounds__(kAmThreads) void attnPrefillDmaKernel(AttnArgs a, i
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 15, h = lane >> 4;
     const int b0 = rb * RPB;
     const int maxLen = rowsMaxLen(a.pos, b0, RPB, nRows);
-    int nSplit = (maxLen + 255) / 256;
-    nSplit = max(1, min(min(nSplit, a.splitGrid), HS / 2));  // combine weights: 64 columns x nSplit in LDS
-    const int ch = ((maxLen + nSplit - 1) / nSplit + kAmTile - 1) / kAmTile * kAmTile;
+    int nSplit, ch;  // combine weights: 64 columns x nSplit in LDS
+    attnPrefillSplit(maxLen, a.splitGrid, HS, kAttnPrefillChunk, nSplit, ch);
     if (c >= nSplit) return;
     const int k0 = c * ch, k1 = min(k0 + ch, maxLen);
     const int sl = a.slot[b0];  // every row of the block (host-checked)
@@ -521,13 +520,18 @@ bool attnPrefillDmaSupported(const AttnArgs &a) {
                                                 a.kvMul == 16);
 }
 
+const char *attnPrefillDmaRefusal(const AttnArgs &a) {
+    if (!attnPrefillDmaSupported(a)) return "launchAttentionPrefillDma: unsupported kvMul";
+    // the longest chunk's tiles fit the kernel's LDS page list
+    const int minSplits = std::max(1, std::min(a.splitGrid, kAmHS / 2));
+    if (a.kvMap.table && ((a.seqLen + minSplits - 1) / minSplits + kAmTile - 1) / kAmTile + 1 > kApMaxTiles)
+        return "launchAttentionPrefillDma: paged context too long for the per-chunk page list";
+    return nullptr;
+}
+
 void launchAttentionPrefillDma(const AttnArgs &a, int nRows, hipStream_t s) {
     const int nKv = a.nHeads0 / a.kvMul, rpb = kAmWaves * (16 / a.kvMul);
-    {  // the longest chunk's tiles fit the kernel's LDS page list
-        const int minSplits = std::max(1, std::min(a.splitGrid, kAmHS / 2));
-        if (a.kvMap.table && ((a.seqLen + minSplits - 1) / minSplits + kAmTile - 1) / kAmTile + 1 > kApMaxTiles)
-            throw Error("launchAttentionPrefillDma: paged context too long for the per-chunk page list");
-    }
+    if (const char *why = attnPrefillDmaRefusal(a)) throw Error(why);
     const dim3 grid(nKv * ((nRows + rpb - 1) / rpb), a.splitGrid);
 #define DL_AP_CASE(K)                                                                                 \
     if (a.kvMul == K) {                                                                               \
@@ -566,11 +570,17 @@ bool attnUsesMfma(const AttnArgs &a) {
 // preloadModules(): one kernel of this translation unit's code object
 const void *attnMfmaModuleKernel() { return (const void *)attnDecodeMfmaKernel<4>; }
 
+const char *attnMfmaRefusal(const AttnArgs &a) {
+    if (!attnMfmaSupported(a)) return "launchAttentionMfma: unsupported kvMul";
+    if (2 * a.kvMul * a.splitGrid * 4 + 4096 > (int)kAmLds) return "attention split grid too large";
+    if (a.kvMap.table && (a.chunkMax >> a.kvMap.pageShift) + 2 > 64)
+        return "launchAttentionMfma: a chunk spans more than 64 pages (one page id per lane)";
+    return nullptr;
+}
+
 void launchAttentionMfma(const AttnArgs &a, int B, hipStream_t s) {
     const dim3 grid(a.nHeads0 / a.kvMul, a.splitGrid, B);
-    if (2 * a.kvMul * a.splitGrid * 4 + 4096 > (int)kAmLds) throw Error("attention split grid too large");
-    if (a.kvMap.table && (a.chunkMax >> a.kvMap.pageShift) + 2 > 64)
-        throw Error("launchAttentionMfma: a chunk spans more than 64 pages (one page id per lane)");
+    if (const char *why = attnMfmaRefusal(a)) throw Error(why);
 #define DL_AM_CASE(K)                                                                             \
     if (a.kvMul == K) {                                                                           \
         allowLds((const void *)attnDecodeMfmaKernel<K>, kAmLds);                                  \

@@ -26,7 +26,7 @@ namespace hipk {
 // ------------------------------------------------------------------------------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-static constexpr int kPfThreads = 256, kPfWaves = 4, kPfChunk = 256, kPfTile = 32;
+static constexpr int kPfThreads = 256, kPfWaves = 4, kPfChunk = kAttnPrefillChunk, kPfTile = kAttnPrefillTile;
 static constexpr int kPfVtStride = 40;  // bf16 per transposed-V row in LDS (32 keys + 8 pad)
 #ifndef DL_PF_F32_SMALL_CHUNK
 #define DL_PF_F32_SMALL_CHUNK 128
@@ -162,9 +162,8 @@ __global__ __launch_bounds__(kPfThreads) void attnPrefillKernel(AttnArgs a, int 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 15, h = lane >> 4;
     const int b0 = rb * rpb;
     const int maxLen = rowsMaxLen(a.pos, b0, rpb, nRows);
-    int nSplit = (maxLen + kPfChunk - 1) / kPfChunk;
-    nSplit = max(1, min(min(nSplit, a.splitGrid), HS / 2));  // combine weights: 64 columns x nSplit in the K tiles' LDS
-    const int ch = ((maxLen + nSplit - 1) / nSplit + kPfTile - 1) / kPfTile * kPfTile;
+    int nSplit, ch;  // combine weights: 64 columns x nSplit in the K tiles' LDS
+    attnPrefillSplit(maxLen, a.splitGrid, HS, kPfChunk, nSplit, ch);
     if (c >= nSplit) return;
     const int k0 = c * ch, k1 = min(k0 + ch, maxLen);
     const int sl = a.slot[b0];  // every row of the block (host-checked)
@@ -305,9 +304,8 @@ __global__ __launch_bounds__(kPfThreads) void attnPrefillF32Kernel(AttnArgs a, i
     // with few row blocks (a 32-row chunk: 16 workgroups per split) the keys are split finer so
     // more CUs share them (4k prompt in 32-row chunks 0.1526 -> 0.1498 ms/token, raw/r6_prefill_f32_chunk_ab.txt)
     const int chunkKeys = gridDim.x >= 256 ? kPfChunk : kPfChunkF32Small;
-    int nSplit = (maxLen + chunkKeys - 1) / chunkKeys;
-    nSplit = max(1, min(min(nSplit, a.splitGrid), HS / 2));
-    const int ch = ((maxLen + nSplit - 1) / nSplit + kPfTile - 1) / kPfTile * kPfTile;
+    int nSplit, ch;
+    attnPrefillSplit(maxLen, a.splitGrid, HS, chunkKeys, nSplit, ch);
     if (c >= nSplit) return;
     const int k0 = c * ch, k1 = min(k0 + ch, maxLen);
     const int sl = a.slot[b0];
@@ -421,6 +419,23 @@ __global__ __launch_bounds__(kPfThreads) void attnPrefillF32Kernel(AttnArgs a, i
     pfFinish<HS>(a, nRows, o, m, lsum, nSplit, rb, g, c, b0, row, head, &kT[0][0], &vT[0][0], flagL);
 }
 
+const char *attnPrefillDmaRefusal(const AttnArgs &a);  // attn_mfma.hip
+
+int attnPrefillChunkKeys(const AttnArgs &a, int gridX) {  // as attnPrefillF32Kernel picks it from gridDim.x
+    return !a.kvBf16 && gridX < 256 ? kPfChunkF32Small : kPfChunk;
+}
+
+const char *attnPrefillRefusal(const AttnArgs &a) {
+    if (attnPrefillDmaSupported(a)) return attnPrefillDmaRefusal(a);
+    if (!attnPrefillSupported(a.hs, a.kvMul, a.kvBf16 != 0) || a.nHeads0 % a.kvMul)
+        return "launchAttentionPrefill: head size 64 / 128 and a power-of-two GQA group <= 16";
+    // the longest split chunk's tiles fit the kernels' LDS page list (pfPages)
+    const int minSplits = std::max(1, std::min(a.splitGrid, a.hs / 2));
+    if (a.kvMap.table && ((a.seqLen + minSplits - 1) / minSplits + kPfTile - 1) / kPfTile + 1 > kPfMaxTiles)
+        return "launchAttentionPrefill: paged context too long for the per-chunk page list";
+    return nullptr;
+}
+
 void launchAttentionPrefill(const AttnArgs &a, int nRows, hipStream_t s) {
     if (attnPrefillDmaSupported(a)) {  // LDS-DMA staged kernel (attn_mfma.hip)
         launchAttentionPrefillDma(a, nRows, s);
@@ -428,13 +443,7 @@ void launchAttentionPrefill(const AttnArgs &a, int nRows, hipStream_t s) {
     }
     const int nKv = a.nHeads0 / a.kvMul, rpb = attnPrefillRowsPerBlock(a.kvMul);
     const dim3 grid(nKv * ((nRows + rpb - 1) / rpb), a.splitGrid);
-    if (!attnPrefillSupported(a.hs, a.kvMul, a.kvBf16 != 0) || a.nHeads0 % a.kvMul)
-        throw Error("launchAttentionPrefill: head size 64 / 128 and a power-of-two GQA group <= 16");
-    {  // the longest split chunk's tiles fit the kernels' LDS page list (pfPages)
-        const int minSplits = std::max(1, std::min(a.splitGrid, a.hs / 2));
-        if (a.kvMap.table && ((a.seqLen + minSplits - 1) / minSplits + kPfTile - 1) / kPfTile + 1 > kPfMaxTiles)
-            throw Error("launchAttentionPrefill: paged context too long for the per-chunk page list");
-    }
+    if (const char *why = attnPrefillRefusal(a)) throw Error(why);
     if (!a.kvBf16) {
         if (a.hs == 128) hipLaunchKernelGGL(attnPrefillF32Kernel<128>, grid, dim3(kPfThreads), 0, s, a, nRows);
         else hipLaunchKernelGGL(attnPrefillF32Kernel<64>, grid, dim3(kPfThreads), 0, s, a, nRows);

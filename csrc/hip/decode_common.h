@@ -790,22 +790,7 @@ __device__ __forceinline__ int rowsMaxLen(const int *pos, int b0, int n, int nRo
     return v;
 }
 
-// Sequence split of a decode-attention row of length `len`: nSplit chunks of ch positions
-// (~256 per chunk, at most splitGrid chunks). Shorter chunks for the few heads of a TP8 shard
-// (4 per rank) measured slower: 5.4 -> 7.6 us at 100 positions (profiles/r5_tp_rank.md).
-__device__ __forceinline__ void attnSplit(int len, int splitGrid, int &nSplit, int &ch, int chunkMin = 256,
-                                          int shortLen = 0) {
-    // single decode rows (shortLen set) of <= shortLen keys split at 128 keys: one 256-thread task
-    // walks 112-128 keys per memory round trip, so 129..256 keys in one chunk cost a second
-    // dependent round trip per layer (decode at 164-204: 1.39-1.44 vs 1.35-1.37 ms/token,
-    // r6_decode.md). Batched launches keep 256 (their grid would double for it).
-    if (chunkMin >= 256 && len <= shortLen) chunkMin = kAttnShortChunk;
-    int ns = (len + chunkMin - 1) / chunkMin;
-    if (ns > splitGrid) ns = splitGrid;
-    if (ns < 1) ns = 1;
-    ch = (((len + ns - 1) / ns) + 15) & ~15;
-    nSplit = (len + ch - 1) / ch;
-}
+// attnSplit (the sequence split of a decode-attention row) is in kernels.h: host and device share it.
 
 }  // namespace hipk
 }  // namespace dl

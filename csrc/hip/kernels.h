@@ -356,6 +356,12 @@ bool attnMfmaSupported(const AttnArgs &a);
 bool attnUsesMfma(const AttnArgs &a);
 void launchAttentionMfma(const AttnArgs &a, int B, hipStream_t s);
 void launchAttentionValu(const AttnArgs &a, int B, hipStream_t s);  // the VALU kernel (attnTask)
+// query heads per workgroup launchAttentionValu takes for B rows (AttnArgs::headGroup, else by grid size)
+int attnValuHeadGroup(const AttnArgs &a, int B);
+// Why a launcher refuses these arguments (the message it throws), or null when it launches them;
+// host only, no device needed.
+const char *attnMfmaRefusal(const AttnArgs &a);
+const char *attnPrefillRefusal(const AttnArgs &a);     // launchAttentionPrefill, either kernel family
 // Prefill rows with LDS-DMA staged K / V (attn_mfma.hip; other shapes take the register-staged
 // kernels.hip kernel): bf16 cache, head size 128, kvMul 1..16.
 bool attnPrefillDmaSupported(const AttnArgs &a);
@@ -439,6 +445,39 @@ bool attnPrefillSupported(int hs, int kvMul, bool kvBf16);
 int attnSplitGrid(int seqLen, bool shortChunks = false);
 // single decode rows of at most kAttnShortLen keys split into chunks of kAttnShortChunk (attnSplit)
 constexpr int kAttnShortLen = 512, kAttnShortChunk = 128;
+// Sequence split of a decode-attention row of length `len`: nSplit chunks of ch positions
+// (~256 per chunk, at most splitGrid chunks). Shorter chunks for the few heads of a TP8 shard
+// (4 per rank) measured slower: 5.4 -> 7.6 us at 100 positions (profiles/r5_tp_rank.md).
+// Host-callable: the kernels and the host's plan of a launch (ops::attentionPlan) share this one rule.
+__host__ __device__ __forceinline__ void attnSplit(int len, int splitGrid, int &nSplit, int &ch, int chunkMin = 256,
+                                                   int shortLen = 0) {
+    // single decode rows (shortLen set) of <= shortLen keys split at 128 keys: one 256-thread task
+    // walks 112-128 keys per memory round trip, so 129..256 keys in one chunk cost a second
+    // dependent round trip per layer (decode at 164-204: 1.39-1.44 vs 1.35-1.37 ms/token,
+    // r6_decode.md). Batched launches keep 256 (their grid would double for it).
+    if (chunkMin >= 256 && len <= shortLen) chunkMin = kAttnShortChunk;
+    int ns = (len + chunkMin - 1) / chunkMin;
+    if (ns > splitGrid) ns = splitGrid;
+    if (ns < 1) ns = 1;
+    ch = (((len + ns - 1) / ns) + 15) & ~15;
+    nSplit = (len + ch - 1) / ch;
+}
+// Key split of a prefill row block whose longest row has maxLen keys: chunks of ~chunkKeys keys, at
+// most splitGrid and hs / 2 of them (the combine keeps 64 columns x nSplit weights in LDS), ch a whole
+// number of 32-key tiles. The three prefill kernels and the host's plan of a launch share this rule.
+constexpr int kAttnPrefillChunk = 256, kAttnPrefillTile = 32;
+__host__ __device__ __forceinline__ void attnPrefillSplit(int maxLen, int splitGrid, int hs, int chunkKeys, int &nSplit,
+                                                          int &ch) {
+    int ns = (maxLen + chunkKeys - 1) / chunkKeys;
+    if (ns > splitGrid) ns = splitGrid;
+    if (ns > hs / 2) ns = hs / 2;
+    if (ns < 1) ns = 1;
+    nSplit = ns;
+    ch = ((maxLen + ns - 1) / ns + kAttnPrefillTile - 1) / kAttnPrefillTile * kAttnPrefillTile;
+}
+// keys per split the prefill launch of these arguments aims at on a grid of gridX workgroups per
+// split (the f32 kernel splits finer on small grids; host only)
+int attnPrefillChunkKeys(const AttnArgs &a, int gridX);
 // Fewest keys per attention split (DL_ATTN_CHUNK, default 256): sets the split grid of a context.
 int attnChunkMin();
 int attnChunkMax(int seqLen, int splitGrid);

@@ -209,7 +209,7 @@ void launchAttention(const AttnArgs &a, int B, hipStream_t s) {
         launchAttentionValu(a, B, s);
 }
 
-void launchAttentionValu(const AttnArgs &a, int B, hipStream_t s) {
+int attnValuHeadGroup(const AttnArgs &a, int B) {
     // Query heads per workgroup: sharing a KV head's loads between HG heads costs HG x the serial
     // work per workgroup, so take the fewest heads per workgroup that keep the grid (at the
     // longest context this launch can see) within one workgroup per CU. Measured on MI355X
@@ -223,6 +223,11 @@ void launchAttentionValu(const AttnArgs &a, int B, hipStream_t s) {
     int HG = 1;
     while (HG < hgMax && (long)(a.nHeads0 / HG) * a.splitGrid * B > gridMax) HG *= 2;
     if (a.headGroup > 0) HG = a.headGroup < hgMax ? a.headGroup : hgMax;
+    return HG;
+}
+
+void launchAttentionValu(const AttnArgs &a, int B, hipStream_t s) {
+    const int HG = attnValuHeadGroup(a, B);
     if (a.hs == 128) {
         if (a.kvBf16) attnDispatchHG<128, true>(a, B, HG, s);
         else attnDispatchHG<128, false>(a, B, HG, s);

@@ -869,6 +869,282 @@ std::vector<float> attention(const std::vector<float> &q, const std::vector<floa
     return sc.download(a.out, (size_t)B * q0);
 }
 
+namespace {
+
+// The scalar half of the engine's attnArgs (engine_forward.cpp) for an AttnLaunchArgs call: every
+// field the launchers' predicates read. The table pointer is a non-null placeholder for paged
+// calls (the predicates only test it); attentionLaunch replaces it with the device table.
+struct AttnGeom {
+    hipk::AttnArgs a;
+    int B = 0, q0 = 0, kv0 = 0, nKv = 0, ldq = 0, ldOut = 0, pagesPerSlot = 0, pageShift = 0;
+    bool prefill = false;
+};
+const int kAttnTablePlaceholder = 0;
+
+AttnGeom attnGeom(const AttnLaunchArgs &l) {
+    AttnGeom g;
+    const int B = g.B = (int)l.pos.size();
+    DL_CHECK(B >= 1 && l.slot.size() == l.pos.size(), "attention rows");
+    DL_CHECK(l.kvMul >= 1 && l.nHeads0 >= 1 && l.nHeads0 % l.kvMul == 0 && (l.hs == 64 || l.hs == 128), "attention head layout");
+    DL_CHECK(l.nSlots >= 1 && l.seqLen >= 1, "attention cache shape");
+    g.q0 = l.nHeads0 * l.hs;
+    g.nKv = l.nHeads0 / l.kvMul;
+    g.kv0 = g.nKv * l.hs;
+    g.ldq = l.ldq > 0 ? l.ldq : g.q0;
+    g.ldOut = l.ldOut > 0 ? l.ldOut : g.q0;
+    DL_CHECK(g.ldq >= g.q0 && g.ldq % 4 == 0, "attention ldq: at least q0, whole float4 loads");
+    DL_CHECK(g.ldOut >= g.q0 && g.ldOut % 32 == 0, "attention ldOut: at least q0, whole Q80 blocks");
+    const size_t cacheElems = (size_t)l.nSlots * l.seqLen * g.kv0;
+    DL_CHECK(l.q.size() == (size_t)B * g.ldq && l.k.size() == cacheElems && l.v.size() == cacheElems, "attention sizes");
+    for (int b = 0; b < B; b++)
+        DL_CHECK(l.pos[b] >= 0 && l.pos[b] < l.seqLen && l.slot[b] >= 0 && l.slot[b] < l.nSlots, "attention row out of range");
+    DL_CHECK(l.kernel >= ATTN_AUTO && l.kernel <= ATTN_PREFILL && (l.mode == ATTN_DECODE || l.mode == ATTN_PREFILL_ROWS),
+             "attention kernel / mode");
+    g.prefill = l.mode == ATTN_PREFILL_ROWS;
+    DL_CHECK(g.prefill ? (l.kernel == ATTN_AUTO || l.kernel == ATTN_PREFILL) : l.kernel != ATTN_PREFILL,
+             "attention: the prefill kernels run prefill rows, the decode kernels decode rows");
+    DL_CHECK(l.headGroup == 0 || l.headGroup == 1 || l.headGroup == 2 || l.headGroup == 4 || l.headGroup == 8,
+             "attention headGroup must be 0 (the launcher's pick), 1, 2, 4 or 8");
+    DL_CHECK(l.splitGrid >= 0 && l.splitGrid <= 128, "attention splitGrid must be 0 (the engine's rule) or 1..128");
+    DL_CHECK(l.out == ATTN_OUT_F32 || l.out == ATTN_OUT_F16 || l.out == ATTN_OUT_Q80, "attention output format");
+    DL_CHECK(l.repeat >= 1, "attention repeat must be at least 1");
+    DL_CHECK(l.warmPos.empty() || l.warmPos.size() == l.pos.size(), "attention warm positions: one per row");
+    for (int p : l.warmPos) DL_CHECK(p >= 0 && p < l.seqLen, "attention warm position out of range");
+    DL_CHECK(!(g.prefill && l.out == ATTN_OUT_Q80), "attention: the prefill kernels ignore outQ (no Q80 output)");
+    DL_CHECK((l.poisonK.empty() || l.poisonK.size() == (size_t)g.kv0) && (l.poisonV.empty() || l.poisonV.size() == (size_t)g.kv0),
+             "attention poison rows: [kv0]");
+    hipk::AttnArgs &a = g.a;
+    if (l.pageSize) {
+        DL_CHECK(l.pageSize >= 32 && (l.pageSize & (l.pageSize - 1)) == 0, "attention pageSize must be a power of two >= 32");
+        while ((1 << g.pageShift) < l.pageSize) g.pageShift++;
+        g.pagesPerSlot = (l.seqLen + l.pageSize - 1) / l.pageSize;
+        const int nPages = l.nSlots * g.pagesPerSlot;
+        DL_CHECK(l.pageOf.size() == (size_t)nPages, "attention pageOf: [nSlots][ceil(seqLen / pageSize)]");
+        for (int p : l.pageOf) DL_CHECK(p >= -1 && p < nPages, "attention pageOf: -1 or a pool page below nSlots * pagesPerSlot");
+        a.kvMap.table = &kAttnTablePlaceholder;
+        a.kvMap.pageShift = g.pageShift;
+        a.kvMap.pagesPerSlot = g.pagesPerSlot;
+    } else {
+        DL_CHECK(l.pageOf.empty(), "attention pageOf needs a pageSize");
+    }
+    a.ldq = g.ldq;
+    a.nHeads0 = l.nHeads0;
+    a.kvMul = l.kvMul;
+    a.hs = l.hs;
+    a.kv0 = g.kv0;
+    a.seqLen = l.seqLen;
+    a.chunkMin = hipk::attnChunkMin();
+    a.shortLen = l.single ? hipk::kAttnShortLen : 0;
+    if (l.splitGrid > 0) {
+        a.splitGrid = l.splitGrid;
+        a.chunkMax = hipk::attnChunkMax(l.seqLen, a.splitGrid);
+    } else {
+        a.splitGrid = hipk::attnSplitGrid(l.seqLen, l.single);
+        a.chunkMax = hipk::attnChunkMax(l.seqLen, hipk::attnSplitGrid(l.seqLen, false));
+    }
+    a.ldOut = g.ldOut;
+    a.kvBf16 = l.kvBf16 ? 1 : 0;
+    a.mfma = l.kernel == ATTN_MFMA ? 1 : l.kernel == ATTN_VALU ? 0 : -1;
+    a.headGroup = l.headGroup;
+    return g;
+}
+
+}  // namespace
+
+AttnLaunchPlan attentionPlan(const AttnLaunchArgs &l) {
+    const AttnGeom g = attnGeom(l);
+    const hipk::AttnArgs &a = g.a;
+    AttnLaunchPlan p;
+    p.splitGrid = a.splitGrid;
+    p.chunkMax = a.chunkMax;
+    p.shortLen = a.shortLen;
+    const std::string hsS = std::to_string(a.hs), kmS = std::to_string(a.kvMul);
+    if (g.prefill) {
+        if (const char *why = hipk::attnPrefillRefusal(a)) throw Error(why);
+        const int rpb = hipk::attnPrefillRowsPerBlock(a.kvMul);
+        for (int b = 0; b < g.B; b++) DL_CHECK(l.slot[b] == l.slot[b - b % rpb], "prefill row blocks must share a slot");
+        p.kernel = hipk::attnPrefillDmaSupported(a) ? "attnPrefillDmaKernel<" + kmS + ">"
+                   : a.kvBf16                       ? "attnPrefillKernel<" + hsS + ">"
+                                                    : "attnPrefillF32Kernel<" + hsS + ">";
+        p.grid[0] = g.nKv * ((g.B + rpb - 1) / rpb);
+        p.grid[1] = a.splitGrid;
+        p.grid[2] = 1;
+        const int chunkKeys = hipk::attnPrefillChunkKeys(a, p.grid[0]);
+        for (int b0 = 0; b0 < g.B; b0 += rpb) {
+            int maxLen = 0, ns, ch;
+            for (int b = b0; b < std::min(g.B, b0 + rpb); b++) maxLen = std::max(maxLen, l.pos[b] + 1);
+            hipk::attnPrefillSplit(maxLen, a.splitGrid, a.hs, chunkKeys, ns, ch);
+            p.nSplit.push_back(ns);
+            p.ch.push_back(ch);
+        }
+        return p;
+    }
+    bool mfma;
+    if (l.kernel == ATTN_MFMA) {
+        DL_CHECK(hipk::attnMfmaSupported(a), "MFMA decode attention: bf16 cache, head size 128, kvMul 1/2/4/8");
+        mfma = true;
+    } else {
+        mfma = l.kernel == ATTN_AUTO && hipk::attnUsesMfma(a);
+    }
+    if (mfma) {
+        if (const char *why = hipk::attnMfmaRefusal(a)) throw Error(why);
+        p.kernel = "attnDecodeMfmaKernel<" + kmS + ">";
+        p.grid[0] = g.nKv;
+    } else {
+        p.hg = hipk::attnValuHeadGroup(a, g.B);
+        p.kernel = "attnKernel<" + std::to_string(p.hg) + "," + hsS + (a.kvBf16 ? ",bf16>" : ",f32>");
+        p.grid[0] = a.nHeads0 / p.hg;
+    }
+    p.grid[1] = a.splitGrid;
+    p.grid[2] = g.B;
+    for (int b = 0; b < g.B; b++) {
+        int ns, ch;
+        hipk::attnSplit(l.pos[b] + 1, a.splitGrid, ns, ch, a.chunkMin, a.shortLen);
+        p.nSplit.push_back(ns);
+        p.ch.push_back(ch);
+    }
+    return p;
+}
+
+AttnLaunchResult attentionLaunch(const AttnLaunchArgs &l) {
+    AttnLaunchResult res;
+    res.plan = attentionPlan(l);  // refusals: before any device work
+    AttnGeom g = attnGeom(l);
+    hipk::AttnArgs &a = g.a;
+    const int B = g.B, q0 = g.q0, kv0 = g.kv0, nKv = g.nKv, hs = l.hs, seqLen = l.seqLen;
+    Scratch sc;
+    // caches: the caller's [slot][seqLen][kv0] rows -> the engine's head-major layout through kvOff,
+    // contiguous [slot][nKv][seqLen][hs] or a pool [page][nKv][pageSize][hs] (+ the poison page)
+    hipk::KvMap hostMap;  // contiguous: no table
+    size_t poolElems = (size_t)l.nSlots * seqLen * kv0;
+    const int nPages = l.nSlots * g.pagesPerSlot;
+    std::vector<int> table;
+    if (l.pageSize) {
+        table = l.pageOf;
+        for (int &t : table)
+            if (t < 0) t = nPages;  // the poison page
+        hostMap.table = table.data();
+        hostMap.pageShift = g.pageShift;
+        hostMap.pagesPerSlot = g.pagesPerSlot;
+        poolElems = (size_t)(nPages + 1) * kv0 * l.pageSize;
+    }
+    auto cache = [&](const std::vector<float> &xs, const std::vector<float> &poison) -> void * {
+        std::vector<float> x(poolElems, 0.f);
+        if (l.pageSize) {  // every page holds the poison row until a table entry claims it
+            for (int pg = 0; pg <= nPages; pg++)
+                for (int kh = 0; kh < nKv; kh++)
+                    for (int p = 0; p < l.pageSize; p++)
+                        for (int d = 0; d < hs; d++)
+                            x[(((size_t)pg * nKv + kh) * l.pageSize + p) * hs + d] = poison.empty() ? 0.f : poison[(size_t)kh * hs + d];
+        }
+        for (int sl = 0; sl < l.nSlots; sl++)
+            for (int p = 0; p < seqLen; p++) {
+                if (l.pageSize && l.pageOf[(size_t)sl * g.pagesPerSlot + (p >> g.pageShift)] < 0) continue;
+                for (int kh = 0; kh < nKv; kh++)
+                    std::memcpy(&x[hipk::kvOff(hostMap, seqLen, nKv, hs, sl, p, kh)],
+                                &xs[((size_t)sl * seqLen + p) * kv0 + (size_t)kh * hs], hs * sizeof(float));
+            }
+        if (!l.kvBf16) return sc.upload(x);
+        std::vector<uint16_t> h(x.size());
+        for (size_t i = 0; i < x.size(); i++) {  // round to nearest even, as the QKV epilogue stores
+            uint32_t u;
+            std::memcpy(&u, &x[i], 4);
+            h[i] = (uint16_t)((u + 0x7FFF + ((u >> 16) & 1)) >> 16);
+        }
+        return sc.upload(h);
+    };
+    a.q = sc.upload(l.q);
+    a.kcache = cache(l.k, l.poisonK);
+    a.vcache = cache(l.v, l.poisonV);
+    if (l.pageSize) a.kvMap.table = sc.upload(table);
+    a.pos = sc.upload(l.pos);
+    a.slot = sc.upload(l.slot);
+    // scratch of the engine's sizes (engine_load.cpp), each followed by a guard
+    const size_t nPartO = (size_t)B * l.nHeads0 * a.splitGrid * hs, nPartML = (size_t)B * l.nHeads0 * a.splitGrid * 2;
+    const size_t nCnt = (size_t)B * l.nHeads0, guard = 256;
+    a.partO = sc.allocGuarded<float>(1, nPartO, nPartO + guard, "partO");
+    a.partML = sc.allocGuarded<float>(1, nPartML, nPartML + guard, "partML");
+    a.counters = sc.allocGuarded<int>(1, nCnt, nCnt + guard, "the arrival counters");
+    DL_HIP(hipMemsetAsync(a.counters, 0, nCnt * sizeof(int), sc.s));
+    // the output: a guard after each row's q0 valid elements (ldOut > q0) and two guard rows after the last
+    const size_t ldO = g.ldOut, ldS = ldO / 32, tail = 2;
+    void *outBuf = nullptr;
+    size_t outBytes = 0, sBytes = 0;
+    if (l.out == ATTN_OUT_Q80) {
+        a.outQ = sc.allocGuardedTail<int8_t>(B, q0, ldO, tail, "the Q80 codes");
+        a.outS = reinterpret_cast<float2 *>(sc.allocGuardedTail<float>(B, (size_t)q0 / 32 * 2, ldS * 2, tail, "the Q80 scales"));
+        outBuf = a.outQ;
+        outBytes = (B + tail) * ldO;
+        sBytes = (B + tail) * ldS * 2 * sizeof(float);
+    } else if (l.out == ATTN_OUT_F16) {
+        a.outH = reinterpret_cast<_Float16 *>(sc.allocGuardedTail<uint16_t>(B, q0, ldO, tail, "the f16 output"));
+        outBuf = a.outH;
+        outBytes = (B + tail) * ldO * 2;
+    } else {
+        a.out = sc.allocGuardedTail<float>(B, q0, ldO, tail, "the attention output");
+        outBuf = a.out;
+        outBytes = (B + tail) * ldO * 4;
+    }
+    auto run = [&] {
+        if (g.prefill)
+            hipk::launchAttentionPrefill(a, B, sc.s);
+        else if (l.kernel == ATTN_VALU)
+            hipk::launchAttentionValu(a, B, sc.s);
+        else if (l.kernel == ATTN_MFMA)
+            hipk::launchAttentionMfma(a, B, sc.s);
+        else
+            hipk::launchAttention(a, B, sc.s);
+        sc.sync();
+        sc.checkGuards();
+    };
+    if (!l.warmPos.empty()) {  // an earlier launch of other row lengths leaves its partials behind
+        const int *measured = a.pos;
+        a.pos = sc.upload(l.warmPos);
+        run();
+        a.pos = measured;
+    }
+    std::vector<uint8_t> first, firstS;
+    for (int r = 0; r < l.repeat; r++) {
+        if (r > 0 || !l.warmPos.empty()) {  // same scratch, same output buffer, re-filled with the guard pattern
+            DL_HIP(hipMemsetAsync(outBuf, Scratch::kGuardByte, outBytes, sc.s));
+            if (a.outS) DL_HIP(hipMemsetAsync(a.outS, Scratch::kGuardByte, sBytes, sc.s));
+        }
+        run();
+        const std::vector<int> cnt = sc.download(a.counters, nCnt);
+        for (size_t i = 0; i < nCnt; i++)
+            DL_CHECK(cnt[i] == 0, "ops: attention arrival counter " + std::to_string(i) + " is " + std::to_string(cnt[i]) +
+                                      " after launch " + std::to_string(r) + " (must reset itself to zero)");
+        const std::vector<uint8_t> now = sc.download(static_cast<const uint8_t *>(outBuf), outBytes);
+        std::vector<uint8_t> nowS;
+        if (a.outS) nowS = sc.download(reinterpret_cast<const uint8_t *>(a.outS), sBytes);
+        if (r == 0) {
+            first = now;
+            firstS = nowS;
+        } else {
+            DL_CHECK(now == first && nowS == firstS,
+                     "ops: attention launch " + std::to_string(r) + " on the same scratch differs bitwise from the first");
+        }
+    }
+    res.out.resize((size_t)B * q0);
+    for (int b = 0; b < B; b++)
+        for (int i = 0; i < q0; i++) {
+            const size_t at = (size_t)b * ldO + i;
+            if (l.out == ATTN_OUT_Q80)
+                res.out[(size_t)b * q0 + i] = (float)reinterpret_cast<const int8_t *>(first.data())[at];
+            else if (l.out == ATTN_OUT_F16)
+                res.out[(size_t)b * q0 + i] = f16ToF32(reinterpret_cast<const uint16_t *>(first.data())[at]);
+            else
+                res.out[(size_t)b * q0 + i] = reinterpret_cast<const float *>(first.data())[at];
+        }
+    if (l.out == ATTN_OUT_Q80) {
+        res.scales.resize((size_t)B * (q0 / 32) * 2);
+        for (int b = 0; b < B; b++)
+            for (int i = 0; i < q0 / 32 * 2; i++)
+                res.scales[(size_t)b * (q0 / 32) * 2 + i] = reinterpret_cast<const float *>(firstS.data())[(size_t)b * ldS * 2 + i];
+    }
+    return res;
+}
+
 std::vector<int> argmax(const std::vector<float> &logits, int B, int vocab) {
     DL_CHECK(B >= 1 && vocab >= 1 && logits.size() == (size_t)B * vocab, "argmax sizes");
     Scratch sc;

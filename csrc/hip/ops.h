@@ -7,6 +7,7 @@
 #pragma once
 
 #include <cstdint>
+#include <string>
 #include <vector>
 
 namespace dl {
@@ -145,6 +146,68 @@ std::vector<float> attention(const std::vector<float> &q, const std::vector<floa
                              const std::vector<int> &slot, bool kvBf16, int impl = 0);
 // attention impl: 0 = launchAttention's choice, 1 = MFMA prefill kernel, 2 = VALU decode kernel,
 // 3 = MFMA decode kernel
+
+// One attention launch as the engine's attnArgs / enqueueAttention set it up (engine_forward.cpp),
+// which ops::attention above cannot: a page table, the single-row split geometry, the f16 and Q80
+// writers, a pinned head group, strided rows and reused scratch.
+//   kernel   ATTN_AUTO: launchAttention's choice (decode) / launchAttentionPrefill's (prefill);
+//            ATTN_VALU / ATTN_MFMA: that decode kernel; ATTN_PREFILL: the prefill launcher
+//   mode     ATTN_DECODE or ATTN_PREFILL_ROWS (blocks of attnPrefillRowsPerBlock rows share a slot)
+//   single   the engine's single-row setup: shortLen = kAttnShortLen, splitGrid =
+//            attnSplitGrid(seqLen, true), chunkMax from the *batched* grid attnSplitGrid(seqLen, false);
+//            else the batched setup (shortLen 0). splitGrid > 0 forces the grid (chunkMax =
+//            attnChunkMax(seqLen, splitGrid)).
+//   headGroup 0 (the launcher's pick) or 1 / 2 / 4 / 8 (AttnArgs::headGroup)
+//   out      ATTN_OUT_F32 / _F16 (outH) / _Q80 (outQ + outS; decode kernels only: the prefill
+//            kernels ignore outQ, so that combination is refused)
+//   ldq / ldOut  row strides, 0 = q0, else >= q0 (multiples of 4 / 32: vector loads, Q80 blocks)
+//   pageSize 0: contiguous caches; else a power of two >= 32: the caches go to a page pool in the
+//            engine's paged layout (kvOff with a table), pageOf = [nSlots][ceil(seqLen / pageSize)]
+//            pool pages (ids below nSlots * pagesPerSlot), -1 = not mapped. The pool has one extra
+//            *poison page* every unmapped entry points to; it and every pool page no entry names hold
+//            poisonK / poisonV ([kv0] each, zeros when empty) at every position.
+//   repeat   launches on the same scratch and output buffer (re-filled with the guard pattern in
+//            between): all must give bitwise the same result and leave every counter zero.
+// Guards of the fixed pattern of gemmBatched: after each output row's valid part (ldOut > q0), after
+// the last row, behind partO, partML and counters; for f16 / Q80 around the code and scale arrays
+// separately. The op throws when a launch changed one. A launch the launchers refuse, or whose
+// operands are outside their contract, throws before any device work (attentionPlan).
+enum AttnKernelSel : int { ATTN_AUTO = 0, ATTN_VALU = 1, ATTN_MFMA = 2, ATTN_PREFILL = 3 };
+enum AttnMode : int { ATTN_DECODE = 0, ATTN_PREFILL_ROWS = 1 };
+enum AttnOut : int { ATTN_OUT_F32 = 0, ATTN_OUT_F16 = 1, ATTN_OUT_Q80 = 2 };
+struct AttnLaunchArgs {
+    std::vector<float> q, k, v;  // q [B][ldq], k / v [nSlots][seqLen][kv0]
+    int nSlots = 0, seqLen = 0, nHeads0 = 0, kvMul = 1, hs = 0;
+    std::vector<int> pos, slot;
+    bool kvBf16 = true;
+    int kernel = ATTN_AUTO, mode = ATTN_DECODE;
+    bool single = false;
+    int splitGrid = 0, headGroup = 0;
+    int out = ATTN_OUT_F32;
+    int ldq = 0, ldOut = 0;
+    int pageSize = 0;
+    std::vector<int> pageOf;
+    std::vector<float> poisonK, poisonV;
+    int repeat = 1;
+    // optional [B]: one launch with these positions (same rows, slots and caches) runs first on the
+    // same scratch and output buffer, so that the measured launches find its partials and counters
+    std::vector<int> warmPos;
+};
+// Host side of the launch, from the launchers' own predicates; no device needed.
+struct AttnLaunchPlan {
+    std::string kernel;       // the instance, e.g. "attnKernel<2,128,bf16>", "attnDecodeMfmaKernel<4>"
+    int hg = 0;               // VALU decode: heads per workgroup (attnValuHeadGroup); else 0
+    int grid[3] = {0, 0, 0};
+    int splitGrid = 0, chunkMax = 0, shortLen = 0;
+    std::vector<int> nSplit, ch;  // decode: attnSplit of every row; prefill: attnPrefillSplit of every row block
+};
+struct AttnLaunchResult {
+    std::vector<float> out;     // [B][q0]: f32, the f16 values, or the Q80 codes
+    std::vector<float> scales;  // Q80: [B][q0 / 32][2] (d, sum of codes)
+    AttnLaunchPlan plan;
+};
+AttnLaunchPlan attentionPlan(const AttnLaunchArgs &a);
+AttnLaunchResult attentionLaunch(const AttnLaunchArgs &a);
 
 // Parallel argmax over [B][vocab] (ties -> lowest index).
 std::vector<int> argmax(const std::vector<float> &logits, int B, int vocab);

@@ -465,6 +465,69 @@ void bindOps(py::module_ &m) {
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("n_slots"), py::arg("seq_len"), py::arg("n_heads0"),
           py::arg("kv_mul"), py::arg("head_size"), py::arg("pos"), py::arg("slot"), py::arg("kv_bf16") = true,
           py::arg("impl") = 0);
+    // ops::attentionLaunch: `plan_only` returns the plan (and raises the refusals) without a device
+    o.def("attention_launch",
+          [](py::object q, py::object k, py::object v, int nSlots, int seqLen, int nHeads0, int kvMul, int hs,
+             std::vector<int> pos, std::vector<int> slot, bool kvBf16, int kernel, int mode, bool single, int splitGrid,
+             int headGroup, int out, int ldq, int ldOut, int pageSize, std::vector<int> pageOf, py::object poisonK,
+             py::object poisonV, int repeat, std::vector<int> warmPos, bool planOnly) {
+              ops::AttnLaunchArgs a;
+              a.warmPos = warmPos;
+              a.q = vec<float>(q);
+              a.k = vec<float>(k);
+              a.v = vec<float>(v);
+              a.nSlots = nSlots;
+              a.seqLen = seqLen;
+              a.nHeads0 = nHeads0;
+              a.kvMul = kvMul;
+              a.hs = hs;
+              a.pos = pos;
+              a.slot = slot;
+              a.kvBf16 = kvBf16;
+              a.kernel = kernel;
+              a.mode = mode;
+              a.single = single;
+              a.splitGrid = splitGrid;
+              a.headGroup = headGroup;
+              a.out = out;
+              a.ldq = ldq;
+              a.ldOut = ldOut;
+              a.pageSize = pageSize;
+              a.pageOf = pageOf;
+              a.poisonK = vec<float>(poisonK);
+              a.poisonV = vec<float>(poisonV);
+              a.repeat = repeat;
+              ops::AttnLaunchResult r;
+              {
+                  py::gil_scoped_release rel;
+                  if (planOnly)
+                      r.plan = ops::attentionPlan(a);
+                  else
+                      r = ops::attentionLaunch(a);
+              }
+              py::dict res;
+              res["kernel"] = r.plan.kernel;
+              res["hg"] = r.plan.hg;
+              res["grid"] = py::make_tuple(r.plan.grid[0], r.plan.grid[1], r.plan.grid[2]);
+              res["split_grid"] = r.plan.splitGrid;
+              res["chunk_max"] = r.plan.chunkMax;
+              res["short_len"] = r.plan.shortLen;
+              py::list splits;
+              for (size_t b = 0; b < r.plan.nSplit.size(); b++) splits.append(py::make_tuple(r.plan.nSplit[b], r.plan.ch[b]));
+              res["splits"] = splits;
+              if (planOnly) return res;
+              const py::ssize_t B = (py::ssize_t)pos.size(), q0 = (py::ssize_t)nHeads0 * hs;
+              res["out"] = arr(r.out, {B, q0});
+              if (!r.scales.empty()) res["scales"] = arr(r.scales, {B, q0 / 32, (py::ssize_t)2});
+              return res;
+          },
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("n_slots"), py::arg("seq_len"), py::arg("n_heads0"),
+          py::arg("kv_mul"), py::arg("head_size"), py::arg("pos"), py::arg("slot"), py::arg("kv_bf16") = true,
+          py::arg("kernel") = 0, py::arg("mode") = 0, py::arg("single") = false, py::arg("split_grid") = 0,
+          py::arg("head_group") = 0, py::arg("out") = 0, py::arg("ldq") = 0, py::arg("ld_out") = 0,
+          py::arg("page_size") = 0, py::arg("page_of") = std::vector<int>(), py::arg("poison_k") = py::none(),
+          py::arg("poison_v") = py::none(), py::arg("repeat") = 1, py::arg("warm_pos") = std::vector<int>(),
+          py::arg("plan_only") = false);
     o.def("sample",
           [](py::object logits, int B, py::object specs) {
               const std::vector<float> l = vec<float>(logits), sp = vec<float>(specs);

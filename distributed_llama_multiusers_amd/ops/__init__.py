@@ -172,6 +172,38 @@ def attention(q, k_cache, v_cache, n_heads0: int, kv_mul: int, head_size: int, p
                                                    kv_bf16, code))
 
 
+ATTN_KERNELS = {"auto": 0, "valu": 1, "mfma": 2, "prefill": 3}
+ATTN_OUTPUTS = {"f32": 0, "f16": 1, "q80": 2}
+
+
+def attention_launch(q, k_cache, v_cache, n_heads0: int, kv_mul: int, head_size: int, pos, slot,
+                     kv_bf16: bool = True, kernel: str = "auto", prefill: bool = False, single: bool = False,
+                     split_grid: int = 0, head_group: int = 0, out: str = "f32", ldq: int = 0, ld_out: int = 0,
+                     page_size: int = 0, page_of=None, poison_k=None, poison_v=None, repeat: int = 1,
+                     warm_pos=None, plan_only: bool = False) -> dict:
+    """One attention launch set up as the engine sets it up (ops::attentionLaunch, csrc/hip/ops.h).
+    q [B, ldq or q0], k_cache / v_cache [slots, seq_len, kv0]. kernel "auto" / "valu" / "mfma" /
+    "prefill"; prefill: prefill rows (row blocks share a slot). single: the engine's single-row split
+    geometry; split_grid > 0 forces the grid. head_group 0 / 1 / 2 / 4 / 8. out "f32" / "f16" / "q80".
+    page_size > 0: a paged cache, page_of [slots, ceil(seq_len / page_size)] pool pages (-1: not mapped:
+    the poison page, which holds poison_k / poison_v [kv0] at every position). repeat: launches on
+    the same scratch, which must agree bitwise and leave the counters zero; warm_pos [B]: one launch at these
+    positions runs first on that scratch and output (its partials stay behind). Outputs and scratch are
+    guarded: a store outside their valid part raises. Returns {"kernel", "hg", "grid", "split_grid",
+    "chunk_max", "short_len", "splits": [(nSplit, ch) per decode row, or per prefill row block], "out" [B, q0] (f32, the f16
+    values or the Q80 codes), "scales" [B, q0 / 32, 2] (Q80: d, sum of codes)}. plan_only: just the
+    plan and the refusals, no device needed."""
+    n_slots, seq_len, _ = k_cache.shape
+    po = [] if page_of is None else [int(p) for p in np.asarray(page_of).reshape(-1)]
+    r = native().ops.attention_launch(_np(q), _np(k_cache), _np(v_cache), n_slots, seq_len, n_heads0, kv_mul,
+                                      head_size, [int(p) for p in pos], [int(s) for s in slot], kv_bf16,
+                                      ATTN_KERNELS["prefill" if prefill and kernel == "auto" else kernel],
+                                      1 if prefill else 0, single, split_grid, head_group, ATTN_OUTPUTS[out], ldq,
+                                      ld_out, page_size, po, _np(poison_k), _np(poison_v), repeat,
+                                      [] if warm_pos is None else [int(p) for p in warm_pos], plan_only)
+    return {k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()}
+
+
 def sample(logits, temperatures, topps, coins) -> list:
     """Device sampler: per row softmax(logits / T) then multinomial (top-p >= 1) or nucleus draw."""
     x = _np(logits)
@@ -298,14 +330,14 @@ def ref_rope_table(seq_len: int, head_size: int, theta: float = 10000.0) -> torc
 
 
 def ref_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, n_heads0: int, kv_mul: int,
-                  head_size: int, pos, slot) -> torch.Tensor:
-    out = torch.zeros(q.shape[0], n_heads0 * head_size)
+                  head_size: int, pos, slot, dtype=torch.float32) -> torch.Tensor:
+    out = torch.zeros(q.shape[0], n_heads0 * head_size, dtype=dtype)
     for b in range(q.shape[0]):
         for h in range(n_heads0):
             kvh = h // kv_mul
-            qh = q[b, h * head_size:(h + 1) * head_size].float()
-            K = k_cache[slot[b], :pos[b] + 1, kvh * head_size:(kvh + 1) * head_size].float()
-            V = v_cache[slot[b], :pos[b] + 1, kvh * head_size:(kvh + 1) * head_size].float()
+            qh = q[b, h * head_size:(h + 1) * head_size].to(dtype)
+            K = k_cache[slot[b], :pos[b] + 1, kvh * head_size:(kvh + 1) * head_size].to(dtype)
+            V = v_cache[slot[b], :pos[b] + 1, kvh * head_size:(kvh + 1) * head_size].to(dtype)
             p = torch.softmax(K @ qh / head_size ** 0.5, dim=0)
             out[b, h * head_size:(h + 1) * head_size] = p @ V
     return out

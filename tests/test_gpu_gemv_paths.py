@@ -22,6 +22,8 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_checks
+
 gpu = pytest.mark.gpu
 
 
@@ -299,20 +301,9 @@ def swiglu_q80_case(L, passes, B):
 
 
 def check_q80_row(codes, d, sums, h, what):
-    """codes [B, H] int, d / sums [B, H / 32], h [B, H] float64: the hand-off's contract.
-    |code * d - h| <= d / 2 (rounding half-step) + A * 2^-10 (f16 rounding of the scale, A the
-    block's largest |h|, a factor 2 of slack) + 2e-4 * max|h| (the GEMV's own bound)."""
-    Bn, H = h.shape
-    codes, d, sums = codes.double().reshape(Bn, H // 32, 32), d.double(), sums.double()
-    hb = h.reshape(Bn, H // 32, 32)
-    A = hb.abs().amax(-1, keepdim=True)
-    bound = d[..., None] / 2 + A * 2.0 ** -10 + 2e-4 * h.abs().max()
-    err = (codes * d[..., None] - hb).abs()
-    print(f"{what}: worst error / bound {float((err / bound).max()):.3f}")
-    assert bool((err <= bound).all()), float((err / bound).max())
-    assert torch.equal(d.float().half().float().double(), d)  # the scale is an f16 value
-    assert torch.equal(sums, codes.sum(-1))
-    assert int(codes.abs().max()) <= 127
+    """The hand-off's contract (kernel_checks.check_q80_row, shared with the attention suite) with the
+    GEMV's own bound of 2e-4 * max|h|."""
+    kernel_checks.check_q80_row(codes, d, sums, h, what, kernel_bound=2e-4)
 
 
 def test_host_q80_meets_handoff_bound(C):
