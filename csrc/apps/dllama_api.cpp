@@ -8,6 +8,12 @@
 //           "stream": true -> server-sent events with chat.completion.chunk objects + [DONE]
 //           "logprobs": true (+ "top_logprobs": 0..20) -> choices[0].logprobs.content, one entry
 //           per generated token: log_softmax of the raw logits, whatever temperature / top_p
+//   POST /v1/embeddings        {"input": <string | [strings] | [token ids] | [[token ids]]>, "model",
+//                               "encoding_format": "float"|"base64", "pooling": "mean"|"last"}
+//        -> {"object":"list","data":[{"object":"embedding","index":i,"embedding":[...]}...],
+//            "model":...,"usage":{"prompt_tokens","total_tokens"}}: per input the L2-normalised mean
+//           (or last row) of its prompt rows' final hidden states; the inputs batch with each other
+//           and with the chat traffic; "pooling" is this server's extension
 //   GET  /v1/models            {"object":"list","data":[{"id":<model file name>, ...}]}
 //   GET  /health               scheduler counters (JSON)
 //   GET  /v1/metrics           the same counters in Prometheus text format
@@ -317,6 +323,143 @@ struct Api {
         }
     }
 
+    static std::string base64(const unsigned char *p, size_t n) {
+        static const char *tab = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";
+        std::string out;
+        out.reserve((n + 2) / 3 * 4);
+        for (size_t i = 0; i < n; i += 3) {
+            const unsigned v = (unsigned)p[i] << 16 | (i + 1 < n ? (unsigned)p[i + 1] << 8 : 0u) | (i + 2 < n ? (unsigned)p[i + 2] : 0u);
+            out.push_back(tab[v >> 18 & 63]);
+            out.push_back(tab[v >> 12 & 63]);
+            out.push_back(i + 1 < n ? tab[v >> 6 & 63] : '=');
+            out.push_back(i + 2 < n ? tab[v & 63] : '=');
+        }
+        return out;
+    }
+
+    // One item of "input" as token ids: a string is tokenised as a raw prompt (BOS as for any
+    // prompt, no chat template), a list of token ids is taken as it is. Throws what the 400 says.
+    std::vector<int> embeddingInput(const Value &item, size_t index) {
+        const std::string at = "input[" + std::to_string(index) + "]";
+        const int vocab = (int)sess->header().vocabSize;
+        std::vector<int> ids;
+        if (item.isString()) {
+            if (item.asString().empty()) throw std::runtime_error(at + " is an empty string");
+            ids = sess->tokenizer().encode(item.asString(), true, false);
+        } else if (item.isArray()) {
+            if (item.size() == 0) throw std::runtime_error(at + " is an empty list of token ids");
+            for (const Value &t : item.items()) {
+                if (!t.isNumber() || t.asNumber() != std::floor(t.asNumber()) || t.asNumber() < 0 || t.asNumber() >= vocab)
+                    throw std::runtime_error(at + " holds a token id outside 0.." + std::to_string(vocab - 1));
+                ids.push_back((int)t.asNumber());
+            }
+        } else {
+            throw std::runtime_error(at + " must be a string or a list of token ids");
+        }
+        if (ids.empty()) throw std::runtime_error(at + " has no tokens");
+        if (ids.size() > sess->header().seqLen)
+            throw std::runtime_error(at + " has " + std::to_string(ids.size()) + " tokens, the context holds " +
+                                     std::to_string(sess->header().seqLen));
+        return ids;
+    }
+
+    // POST /v1/embeddings: every item of "input" becomes one embedding request; they are submitted
+    // together, so they batch with each other and with the chat traffic.
+    void embeddings(const HttpRequest &req, HttpConnection &conn) {
+        constexpr size_t kMaxItems = 2048;
+        std::vector<std::vector<int>> inputs;
+        GenParams p;
+        p.embed = EmbedMode::MEAN;
+        p.maxTokens = 0;
+        bool b64 = false;
+        try {
+            const Value body = Value::parse(req.body);
+            if (!body.isObject()) throw std::runtime_error("a JSON object is required");
+            const Value &in = body["input"];
+            if (in.isString()) {
+                inputs.push_back(embeddingInput(in, 0));
+            } else if (in.isArray()) {
+                if (in.size() == 0) throw std::runtime_error("input is empty");
+                if (in.items()[0].isNumber()) {  // one list of token ids
+                    inputs.push_back(embeddingInput(in, 0));
+                } else {
+                    if (in.size() > kMaxItems) throw std::runtime_error("input holds at most " + std::to_string(kMaxItems) + " items");
+                    const bool strings = in.items()[0].isString();
+                    for (size_t i = 0; i < in.size(); i++) {
+                        if (in.items()[i].isString() != strings) throw std::runtime_error("input mixes strings and token lists");
+                        inputs.push_back(embeddingInput(in.items()[i], i));
+                    }
+                }
+            } else {
+                throw std::runtime_error("input required: a string, a list of strings, a list of token ids or a list of such lists");
+            }
+            if (!body["dimensions"].isNull()) throw std::runtime_error("dimensions is not supported");
+            const Value &ef = body["encoding_format"], &pl = body["pooling"];
+            if (!ef.isNull()) {
+                if (!ef.isString() || (ef.asString() != "float" && ef.asString() != "base64"))
+                    throw std::runtime_error("encoding_format must be \"float\" or \"base64\"");
+                b64 = ef.asString() == "base64";
+            }
+            if (!pl.isNull()) {
+                if (!pl.isString() || (pl.asString() != "mean" && pl.asString() != "last"))
+                    throw std::runtime_error("pooling must be \"mean\" or \"last\"");
+                if (pl.asString() == "last") p.embed = EmbedMode::LAST;
+            }
+        } catch (const std::exception &e) {
+            Value err = Value::object();
+            err.set("error", std::string("Invalid request: ") + e.what());
+            conn.writeJson(400, err.dump());
+            return;
+        }
+        std::vector<std::shared_ptr<GenRequest>> reqs;
+        struct CancelOnExit {  // the client went away, or one item failed: drop the rest
+            std::vector<std::shared_ptr<GenRequest>> &rs;
+            ~CancelOnExit() {
+                for (auto &r : rs) r->cancel();
+            }
+        } cancelGuard{reqs};
+        size_t promptTokens = 0;
+        for (auto &ids : inputs) {
+            promptTokens += ids.size();
+            reqs.push_back(sched->submit(std::move(ids), p));
+        }
+        Value data = Value::array();
+        for (size_t i = 0; i < reqs.size(); i++) {
+            GenRequest &r = *reqs[i];
+            r.wait();
+            if (r.finishReason != "stop") {
+                Value err = Value::object();
+                err.set("error", r.error.empty() ? "embedding failed" : r.error);
+                conn.writeJson(500, err.dump());
+                return;
+            }
+            Value e = Value::object();
+            e.set("object", "embedding");
+            e.set("index", (int)i);
+            if (b64) {
+                e.set("embedding", base64(reinterpret_cast<const unsigned char *>(r.embedding.data()), r.embedding.size() * sizeof(float)));
+            } else {
+                Value v = Value::array();
+                for (float x : r.embedding) v.push((double)x);
+                e.set("embedding", v);
+            }
+            data.push(e);
+        }
+        Value resp = Value::object();
+        resp.set("object", "list");
+        resp.set("data", data);
+        resp.set("model", model);
+        Value usage = Value::object();
+        usage.set("prompt_tokens", (double)promptTokens);
+        usage.set("total_tokens", (double)promptTokens);
+        resp.set("usage", usage);
+        conn.writeJson(200, resp.dump());
+        if (logLevel() >= 1) {
+            std::printf("🔷 embeddings: %zu inputs, %zu prompt tokens\n", reqs.size(), promptTokens);
+            std::fflush(stdout);
+        }
+    }
+
     void models(const HttpRequest &, HttpConnection &conn) {
         Value m = Value::object();
         m.set("id", model);
@@ -358,6 +501,7 @@ struct Api {
                (double)s.logitProcRequests);
         metric("dllama_logit_filter_requests_total", "counter", "Finished requests with top_k or min_p on.",
                (double)s.logitFilterRequests);
+        metric("dllama_embedding_requests_total", "counter", "Finished embedding requests.", (double)s.embeddingRequests);
         metric("dllama_active_requests", "gauge", "Requests holding a KV slot.", (double)s.active);
         metric("dllama_queued_requests", "gauge", "Requests waiting for a KV slot.", (double)s.queued);
         metric("dllama_kv_slots", "gauge", "KV-cache slots (max concurrent sequences).", (double)sess->nSlots());
@@ -390,6 +534,7 @@ struct Api {
         v.set("prefix_evictions", (double)s.prefixEvictions);
         v.set("logit_proc_requests", (double)s.logitProcRequests);
         v.set("logit_filter_requests", (double)s.logitFilterRequests);
+        v.set("embedding_requests", (double)s.embeddingRequests);
         conn.writeJson(200, v.dump());
     }
 };
@@ -461,6 +606,7 @@ int main(int argc, char **argv) {
         api.sched = &sched;
         HttpServer server(args.port);
         server.route("POST", "/v1/chat/completions", [&](const HttpRequest &r, HttpConnection &c) { api.complete(r, c); });
+        server.route("POST", "/v1/embeddings", [&](const HttpRequest &r, HttpConnection &c) { api.embeddings(r, c); });
         server.route("GET", "/v1/models", [&](const HttpRequest &r, HttpConnection &c) { api.models(r, c); });
         server.route("GET", "/health", [&](const HttpRequest &r, HttpConnection &c) { api.health(r, c); });
         server.route("GET", "/v1/metrics",

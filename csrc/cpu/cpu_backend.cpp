@@ -165,6 +165,12 @@ class CpuBackend : public Backend {
         for (int i = 0; i < n; i++) out[i] = (int)ids[i];
     }
 
+    void forwardHidden(int n, const int *tokens, const int *positions, const int *slots, float *hidden, bool withLogits,
+                       float *logits) override {
+        forwardImpl(n, tokens, positions, slots, logits, hidden, withLogits);
+    }
+    const float *finalNormWeights() const override { return rmsFinal_; }
+
     // rank-local: a slot's positions [0, n) are contiguous per layer ([layer][slot][pos][kv0])
     void copyPrefix(int src, int dst, int n) override {
         DL_CHECK(src != dst, "copyPrefix: source and destination slot are the same");
@@ -272,7 +278,10 @@ class CpuBackend : public Backend {
         return &vcache_[(((u64)layer * cfg_.nSlots + slot) * h_.seqLen + pos) * plan_.kv0];
     }
 
-    void forwardImpl(int n, const int *tokens, const int *positions, const int *slots, float *logitsOut) {
+    // hiddenOut (may be null): the rows' final residual [n][dim], before the final norm. withLogits
+    // false: no final norm, classifier or logits gather on any rank (an all-embedding forward).
+    void forwardImpl(int n, const int *tokens, const int *positions, const int *slots, float *logitsOut,
+                     float *hiddenOut = nullptr, bool withLogits = true) {
         Timer timer;
         double syncMs = 0;
         const u32 dim = h_.dim, hs = plan_.headSize;
@@ -377,6 +386,14 @@ class CpuBackend : public Backend {
             for (u64 i = 0; i < (u64)n * dim; i++) x[i] += y[i];
         }
 
+        if (hiddenOut) std::memcpy(hiddenOut, x.data(), x.size() * sizeof(float));
+        if (!withLogits) {
+            stats_.syncMs = syncMs;
+            stats_.xchgMs = syncMs;
+            stats_.computeMs = timer.elapsedMs() - syncMs;
+            comm_->stats(stats_.sentBytes, stats_.recvBytes);
+            return;
+        }
         // final norm + vocab-sharded classifier, gathered to the root
         std::vector<float> lg((u64)n * p.vocab0);
         const std::vector<float *> lR = rows(lg, p.vocab0);

@@ -154,19 +154,12 @@ void HipEngineImpl::forwardArgmax(int n, const int *tokens, const int *positions
 void HipEngineImpl::forwardSample(int n, const int *tokens, const int *positions, const int *slots,
                                   const SampleSpec *specs, int *out) {
     Timer t;
-    std::vector<LogitProc> procs;
-    const GraphKind kind = beginProcs(n, slots, specs, procs);
-    const bool proc = kind != GraphKind::SAMPLE;
-    setInputs(n, tokens, positions, slots, specs, 0, proc ? procRows_.data() : nullptr,
-              kind == GraphKind::SAMPLE_PROC_FILTER ? filterRows_.data() : nullptr);
-    if (proc) enqueueProcState(n, slots, procs);
-    runGraph(n, kind);
-    enqueueLogprobs(n, specs);
-    DL_HIP(hipMemcpyAsync(hIds_, dIds_, n * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    enqueueSampled(n, tokens, positions, slots, specs);
     syncAndCheckComm();
     inputsInFlight_ = false;
     std::memcpy(out, hIds_, n * sizeof(int));
     readLogprobs();
+    readPooled();
     stats_.computeMs = t.elapsedMs();
     setSyncStats(readSync(hSync_, false), stats_.computeMs);
 }
@@ -177,15 +170,7 @@ void HipEngineImpl::launchIds(int n, const int *tokens, const int *positions, co
                               const SampleSpec *specs) {
     DL_CHECK(pendingN_ == 0, "launchIds: the previous forward was not collected");
     Timer t;
-    std::vector<LogitProc> procs;
-    const GraphKind kind = beginProcs(n, slots, specs, procs);
-    const bool proc = kind != GraphKind::SAMPLE;
-    setInputs(n, tokens, positions, slots, specs, 0, proc ? procRows_.data() : nullptr,
-              kind == GraphKind::SAMPLE_PROC_FILTER ? filterRows_.data() : nullptr);
-    if (proc) enqueueProcState(n, slots, procs);
-    runGraph(n, specs ? kind : GraphKind::ARGMAX);
-    enqueueLogprobs(n, specs);
-    DL_HIP(hipMemcpyAsync(hIds_, dIds_, n * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    enqueueSampled(n, tokens, positions, slots, specs);
     pendingN_ = n;
     stats_.computeMs = t.elapsedMs();  // host enqueue time; the sync is read when collected
 }
@@ -198,7 +183,134 @@ void HipEngineImpl::collectIds(int *out) {
     inputsInFlight_ = false;
     std::memcpy(out, hIds_, n * sizeof(int));
     readLogprobs();
+    readPooled();
     setSyncStats(readSync(hSync_, false), -1);
+}
+
+// A forward whose result is one id per row (forwardSample, launchIds; specs null: argmax), enqueued up
+// to the D2H copy of the ids. With a pooling handed over (Backend::setPooling) and a taking-part row:
+// an all-embedding forward (no row draws) runs the EMBED kind, whose ids are all -1; any other keeps
+// its kind and the graphs it always replayed, and launchPool follows the token pick on the same
+// stream - not inside the graph, like launchLogprobs.
+void HipEngineImpl::enqueueSampled(int n, const int *tokens, const int *positions, const int *slots,
+                                   const SampleSpec *specs) {
+    std::vector<LogitProc> procs;
+    GraphKind kind = beginProcs(n, slots, specs, procs);
+    const std::vector<PoolSpec> pool = beginPooling(n, positions, slots);
+    if (!pool.empty()) {
+        if (!specs) throw Error("launchIds: pooling needs a sampled forward (specs)");
+        if (noRowDraws(n, specs))
+            kind = GraphKind::EMBED;
+        else  // (a single row takes paths that keep the residual elsewhere: setupPrenorm)
+            DL_CHECK(n >= 2, "pooling: a pooled row that draws needs a forward of its own kind with >= 2 rows");
+    }
+    const bool proc = kind == GraphKind::SAMPLE_PROC || kind == GraphKind::SAMPLE_PROC_FILTER;
+    setInputs(n, tokens, positions, slots, specs, 0, proc ? procRows_.data() : nullptr,
+              kind == GraphKind::SAMPLE_PROC_FILTER ? filterRows_.data() : nullptr);
+    if (proc) enqueueProcState(n, slots, procs);
+    stagePooling(n, slots, pool);
+    runGraph(n, specs ? kind : GraphKind::ARGMAX);
+    if (kind == GraphKind::EMBED) {
+        logprobReq_.clear();
+        DL_HIP(hipMemsetAsync(dIds_, 0xff, n * sizeof(int), stream_));  // no row drew: ids -1
+    } else {
+        enqueueLogprobs(n, specs);
+        if (poolStaged_) {
+            enqueuePool(n);
+            DL_HIP(hipGetLastError());
+        }
+    }
+    enqueuePoolReadback();
+    DL_HIP(hipMemcpyAsync(hIds_, dIds_, n * sizeof(int), hipMemcpyDeviceToHost, stream_));
+}
+
+// The all-embedding forward on its own: the root pools (a setPooling precedes it), the other ranks
+// run the same layers and skip wcls and the logits exchange with it.
+void HipEngineImpl::forwardEmbed(int n, const int *tokens, const int *positions, const int *slots) {
+    Timer t;
+    DL_CHECK(pendingN_ == 0, "forwardEmbed: the previous forward was not collected");
+    const std::vector<PoolSpec> pool = beginPooling(n, positions, slots);
+    if (rank() == 0 && pool.empty()) throw Error("forwardEmbed: no row takes part (setPooling)");
+    logprobReq_.clear();
+    setInputs(n, tokens, positions, slots);
+    stagePooling(n, slots, pool);
+    runGraph(n, GraphKind::EMBED);
+    enqueuePoolReadback();
+    syncAndCheckComm();
+    inputsInFlight_ = false;
+    readLogprobs();
+    readPooled();
+    stats_.computeMs = t.elapsedMs();
+    setSyncStats(readSync(hSync_, false), stats_.computeMs);
+}
+
+std::vector<PoolSpec> HipEngineImpl::beginPooling(int n, const int *positions, const int *slots) {
+    if (pendingPool_.empty()) return {};
+    std::vector<PoolSpec> pool = takePooling(n, positions, slots);
+    if (rank() != 0) pool.clear();  // the final residual is replicated: the root pools
+    return pool;
+}
+
+void HipEngineImpl::stagePooling(int n, const int *slots, const std::vector<PoolSpec> &pool) {
+    poolStaged_ = false;
+    poolDone_.clear();
+    if (pool.empty()) return;
+    DL_CHECK(h_.dim % 4 == 0, "pooling needs dim % 4 == 0");
+    int *idx = reinterpret_cast<int *>(hPoolRows_ + n);
+    for (int b = 0; b < n; b++) {
+        const PoolSpec &p = pool[b];
+        hipk::PoolRow r{};
+        r.slot = slots[b];
+        r.flags = !p.active ? 0
+                            : hipk::kPoolTake | (p.first ? hipk::kPoolFirst : 0) | (p.last ? hipk::kPoolLast : 0) |
+                                  (p.mode == PoolMode::LAST ? hipk::kPoolModeLast : 0);
+        r.count = p.count;
+        hPoolRows_[b] = r;
+        if (p.active && p.last) poolDone_.push_back(slots[b]);
+    }
+    hipk::poolPlan(hPoolRows_, idx, n);
+    DL_HIP(hipMemcpyAsync(dPoolRows_, hPoolRows_, (size_t)n * (sizeof(hipk::PoolRow) + sizeof(int)),
+                          hipMemcpyHostToDevice, stream_));
+    poolStaged_ = true;
+}
+
+// The final residual of a forward of n rows: enqueueForward leaves it in dX_[1] + dY_ (the parity
+// after any number of layers), or whole in dX_[0] when the batched GEMMs fuse the residual update.
+hipk::PoolArgs HipEngineImpl::poolArgs(int n) const {
+    const bool fz = batchedPath(n) && fuseNorm(n);
+    hipk::PoolArgs a;
+    a.in = fz ? dX_[0] : dX_[1];
+    a.add = fz ? nullptr : dY_;
+    a.ld = dim();
+    a.normW = rmsFinal_;
+    a.eps = h_.normEpsilon;
+    a.dim = dim();
+    a.rows = dPoolRows_;
+    a.idx = reinterpret_cast<const int *>(dPoolRows_ + n);
+    a.scale = dPoolScale_;
+    a.acc = dPoolAcc_;
+    a.out = dPoolOut_;
+    a.part = dPoolPart_;
+    a.counters = dPoolCnt_;
+    return a;
+}
+
+void HipEngineImpl::enqueuePool(int n) {
+    ProfScope ps(this, "pool");
+    hipk::launchPool(poolArgs(n), n, stream_);
+}
+
+void HipEngineImpl::enqueuePoolReadback() {
+    for (size_t k = 0; k < poolDone_.size(); k++)
+        DL_HIP(hipMemcpyAsync(hPoolOut_ + k * h_.dim, dPoolOut_ + (size_t)poolDone_[k] * h_.dim, h_.dim * sizeof(float),
+                              hipMemcpyDeviceToHost, stream_));
+}
+
+void HipEngineImpl::readPooled() {
+    pooled_.slots = poolDone_;
+    pooled_.values.assign(hPoolOut_ ? hPoolOut_ : nullptr, hPoolOut_ ? hPoolOut_ + poolDone_.size() * h_.dim : nullptr);
+    poolDone_.clear();
+    poolStaged_ = false;
 }
 
 // The logit processors handed over for this forward (Backend::setLogitProcs). Ranks other than the
@@ -400,13 +512,38 @@ double HipEngineImpl::decodeGreedyBatch(int steps, int nSeq, const int *tokens, 
 }
 
 void HipEngineImpl::profileForward(int n, const int *tokens, const int *positions, const int *slots) {
-    setInputs(n, tokens, positions, slots);
+    const std::map<std::string, double> agg = profileClasses(n, tokens, positions, slots, nullptr, nullptr);
+    double total = 0;
+    for (auto &kv : agg) total += kv.second;
+    std::printf("⏱️  per-kernel-class device time (eager, batch %d):\n", n);
+    for (auto &kv : agg) std::printf("   %-14s %8.3f ms (%5.1f%%)\n", kv.first.c_str(), kv.second, 100.0 * kv.second / total);
+    std::printf("   %-14s %8.3f ms\n", "total", total);
+}
+
+std::map<std::string, double> HipEngineImpl::profileClasses(int n, const int *tokens, const int *positions,
+                                                            const int *slots, const SampleSpec *specs,
+                                                            const PoolSpec *pool) {
+    DL_CHECK(plan_.nRanks == 1, "profileClasses: single-process engines");
+    GraphKind kind = GraphKind::LOGITS;
+    std::vector<PoolSpec> pl;
+    if (specs) {
+        kind = GraphKind::SAMPLE;
+        if (pool) setPooling(n, pool);
+        pl = beginPooling(n, positions, slots);
+        if (!pl.empty() && noRowDraws(n, specs)) kind = GraphKind::EMBED;
+        DL_CHECK(pl.empty() || kind == GraphKind::EMBED || n >= 2, "pooling: a pooled row that draws needs >= 2 rows");
+    }
+    setInputs(n, tokens, positions, slots, specs);
+    stagePooling(n, slots, pl);
     profile_ = true;
     profTimes_.clear();
-    enqueueForward(n, GraphKind::LOGITS);
+    enqueueForward(n, kind);
+    if (kind != GraphKind::EMBED && poolStaged_) enqueuePool(n);
     DL_HIP(hipStreamSynchronize(stream_));
     inputsInFlight_ = false;
     profile_ = false;
+    poolDone_.clear();
+    poolStaged_ = false;
     std::map<std::string, double> agg;
     for (auto &p : profTimes_) {
         float ms = 0;
@@ -415,12 +552,8 @@ void HipEngineImpl::profileForward(int n, const int *tokens, const int *position
         (void)hipEventDestroy(p.second.first);
         (void)hipEventDestroy(p.second.second);
     }
-    double total = 0;
-    for (auto &kv : agg) total += kv.second;
-    std::printf("⏱️  per-kernel-class device time (eager, batch %d):\n", n);
-    for (auto &kv : agg) std::printf("   %-14s %8.3f ms (%5.1f%%)\n", kv.first.c_str(), kv.second, 100.0 * kv.second / total);
-    std::printf("   %-14s %8.3f ms\n", "total", total);
     profTimes_.clear();
+    return agg;
 }
 
 // Wait for the stream, then turn a tensor-parallel transport failure into an exception (the
@@ -483,6 +616,7 @@ void HipEngineImpl::accountForward(int n, GraphKind kind, int times) {
     if (kind == GraphKind::ARGMAX || kind == GraphKind::CHAIN) {  // (value, index) winners only
         sent += peers * (u64)n * 8;
         recv += peers * (u64)n * 8;
+    } else if (kind == GraphKind::EMBED) {  // nothing but the residual updates crosses the links
     } else if (rank() == 0) {  // LOGITS / SAMPLE: the vocab slices go to the root
         recv += peers * slice;
     } else {

@@ -2,7 +2,9 @@
 // one hipGraph per batch size (replaces the reference's per-op executor + barrier).
 #pragma once
 
+#include <map>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "../runtime/backend.h"
@@ -24,6 +26,12 @@ class HipEngine : public Backend {
     virtual size_t deviceBytes() const = 0;
     // Run one forward eagerly with a per-kernel-class timing breakdown (ms) printed to stdout.
     virtual void profileForward(int n, const int *tokens, const int *positions, const int *slots) = 0;
+    // The same eager forward, returned as device ms per kernel class. specs null: host logits; else
+    // the sampled forward of these specs, with `pool` (may be null) as its Backend::setPooling - an
+    // all-embedding forward then runs its own schedule. Single-process engines.
+    virtual std::map<std::string, double> profileClasses(int n, const int *tokens, const int *positions,
+                                                         const int *slots, const SampleSpec *specs,
+                                                         const PoolSpec *pool) = 0;
     // Tensor parallel: whether the partial-sum exchange runs fused in the wo / w2 GEMV tails (it is
     // switched off when a launch's grid would not be fully co-resident), and the largest grid of
     // such a launch (checked against the device's occupancy at construction).
@@ -83,4 +91,8 @@ namespace dl {
 // attnBlocks (optional): per rank, whether its single decode rows run the fused attention block.
 std::vector<float> simulateTensorParallel(const EngineConfig &cfg, int world, const std::vector<int> &tokens,
                                           std::vector<int> *attnBlocks = nullptr);
+// The same ranks embedding `tokens` (positions 0.., slot 0) in all-embedding forwards of `chunk` rows:
+// the root's pooled vector [dim].
+std::vector<float> simulateTensorParallelEmbed(const EngineConfig &cfg, int world, const std::vector<int> &tokens,
+                                               int chunk, PoolMode mode);
 }  // namespace dl

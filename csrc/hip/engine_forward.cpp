@@ -796,7 +796,9 @@ void HipEngineImpl::enqueueForward(int n, GraphKind kind) {
     f.fz = f.bat && fuseNorm(n);
     f.blk = blockOn_ && buckets_[bucket_].block && n == 1 && !f.bat;
     const bool row = n == 1 && !f.bat && !f.blk;  // a single decode row outside the block
-    f.pre = prenormOn_ && row;
+    // (an all-embedding forward keeps the norm-prologue schedule, whose final residual is the
+    //  dX_ / dY_ pair the pooling kernel reads; the pre-normalized hand-off holds Q80 images instead)
+    f.pre = prenormOn_ && row && kind != GraphKind::EMBED;
     f.woAttn = woAttnOn_ && row && buckets_[bucket_].maxLen <= woAttnMaxLen_;
     // one greedy decode row: the logits GEMV ends in the row's argmax (EPI_ARGMAX: no logits
     // written, no argmax launch; under TP the winners trade over the fused exchange's region)
@@ -836,11 +838,16 @@ void HipEngineImpl::enqueueForward(int n, GraphKind kind) {
         enqueueW2(f, l, cur);
         if (sepReduce) allReduce(dY_, (size_t)n * dim());
     }
-    if (f.pre)
-        enqueuePrenormLayers(f, kind);
-    else
-        enqueueLogits(f, kind, cur);
-    if (!f.argTail) enqueueTokenPick(n, kind);
+    if (kind == GraphKind::EMBED) {  // no wcls, no logits exchange, no token pick on any rank
+        DL_CHECK(cur == 1, "final residual parity");  // what poolArgs reads
+        if (poolStaged_) enqueuePool(n);
+    } else {
+        if (f.pre)
+            enqueuePrenormLayers(f, kind);
+        else
+            enqueueLogits(f, kind, cur);
+        if (!f.argTail) enqueueTokenPick(n, kind);
+    }
     DL_HIP(hipGetLastError());
 }
 

@@ -73,6 +73,7 @@ class HipEngineImpl : public HipEngine {
                        int *out) override;
     void launchIds(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs) override;
     void collectIds(int *out) override;
+    void forwardEmbed(int n, const int *tokens, const int *positions, const int *slots) override;
     bool chainSupported() const override { return true; }
     void chainLaunch(int token, int pos, int slot) override;
     int chainCollect() override;
@@ -91,6 +92,8 @@ class HipEngineImpl : public HipEngine {
     void synchronize() override { DL_HIP(hipStreamSynchronize(stream_)); }
     size_t deviceBytes() const override { return deviceBytes_; }
     void profileForward(int n, const int *tokens, const int *positions, const int *slots) override;
+    std::map<std::string, double> profileClasses(int n, const int *tokens, const int *positions, const int *slots,
+                                                 const SampleSpec *specs, const PoolSpec *pool) override;
     bool tpFused() const override { return tpFused_; }
     bool attnBlock() const override { return blockOn_; }
     bool woAttn() const override { return woAttnOn_; }
@@ -105,7 +108,9 @@ class HipEngineImpl : public HipEngine {
     // forward with an active LogitProc row; every other forward takes the kinds it always took)
     // SAMPLE_PROC_FILTER: SAMPLE_PROC with the candidate filter (top_k / min_p) between the processors
     // and the draw (a forward with a row whose filter is on)
-    enum class GraphKind { LOGITS = 0, ARGMAX = 1, CHAIN = 2, SAMPLE = 3, SAMPLE_PROC = 4, SAMPLE_PROC_FILTER = 5 };
+    // EMBED: every row is a non-drawing row and one of them is pooled (Backend::setPooling): all the
+    // layers, then launchPool on the root; no wcls, no logits exchange, no token pick on any rank
+    enum class GraphKind { LOGITS = 0, ARGMAX = 1, CHAIN = 2, SAMPLE = 3, SAMPLE_PROC = 4, SAMPLE_PROC_FILTER = 5, EMBED = 6 };
 
     // engine.cpp
     void syncAndCheckComm();
@@ -414,6 +419,7 @@ class HipEngineImpl : public HipEngine {
     hipk::LogprobEntry *dLogprobs_ = nullptr, *hLogprobs_ = nullptr;
     std::vector<int> logprobReq_;  // per row of the forward in flight (empty: no row asked)
     void enqueueLogprobs(int n, const SampleSpec *specs);
+    void enqueueSampled(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs);
     void readLogprobs();
     // logit processors (Backend::setLogitProcs), root rank only: per slot the dense token counts and
     // the bias entries, the processed logits the sampler of a SAMPLE_PROC forward reads, and pinned
@@ -431,6 +437,27 @@ class HipEngineImpl : public HipEngine {
     std::vector<hipk::LogitFilterRow> filterRows_;
     uint32_t *dFilterState_ = nullptr;             // [maxBatch][kLogitFilterStateWords], zero between launches
     size_t procBytes() const;
+    // pooling (Backend::setPooling), root rank only: the forward's pool rows and their per-slot run
+    // index (hipk::poolPlan) behind one pinned staging block (free once the previous forward was
+    // collected), the rows' RMS scales, per slot the f32 accumulator, the output, the L2 norm's slice
+    // partials and the arrival counter, and a pinned row per slot finalised by the forward in flight
+    hipk::PoolRow *dPoolRows_ = nullptr, *hPoolRows_ = nullptr;  // [maxBatch] rows | [maxBatch] ints
+    float *dPoolScale_ = nullptr;                   // [maxBatch]
+    float *dPoolAcc_ = nullptr, *dPoolOut_ = nullptr;  // [nSlots][dim]
+    float *dPoolPart_ = nullptr;                    // [nSlots][kPoolMaxGroups]
+    int *dPoolCnt_ = nullptr;                       // [nSlots], zero between launches
+    float *hPoolOut_ = nullptr;                     // [min(maxBatch, nSlots)][dim]
+    std::vector<int> poolDone_;                     // slots the forward in flight finalises, by last row
+    bool poolStaged_ = false;                       // the forward being set up has a taking-part row
+    size_t poolBytes() const;
+    // the pending pooling of a forward (root; other ranks drop it): empty when no row takes part
+    std::vector<PoolSpec> beginPooling(int n, const int *positions, const int *slots);
+    // pool rows to the device, in stream order ahead of the forward (after setInputs)
+    void stagePooling(int n, const int *slots, const std::vector<PoolSpec> &pool);
+    hipk::PoolArgs poolArgs(int n) const;  // over the final residual a forward of n rows leaves
+    void enqueuePool(int n);               // launchPool, when a row was staged
+    void enqueuePoolReadback();            // the finalised slots' vectors to pinned memory
+    void readPooled();                     // after the stream sync: Backend::lastEmbeddings()
     hipk::LogitProcArgs logitProcArgs(const float *raw) const;
     // takes the pending processors of a sampled forward and returns its graph kind (SAMPLE: no row is
     // active); beginProcs fills procRows_ / filterRows_, enqueueProcState resets / uploads fresh slots

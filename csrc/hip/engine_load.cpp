@@ -22,7 +22,7 @@ void HipEngineImpl::checkFits() {
     size_t w = (size_t)h_.nLayers * (matStageBytes(p.q0 + 2 * p.kv0, h_.dim) + matStageBytes(h_.dim, p.q0) +
                                      matStageBytes(2 * p.hidden0, h_.dim) + matStageBytes(h_.dim, p.hidden0));
     w += matStageBytes(p.vocab0, h_.dim) + (size_t)h_.vocabSize * h_.dim * 4;
-    const size_t act = (size_t)cfg_.maxBatch * h_.vocabSize * 4 * 3 + ((size_t)256 << 20) + procBytes();
+    const size_t act = (size_t)cfg_.maxBatch * h_.vocabSize * 4 * 3 + ((size_t)256 << 20) + procBytes() + poolBytes();
     if (kv + w + act > freeB) {
         // the page pool that would fit (positions shared by all slots), as a hint
         const size_t perPos = (size_t)h_.nLayers * 2 * p.kv0 * (kvBf16_ ? 2 : 4);
@@ -93,6 +93,14 @@ size_t HipEngineImpl::procBytes() const {
            (size_t)cfg_.maxBatch * (h_.vocabSize * sizeof(float) + hipk::kLogitFilterStateWords * sizeof(uint32_t));
 }
 
+// Device state of the pooling kernel (root rank): per slot the accumulator, the output, the norm's
+// partials and the counter; per row of a forward the pool row, its index entry and its RMS scale.
+size_t HipEngineImpl::poolBytes() const {
+    if (rank() != 0) return 0;
+    return (size_t)cfg_.nSlots * (2 * (size_t)h_.dim * sizeof(float) + hipk::kPoolMaxGroups * sizeof(float) + sizeof(int)) +
+           (size_t)cfg_.maxBatch * (sizeof(hipk::PoolRow) + sizeof(int) + sizeof(float));
+}
+
 int HipEngineImpl::tpPasses(const DevMat &m, int bc) const {
     int passes = passesFor(m, hipk::EPI_STORE_TP, bc);
     if (tpVec_.q80)  // whole Q80 blocks of 32 rows per workgroup
@@ -127,6 +135,19 @@ void HipEngineImpl::allocBuffers() {
         DL_HIP(hipMemsetAsync(dProcNBias_, 0, S * sizeof(int), stream_));
         dFilterState_ = dalloc<uint32_t>((size_t)MB * hipk::kLogitFilterStateWords);
         DL_HIP(hipMemsetAsync(dFilterState_, 0, (size_t)MB * hipk::kLogitFilterStateWords * sizeof(uint32_t), stream_));
+    }
+    if (rank() == 0) {  // pooling: the root pools
+        const size_t S = cfg_.nSlots, rowBytes = sizeof(hipk::PoolRow) + sizeof(int);
+        dPoolRows_ = reinterpret_cast<hipk::PoolRow *>(dalloc<uint8_t>((size_t)MB * rowBytes));
+        hPoolRows_ = reinterpret_cast<hipk::PoolRow *>(halloc<uint8_t>((size_t)MB * rowBytes));
+        dPoolScale_ = dalloc<float>(MB);
+        dPoolAcc_ = dalloc<float>(S * h_.dim);
+        dPoolOut_ = dalloc<float>(S * h_.dim);
+        dPoolPart_ = dalloc<float>(S * hipk::kPoolMaxGroups);
+        dPoolCnt_ = dalloc<int>(S);
+        hPoolOut_ = halloc<float>(std::min<size_t>(MB, S) * h_.dim);
+        DL_HIP(hipMemsetAsync(dPoolAcc_, 0, S * h_.dim * sizeof(float), stream_));
+        DL_HIP(hipMemsetAsync(dPoolCnt_, 0, S * sizeof(int), stream_));
     }
     hIds_ = halloc<int>(MB);
     hErr_ = halloc<int>(2);

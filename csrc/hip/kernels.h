@@ -665,6 +665,55 @@ struct LogitFilterArgs {
 };
 void launchLogitFilter(const LogitFilterArgs &a, int B, hipStream_t s);
 
+// Pooled, L2-normalised final hidden states (embeddings) of the rows of a forward, per KV slot. For a
+// row b that takes part (kPoolTake), slot s = rows[b].slot:
+//   xs   = in[b] + add[b]                           (add may be null)
+//   h    = normW * (xs / sqrt(sum(xs^2) / dim + eps))   (the vector the logits matmul consumes)
+//   mean: acc[s] = first ? h : acc[s] + h           (one f32 add per element per row, in row order)
+//   last: acc[s] = h for the row flagged kPoolLast
+// and at the slot's kPoolLast row, N = rows[b].count:
+//   p = mean ? acc[s] / N : acc[s];  out[s] = p / sqrt(sum(p^2))  (all zeros when the sum is 0)
+// Rows that do not take part are neither read nor written. Rows of one slot are added in the order
+// they appear in the launch, so a slot's result is bitwise the same however its rows are split over
+// launches and whatever other rows and slots share them. Two kernels: per taking-part row the RMS
+// scale (one workgroup per row, fixed-order reduction), then grid (poolGroups(dim), B) in which the
+// workgroups of a slot's first row of the launch (kPoolHead) walk the slot's rows of this launch
+// (idx[start .. start + len)), each owning a slice of dim in 16-byte accesses; the L2 norm's slice
+// partials go to `part` and the slot's last arriver (splitArrive) sums them in workgroup order and
+// writes out. No float atomics in memory. `counters` must be zero-initialised once.
+constexpr int kPoolTake = 1, kPoolFirst = 2, kPoolLast = 4, kPoolModeLast = 8, kPoolHead = 16;
+constexpr int kPoolMaxGroups = 16;
+struct PoolRow {
+    int slot;
+    int flags;
+    int count;   // N, read at the kPoolLast row
+    int start;   // kPoolHead rows (poolPlan): the slot's rows of this launch are idx[start .. start + len)
+    int len;
+    int pad[3];
+};
+int poolGroups(int dim);
+// Host: fills flags' kPoolHead, start and len of rows[0, B) and idx[0, B) from the rows' slot and
+// kPoolTake / First / Last / ModeLast flags; returns the number of taking-part rows. Throws when a
+// slot's kPoolFirst (kPoolLast) row is not its first (last) taking-part row of the launch, its rows
+// disagree on the mode, or a kPoolLast row has count < 1.
+int poolPlan(PoolRow *rows, int *idx, int B);
+struct PoolArgs {
+    const float *in = nullptr;     // [B][ld]
+    const float *add = nullptr;    // [B][ld] or null
+    int ld = 0;
+    const float *normW = nullptr;  // [dim]
+    float eps = 0.f;
+    int dim = 0;                   // multiple of 4
+    const PoolRow *rows = nullptr; // [B]
+    const int *idx = nullptr;      // [B]
+    float *scale = nullptr;        // [B] scratch: the rows' 1 / rms
+    float *acc = nullptr;          // [nSlots][dim]
+    float *out = nullptr;          // [nSlots][dim]
+    float *part = nullptr;         // [nSlots][kPoolMaxGroups] scratch
+    int *counters = nullptr;       // [nSlots]
+};
+void launchPool(const PoolArgs &a, int B, hipStream_t s);
+
 // Round-trip f32 partial sums through Q80 blocks in place (the reference's ZQ cast before the
 // exchange) - used ahead of a plain all-reduce when the fused exchange is not available.
 void launchQ80Roundtrip(float *x, size_t n, hipStream_t s);

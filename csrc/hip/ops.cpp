@@ -1389,6 +1389,95 @@ void benchLogitProc(int B, int vocab, int nBias, int iters, double &procUs, doub
     (void)hipEventDestroy(e1);
 }
 
+void pool(const std::vector<PoolLaunch> &launches, int dim, int nSlots, const std::vector<float> &normW, float eps,
+          std::vector<float> &out, std::vector<float> &acc) {
+    DL_CHECK(dim >= 4 && dim % 4 == 0 && nSlots >= 1 && normW.size() == (size_t)dim, "pool: dim % 4 == 0, one weight per element");
+    DL_CHECK(out.size() == (size_t)nSlots * dim && acc.size() == out.size(), "pool: out / acc are [nSlots][dim]");
+    Scratch sc;
+    hipk::PoolArgs g;
+    g.ld = g.dim = dim;
+    g.normW = sc.upload(normW);
+    g.eps = eps;
+    g.acc = sc.upload(acc);
+    g.out = sc.upload(out);
+    g.part = sc.alloc<float>((size_t)nSlots * hipk::kPoolMaxGroups);
+    g.counters = sc.alloc<int>(nSlots);  // (alloc zero-fills)
+    for (const PoolLaunch &l : launches) {
+        const int B = (int)l.slots.size();
+        DL_CHECK(B >= 1 && l.x.size() == (size_t)B * dim && (l.add.empty() || l.add.size() == l.x.size()) &&
+                     l.flags.size() == (size_t)B && l.counts.size() == (size_t)B, "pool: launch sizes");
+        std::vector<hipk::PoolRow> rows(B);
+        std::vector<int> idx(B, 0);
+        for (int b = 0; b < B; b++) {
+            DL_CHECK(!(l.flags[b] & hipk::kPoolTake) || (l.slots[b] >= 0 && l.slots[b] < nSlots), "pool: slot out of range");
+            rows[b] = hipk::PoolRow{l.slots[b], l.flags[b] & 15, l.counts[b], 0, 0, {0, 0, 0}};
+        }
+        if (hipk::poolPlan(rows.data(), idx.data(), B) == 0) continue;  // no row takes part: never enqueued
+        g.in = sc.upload(l.x);
+        g.add = l.add.empty() ? nullptr : sc.upload(l.add);
+        g.rows = sc.upload(rows);
+        g.idx = sc.upload(idx);
+        g.scale = sc.alloc<float>(B);
+        hipk::launchPool(g, B, sc.s);
+    }
+    sc.sync();
+    out = sc.download(g.out, out.size());
+    acc = sc.download(g.acc, acc.size());
+    for (int c : sc.download(g.counters, nSlots)) DL_CHECK(c == 0, "pool: a slot's counter is not back to zero");
+}
+
+void benchPool(int B, int dim, int slots, bool withAdd, int iters, double &poolUs, double &copyUs) {
+    DL_CHECK(B >= 1 && dim >= 4 && dim % 4 == 0 && slots >= 1 && slots <= B && iters >= 1, "bench_pool arguments");
+    Scratch sc;
+    std::vector<float> x((size_t)B * dim);
+    for (size_t i = 0; i < x.size(); i++) x[i] = (float)((i * 2654435761u >> 8) & 1023) / 512.f - 1.f;
+    std::vector<hipk::PoolRow> rows(B);
+    std::vector<int> idx(B, 0);
+    const int per = (B + slots - 1) / slots;
+    for (int b = 0; b < B; b++) {
+        const int s = b / per, i = b % per, n = std::min(per, B - s * per);
+        rows[b] = hipk::PoolRow{s, hipk::kPoolTake | (i == 0 ? hipk::kPoolFirst : 0) | (i == n - 1 ? hipk::kPoolLast : 0), n, 0, 0,
+                                {0, 0, 0}};
+    }
+    hipk::poolPlan(rows.data(), idx.data(), B);
+    hipk::PoolArgs g;
+    g.ld = g.dim = dim;
+    g.normW = sc.upload(std::vector<float>(dim, 1.f));
+    g.eps = 1e-5f;
+    g.in = sc.upload(x);
+    g.add = withAdd ? sc.upload(x) : nullptr;
+    g.rows = sc.upload(rows);
+    g.idx = sc.upload(idx);
+    g.scale = sc.alloc<float>(B);
+    g.acc = sc.alloc<float>((size_t)slots * dim);
+    g.out = sc.alloc<float>((size_t)slots * dim);
+    g.part = sc.alloc<float>((size_t)slots * hipk::kPoolMaxGroups);
+    g.counters = sc.alloc<int>(slots);
+    float *dst = sc.alloc<float>((size_t)B * dim * (withAdd ? 2 : 1));
+    hipEvent_t e0, e1;
+    DL_HIP(hipEventCreate(&e0));
+    DL_HIP(hipEventCreate(&e1));
+    auto timed = [&](auto launch) {
+        for (int i = 0; i < 5; i++) launch();
+        DL_HIP(hipEventRecord(e0, sc.s));
+        for (int i = 0; i < iters; i++) launch();
+        DL_HIP(hipEventRecord(e1, sc.s));
+        DL_HIP(hipEventSynchronize(e1));
+        float ms = 0;
+        DL_HIP(hipEventElapsedTime(&ms, e0, e1));
+        return (double)ms * 1000.0 / iters;
+    };
+    const size_t bytes = (size_t)B * dim * sizeof(float);
+    copyUs = timed([&] {
+        DL_HIP(hipMemcpyAsync(dst, g.in, bytes, hipMemcpyDeviceToDevice, sc.s));
+        if (withAdd) DL_HIP(hipMemcpyAsync(dst + (size_t)B * dim, g.add, bytes, hipMemcpyDeviceToDevice, sc.s));
+    });
+    poolUs = timed([&] { hipk::launchPool(g, B, sc.s); });
+    sc.sync();
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+}
+
 namespace {
 // spec / filter rows and the scratch of a LogitFilterArgs
 hipk::LogitFilterArgs logitFilterArgs(Scratch &sc, int B, int vocab, const std::vector<float> &temps,

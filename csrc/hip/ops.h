@@ -245,6 +245,22 @@ std::vector<uint32_t> logitProcCount(const std::vector<uint32_t> &counts, int nS
 // between two events, after a warm-up.
 void benchLogitProc(int B, int vocab, int nBias, int iters, double &procUs, double &countUs);
 
+// launchPool, one launch per entry of `launches` on the same per-slot state (accumulators, outputs,
+// counters), in order. A launch holds B rows x[B][dim] (+ add[B][dim], may be empty); row b belongs
+// to slots[b] and flags[b] carries kPoolTake / kPoolFirst / kPoolLast / kPoolModeLast (kernels.h),
+// counts[b] the request's row count at its last row. out / acc [nSlots][dim] come in as the buffers'
+// initial contents (sentinels) and go out as the launches left them; every slot's counter must be
+// back to zero.
+struct PoolLaunch {
+    std::vector<float> x, add;
+    std::vector<int> slots, flags, counts;
+};
+void pool(const std::vector<PoolLaunch> &launches, int dim, int nSlots, const std::vector<float> &normW, float eps,
+          std::vector<float> &out, std::vector<float> &acc);
+// Device microseconds per launchPool over B rows of dim (+ add), `slots` requests of B / slots rows
+// each, all finalised (mean), and per device copy of the same B x dim x 4 bytes (x 2 with add).
+void benchPool(int B, int dim, int slots, bool withAdd, int iters, double &poolUs, double &copyUs);
+
 // launchLogitFilter over a copy of [B][vocab] logits. Row b: temps[b], topK[b], delta[b] (-inf: min_p
 // off), active[b]. Returns the [B][vocab] buffer after the launch; a write behind its last row, or a
 // row counter left non-zero, is an error.

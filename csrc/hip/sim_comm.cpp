@@ -184,4 +184,54 @@ std::vector<float> simulateTensorParallel(const EngineConfig &cfg0, int world, c
     return out;
 }
 
+// The embedding of `tokens` (positions 0.., slot 0) on `world` simulated ranks, prefilled in
+// all-embedding forwards of `chunk` rows: the root pools (setPooling + forwardEmbed), the other ranks
+// run forwardEmbed alone, as the workers of a session do. Returns the root's vector [dim].
+std::vector<float> simulateTensorParallelEmbed(const EngineConfig &cfg0, int world, const std::vector<int> &tokens,
+                                               int chunk, PoolMode mode) {
+    DL_CHECK(!tokens.empty() && chunk >= 1, "simulate_tp_embed arguments");
+    SimShared sh(world);
+    std::vector<std::unique_ptr<SimComm>> comms;
+    std::vector<std::unique_ptr<HipEngine>> engines;
+    EngineConfig cfg = cfg0;
+    cfg.useGraphs = false;  // host-staged collectives cannot be captured
+    for (int r = 0; r < world; r++) {
+        comms.emplace_back(new SimComm(&sh, r));
+        engines.push_back(makeHipEngine(cfg, comms.back().get()));
+    }
+    std::vector<float> out;
+    std::vector<std::thread> th;
+    std::vector<std::string> errors(world);
+    for (int r = 0; r < world; r++) {
+        th.emplace_back([&, r] {
+            try {
+                (void)hipSetDevice(cfg.gpuIndex >= 0 ? cfg.gpuIndex : 0);
+                const int N = (int)tokens.size();
+                for (int c0 = 0; c0 < N; c0 += chunk) {
+                    const int n = std::min(chunk, N - c0);
+                    std::vector<int> pos(n), slots(n, 0);
+                    std::vector<PoolSpec> pool(n);
+                    for (int i = 0; i < n; i++) {
+                        pos[i] = c0 + i;
+                        pool[i].active = true;
+                        pool[i].first = c0 + i == 0;
+                        pool[i].last = c0 + i == N - 1;
+                        pool[i].count = N;
+                        pool[i].mode = mode;
+                    }
+                    if (r == 0) engines[r]->setPooling(n, pool.data());
+                    engines[r]->forwardEmbed(n, &tokens[c0], pos.data(), slots.data());
+                }
+                if (r == 0) out = engines[r]->lastEmbeddings().values;
+            } catch (const std::exception &e) {
+                errors[r] = e.what();
+            }
+        });
+    }
+    for (auto &t : th) t.join();
+    for (auto &e : errors)
+        if (!e.empty()) throw Error("simulated TP rank failed: " + e);
+    return out;
+}
+
 }  // namespace dl

@@ -94,7 +94,7 @@ void exchangeAll(const std::vector<Socket *> &peers, const void *send, u64 n, co
 // ---- control protocol ------------------------------------------------------------------------
 constexpr u32 kProtoMagic = 0xD11A3355;  // "dllama MI355"
 constexpr u32 kMeshMagic = 0xD11A3356;   // worker -> worker data-plane connection
-constexpr u32 kProtoVersion = 2;         // 2: Cmd::COPY_PREFIX (a version 1 worker would ignore it)
+constexpr u32 kProtoVersion = 3;         // 2: Cmd::COPY_PREFIX, 3: Cmd::FORWARD_EMBED (an older worker would ignore them)
 constexpr u32 kAck = 23571114;           // same ACK value as the reference (nn-network.cpp:23)
 
 // RELEASE: the first n ints of the payload are KV slots whose sequences ended (paged KV cache:
@@ -104,6 +104,9 @@ constexpr u32 kAck = 23571114;           // same ACK value as the reference (nn-
 // before any other command.
 // COPY_PREFIX: a control-only command like RELEASE (Backend::copyPrefix on every rank), n = 1:
 // tokens[0] = source slot, positions[0] = positions to copy, slots[0] = destination slot.
+// FORWARD_EMBED: an all-embedding forward (Backend::forwardEmbed): the row arrays like FORWARD_ARGMAX,
+// nothing behind them. Every rank runs the layers and skips wcls and the logits exchange; the root
+// pools. A forward that mixes pooled rows with drawn ones goes out as the FORWARD_SAMPLE it is.
 enum class Cmd : u32 {
     FORWARD = 1,
     FORWARD_ARGMAX = 2,
@@ -112,7 +115,8 @@ enum class Cmd : u32 {
     FORWARD_SAMPLE = 5,
     RELEASE = 6,
     CHAIN = 7,
-    COPY_PREFIX = 8
+    COPY_PREFIX = 8,
+    FORWARD_EMBED = 9
 };
 
 struct ControlHeader {

@@ -197,6 +197,67 @@ py::tuple runLogprobs(Backend &b, const std::vector<int> &tokens, const std::vec
     return py::make_tuple(out, v, ids);
 }
 
+// Per-row pooling (Backend PoolSpec) from Python: a sequence of n entries, each None (the row takes
+// no part) or a dict with the keys "first", "last", "count" and "mode" ("mean" | "last").
+std::vector<PoolSpec> parsePool(const py::object &o, size_t n) {
+    std::vector<PoolSpec> pool;
+    if (o.is_none()) return pool;
+    const py::sequence seq = o.cast<py::sequence>();
+    DL_CHECK(seq.size() == n, "pooling: one entry (or None) per row");
+    pool.resize(n);
+    for (size_t i = 0; i < n; i++) {
+        const py::object e = seq[i];
+        if (e.is_none()) continue;
+        const py::dict d = e.cast<py::dict>();
+        PoolSpec &p = pool[i];
+        p.active = true;
+        if (d.contains("first")) p.first = d["first"].cast<bool>();
+        if (d.contains("last")) p.last = d["last"].cast<bool>();
+        if (d.contains("count")) p.count = d["count"].cast<int>();
+        if (d.contains("mode")) {
+            const std::string m = d["mode"].cast<std::string>();
+            DL_CHECK(m == "mean" || m == "last", "pooling mode: mean | last");
+            p.mode = m == "last" ? PoolMode::LAST : PoolMode::MEAN;
+        }
+    }
+    return pool;
+}
+
+// A forward with pooling (Backend::setPooling): temperatures None = an all-embedding forward
+// (forwardEmbed), else forwardSample of these rows (a row with temperature < 0 draws nothing).
+// Returns (ids, finalised slots, float32 [len(slots)][dim] vectors); see Backend::lastEmbeddings.
+py::tuple runEmbed(Backend &b, const std::vector<int> &tokens, const std::vector<int> &positions,
+                   const std::vector<int> &slots, const py::object &pooling, const py::object &temps,
+                   const py::object &topps, const py::object &coins) {
+    const size_t n = tokens.size();
+    DL_CHECK(positions.size() == n && slots.size() == n, "input lengths");
+    const std::vector<PoolSpec> pool = parsePool(pooling, n);
+    std::vector<int> out(n, -1);
+    std::vector<SampleSpec> specs;
+    if (!temps.is_none()) {
+        const std::vector<float> t = temps.cast<std::vector<float>>();
+        const std::vector<float> tp = topps.is_none() ? std::vector<float>(n, 0.f) : topps.cast<std::vector<float>>();
+        const std::vector<float> c = coins.is_none() ? std::vector<float>(n, 0.f) : coins.cast<std::vector<float>>();
+        DL_CHECK(t.size() == n && tp.size() == n && c.size() == n, "one (temperature, topp, coin) per row");
+        specs.resize(n);
+        for (size_t i = 0; i < n; i++) specs[i] = SampleSpec{t[i], tp[i], c[i], 0.f};
+    }
+    PooledSlots done;
+    {
+        py::gil_scoped_release rel;
+        if (!pool.empty()) b.setPooling((int)n, pool.data());
+        if (specs.empty())
+            b.forwardEmbed((int)n, tokens.data(), positions.data(), slots.data());
+        else
+            b.forwardSample((int)n, tokens.data(), positions.data(), slots.data(), specs.data(), out.data());
+        done = b.lastEmbeddings();
+    }
+    const size_t dim = b.header().dim;
+    py::array_t<float> v({(py::ssize_t)done.slots.size(), (py::ssize_t)dim});
+    if (!done.values.empty()) std::memcpy(v.mutable_data(), done.values.data(), done.values.size() * sizeof(float));
+    return py::make_tuple(out, done.slots, v);
+}
+
 // Device communicator owned from Python (xGMI one-shot collectives); shared with engines.
 struct PyComm {
     std::shared_ptr<DeviceComm> comm;
@@ -626,6 +687,47 @@ void bindOps(py::module_ &m) {
           },
           py::arg("batch"), py::arg("vocab"), py::arg("top_k"), py::arg("delta"), py::arg("iters") = 200,
           "(us per device copy of the logits, us per copy + launchLogitFilter, us per launchSample on the filtered rows)");
+    o.def("pool",
+          [](py::list launches, int dim, int nSlots, py::array_t<float, py::array::c_style | py::array::forcecast> normW,
+             float eps, py::array_t<float, py::array::c_style | py::array::forcecast> outInit,
+             py::array_t<float, py::array::c_style | py::array::forcecast> accInit) {
+              std::vector<ops::PoolLaunch> ls;
+              for (auto item : launches) {
+                  const py::dict d = item.cast<py::dict>();
+                  ops::PoolLaunch l;
+                  auto x = d["x"].cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+                  l.x.assign(x.data(), x.data() + x.size());
+                  if (d.contains("add") && !d["add"].is_none()) {
+                      auto a = d["add"].cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+                      l.add.assign(a.data(), a.data() + a.size());
+                  }
+                  l.slots = d["slots"].cast<std::vector<int>>();
+                  l.flags = d["flags"].cast<std::vector<int>>();
+                  l.counts = d["counts"].cast<std::vector<int>>();
+                  ls.push_back(std::move(l));
+              }
+              std::vector<float> w(normW.data(), normW.data() + normW.size());
+              std::vector<float> out(outInit.data(), outInit.data() + outInit.size());
+              std::vector<float> acc(accInit.data(), accInit.data() + accInit.size());
+              {
+                  py::gil_scoped_release rel;
+                  ops::pool(ls, dim, nSlots, w, eps, out, acc);
+              }
+              return py::make_tuple(arr(out, {(py::ssize_t)nSlots, (py::ssize_t)dim}), arr(acc, {(py::ssize_t)nSlots, (py::ssize_t)dim}));
+          },
+          py::arg("launches"), py::arg("dim"), py::arg("n_slots"), py::arg("norm_w"), py::arg("eps"), py::arg("out"),
+          py::arg("acc"), "launchPool per entry of launches on one per-slot state: (out, acc) [n_slots][dim]");
+    o.def("bench_pool",
+          [](int B, int dim, int slots, bool withAdd, int iters) {
+              double pu = 0, cu = 0;
+              {
+                  py::gil_scoped_release rel;
+                  ops::benchPool(B, dim, slots, withAdd, iters, pu, cu);
+              }
+              return py::make_tuple(pu, cu);
+          },
+          py::arg("rows"), py::arg("dim"), py::arg("slots") = 1, py::arg("add") = true, py::arg("iters") = 50,
+          "(us per launchPool, us per device copy of the same rows)");
     o.def("bench_logprobs",
           [](py::object logits, int B, int k, int iters) {
               const std::vector<float> l = vec<float>(logits);
@@ -729,6 +831,25 @@ PYBIND11_MODULE(_C, m) {
            "One row through logitFilterHost: top_k (0 or >= vocab: off), delta = min_p_delta(T, min_p) (-inf: off).");
     co.def("min_p_delta", &minPDelta, py::arg("temperature"), py::arg("min_p"),
            "T * log(min_p) as float32 (-inf for min_p <= 0): the distance below the row maximum that min_p keeps.");
+    co.def("pool_host",
+           [](py::array_t<float, py::array::c_style | py::array::forcecast> x, py::array_t<float, py::array::c_style | py::array::forcecast> normW,
+              float eps, const std::string &mode, py::object add) {
+               DL_CHECK(x.ndim() == 2 && normW.size() == x.shape(1), "pool_host: x is [N][dim], norm_w [dim]");
+               DL_CHECK(mode == "mean" || mode == "last", "pooling mode: mean | last");
+               const int n = (int)x.shape(0), dim = (int)x.shape(1);
+               std::vector<float> a;
+               if (!add.is_none()) {
+                   auto av = add.cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+                   DL_CHECK(av.size() == x.size(), "pool_host: add has x's shape");
+                   a.assign(av.data(), av.data() + av.size());
+               }
+               py::array_t<float> out((py::ssize_t)dim);
+               poolHost(x.data(), a.empty() ? nullptr : a.data(), n, dim, normW.data(), eps,
+                        mode == "last" ? PoolMode::LAST : PoolMode::MEAN, out.mutable_data());
+               return out;
+           },
+           py::arg("x"), py::arg("norm_w"), py::arg("eps"), py::arg("mode") = "mean", py::arg("add") = py::none(),
+           "One request's rows through poolHost: the pooled, L2-normalised vector [dim].");
     co.def("logprobs_host", [](py::array_t<float, py::array::c_style | py::array::forcecast> logits, int chosen, int k) {
         std::vector<TokenLogprob> e(kLogprobEntries);
         logprobsHost(logits.data(), (int)logits.size(), chosen, k, e.data());
@@ -909,6 +1030,25 @@ PYBIND11_MODULE(_C, m) {
              py::arg("logit_procs") = py::none())
         .def("forward_argmax", [](Backend &b, std::vector<int> t, std::vector<int> p, std::vector<int> s) { return runArgmax(b, t, p, s); },
              py::arg("tokens"), py::arg("positions"), py::arg("slots"))
+        .def("forward_embed", &runEmbed, py::arg("tokens"), py::arg("positions"), py::arg("slots"), py::arg("pooling"),
+             py::arg("temperatures") = py::none(), py::arg("topps") = py::none(), py::arg("coins") = py::none())
+        // host backends: (final residual rows [n][dim] before the final norm, the final norm's weights [dim])
+        .def("forward_hidden",
+             [](Backend &b, std::vector<int> t, std::vector<int> p, std::vector<int> s) {
+                 DL_CHECK(p.size() == t.size() && s.size() == t.size(), "input lengths");
+                 const py::ssize_t n = (py::ssize_t)t.size(), dim = (py::ssize_t)b.header().dim;
+                 py::array_t<float> h({n, dim});
+                 {
+                     py::gil_scoped_release rel;
+                     b.forwardHidden((int)n, t.data(), p.data(), s.data(), h.mutable_data(), false, nullptr);
+                 }
+                 const float *w = b.finalNormWeights();
+                 DL_CHECK(w, "backend keeps no host weights");
+                 py::array_t<float> nw(dim);
+                 std::memcpy(nw.mutable_data(), w, (size_t)dim * sizeof(float));
+                 return py::make_tuple(h, nw);
+             },
+             py::arg("tokens"), py::arg("positions"), py::arg("slots"))
         .def("last_stats", [](const Backend &b) {
             ForwardStats s = b.lastStats();
             return py::make_tuple(s.computeMs, s.syncMs, s.sentBytes, s.recvBytes, s.xchgMs);
@@ -1064,6 +1204,25 @@ PYBIND11_MODULE(_C, m) {
           },
           py::arg("model"), py::arg("buffer_type"), py::arg("world"), py::arg("tokens"), py::arg("kv_bf16") = false,
           py::arg("gpu_index") = 0, py::arg("attn_block_flags") = false);
+
+    m.def("simulate_tp_embed",
+          [](const std::string &model, const std::string &bufferType, int world, std::vector<int> tokens, int chunk,
+             const std::string &mode, bool kvBf16, int gpuIndex) {
+              EngineConfig c = makeConfig(model, bufferType, 1, 0, (u32)std::max(8, chunk), 1, gpuIndex, false, kvBf16,
+                                          py::none(), 1);
+              DL_CHECK(mode == "mean" || mode == "last", "pooling mode: mean | last");
+              std::vector<float> out;
+              {
+                  py::gil_scoped_release rel;
+                  out = simulateTensorParallelEmbed(c, world, tokens, chunk, mode == "last" ? PoolMode::LAST : PoolMode::MEAN);
+              }
+              py::array_t<float> a((py::ssize_t)out.size());
+              std::memcpy(a.mutable_data(), out.data(), out.size() * 4);
+              return a;
+          },
+          py::arg("model"), py::arg("buffer_type"), py::arg("world"), py::arg("tokens"), py::arg("chunk") = 1,
+          py::arg("mode") = "mean", py::arg("kv_bf16") = false, py::arg("gpu_index") = 0,
+          "The embedding of `tokens` on `world` simulated tensor-parallel ranks (the root's vector [dim]).");
 
     m.def("shard_bytes",
           [](const std::string &model, u32 world, u32 rank) {
@@ -1313,6 +1472,13 @@ PYBIND11_MODULE(_C, m) {
              py::arg("coins"), py::arg("top_logprobs"), py::arg("logit_procs") = py::none())
         .def("forward_argmax", [](PyHipEngine &e, std::vector<int> t, std::vector<int> p, std::vector<int> s) { return runArgmax(*e.engine, t, p, s); },
              py::arg("tokens"), py::arg("positions"), py::arg("slots"))
+        .def("forward_embed",
+             [](PyHipEngine &e, std::vector<int> t, std::vector<int> p, std::vector<int> s, py::object pooling,
+                py::object temps, py::object topps, py::object coins) {
+                 return runEmbed(*e.engine, t, p, s, pooling, temps, topps, coins);
+             },
+             py::arg("tokens"), py::arg("positions"), py::arg("slots"), py::arg("pooling"),
+             py::arg("temperatures") = py::none(), py::arg("topps") = py::none(), py::arg("coins") = py::none())
         .def("last_stats",
              [](const PyHipEngine &e) {  // (compute ms, sync ms, sent B, recv B, xchg ms) of the last call
                  ForwardStats s = e.engine->lastStats();
@@ -1330,9 +1496,25 @@ PYBIND11_MODULE(_C, m) {
                  return py::make_tuple(ms, out);
              },
              py::arg("steps"), py::arg("tokens"), py::arg("positions"), py::arg("slots"))
-        .def("profile_forward", [](PyHipEngine &e, std::vector<int> t, std::vector<int> p, std::vector<int> s) {
-            e.engine->profileForward((int)t.size(), t.data(), p.data(), s.data());
-        })
+        // prints the per-kernel-class table; with temperatures (and pooling) the sampled forward of
+        // these rows instead of the host-logits one; returns {kernel class: device ms}
+        .def("profile_forward",
+             [](PyHipEngine &e, std::vector<int> t, std::vector<int> p, std::vector<int> s, py::object temps,
+                py::object pooling) {
+                 if (temps.is_none()) {
+                     e.engine->profileForward((int)t.size(), t.data(), p.data(), s.data());
+                     return std::map<std::string, double>();
+                 }
+                 const std::vector<float> tv = temps.cast<std::vector<float>>();
+                 DL_CHECK(tv.size() == t.size() && p.size() == t.size() && s.size() == t.size(), "input lengths");
+                 std::vector<SampleSpec> specs(t.size());
+                 for (size_t i = 0; i < t.size(); i++) specs[i] = SampleSpec{tv[i], 0.f, 0.f, 0.f};
+                 const std::vector<PoolSpec> pool = parsePool(pooling, t.size());
+                 return e.engine->profileClasses((int)t.size(), t.data(), p.data(), s.data(), specs.data(),
+                                                 pool.empty() ? nullptr : pool.data());
+             },
+             py::arg("tokens"), py::arg("positions"), py::arg("slots"), py::arg("temperatures") = py::none(),
+             py::arg("pooling") = py::none())
         .def("copy_prefix", [](PyHipEngine &e, int src, int dst, int n) { e.engine->copyPrefix(src, dst, n); },
              py::arg("src"), py::arg("dst"), py::arg("n"))
         .def("synchronize", [](PyHipEngine &e) { e.engine->synchronize(); });

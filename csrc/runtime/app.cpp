@@ -302,12 +302,28 @@ void InferenceSession::forwardArgmax(int n, const int *tokens, const int *positi
     recordMetrics("forward_argmax", n, t.elapsedMs());
 }
 
+void InferenceSession::setPooling(int n, const PoolSpec *pool) {
+    poolPending_ = false;
+    for (int i = 0; i < n; i++) poolPending_ = poolPending_ || pool[i].active;
+    backend_->setPooling(n, pool);
+}
+
+bool InferenceSession::sendEmbed(int n, const int *tokens, const int *positions, const int *slots,
+                                 const SampleSpec *specs) {
+    bool embed = poolPending_ && specs != nullptr;
+    poolPending_ = false;
+    for (int i = 0; embed && i < n; i++) embed = specs[i].temperature < 0.f;
+    if (embed) sendControl(Cmd::FORWARD_EMBED, n, tokens, positions, slots);
+    return embed;
+}
+
 void InferenceSession::forwardSample(int n, const int *tokens, const int *positions, const int *slots,
                                      const SampleSpec *specs, int *out) {
     TraceRange tr("dllama.forward_sample");
     Timer t;
-    sendControl(Cmd::FORWARD_SAMPLE, n, tokens, positions, slots);
-    if (!workers_.empty()) {  // the specs follow the row arrays (every rank runs the same draw graph)
+    if (!sendEmbed(n, tokens, positions, slots, specs)) {
+        sendControl(Cmd::FORWARD_SAMPLE, n, tokens, positions, slots);
+        // the specs follow the row arrays (every rank runs the same draw graph)
         for (auto &s : workers_) s.sendAll(specs, n * sizeof(SampleSpec));
     }
     backend_->forwardSample(n, tokens, positions, slots, specs, out);
@@ -317,7 +333,8 @@ void InferenceSession::forwardSample(int n, const int *tokens, const int *positi
 void InferenceSession::launchIds(int n, const int *tokens, const int *positions, const int *slots,
                                  const SampleSpec *specs) {
     launchTimer_.reset();
-    if (specs) {
+    if (sendEmbed(n, tokens, positions, slots, specs)) {
+    } else if (specs) {
         sendControl(Cmd::FORWARD_SAMPLE, n, tokens, positions, slots);
         for (auto &s : workers_) s.sendAll(specs, n * sizeof(SampleSpec));
     } else {
@@ -516,6 +533,8 @@ void runWorker(const AppArgs &args) {
                     for (int i = 0; i < n; i++) backend->releaseSlot(buf[i]);
                 } else if (cmd == Cmd::COPY_PREFIX) {
                     backend->copyPrefix(buf[0], buf[2 * n], buf[n]);
+                } else if (cmd == Cmd::FORWARD_EMBED) {
+                    backend->forwardEmbed(n, &buf[0], &buf[n], &buf[2 * n]);
                 } else if (cmd == Cmd::FORWARD_SAMPLE) {
                     ids.resize(n);
                     specs.resize(n);

@@ -102,6 +102,11 @@ class InferenceSession {
     // logit processors of the next forwardSample / launchIds (Backend::setLogitProcs; the root
     // draws, so nothing goes to the workers)
     void setLogitProcs(int n, const LogitProc *procs) { backend_->setLogitProcs(n, procs); }
+    // pooling of the next forwardSample / launchIds (Backend::setPooling; the root pools). When no
+    // row of that forward draws, the workers get a FORWARD_EMBED instead of the FORWARD_SAMPLE.
+    void setPooling(int n, const PoolSpec *pool);
+    // the slots finalised by the forward just collected (Backend::lastEmbeddings)
+    const PooledSlots &lastEmbeddings() const { return backend_->lastEmbeddings(); }
     // Chained greedy decode of one sequence (Backend::chainLaunch; workers follow each step).
     bool chainSupported() const { return backend_->chainSupported(); }
     void chainLaunch(int token, int pos, int slot);
@@ -128,6 +133,9 @@ class InferenceSession {
     unsigned long long mSent_ = 0, mRecv_ = 0;  // control-plane bytes at the previous metrics record
     Timer launchTimer_;                          // launchIds -> collectIds (metrics)
     bool launchedSample_ = false;
+    bool poolPending_ = false;  // setPooling with a taking-part row, until the next forward
+    // the next forward is an all-embedding one: the workers run it as FORWARD_EMBED (true: sent)
+    bool sendEmbed(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs);
 };
 
 // `dllama worker`: serve forever; a root disconnect returns to listening.

@@ -78,6 +78,113 @@ void logitFilterHost(float *x, int vocab, int topK, float delta) {
         if (!(x[t] >= thr)) x[t] = -INFINITY;
 }
 
+void poolAddHost(float *acc, const float *x, const float *add, int dim, const float *normW, float eps, bool first,
+                 PoolMode mode) {
+    if (mode == PoolMode::LAST) first = true;
+    double ss = 0.0;
+    for (int d = 0; d < dim; d++) {
+        const float xs = add ? x[d] + add[d] : x[d];
+        ss += (double)xs * (double)xs;
+    }
+    const float inv = (float)(1.0 / std::sqrt(ss / (double)dim + (double)eps));
+    for (int d = 0; d < dim; d++) {
+        const float xs = add ? x[d] + add[d] : x[d];
+        volatile float t = inv * xs;  // (volatile: every step rounded on its own, nothing fused)
+        volatile float h = normW[d] * t;
+        volatile float sum = first ? h : acc[d] + h;
+        acc[d] = sum;
+    }
+}
+
+void poolFinishHost(const float *acc, int dim, int count, PoolMode mode, float *out) {
+    double ss = 0.0;
+    for (int d = 0; d < dim; d++) {
+        volatile float p = mode == PoolMode::MEAN ? acc[d] / (float)count : acc[d];
+        out[d] = p;
+        ss += (double)p * (double)p;
+    }
+    const float nrm = (float)std::sqrt(ss);
+    for (int d = 0; d < dim; d++) out[d] = ss > 0.0 ? out[d] / nrm : 0.f;
+}
+
+void poolHost(const float *x, const float *add, int n, int dim, const float *normW, float eps, PoolMode mode, float *out) {
+    std::vector<float> acc(dim, 0.f);
+    for (int i = 0; i < n; i++)
+        if (mode == PoolMode::MEAN || i == n - 1)
+            poolAddHost(acc.data(), x + (size_t)i * dim, add ? add + (size_t)i * dim : nullptr, dim, normW, eps, i == 0, mode);
+    poolFinishHost(acc.data(), dim, n, mode, out);
+}
+
+void Backend::setPooling(int n, const PoolSpec *pool) { pendingPool_.assign(pool, pool + n); }
+
+std::vector<PoolSpec> Backend::takePooling(int n, const int *positions, const int *slots) {
+    std::vector<PoolSpec> pool;
+    pool.swap(pendingPool_);
+    if (pool.empty()) return pool;
+    if ((int)pool.size() != n) throw Error("setPooling: one spec per row of the forward");
+    bool any = false;
+    std::vector<std::pair<int, int>> seen;  // (slot, its latest position) of the taking-part rows
+    for (int i = 0; i < n; i++) {
+        if (!pool[i].active) continue;
+        any = true;
+        if (pool[i].last && pool[i].count < 1) throw Error("setPooling: the last row carries the request's row count");
+        auto it = std::find_if(seen.begin(), seen.end(), [&](const std::pair<int, int> &e) { return e.first == slots[i]; });
+        if (it == seen.end())
+            seen.push_back({slots[i], positions[i]});
+        else if (positions[i] <= it->second)
+            throw Error("setPooling: the rows of a slot come in ascending position");
+        else
+            it->second = positions[i];
+    }
+    if (!any) pool.clear();
+    return pool;
+}
+
+bool Backend::noRowDraws(int n, const SampleSpec *specs) {
+    if (!specs) return false;
+    for (int i = 0; i < n; i++)
+        if (specs[i].temperature >= 0.f) return false;
+    return true;
+}
+
+void Backend::forwardHidden(int, const int *, const int *, const int *, float *, bool, float *) {
+    throw Error(name() + " backend: no host pooling");
+}
+
+// Default pooling (host backends): the rows' final residuals through poolAddHost / poolFinishHost.
+void Backend::poolRowsHost(int n, const int *slots, const std::vector<PoolSpec> &pool, const float *hidden) {
+    const int dim = (int)header().dim;
+    const float *w = finalNormWeights();
+    if (!w) throw Error(name() + " backend: no host pooling");
+    for (int i = 0; i < n; i++) {
+        if (!pool[i].active) continue;
+        const size_t s = (size_t)slots[i];
+        if (poolAcc_.size() <= s) poolAcc_.resize(s + 1);
+        if (poolAcc_[s].empty()) poolAcc_[s].assign(dim, 0.f);
+        if (pool[i].mode == PoolMode::MEAN || pool[i].last)
+            poolAddHost(poolAcc_[s].data(), hidden + (size_t)i * dim, nullptr, dim, w, header().normEpsilon, pool[i].first,
+                        pool[i].mode);
+        if (!pool[i].last) continue;
+        pooled_.slots.push_back(slots[i]);
+        pooled_.values.resize(pooled_.slots.size() * dim);
+        poolFinishHost(poolAcc_[s].data(), dim, pool[i].count, pool[i].mode, &pooled_.values[(pooled_.slots.size() - 1) * dim]);
+    }
+}
+
+void Backend::forwardEmbed(int n, const int *tokens, const int *positions, const int *slots) {
+    const std::vector<PoolSpec> pool = takePooling(n, positions, slots);
+    pooled_ = PooledSlots{};
+    logprobs_.clear();
+    if (plan().rank != 0) {
+        forwardHidden(n, tokens, positions, slots, nullptr, false, nullptr);
+        return;
+    }
+    if (pool.empty()) throw Error("forwardEmbed: no row takes part (setPooling)");
+    std::vector<float> hidden((size_t)n * header().dim);
+    forwardHidden(n, tokens, positions, slots, hidden.data(), false, nullptr);
+    poolRowsHost(n, slots, pool, hidden.data());
+}
+
 void Backend::setLogitProcs(int n, const LogitProc *procs) { pendingProcs_.assign(procs, procs + n); }
 
 std::vector<LogitProc> Backend::takeLogitProcs(int n) {
@@ -111,13 +218,28 @@ void Backend::forwardSample(int n, const int *tokens, const int *positions, cons
     const int vocab = (int)header().vocabSize;
     const std::vector<LogitProc> procs = takeLogitProcs(n);
     if (plan().rank != 0) {  // workers take part in the forward; the root draws
+        pendingPool_.clear();
+        pooled_ = PooledSlots{};
         forward(n, tokens, positions, slots, nullptr);
         for (int i = 0; i < n; i++) out[i] = -1;
         logprobs_.clear();
         return;
     }
+    if (!pendingPool_.empty() && noRowDraws(n, specs)) {  // an all-embedding forward: no logits at all
+        forwardEmbed(n, tokens, positions, slots);
+        for (int i = 0; i < n; i++) out[i] = -1;
+        return;
+    }
+    const std::vector<PoolSpec> pool = takePooling(n, positions, slots);
+    pooled_ = PooledSlots{};
     std::vector<float> logits((size_t)n * vocab);
-    forward(n, tokens, positions, slots, logits.data());
+    if (pool.empty()) {
+        forward(n, tokens, positions, slots, logits.data());
+    } else {  // a mixed forward: the logits as ever, the taking-part rows pooled behind them
+        std::vector<float> hidden((size_t)n * header().dim);
+        forwardHidden(n, tokens, positions, slots, hidden.data(), true, logits.data());
+        poolRowsHost(n, slots, pool, hidden.data());
+    }
     bool anyLogprobs = false;
     for (int i = 0; i < n; i++) anyLogprobs = anyLogprobs || specs[i].logprobs >= 1.f;
     logprobs_.assign(anyLogprobs ? (size_t)n * kLogprobEntries : 0, TokenLogprob{0.f, -1});
@@ -158,6 +280,11 @@ void Backend::launchIds(int n, const int *tokens, const int *positions, const in
             pendingProcs_.clear();
             throw Error("launchIds: logit processors need a sampled forward (specs)");
         }
+        if (!pendingPool_.empty()) {
+            pendingPool_.clear();
+            throw Error("launchIds: pooling needs a sampled forward (specs)");
+        }
+        pooled_ = PooledSlots{};
         logprobs_.clear();
         forwardArgmax(n, tokens, positions, slots, pendingIds_.data());
     }

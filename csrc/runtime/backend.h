@@ -121,6 +121,39 @@ void logitProcHost(const float *logits, int vocab, const u32 *counts, float pres
 float minPDelta(float T, float minP);
 void logitFilterHost(float *x, int vocab, int topK, float delta);
 
+// Embeddings: the pooled, L2-normalised final hidden state of a request's prompt rows. For a request
+// whose prompt is N >= 1 rows at positions 0 .. N - 1, with x[i] row i's final residual:
+//   h[i]  = rmsnorm(x[i]) * normW          (the vector the logits matmul consumes for row i: same
+//                                           epsilon, same residual, before any Q80 quantisation)
+//   mean: p = (h[0] + h[1] + ... + h[N-1]) / N   (f32, added in position order, one add per row per element)
+//   last: p = h[N-1]
+//   out   = p / sqrt(sum_d p[d]^2)         (f32; all zeros when the sum is 0)
+// The rows may arrive over several forwards: a PoolSpec per row of a forward says whether the row
+// takes part, whether it is its request's first row (the slot's accumulator restarts) and whether
+// it is the last one (the slot is finalised; count is then N).
+enum class PoolMode : int { MEAN = 0, LAST = 1 };
+struct PoolSpec {
+    bool active = false;
+    bool first = false;
+    bool last = false;
+    int count = 0;
+    PoolMode mode = PoolMode::MEAN;
+};
+// Host implementation (the CPU path and the reference for the device kernel), in the two steps a
+// request split over forwards takes: poolAddHost adds row x (+ add, may be null) to acc[dim] (first:
+// acc restarts; last mode: acc becomes the row's h), poolFinishHost turns acc into out[dim] (out may
+// be acc). The two norms' sums of squares are taken in double and rounded once. poolHost is both
+// over the N rows x[N][dim] of one request.
+void poolAddHost(float *acc, const float *x, const float *add, int dim, const float *normW, float eps, bool first,
+                 PoolMode mode);
+void poolFinishHost(const float *acc, int dim, int count, PoolMode mode, float *out);
+void poolHost(const float *x, const float *add, int n, int dim, const float *normW, float eps, PoolMode mode, float *out);
+// Finalised slots of a forward and their vectors [slots.size()][dim], in the order of their last rows.
+struct PooledSlots {
+    std::vector<int> slots;
+    std::vector<float> values;
+};
+
 class Backend {
   public:
     virtual ~Backend() = default;
@@ -149,6 +182,21 @@ class Backend {
     // that forward asked for them (SampleSpec::logprobs; rows that did not hold id -1 throughout),
     // empty otherwise and on ranks other than the root. Valid until the next forward is launched.
     virtual const std::vector<TokenLogprob> &lastLogprobs() const { return logprobs_; }
+    // Pooling of the next forwardSample / launchIds (with specs) / forwardEmbed of n rows, which
+    // consumes it: pool[i] belongs to row i. Rows of one slot appear in a forward in ascending
+    // position. Root only (the final residual is replicated: the root pools); without a call,
+    // forwards run as they always did. A forward whose rows all have temperature < 0 and that has a
+    // taking-part row computes no logits at all (the GPU engine: its own graph kind, which ends in
+    // the pooling kernel instead of wcls, the logits exchange and the token pick); any other keeps
+    // its kind and pools behind the token pick.
+    virtual void setPooling(int n, const PoolSpec *pool);
+    // The all-embedding forward on its own (no row draws, no logits, no ids): what a worker rank
+    // runs next to the root's forwardSample / launchIds of such a forward, and a synchronous entry
+    // point for the root (which needs a setPooling before it).
+    virtual void forwardEmbed(int n, const int *tokens, const int *positions, const int *slots);
+    // The slots finalised by the last forwardSample / forwardEmbed / collectIds, on the root only.
+    // Valid until the next forward is launched.
+    virtual const PooledSlots &lastEmbeddings() const { return pooled_; }
     // Chained greedy decode of one sequence (GPU engines; dllama inference): each step's input
     // token is the previous step's argmax, fed back on the device, so step k + 1 is enqueued
     // before the host has read step k (the host decodes and prints while the device runs).
@@ -180,6 +228,13 @@ class Backend {
     virtual void copyPrefix(int src, int dst, int n);
     virtual std::string name() const = 0;
 
+    // Host backends, for the default pooling: the forward with the rows' final residual (before the
+    // final norm) copied to hidden[n][dim] (may be null); withLogits false: wcls and the logits gather are
+    // skipped on every rank. finalNormWeights: the final norm's weights [dim].
+    virtual void forwardHidden(int n, const int *tokens, const int *positions, const int *slots, float *hidden,
+                               bool withLogits, float *logits);
+    virtual const float *finalNormWeights() const { return nullptr; }
+
   protected:
     ForwardStats stats_;
     std::vector<int> pendingIds_;  // default launchIds / collectIds
@@ -190,6 +245,15 @@ class Backend {
     // host state of the default forwardSample, per slot (allocated at a slot's first fresh row)
     std::vector<std::vector<u32>> procCounts_;
     std::vector<std::vector<LogitBias>> procBias_;
+    std::vector<PoolSpec> pendingPool_;  // setPooling, until the next forward takes it
+    PooledSlots pooled_;
+    // takes pendingPool_ for a forward of n rows (empty: none set, or no row takes part); checks the
+    // sizes and that each slot's taking-part rows come in ascending position
+    std::vector<PoolSpec> takePooling(int n, const int *positions, const int *slots);
+    // every row of the forward is a non-drawing row (specs null: every row draws)
+    static bool noRowDraws(int n, const SampleSpec *specs);
+    std::vector<std::vector<float>> poolAcc_;  // default pooling: per slot
+    void poolRowsHost(int n, const int *slots, const std::vector<PoolSpec> &pool, const float *hidden);
 };
 
 // Host data plane used by the CPU backend for tensor parallelism.

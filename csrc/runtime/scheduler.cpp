@@ -276,14 +276,15 @@ bool Scheduler::admitWithPrefix() {
             stats_.cancelled++;
             return true;
         }
-        if (r->prompt.empty() || r->prompt.size() >= seqLen) {
+        if (r->prompt.empty() || promptTooLong(*r, seqLen)) {
             queue_.pop_front();
             r->error = r->prompt.empty() ? "empty prompt" : "prompt longer than the context";
             r->finish("error");
             return true;
         }
         if (freeSlots_.empty()) return false;
-        const size_t cap = r->prompt.size() - 1;
+        // (an embedding request never takes a hit: mean pooling needs every row's hidden state)
+        const size_t cap = r->params.embed != EmbedMode::OFF ? 0 : r->prompt.size() - 1;
         int idleBest = -1, lru = freeSlots_.back();
         size_t idleL = 0, activeL = 0;
         for (auto it = freeSlots_.rbegin(); it != freeSlots_.rend(); ++it) {
@@ -309,8 +310,7 @@ bool Scheduler::admitWithPrefix() {
             src = -1;
         }
         if (pagesTotal_ >= 0) {
-            const u64 span = r->params.maxTokens > 0 ? (u64)r->prompt.size() + (u64)r->params.maxTokens + 1 : seqLen;
-            const int need = pagesFor(std::min<u64>(span, seqLen));
+            const int need = pagesFor(std::min<u64>(spanOf(*r, seqLen), seqLen));
             if (need > pagesTotal_) {
                 queue_.pop_front();
                 r->error = "request needs more KV pages than the pool holds";
@@ -390,11 +390,32 @@ bool Scheduler::step() {
             r->prefilled += p.prefill;
             if (p.sample) r->generated.push_back(ids[p.row]);
         }
+        const PooledSlots &pooled = sess_.lastEmbeddings();  // (the next launch overwrites them)
         done.swap(flight_.picks);
         inflight_ = false;
         std::lock_guard<std::mutex> lk(mu_);
         for (auto &r : draining_) returnSlot(r->slot);  // their last rows have completed
         draining_.clear();
+        // an embedding request ends with the forward that carried its last prompt row: the vector is
+        // stored and its slot goes back to the pool before this step's admission
+        for (auto &p : done) {
+            if (!p.embedDone || p.r->finished) continue;
+            const size_t dim = sess_.header().dim;
+            const auto it = std::find(pooled.slots.begin(), pooled.slots.end(), p.r->slot);
+            if (it == pooled.slots.end() || pooled.values.size() < pooled.slots.size() * dim) {
+                p.r->error = "the backend returned no embedding";
+                finishRequest(p.r, "error");
+                continue;
+            }
+            const float *v = &pooled.values[(size_t)(it - pooled.slots.begin()) * dim];
+            {
+                std::lock_guard<std::mutex> rl(p.r->mu);
+                p.r->embedding.assign(v, v + dim);
+            }
+            stats_.completed++;
+            stats_.embeddingRequests++;
+            finishRequest(p.r, "stop");
+        }
     }
     flushReleases();  // slots freed by the previous step's text work and by the collection above
 
@@ -414,7 +435,7 @@ bool Scheduler::step() {
                 stats_.cancelled++;
                 continue;
             }
-            if (r->prompt.empty() || r->prompt.size() >= seqLen) {
+            if (r->prompt.empty() || promptTooLong(*r, seqLen)) {
                 queue_.pop_front();
                 r->error = r->prompt.empty() ? "empty prompt" : "prompt longer than the context";
                 r->finish("error");
@@ -422,8 +443,7 @@ bool Scheduler::step() {
             }
             const int slot = freeSlots_.back();
             if (pagesTotal_ >= 0) {
-                const u64 span = r->params.maxTokens > 0 ? (u64)r->prompt.size() + (u64)r->params.maxTokens + 1 : seqLen;
-                const int need = (int)((std::min<u64>(span, seqLen) + pageSize_ - 1) / pageSize_);
+                const int need = (int)((std::min<u64>(spanOf(*r, seqLen), seqLen) + pageSize_ - 1) / pageSize_);
                 int held = 0;  // pages reserved by the active requests
                 for (int p : slotPages_) held += p;
                 if (need > pagesTotal_) {
@@ -459,7 +479,7 @@ bool Scheduler::step() {
     Flight next;
     for (auto &rp : active_) {
         GenRequest *r = rp.get();
-        if (r->prefilled < r->prompt.size()) continue;
+        if (r->prefilled < r->prompt.size() || r->params.embed != EmbedMode::OFF) continue;
         if ((int)tokens.size() >= sess_.maxBatch()) break;
         const int pos = (int)(r->prompt.size() + r->generated.size()) - 1;
         if ((r->params.maxTokens > 0 && (int)r->generated.size() >= r->params.maxTokens) || (u32)(pos + 1) >= seqLen)
@@ -482,7 +502,8 @@ bool Scheduler::step() {
             slots.push_back(r->slot);
         }
         const bool completes = r->prefilled + take == r->prompt.size();
-        next.picks.push_back({rp, (int)tokens.size() - 1, completes, take});
+        const bool embed = r->params.embed != EmbedMode::OFF;  // draws no token
+        next.picks.push_back({rp, (int)tokens.size() - 1, completes && !embed, take, completes && embed});
     }
     next.n = (int)tokens.size();
 
@@ -495,8 +516,11 @@ bool Scheduler::step() {
         // (a greedy request that wants log-probabilities takes the sampler at temperature 0 - the
         //  same lowest-index argmax - because the argmax paths keep no logits to score; so does one
         //  with penalties or a logit bias, which act between the logits and the draw)
-        bool allGreedy = true, anyProc = false;
+        // (a forward with rows of an embedding request takes the specs too: they say which rows draw,
+        //  and a forward in which none does computes no logits at all)
+        bool allGreedy = true, anyProc = false, anyPool = false;
         for (auto &p : next.picks) {
+            if (p.r->params.embed != EmbedMode::OFF) allGreedy = false, anyPool = true;
             if (!p.sample) continue;
             if (p.r->params.temperature != 0.0f || p.r->params.logprobs || p.r->params.logitProc()) allGreedy = false;
             anyProc = anyProc || p.r->params.logitProc();
@@ -531,6 +555,24 @@ bool Scheduler::step() {
                     lp.minP = gp.minP;
                 }
                 sess_.setLogitProcs(next.n, procs.data());
+            }
+            if (anyPool) {  // the prompt rows of the embedding requests: their picks' last `prefill` rows
+                std::vector<PoolSpec> pool(next.n);
+                for (auto &p : next.picks) {
+                    const GenParams &gp = p.r->params;
+                    if (gp.embed == EmbedMode::OFF) continue;
+                    const size_t N = p.r->prompt.size();
+                    for (int i = 0; i < p.prefill; i++) {
+                        PoolSpec &ps = pool[p.row - p.prefill + 1 + i];
+                        const size_t at = p.r->prefilled + i;
+                        ps.active = true;
+                        ps.first = at == 0;
+                        ps.last = at + 1 == N;
+                        ps.count = (int)N;
+                        ps.mode = gp.embed == EmbedMode::LAST ? PoolMode::LAST : PoolMode::MEAN;
+                    }
+                }
+                sess_.setPooling(next.n, pool.data());
             }
             sess_.launchIds(next.n, tokens.data(), positions.data(), slots.data(), specs.data());
         }

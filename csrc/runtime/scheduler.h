@@ -21,6 +21,10 @@
 
 namespace dl {
 
+// An embedding request (POST /v1/embeddings) draws no token: its prompt rows are prefilled like any
+// prompt and their final hidden states pooled (Backend PoolSpec: mean over the rows, or the last row).
+enum class EmbedMode { OFF, MEAN, LAST };
+
 struct GenParams {
     int maxTokens = 128;      // reference default (Request.hpp:33); <= 0 = until EOS / context end
     float temperature = 0.8f;
@@ -41,6 +45,7 @@ struct GenParams {
     // size is off too: callers pass 0). A greedy request ignores both: the argmax always survives.
     int topK = 0;
     float minP = 0.f;
+    EmbedMode embed = EmbedMode::OFF;
     bool penalized() const { return presencePenalty != 0.f || frequencyPenalty != 0.f || !logitBias.empty(); }
     bool logitFilter() const { return temperature != 0.f && (topK > 0 || minP > 0.f); }
     // the request's drawn rows carry a LogitProc
@@ -70,6 +75,7 @@ class GenRequest {
     int completionTokens = 0;
     std::vector<TokenRecord> logprobs;  // one per generated token (params.logprobs), the last one included
     int cachedTokens = 0;  // prompt tokens whose KV was reused instead of prefilled (--prefix-cache)
+    std::vector<float> embedding;  // params.embed: the pooled, L2-normalised vector [dim]
 
     // The client went away (e.g. a streaming connection dropped): the scheduler finishes the
     // request at its next step and frees its KV slot instead of generating to max_tokens.
@@ -104,6 +110,7 @@ struct SchedulerStats {
     u64 prefixHits = 0, prefixTokens = 0, prefixCopies = 0, prefixEvictions = 0;
     u64 logitProcRequests = 0;  // finished requests that used penalties or a logit bias
     u64 logitFilterRequests = 0;  // finished requests with top_k or min_p on
+    u64 embeddingRequests = 0;  // finished embedding requests
 };
 
 class Scheduler {
@@ -122,6 +129,7 @@ class Scheduler {
         int row;      // batch row whose id belongs to the request
         bool sample;  // the row yields the request's next token
         int prefill;  // prompt tokens consumed by this forward
+        bool embedDone = false;  // the row is an embedding request's last prompt row
     };
     struct Flight {
         std::vector<Pick> picks;
@@ -165,6 +173,15 @@ class Scheduler {
     std::vector<size_t> slotReach_;  // positions launched into each slot (its mapped pages, paged)
     u64 useStamp_ = 0;
     std::vector<int> residentOf(const GenRequest &r) const;
+    // positions a request may reach: an embedding request never goes beyond its prompt
+    static u64 spanOf(const GenRequest &r, u32 seqLen) {
+        if (r.params.embed != EmbedMode::OFF) return r.prompt.size();
+        return r.params.maxTokens > 0 ? (u64)r.prompt.size() + (u64)r.params.maxTokens + 1 : seqLen;
+    }
+    // (a chat prompt leaves room for one generated token; an embedding input may fill the context)
+    static bool promptTooLong(const GenRequest &r, u32 seqLen) {
+        return r.params.embed != EmbedMode::OFF ? r.prompt.size() > seqLen : r.prompt.size() >= seqLen;
+    }
     int pagesFor(size_t positions) const { return (int)((positions + pageSize_ - 1) / pageSize_); }
     bool admitWithPrefix();  // one request from the head of the queue; false: nothing admitted
     Flight flight_;

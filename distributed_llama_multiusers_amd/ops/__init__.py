@@ -290,6 +290,45 @@ def logit_filter(logits, temperatures, top_k, delta, active, fill=None):
     return native().ops.logit_filter(x, temps, [int(k) for k in top_k], [float(d) for d in delta], act)
 
 
+POOL_TAKE, POOL_FIRST, POOL_LAST, POOL_MODE_LAST = 1, 2, 4, 8
+
+
+def pool(launches, norm_w, eps, n_slots, out=None, acc=None):
+    """Device pooling (launchPool): the L2-normalised mean (or last row) of the rows' final-norm hidden
+    states, per slot. `launches` is a list of launches run in order on one per-slot state; each is a
+    dict with x [B, dim] (the residual rows), add (None or [B, dim], summed to x first), slots [B] and,
+    per row, take / first / last (does the row take part, is it its request's first / last row),
+    count (the request's row count N, read at its last row) and mode ("mean" | "last"). For a
+    taking-part row: h = norm_w * rmsnorm(x + add); mean: acc[slot] = h if first else acc[slot] + h;
+    at the last row out[slot] = p / |p| with p = acc[slot] / N (mean) or h (last). Rows that do not
+    take part are neither read nor written. out / acc ([n_slots, dim], default zeros) are the buffers'
+    contents before the first launch. Returns float32 (out, acc) after the last one."""
+    w = _np(norm_w).reshape(-1)
+    dim = w.shape[0]
+    ls = []
+    for l in launches:
+        x = _np(l["x"]).reshape(-1, dim)
+        B = x.shape[0]
+        flags = [(POOL_TAKE if l["take"][b] else 0) | (POOL_FIRST if l["first"][b] else 0) |
+                 (POOL_LAST if l["last"][b] else 0) | (POOL_MODE_LAST if l["mode"][b] == "last" else 0) for b in range(B)]
+        ls.append({"x": x, "add": None if l.get("add") is None else _np(l["add"]).reshape(-1, dim),
+                   "slots": [int(s) for s in l["slots"]], "flags": flags, "counts": [int(c) for c in l["count"]]})
+    o = np.zeros((n_slots, dim), np.float32) if out is None else _np(out).reshape(n_slots, dim)
+    a = np.zeros((n_slots, dim), np.float32) if acc is None else _np(acc).reshape(n_slots, dim)
+    return native().ops.pool(ls, dim, int(n_slots), w, float(eps), o, a)
+
+
+def ref_pool(x, norm_w, eps, mode="mean", add=None) -> np.ndarray:
+    """float64 reference of one request's pooled vector: x [N, dim] (+ add) -> [dim]."""
+    xs = np.asarray(_np(x), np.float64)
+    if add is not None:
+        xs = (_np(x) + _np(add)).astype(np.float64)  # the f32 sum the kernel and the host form first
+    h = np.asarray(_np(norm_w), np.float64) * (xs / np.sqrt((xs * xs).mean(-1, keepdims=True) + float(eps)))
+    p = h.mean(0) if mode == "mean" else h[-1]
+    ss = float((p * p).sum())
+    return p / np.sqrt(ss) if ss > 0 else np.zeros_like(p)
+
+
 def argmax(logits) -> list:
     x = _np(logits)
     return native().ops.argmax(x, x.shape[0] if x.ndim == 2 else 1)

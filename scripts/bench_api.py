@@ -7,6 +7,10 @@ and temperature 0.8 / top_p 0.9 with per-request seeds (device sampling: only to
 to the host). One untimed round first captures the graphs.
 
   python scripts/bench_api.py [--n 64] [--max-tokens 64] [--port 0] [--logprobs K] [--penalties] [--filters]
+                              [--embeddings]
+
+--embeddings: after the chat rounds, one /v1/embeddings request of N inputs of token ids (about 48
+tokens each), alone and next to a greedy chat round: inputs/s and prompt tokens/s.
 """
 import argparse
 import http.client
@@ -40,6 +44,20 @@ def _post(port, body, out, i):
         out[i] = data["usage"]["completion_tokens"]
     except Exception as e:  # noqa: BLE001 - counted as a failed request
         out[i] = e
+
+
+def _embed_round(port, n, tokens_each=48):
+    """One /v1/embeddings request of n token-id inputs: (prompt tokens, seconds)."""
+    body = {"input": [[1000 + (37 * i + 11 * j) % 100000 for j in range(tokens_each)] for i in range(n)],
+            "encoding_format": "base64"}
+    t0 = time.perf_counter()
+    c = http.client.HTTPConnection("127.0.0.1", port, timeout=300)
+    c.request("POST", "/v1/embeddings", json.dumps(body), {"Content-Type": "application/json"})
+    r = c.getresponse()
+    data = json.loads(r.read())
+    if r.status != 200 or len(data["data"]) != n:
+        raise RuntimeError(f"embeddings failed: {r.status} {str(data)[:200]}")
+    return data["usage"]["prompt_tokens"], time.perf_counter() - t0
 
 
 EXTRA = {}  # request fields added to every body (--logprobs, --penalties, --filters)
@@ -82,6 +100,8 @@ def main():
     ap.add_argument("--filters", action="store_true",
                     help="every request sends top_k 40 and min_p 0.05: they act in the sampled round "
                          "(temperature 0.8), the greedy round ignores them")
+    ap.add_argument("--embeddings", action="store_true",
+                    help="also time one /v1/embeddings request of --n inputs, alone and next to a greedy chat round")
     args = ap.parse_args()
     if args.filters:
         EXTRA.update(top_k=40, min_p=0.05)
@@ -140,6 +160,18 @@ def main():
         res["top_logprobs"] = args.logprobs if args.logprobs >= 0 else None
         res["penalties"] = bool(args.penalties)
         res["filters"] = bool(args.filters)
+        if args.embeddings:
+            _embed_round(port, args.n)  # untimed: graph capture
+            toks, dt = _embed_round(port, args.n)
+            res["embeddings"] = {"inputs": args.n, "prompt_tokens": toks, "s": round(dt, 3),
+                                 "inputs_s": round(args.n / dt, 1), "tok_s": round(toks / dt, 1)}
+            box = {}
+            th = threading.Thread(target=lambda: box.update(e=_embed_round(port, args.n)))
+            th.start()
+            ctoks, cdt = _round(port, args.n // 2 or 1, args.max_tokens, 0.0, 0)
+            th.join()
+            res["embeddings_next_to_chat"] = {"embed_s": round(box["e"][1], 3), "chat_tok_s": round(ctoks / cdt, 1)}
+            print("embeddings", res["embeddings"], res["embeddings_next_to_chat"], flush=True)
         print(json.dumps(res), flush=True)
     finally:
         srv.terminate()
