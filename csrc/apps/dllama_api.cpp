@@ -49,6 +49,7 @@ struct Api {
     std::unique_ptr<ChatTemplateGenerator> tmpl;
     std::string model;
     std::atomic<u64> counter{0};
+    std::string jsonUnavailable;  // why response_format json_object cannot be served (empty: it can)
 
     std::vector<int> buildPrompt(const Value &messages) {
         std::vector<ChatItem> items;
@@ -198,6 +199,18 @@ struct Api {
                     bad = "min_p must be a number from 0 to 1";
                 else
                     p.minP = (float)mp.asNumber();
+            }
+            const Value &rf = body["response_format"];
+            if (bad.empty() && !rf.isNull()) {
+                const std::string type = rf.isObject() && rf["type"].isString() ? rf["type"].asString() : "";
+                if (type == "json_object") {
+                    if (jsonUnavailable.empty())
+                        p.jsonObject = true;
+                    else
+                        bad = "response_format json_object is unavailable with this tokenizer: " + jsonUnavailable;
+                } else if (type != "text") {
+                    bad = "response_format must be {\"type\": \"text\"} or {\"type\": \"json_object\"}";
+                }
             }
             const Value &lb = body["logit_bias"];
             if (bad.empty() && !lb.isNull()) {
@@ -502,6 +515,7 @@ struct Api {
         metric("dllama_logit_filter_requests_total", "counter", "Finished requests with top_k or min_p on.",
                (double)s.logitFilterRequests);
         metric("dllama_embedding_requests_total", "counter", "Finished embedding requests.", (double)s.embeddingRequests);
+        metric("dllama_json_requests_total", "counter", "Finished requests in JSON mode.", (double)s.jsonRequests);
         metric("dllama_active_requests", "gauge", "Requests holding a KV slot.", (double)s.active);
         metric("dllama_queued_requests", "gauge", "Requests waiting for a KV slot.", (double)s.queued);
         metric("dllama_kv_slots", "gauge", "KV-cache slots (max concurrent sequences).", (double)sess->nSlots());
@@ -534,6 +548,7 @@ struct Api {
         v.set("prefix_evictions", (double)s.prefixEvictions);
         v.set("logit_proc_requests", (double)s.logitProcRequests);
         v.set("logit_filter_requests", (double)s.logitFilterRequests);
+        v.set("json_requests", (double)s.jsonRequests);
         v.set("embedding_requests", (double)s.embeddingRequests);
         conn.writeJson(200, v.dump());
     }
@@ -602,6 +617,9 @@ int main(int argc, char **argv) {
                 std::printf("⚠️  chat template unavailable (%s); using role-prefixed prompts\n", e.what());
             }
         }
+        api.jsonUnavailable = sess.enableJsonMode();
+        if (!api.jsonUnavailable.empty())
+            std::printf("⚠️  response_format json_object is unavailable: %s\n", api.jsonUnavailable.c_str());
         Scheduler sched(sess);
         api.sched = &sched;
         HttpServer server(args.port);

@@ -204,9 +204,9 @@ void HipEngineImpl::enqueueSampled(int n, const int *tokens, const int *position
         else  // (a single row takes paths that keep the residual elsewhere: setupPrenorm)
             DL_CHECK(n >= 2, "pooling: a pooled row that draws needs a forward of its own kind with >= 2 rows");
     }
-    const bool proc = kind == GraphKind::SAMPLE_PROC || kind == GraphKind::SAMPLE_PROC_FILTER;
+    const bool proc = kindProc(kind);
     setInputs(n, tokens, positions, slots, specs, 0, proc ? procRows_.data() : nullptr,
-              kind == GraphKind::SAMPLE_PROC_FILTER ? filterRows_.data() : nullptr);
+              kindFilter(kind) ? filterRows_.data() : nullptr);
     if (proc) enqueueProcState(n, slots, procs);
     stagePooling(n, slots, pool);
     runGraph(n, specs ? kind : GraphKind::ARGMAX);
@@ -330,7 +330,7 @@ HipEngineImpl::GraphKind HipEngineImpl::beginProcs(int n, const int *slots, cons
     std::vector<int> seen;
     procRows_.assign((size_t)n * 4, 0.f);
     filterRows_.assign((size_t)n, hipk::LogitFilterRow{0, -INFINITY, 0, 0});
-    bool any = false, anyFilter = false;
+    bool any = false, anyFilter = false, anyJson = false;
     for (int b = 0; b < n; b++) {
         const LogitProc &p = procs[b];
         if (!p.active || specs[b].temperature < 0.f) continue;
@@ -344,11 +344,18 @@ HipEngineImpl::GraphKind HipEngineImpl::beginProcs(int n, const int *slots, cons
             filterRows_[b] = hipk::LogitFilterRow{p.topK, minPDelta(specs[b].temperature, p.minP), 1, 0};
             anyFilter = true;
         }
+        if (p.json) {
+            DL_CHECK(dJsonMeta_ != nullptr, "json mode: no token table (setJsonTable)");
+            procRows_[(size_t)b * 4 + 3] = 1.f;
+            anyJson = true;
+        }
     }
     std::sort(seen.begin(), seen.end());
     DL_CHECK(std::adjacent_find(seen.begin(), seen.end()) == seen.end(),
              "logit processors: two drawn rows of one forward share a slot");
-    return !any ? GraphKind::SAMPLE : anyFilter ? GraphKind::SAMPLE_PROC_FILTER : GraphKind::SAMPLE_PROC;
+    if (!any) return GraphKind::SAMPLE;
+    if (anyJson) return anyFilter ? GraphKind::SAMPLE_PROC_FILTER_JSON : GraphKind::SAMPLE_PROC_JSON;
+    return anyFilter ? GraphKind::SAMPLE_PROC_FILTER : GraphKind::SAMPLE_PROC;
 }
 
 // Before the forward, in stream order: a fresh slot's counts are zeroed and its bias entries and
@@ -360,6 +367,7 @@ void HipEngineImpl::enqueueProcState(int n, const int *slots, const std::vector<
         const LogitProc &p = procs[b];
         if (procRows_[(size_t)b * 4 + 2] == 0.f || !p.fresh) continue;
         const size_t s = (size_t)slots[b], nb = p.bias.size();
+        if (p.json) DL_HIP(hipMemsetAsync(dJsonStates_ + s, 0, sizeof(uint4), stream_));  // START is all zero bits
         DL_HIP(hipMemsetAsync(dProcCounts_ + s * h_.vocabSize, 0, (size_t)h_.vocabSize * sizeof(uint32_t), stream_));
         hProcNBias_[s] = (int)nb;
         DL_HIP(hipMemcpyAsync(dProcNBias_ + s, hProcNBias_ + s, sizeof(int), hipMemcpyHostToDevice, stream_));
@@ -368,6 +376,45 @@ void HipEngineImpl::enqueueProcState(int n, const int *slots, const std::vector<
         DL_HIP(hipMemcpyAsync(dProcBias_ + s * kMaxLogitBias, hProcBias_ + s * kMaxLogitBias, nb * sizeof(LogitBias),
                               hipMemcpyHostToDevice, stream_));
     }
+}
+
+// The token table of JSON mode, uploaded once (root rank: the root draws). The memory check reserved
+// an estimate (procBytes); the table's real size is checked against what is free now.
+void HipEngineImpl::setJsonTable(std::shared_ptr<const JsonTokenTable> table) {
+    Backend::setJsonTable(table);
+    if (!table || rank() != 0) return;
+    DL_CHECK(pendingN_ == 0 && !dJsonMeta_, "json mode: the token table is set once, with no forward in flight");
+    DL_HIP(hipSetDevice(dev_));
+    size_t freeB = 0, totalB = 0;
+    DL_HIP(hipMemGetInfo(&freeB, &totalB));
+    if (table->bytes() + ((size_t)64 << 20) > freeB)
+        throw Error("json mode: the token table (" + std::to_string(table->bytes() >> 20) + " MB) does not fit on the GPU (" +
+                    std::to_string(freeB >> 20) + " MB free)");
+    const size_t V = h_.vocabSize;
+    std::vector<uint2> meta(V);
+    for (size_t t = 0; t < V; t++) {
+        DL_CHECK((size_t)table->off[t] + (jsonTokenLen(table->info[t]) + 3) / 4 <= table->words.size(), "json mode: malformed token table");
+        meta[t] = make_uint2(table->off[t], table->info[t]);
+    }
+    dJsonMeta_ = dalloc<uint2>(V);
+    dJsonWords_ = dalloc<uint32_t>(table->words.size());
+    DL_HIP(hipMemcpy(dJsonMeta_, meta.data(), V * sizeof(uint2), hipMemcpyHostToDevice));
+    DL_HIP(hipMemcpy(dJsonWords_, table->words.data(), table->words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+}
+
+hipk::JsonMaskArgs HipEngineImpl::jsonMaskArgs() const {
+    static_assert(sizeof(JsonState) == sizeof(uint4), "device and host state layouts");
+    hipk::JsonMaskArgs g;
+    g.logits = dProcLogits_;
+    g.vocab = h_.vocabSize;
+    g.spec = dSpec_;
+    g.proc = dProc_;
+    g.slots = dSlot_;
+    g.table.meta = dJsonMeta_;
+    g.table.words = dJsonWords_;
+    g.states = dJsonStates_;
+    g.ids = dIds_;
+    return g;
 }
 
 hipk::LogitProcArgs HipEngineImpl::logitProcArgs(const float *raw) const {
@@ -757,7 +804,7 @@ void HipEngineImpl::runGraph(int n, GraphKind kind, unsigned *syncDst) {
         copySync();
         return;
     }
-    const int key = ((((n * 8 + (int)kind) * 2 + (prefillOk_ ? 1 : 0)) * 2 + (attnLong_ ? 1 : 0)) << 4) + bucket_;
+    const int key = ((((n * 16 + (int)kind) * 2 + (prefillOk_ ? 1 : 0)) * 2 + (attnLong_ ? 1 : 0)) << 4) + bucket_;
     auto it = graphs_.find(key);
     if (it == graphs_.end()) {
         // capture on the second use of a shape: a one-off row count (the tail chunk of a prompt,

@@ -699,8 +699,8 @@ void HipEngineImpl::enqueueTokenPick(int n, GraphKind kind) {
     // logits for the host (LOGITS) and sampled rows (SAMPLE) are needed on the root only: the
     // vocab slices are gathered to rank 0 (the reference's SYNC_NODE_SLICES_EXCEPT_ROOT), the
     // other ranks publish theirs and skip the unshard and the draw (the root's ids are used)
-    const bool filtered = kind == GraphKind::SAMPLE_PROC_FILTER;
-    const bool sampled = kind == GraphKind::SAMPLE || kind == GraphKind::SAMPLE_PROC || filtered;
+    const bool filtered = kindFilter(kind), json = kindJson(kind);
+    const bool sampled = kind == GraphKind::SAMPLE || kindProc(kind);
     const bool rootOnly = kind == GraphKind::LOGITS || sampled;
     if (p.nRanks > 1 && !distArgmax) {
         ProfScope ps(this, "allgather");
@@ -721,10 +721,17 @@ void HipEngineImpl::enqueueTokenPick(int n, GraphKind kind) {
             // SAMPLE_PROC_FILTER: top_k / min_p then mask the processed rows in place; the filter's
             // partial histograms and maxima live in the sampler's scratch, which the sampler rewrites
             // before it reads it
-            const bool proc = kind == GraphKind::SAMPLE_PROC || filtered;
+            // SAMPLE_PROC_JSON / SAMPLE_PROC_FILTER_JSON: the JSON token mask on the processed rows
+            // ahead of the filter (top_k counts allowed tokens only), and the slots' automaton states
+            // advanced by the drawn tokens behind the draw
+            const bool proc = kindProc(kind);
             if (proc) {
                 ProfScope ps(this, "logit_proc");
                 hipk::launchLogitProc(logitProcArgs(full), n, stream_);
+            }
+            if (json) {
+                ProfScope ps(this, "json_mask");
+                hipk::launchJsonMask(jsonMaskArgs(), n, stream_);
             }
             if (filtered) {
                 ProfScope ps(this, "logit_filter");
@@ -751,6 +758,10 @@ void HipEngineImpl::enqueueTokenPick(int n, GraphKind kind) {
             if (proc) {
                 ProfScope ps(this, "logit_proc");
                 hipk::launchLogitProcCount(logitProcArgs(full), n, stream_);
+            }
+            if (json) {
+                ProfScope ps(this, "json_mask");
+                hipk::launchJsonAdvance(jsonMaskArgs(), n, stream_);
             }
         }
     } else if (kind != GraphKind::LOGITS) {

@@ -110,7 +110,15 @@ class HipEngineImpl : public HipEngine {
     // and the draw (a forward with a row whose filter is on)
     // EMBED: every row is a non-drawing row and one of them is pooled (Backend::setPooling): all the
     // layers, then launchPool on the root; no wcls, no logits exchange, no token pick on any rank
-    enum class GraphKind { LOGITS = 0, ARGMAX = 1, CHAIN = 2, SAMPLE = 3, SAMPLE_PROC = 4, SAMPLE_PROC_FILTER = 5, EMBED = 6 };
+    // SAMPLE_PROC_JSON / SAMPLE_PROC_FILTER_JSON: the two with the JSON token mask behind the processors
+    // and the automaton's advance behind the draw (a forward with a drawn row in JSON mode)
+    enum class GraphKind {
+        LOGITS = 0, ARGMAX = 1, CHAIN = 2, SAMPLE = 3, SAMPLE_PROC = 4, SAMPLE_PROC_FILTER = 5, EMBED = 6,
+        SAMPLE_PROC_JSON = 7, SAMPLE_PROC_FILTER_JSON = 8
+    };
+    static bool kindJson(GraphKind k) { return k == GraphKind::SAMPLE_PROC_JSON || k == GraphKind::SAMPLE_PROC_FILTER_JSON; }
+    static bool kindFilter(GraphKind k) { return k == GraphKind::SAMPLE_PROC_FILTER || k == GraphKind::SAMPLE_PROC_FILTER_JSON; }
+    static bool kindProc(GraphKind k) { return k == GraphKind::SAMPLE_PROC || kindFilter(k) || kindJson(k); }
 
     // engine.cpp
     void syncAndCheckComm();
@@ -436,6 +444,14 @@ class HipEngineImpl : public HipEngine {
     hipk::LogitFilterRow *dFilter_ = nullptr;      // [maxBatch]
     std::vector<hipk::LogitFilterRow> filterRows_;
     uint32_t *dFilterState_ = nullptr;             // [maxBatch][kLogitFilterStateWords], zero between launches
+    // JSON mode (Backend::setJsonTable), root rank only: the token table (per token its offset and
+    // length | class, and the pieces' bytes in 4-byte words) and the automaton's state per KV slot,
+    // reset by a fresh row's memset ahead of the forward and advanced behind the draw; a row's flag
+    // is the 4th float of its dProc_ entry
+    uint2 *dJsonMeta_ = nullptr;                   // [vocab]
+    uint32_t *dJsonWords_ = nullptr;
+    uint4 *dJsonStates_ = nullptr;                 // [nSlots]
+    hipk::JsonMaskArgs jsonMaskArgs() const;
     size_t procBytes() const;
     // pooling (Backend::setPooling), root rank only: the forward's pool rows and their per-slot run
     // index (hipk::poolPlan) behind one pinned staging block (free once the previous forward was
@@ -461,6 +477,7 @@ class HipEngineImpl : public HipEngine {
     hipk::LogitProcArgs logitProcArgs(const float *raw) const;
     // takes the pending processors of a sampled forward and returns its graph kind (SAMPLE: no row is
     // active); beginProcs fills procRows_ / filterRows_, enqueueProcState resets / uploads fresh slots
+    void setJsonTable(std::shared_ptr<const JsonTokenTable> table) override;
     GraphKind beginProcs(int n, const int *slots, const SampleSpec *specs, std::vector<LogitProc> &procs);
     void enqueueProcState(int n, const int *slots, const std::vector<LogitProc> &procs);
     // measured-sync slots (syncSlots, hipk::syncFoldWords) and their host copies: [0] the last

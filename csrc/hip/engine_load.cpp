@@ -90,7 +90,10 @@ void HipEngineImpl::checkFusedResidency() {
 size_t HipEngineImpl::procBytes() const {
     if (rank() != 0) return 0;
     return (size_t)cfg_.nSlots * ((size_t)h_.vocabSize * sizeof(uint32_t) + kMaxLogitBias * sizeof(hipk::LogitBiasEntry) + sizeof(int)) +
-           (size_t)cfg_.maxBatch * (h_.vocabSize * sizeof(float) + hipk::kLogitFilterStateWords * sizeof(uint32_t));
+           (size_t)cfg_.maxBatch * (h_.vocabSize * sizeof(float) + hipk::kLogitFilterStateWords * sizeof(uint32_t)) +
+           // JSON mode: the states, and the token table that setJsonTable uploads later (its entries and
+           // an estimate of 16 padded bytes per piece; setJsonTable checks the real size)
+           (size_t)cfg_.nSlots * sizeof(uint4) + (size_t)h_.vocabSize * (sizeof(uint2) + 16);
 }
 
 // Device state of the pooling kernel (root rank): per slot the accumulator, the output, the norm's
@@ -133,6 +136,8 @@ void HipEngineImpl::allocBuffers() {
         hProcNBias_ = halloc<int>(S);
         DL_HIP(hipMemsetAsync(dProcCounts_, 0, S * V * sizeof(uint32_t), stream_));
         DL_HIP(hipMemsetAsync(dProcNBias_, 0, S * sizeof(int), stream_));
+        dJsonStates_ = dalloc<uint4>(S);
+        DL_HIP(hipMemsetAsync(dJsonStates_, 0, S * sizeof(uint4), stream_));
         dFilterState_ = dalloc<uint32_t>((size_t)MB * hipk::kLogitFilterStateWords);
         DL_HIP(hipMemsetAsync(dFilterState_, 0, (size_t)MB * hipk::kLogitFilterStateWords * sizeof(uint32_t), stream_));
     }

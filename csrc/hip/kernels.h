@@ -714,6 +714,36 @@ struct PoolArgs {
 };
 void launchPool(const PoolArgs &a, int B, hipStream_t s);
 
+// JSON mode (csrc/core/json_grammar.h): the token mask between the logit processors and the candidate
+// filter, and the automaton's advance behind the draw. A row b takes part when proc[b].w != 0 (its
+// request is constrained) and spec[b].x >= 0 (it draws); its state is states[slots[b]].
+// launchJsonMask, in place on [B][vocab] logits: x[t] = -inf for every token t that is not allowed
+// in the row's state (jsonStepToken rejects), the others keep their bits; every other row is neither
+// read nor written. Grid (ceil(vocab / 256), B), one thread per token, which walks the token's bytes
+// (4-byte words of the table) through jsonStep; the row's state is read once per workgroup; four
+// neighbouring lanes' verdicts meet in one lane that stores the 16-byte vector (loading it first
+// only when the verdicts differ), the vocab % 4 tail is stored per element. No atomics, no scratch:
+// a row's result does not depend on the rest of the launch.
+// launchJsonAdvance, behind the draw: one thread per row steps states[slots[b]] by the bytes of
+// ids[b]; a token that is not allowed leaves the state as it is (jsonAdvanceHost). A forward holds
+// at most one drawn row per slot.
+struct JsonTable {
+    const uint2 *meta = nullptr;      // [vocab] (offset in words, length | class << 16)
+    const uint32_t *words = nullptr;  // the pieces' bytes, zero-padded to 4-byte words
+};
+struct JsonMaskArgs {
+    float *logits = nullptr;        // [B][vocab], masked in place
+    int vocab = 0;
+    const float4 *spec = nullptr;   // [B] (temperature, -, -, -)
+    const float4 *proc = nullptr;   // [B] (-, -, -, constrained)
+    const int *slots = nullptr;     // [B]
+    JsonTable table;
+    uint4 *states = nullptr;        // [nSlots] JsonState
+    const int *ids = nullptr;       // [B] the drawn tokens (launchJsonAdvance)
+};
+void launchJsonMask(const JsonMaskArgs &a, int B, hipStream_t s);
+void launchJsonAdvance(const JsonMaskArgs &a, int B, hipStream_t s);
+
 // Round-trip f32 partial sums through Q80 blocks in place (the reference's ZQ cast before the
 // exchange) - used ahead of a plain all-reduce when the fused exchange is not available.
 void launchQ80Roundtrip(float *x, size_t n, hipStream_t s);

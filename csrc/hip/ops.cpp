@@ -1582,6 +1582,149 @@ void benchLogitFilter(int B, int vocab, int topK, float delta, int iters, double
     (void)hipEventDestroy(e1);
 }
 
+namespace {
+// table, spec / proc rows, slots (row b's state is states[b]) and the states of a JsonMaskArgs
+hipk::JsonMaskArgs jsonMaskArgs(Scratch &sc, int B, int vocab, const std::vector<float> &temps,
+                                const std::vector<int> &on, const std::vector<uint32_t> &off,
+                                const std::vector<uint32_t> &info, const std::vector<uint32_t> &words,
+                                const std::vector<uint32_t> &states) {
+    DL_CHECK(B >= 1 && vocab >= 1, "json_mask sizes");
+    DL_CHECK(temps.size() == (size_t)B && on.size() == (size_t)B && states.size() == (size_t)B * 4,
+             "json_mask: one temperature, flag and 4-word state per row");
+    DL_CHECK(off.size() == (size_t)vocab && info.size() == (size_t)vocab && !words.empty(), "json_mask: the table is [vocab]");
+    std::vector<uint32_t> meta((size_t)vocab * 2);
+    for (int t = 0; t < vocab; t++) {
+        const uint32_t len = info[t] & 0xffffu;
+        DL_CHECK((size_t)off[t] + (len + 3) / 4 <= words.size(), "json_mask: a piece lies outside the table's words");
+        meta[(size_t)t * 2] = off[t];
+        meta[(size_t)t * 2 + 1] = info[t];
+    }
+    std::vector<float> spec((size_t)B * 4, 0.f), proc((size_t)B * 4, 0.f);
+    std::vector<int> slots(B);
+    for (int b = 0; b < B; b++) {
+        spec[(size_t)b * 4] = temps[b];
+        proc[(size_t)b * 4 + 3] = on[b] ? 1.f : 0.f;
+        slots[b] = b;
+    }
+    hipk::JsonMaskArgs g;
+    g.vocab = vocab;
+    g.spec = reinterpret_cast<const float4 *>(sc.upload(spec));
+    g.proc = reinterpret_cast<const float4 *>(sc.upload(proc));
+    g.slots = sc.upload(slots);
+    g.table.meta = reinterpret_cast<const uint2 *>(sc.upload(meta));
+    g.table.words = sc.upload(words);
+    g.states = reinterpret_cast<uint4 *>(sc.upload(states));
+    return g;
+}
+}  // namespace
+
+std::vector<float> jsonMask(const std::vector<float> &logits, int B, int vocab, const std::vector<float> &temps,
+                            const std::vector<int> &on, const std::vector<uint32_t> &off,
+                            const std::vector<uint32_t> &info, const std::vector<uint32_t> &words,
+                            const std::vector<uint32_t> &states) {
+    DL_CHECK(B >= 1 && vocab >= 1 && logits.size() == (size_t)B * vocab, "json_mask: logits is [B][vocab]");
+    Scratch sc;
+    hipk::JsonMaskArgs g = jsonMaskArgs(sc, B, vocab, temps, on, off, info, words, states);
+    constexpr size_t kPad = 256;  // guard elements behind the last row
+    const float guard = -7.5f;
+    std::vector<float> padded(logits);
+    padded.resize(logits.size() + kPad, guard);
+    g.logits = sc.upload(padded);
+    hipk::launchJsonMask(g, B, sc.s);
+    sc.sync();
+    std::vector<float> out = sc.download(g.logits, padded.size());
+    for (size_t i = logits.size(); i < out.size(); i++)
+        DL_CHECK(std::memcmp(&out[i], &guard, sizeof(float)) == 0, "json_mask: the launch wrote past the last row");
+    const std::vector<uint32_t> after = sc.download(reinterpret_cast<const uint32_t *>(g.states), states.size());
+    DL_CHECK(after == states, "json_mask: the launch changed a state");
+    out.resize(logits.size());
+    return out;
+}
+
+std::vector<uint32_t> jsonAdvance(int vocab, const std::vector<float> &temps, const std::vector<int> &on,
+                                  const std::vector<int> &ids, const std::vector<uint32_t> &off,
+                                  const std::vector<uint32_t> &info, const std::vector<uint32_t> &words,
+                                  const std::vector<uint32_t> &states) {
+    const int B = (int)temps.size();
+    DL_CHECK(ids.size() == (size_t)B, "json_advance: one drawn id per row");
+    Scratch sc;
+    hipk::JsonMaskArgs g = jsonMaskArgs(sc, B, vocab, temps, on, off, info, words, states);
+    g.ids = sc.upload(ids);
+    hipk::launchJsonAdvance(g, B, sc.s);
+    sc.sync();
+    return sc.download(reinterpret_cast<const uint32_t *>(g.states), states.size());
+}
+
+void benchJsonMask(int B, int vocab, const std::vector<uint32_t> &off, const std::vector<uint32_t> &info,
+                   const std::vector<uint32_t> &words, const std::vector<uint32_t> &state, int iters, double &copyUs,
+                   double &copyMaskUs, double &advanceUs, double &copyFilterUs, double &sampleUs) {
+    DL_CHECK(B >= 1 && vocab >= 2 && iters >= 1 && state.size() == 4, "bench_json_mask arguments");
+    Scratch sc;
+    std::vector<float> logits((size_t)B * vocab);
+    uint32_t r = 12345u;  // sums of 4 uniform draws: a bell shape over about [-8, 8]
+    for (size_t i = 0; i < logits.size(); i++) {
+        float v = 0.f;
+        for (int j = 0; j < 4; j++) {
+            r = r * 1664525u + 1013904223u;
+            v += (float)(r >> 8) * (1.f / 16777216.f);
+        }
+        logits[i] = (v - 2.f) * 4.f;
+    }
+    std::vector<uint32_t> states;
+    for (int b = 0; b < B; b++) states.insert(states.end(), state.begin(), state.end());
+    hipk::JsonMaskArgs g = jsonMaskArgs(sc, B, vocab, std::vector<float>(B, 0.8f), std::vector<int>(B, 1), off, info, words, states);
+    hipk::LogitFilterArgs f = logitFilterArgs(sc, B, vocab, std::vector<float>(B, 0.8f), std::vector<int>(B, 40),
+                                              std::vector<float>(B, -INFINITY), std::vector<int>(B, 1));
+    const float *src = sc.upload(logits);
+    g.logits = sc.alloc<float>(logits.size());
+    f.logits = g.logits;
+    // the advance steps a scratch copy of the states (so that the mask's stay put) by token 0's bytes
+    hipk::JsonMaskArgs adv = g;
+    adv.states = reinterpret_cast<uint4 *>(sc.upload(states));
+    adv.ids = sc.alloc<int>(B);  // (alloc zero-fills)
+    const size_t bytes = logits.size() * sizeof(float);
+    hipk::SampleArgs sa;
+    sa.logits = g.logits;
+    sa.vocab = vocab;
+    std::vector<float> sspec((size_t)B * 4, 0.f);
+    for (int b = 0; b < B; b++) {
+        sspec[(size_t)b * 4] = 0.8f;
+        sspec[(size_t)b * 4 + 1] = 0.9f;
+        sspec[(size_t)b * 4 + 2] = (float)((b * 37 + 11) % 100) * 0.01f;
+    }
+    sa.spec = reinterpret_cast<const float4 *>(sc.upload(sspec));
+    sa.ids = sc.alloc<int>(B);
+    sa.scratch.carve(sc.alloc<uint8_t>(hipk::SampleScratch::bytes(B)), B);  // (alloc zero-fills)
+    hipEvent_t e0, e1;
+    DL_HIP(hipEventCreate(&e0));
+    DL_HIP(hipEventCreate(&e1));
+    auto timed = [&](auto launch) {
+        for (int i = 0; i < 5; i++) launch();
+        DL_HIP(hipEventRecord(e0, sc.s));
+        for (int i = 0; i < iters; i++) launch();
+        DL_HIP(hipEventRecord(e1, sc.s));
+        DL_HIP(hipEventSynchronize(e1));
+        float ms = 0;
+        DL_HIP(hipEventElapsedTime(&ms, e0, e1));
+        return (double)ms * 1000.0 / iters;
+    };
+    auto copy = [&] { DL_HIP(hipMemcpyAsync(g.logits, src, bytes, hipMemcpyDeviceToDevice, sc.s)); };
+    copyUs = timed(copy);
+    copyFilterUs = timed([&] {
+        copy();
+        hipk::launchLogitFilter(f, B, sc.s);
+    });
+    copyMaskUs = timed([&] {
+        copy();
+        hipk::launchJsonMask(g, B, sc.s);
+    });
+    sampleUs = timed([&] { hipk::launchSample(sa, B, sc.s); });  // on the masked rows
+    advanceUs = timed([&] { hipk::launchJsonAdvance(adv, B, sc.s); });
+    sc.sync();
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+}
+
 std::vector<float> embedding(const std::vector<float> &table, int vocab, int dim, const std::vector<int> &tokens) {
     const int B = (int)tokens.size();
     DL_CHECK(dim % 4 == 0 && table.size() == (size_t)vocab * dim, "embedding sizes");

@@ -274,6 +274,26 @@ std::vector<float> logitFilter(const std::vector<float> &logits, int B, int voca
 void benchLogitFilter(int B, int vocab, int topK, float delta, int iters, double &copyUs, double &copyFilterUs,
                       double &sampleUs);
 
+// JSON mode's kernels on their own. The token table is JsonTokenTable's three arrays (backend.h), a
+// state is a JsonState as 4 words; row b takes part when on[b] and temps[b] >= 0, and its state is
+// states[b]. jsonMask: launchJsonMask over a copy of [B][vocab] logits, returns the buffer after the
+// launch; a write behind its last row, or a state that changed, is an error. jsonAdvance:
+// launchJsonAdvance with the drawn ids, returns the states after the launch.
+std::vector<float> jsonMask(const std::vector<float> &logits, int B, int vocab, const std::vector<float> &temps,
+                            const std::vector<int> &on, const std::vector<uint32_t> &off,
+                            const std::vector<uint32_t> &info, const std::vector<uint32_t> &words,
+                            const std::vector<uint32_t> &states);
+std::vector<uint32_t> jsonAdvance(int vocab, const std::vector<float> &temps, const std::vector<int> &on,
+                                  const std::vector<int> &ids, const std::vector<uint32_t> &off,
+                                  const std::vector<uint32_t> &info, const std::vector<uint32_t> &words,
+                                  const std::vector<uint32_t> &states);
+// Device microseconds as in benchLogitFilter, on B constrained rows that all sit in `state`: a device
+// copy of the logits; the copy + launchJsonMask; launchJsonAdvance (by token 0); the copy +
+// launchLogitFilter (top_k 40) on the same logits; launchSample on the masked rows.
+void benchJsonMask(int B, int vocab, const std::vector<uint32_t> &off, const std::vector<uint32_t> &info,
+                   const std::vector<uint32_t> &words, const std::vector<uint32_t> &state, int iters, double &copyUs,
+                   double &copyMaskUs, double &advanceUs, double &copyFilterUs, double &sampleUs);
+
 // Embedding row gather: table [vocab][dim] -> [B][dim].
 std::vector<float> embedding(const std::vector<float> &table, int vocab, int dim, const std::vector<int> &tokens);
 

@@ -121,9 +121,28 @@ std::vector<int> runArgmax(Backend &b, const std::vector<int> &tokens, const std
     return out;
 }
 
+// A JsonState from / to Python: 4 uint32 words, the struct's 16 bytes (word 0 = lex | aux << 8 |
+// ws << 16 | depth << 24, words 2 and 3 the stack); lex 255 = rejected.
+JsonState stateFromWords(const std::vector<uint32_t> &w) {
+    DL_CHECK(w.size() == 4, "a JSON state is 4 words");
+    JsonState s;
+    std::memcpy(&s, w.data(), sizeof(s));
+    s.pad = 0;
+    return s;
+}
+std::vector<uint32_t> stateToWords(const JsonState &s) {
+    std::vector<uint32_t> w(4);
+    std::memcpy(w.data(), &s, sizeof(s));
+    return w;
+}
+struct PyJsonTable {
+    std::shared_ptr<JsonTokenTable> t;
+};
+
 // Per-row logit processors (Backend LogitProc) from Python: None (no row has one) or a sequence
 // of n entries, each None (the row has none) or a dict with the optional keys "presence",
-// "frequency", "fresh" and "bias" (a dict token id -> value, read when fresh).
+// "frequency", "fresh", "bias" (a dict token id -> value, read when fresh), "top_k", "min_p" and
+// "json" (the row is in JSON mode: set_json_table first).
 std::vector<LogitProc> parseProcs(const py::object &o, size_t n) {
     std::vector<LogitProc> procs;
     if (o.is_none()) return procs;
@@ -141,6 +160,7 @@ std::vector<LogitProc> parseProcs(const py::object &o, size_t n) {
         if (d.contains("fresh")) p.fresh = d["fresh"].cast<bool>();
         if (d.contains("top_k") && !d["top_k"].is_none()) p.topK = d["top_k"].cast<int>();
         if (d.contains("min_p") && !d["min_p"].is_none()) p.minP = d["min_p"].cast<float>();
+        if (d.contains("json") && !d["json"].is_none()) p.json = d["json"].cast<bool>();
         if (d.contains("bias") && !d["bias"].is_none())
             for (auto kv : d["bias"].cast<py::dict>()) p.bias.push_back(LogitBias{kv.first.cast<int>(), kv.second.cast<float>()});
     }
@@ -687,6 +707,58 @@ void bindOps(py::module_ &m) {
           },
           py::arg("batch"), py::arg("vocab"), py::arg("top_k"), py::arg("delta"), py::arg("iters") = 200,
           "(us per device copy of the logits, us per copy + launchLogitFilter, us per launchSample on the filtered rows)");
+    o.def("json_mask",
+          [](py::object logits, std::vector<float> temps, std::vector<int> on, const PyJsonTable &tb,
+             std::vector<std::vector<uint32_t>> states) {
+              const std::vector<float> l = vec<float>(logits);
+              const int B = (int)temps.size();
+              DL_CHECK(B >= 1 && l.size() % B == 0 && states.size() == (size_t)B, "json_mask: one temperature and state per row");
+              const int vocab = (int)(l.size() / B);
+              std::vector<uint32_t> st;
+              for (auto &s : states) {
+                  const std::vector<uint32_t> w = stateToWords(stateFromWords(s));
+                  st.insert(st.end(), w.begin(), w.end());
+              }
+              std::vector<float> out;
+              {
+                  py::gil_scoped_release rel;
+                  out = ops::jsonMask(l, B, vocab, temps, on, tb.t->off, tb.t->info, tb.t->words, st);
+              }
+              return arr(out, {B, vocab});
+          },
+          py::arg("logits"), py::arg("temperatures"), py::arg("on"), py::arg("table"), py::arg("states"));
+    o.def("json_advance",
+          [](std::vector<float> temps, std::vector<int> on, std::vector<int> ids, const PyJsonTable &tb,
+             std::vector<std::vector<uint32_t>> states) {
+              DL_CHECK(states.size() == temps.size(), "json_advance: one state per row");
+              std::vector<uint32_t> st;
+              for (auto &s : states) {
+                  const std::vector<uint32_t> w = stateToWords(stateFromWords(s));
+                  st.insert(st.end(), w.begin(), w.end());
+              }
+              std::vector<uint32_t> out;
+              {
+                  py::gil_scoped_release rel;
+                  out = ops::jsonAdvance(tb.t->vocab(), temps, on, ids, tb.t->off, tb.t->info, tb.t->words, st);
+              }
+              std::vector<std::vector<uint32_t>> res;
+              for (size_t b = 0; b < temps.size(); b++) res.emplace_back(out.begin() + 4 * b, out.begin() + 4 * b + 4);
+              return res;
+          },
+          py::arg("temperatures"), py::arg("on"), py::arg("ids"), py::arg("table"), py::arg("states"));
+    o.def("bench_json_mask",
+          [](int B, const PyJsonTable &tb, std::vector<uint32_t> state, int iters) {
+              double cu = 0, mu = 0, au = 0, fu = 0, su = 0;
+              {
+                  py::gil_scoped_release rel;
+                  ops::benchJsonMask(B, tb.t->vocab(), tb.t->off, tb.t->info, tb.t->words, stateToWords(stateFromWords(state)), iters,
+                                     cu, mu, au, fu, su);
+              }
+              return py::make_tuple(cu, mu, au, fu, su);
+          },
+          py::arg("batch"), py::arg("table"), py::arg("state"), py::arg("iters") = 200,
+          "(us per device copy of the logits, per copy + launchJsonMask, per launchJsonAdvance, per copy + "
+          "launchLogitFilter with top_k 40, per launchSample on the masked rows), every row in `state`");
     o.def("pool",
           [](py::list launches, int dim, int nSlots, py::array_t<float, py::array::c_style | py::array::forcecast> normW,
              float eps, py::array_t<float, py::array::c_style | py::array::forcecast> outInit,
@@ -829,6 +901,14 @@ PYBIND11_MODULE(_C, m) {
            },
            py::arg("logits"), py::arg("top_k"), py::arg("delta"),
            "One row through logitFilterHost: top_k (0 or >= vocab: off), delta = min_p_delta(T, min_p) (-inf: off).");
+    co.def("json_walk",
+           [](py::bytes data, py::object state) {
+               JsonState s = state.is_none() ? jsonStart() : stateFromWords(state.cast<std::vector<uint32_t>>());
+               for (unsigned char c : std::string(data)) s = jsonStep(s, c);
+               return stateToWords(s);
+           },
+           py::arg("data"), py::arg("state") = py::none(),
+           "The JSON automaton's state (4 words; word 0 & 255 == 255: rejected) behind `data`, from `state` (None: START).");
     co.def("min_p_delta", &minPDelta, py::arg("temperature"), py::arg("min_p"),
            "T * log(min_p) as float32 (-inf for min_p <= 0): the distance below the row maximum that min_p keeps.");
     co.def("pool_host",
@@ -1018,7 +1098,33 @@ PYBIND11_MODULE(_C, m) {
             return py::make_tuple(py::bytes(c.content), py::bytes(c.publicPrompt));
         });
 
+    py::class_<PyJsonTable>(m, "JsonTable")
+        .def(py::init([](std::vector<py::bytes> pieces, int bosId, std::vector<int> eosIds) {
+                 std::vector<std::string> p;
+                 for (auto &b : pieces) p.push_back(std::string(b));
+                 return PyJsonTable{std::make_shared<JsonTokenTable>(makeJsonTokenTable(p, bosId, eosIds))};
+             }),
+             py::arg("pieces"), py::arg("bos_id"), py::arg("eos_ids"))
+        .def_property_readonly("vocab", [](const PyJsonTable &t) { return t.t->vocab(); })
+        .def_property_readonly("bytes", [](const PyJsonTable &t) { return t.t->bytes(); })
+        .def("mask_host",
+             [](const PyJsonTable &t, py::array_t<float, py::array::c_style | py::array::forcecast> logits,
+                std::vector<uint32_t> state) {
+                 py::array_t<float> out((py::ssize_t)logits.size());
+                 std::copy(logits.data(), logits.data() + logits.size(), out.mutable_data());
+                 jsonMaskHost(out.mutable_data(), (int)logits.size(), *t.t, stateFromWords(state));
+                 return out;
+             },
+             py::arg("logits"), py::arg("state"), "One row through jsonMaskHost.")
+        .def("advance_host",
+             [](const PyJsonTable &t, std::vector<uint32_t> state, int token) {
+                 return stateToWords(jsonAdvanceHost(*t.t, stateFromWords(state), token));
+             },
+             py::arg("state"), py::arg("token"))
+        .def("dead_end", [](const PyJsonTable &t) { return jsonDeadEnd(*t.t); });
+
     py::class_<Backend>(m, "Backend")
+        .def("set_json_table", [](Backend &b, const PyJsonTable &t) { b.setJsonTable(t.t); }, py::arg("table"))
         .def_property_readonly("header", [](const Backend &b) { return headerToDict(b.header()); })
         .def_property_readonly("name", &Backend::name)
         .def("forward", [](Backend &b, std::vector<int> t, std::vector<int> p, std::vector<int> s) { return runForward(b, t, p, s); },
@@ -1454,6 +1560,7 @@ PYBIND11_MODULE(_C, m) {
                                    d["device_bytes"] = l.deviceBytes;
                                    return d;
                                })
+        .def("set_json_table", [](PyHipEngine &e, const PyJsonTable &t) { e.engine->setJsonTable(t.t); }, py::arg("table"))
         .def("forward", [](PyHipEngine &e, std::vector<int> t, std::vector<int> p, std::vector<int> s) { return runForward(*e.engine, t, p, s); },
              py::arg("tokens"), py::arg("positions"), py::arg("slots"))
         .def("forward_sample",

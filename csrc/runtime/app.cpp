@@ -257,6 +257,18 @@ InferenceSession::InferenceSession(const AppArgs &args, int nSlots) : args_(args
     for (auto &s : workers_) s.resetStats();
 }
 
+std::string InferenceSession::enableJsonMode() {
+    if (!tokenizer_) return "no tokenizer";
+    const int V = tokenizer_->vocabSize();
+    std::vector<std::string> pieces(V);
+    for (int t = 0; t < V; t++) pieces[t] = tokenizer_->piece(t);
+    auto table = std::make_shared<JsonTokenTable>(makeJsonTokenTable(pieces, tokenizer_->bosId(), tokenizer_->eosTokenIds()));
+    const std::string why = jsonDeadEnd(*table);
+    if (!why.empty()) return why;
+    backend_->setJsonTable(table);
+    return "";
+}
+
 InferenceSession::~InferenceSession() {
     try {
         finish();

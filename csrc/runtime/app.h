@@ -102,6 +102,10 @@ class InferenceSession {
     // logit processors of the next forwardSample / launchIds (Backend::setLogitProcs; the root
     // draws, so nothing goes to the workers)
     void setLogitProcs(int n, const LogitProc *procs) { backend_->setLogitProcs(n, procs); }
+    // JSON mode (LogitProc::json): builds the token table from the tokenizer, checks that the
+    // vocabulary cannot dead-end (jsonDeadEnd) and hands the table to the backend. Returns an empty
+    // string, or why JSON mode is unavailable (the backend then has no table).
+    std::string enableJsonMode();
     // pooling of the next forwardSample / launchIds (Backend::setPooling; the root pools). When no
     // row of that forward draws, the workers get a FORWARD_EMBED instead of the FORWARD_SAMPLE.
     void setPooling(int n, const PoolSpec *pool);

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <functional>
 #include <numeric>
+#include <string>
 #include <vector>
 
 #include "../text/tokenizer.h"
@@ -76,6 +77,80 @@ void logitFilterHost(float *x, int vocab, int topK, float delta) {
     }
     for (int t = 0; t < vocab; t++)
         if (!(x[t] >= thr)) x[t] = -INFINITY;
+}
+
+JsonTokenTable makeJsonTokenTable(const std::vector<std::string> &pieces, int bosId, const std::vector<int> &eosIds) {
+    JsonTokenTable t;
+    const size_t V = pieces.size();
+    t.off.resize(V);
+    t.info.resize(V);
+    for (size_t id = 0; id < V; id++) {
+        const std::string &p = pieces[id];
+        if (p.size() > 0xffffu) throw Error("json mode: a vocabulary piece is longer than 65535 bytes");
+        u32 cls = (int)id < bosId ? JT_REGULAR : JT_BANNED;
+        if (std::find(eosIds.begin(), eosIds.end(), (int)id) != eosIds.end()) cls = JT_EOS;
+        t.off[id] = (u32)t.words.size();
+        t.info[id] = (u32)p.size() | cls << 16;
+        for (size_t i = 0; i < p.size(); i += 4) {
+            u32 w = 0;
+            for (size_t j = i; j < std::min(i + 4, p.size()); j++) w |= (u32)(u8)p[j] << (8 * (j - i));
+            t.words.push_back(w);
+        }
+    }
+    t.words.push_back(0);  // (never empty: an all-special vocabulary still uploads)
+    return t;
+}
+
+void jsonMaskHost(float *x, int vocab, const JsonTokenTable &table, const JsonState &state) {
+    if (vocab != table.vocab()) throw Error("json mode: the token table is not the model's vocabulary");
+    for (int t = 0; t < vocab; t++)
+        if (jsonRejected(jsonStepToken(state, table.words.data(), table.off[t], table.info[t]))) x[t] = -INFINITY;
+}
+
+JsonState jsonAdvanceHost(const JsonTokenTable &table, const JsonState &state, int token) {
+    if (token < 0 || token >= table.vocab()) return state;
+    const JsonState next = jsonStepToken(state, table.words.data(), table.off[token], table.info[token]);
+    return jsonRejected(next) ? state : next;
+}
+
+std::string jsonDeadEnd(const JsonTokenTable &table) {
+    bool eos = false;
+    std::vector<u8> single;  // the bytes that some regular one-byte piece spells
+    for (int t = 0; t < table.vocab(); t++) {
+        if (jsonTokenClass(table.info[t]) == JT_EOS) eos = true;
+        if (jsonTokenClass(table.info[t]) == JT_REGULAR && jsonTokenLen(table.info[t]) == 1)
+            single.push_back((u8)(table.words[table.off[t]] & 0xffu));
+    }
+    if (!eos) return "the vocabulary has no EOS token to end a finished object with";
+    for (int lex = 0; lex < JL_DONE; lex++) {
+        std::vector<u8> auxes = {0};
+        if (lex == JL_KEY_HEX || lex == JL_STR_HEX) auxes = {1, 2, 3, 4};
+        if (lex == JL_KEY_UTF8 || lex == JL_STR_UTF8) auxes = {1, 2, 3, 2 | 1 << 2, 2 | 2 << 2, 3 | 3 << 2, 3 | 4 << 2};
+        if (lex == JL_LIT) auxes = {1, 2, 3, 1 << 4 | 1, 1 << 4 | 2, 1 << 4 | 3, 1 << 4 | 4, 2 << 4 | 1, 2 << 4 | 2, 2 << 4 | 3};
+        for (u8 aux : auxes)
+            for (int obj = 0; obj < 2; obj++) {
+                JsonState s = jsonStart();
+                s.lex = (u8)lex;
+                s.aux = aux;
+                if (lex != JL_START) {
+                    const bool between = lex <= JL_KEY_NEXT || (lex >= JL_COLON && lex <= JL_ARR_OPEN) || lex == JL_AFTER;
+                    s.ws = between ? kJsonMaxWs : 0;
+                    s.depth = kJsonMaxDepth;
+                    s.stack = obj ? ~0ull : ~0ull >> 1;
+                } else {
+                    s.ws = kJsonMaxWs;
+                }
+                // (a state's kind of innermost container is fixed where it opens or names one)
+                if ((lex == JL_OBJ_OPEN || lex == JL_KEY_NEXT || (lex >= JL_KEY && lex <= JL_COLON)) && !obj) continue;
+                if (lex == JL_ARR_OPEN && obj) continue;
+                bool ok = false;
+                for (u8 c : single) ok = ok || !jsonRejected(jsonStep(s, c));
+                if (!ok)
+                    return "no single-byte token continues lexer state " + std::to_string(lex) + " (aux " +
+                           std::to_string((int)aux) + ", inside an " + (obj ? "object" : "array") + ")";
+            }
+    }
+    return "";
 }
 
 void poolAddHost(float *acc, const float *x, const float *add, int dim, const float *normW, float eps, bool first,
@@ -187,6 +262,11 @@ void Backend::forwardEmbed(int n, const int *tokens, const int *positions, const
 
 void Backend::setLogitProcs(int n, const LogitProc *procs) { pendingProcs_.assign(procs, procs + n); }
 
+void Backend::setJsonTable(std::shared_ptr<const JsonTokenTable> table) {
+    if (table && table->vocab() != (int)header().vocabSize) throw Error("json mode: the token table is not the model's vocabulary");
+    jsonTable_ = std::move(table);
+}
+
 std::vector<LogitProc> Backend::takeLogitProcs(int n) {
     std::vector<LogitProc> procs;
     procs.swap(pendingProcs_);
@@ -199,6 +279,7 @@ std::vector<LogitProc> Backend::takeLogitProcs(int n) {
         any = true;
         if (p.topK < 0) throw Error("top_k: a count >= 0");
         if (!(p.minP >= 0.f && p.minP <= 1.f)) throw Error("min_p: a number from 0 to 1");
+        if (p.json && plan().rank == 0 && !jsonTable_) throw Error("json mode: no token table (setJsonTable)");
         if (!p.fresh) continue;
         if (p.bias.size() > (size_t)kMaxLogitBias) throw Error("logit_bias: at most 300 entries");
         std::vector<int> seen;
@@ -260,11 +341,17 @@ void Backend::forwardSample(int n, const int *tokens, const int *positions, cons
             if (p.fresh) procBias_[s] = p.bias;
             logitProcHost(row, vocab, procCounts_[s].data(), p.presence, p.frequency, procBias_[s].data(),
                           (int)procBias_[s].size(), row);
+            if (p.json) {  // behind the bias, ahead of the candidate filter: top_k counts allowed tokens
+                if (jsonStates_.size() <= s) jsonStates_.resize(s + 1, jsonStart());
+                if (p.fresh) jsonStates_[s] = jsonStart();
+                jsonMaskHost(row, vocab, *jsonTable_, jsonStates_[s]);
+            }
             if (p.filter(specs[i].temperature, vocab))
                 logitFilterHost(row, vocab, p.topK, minPDelta(specs[i].temperature, p.minP));
         }
         out[i] = sampleHost(row, vocab, specs[i]);
         if (proc && out[i] >= 0 && out[i] < vocab) procCounts_[(size_t)slots[i]][out[i]]++;
+        if (proc && procs[i].json) jsonStates_[(size_t)slots[i]] = jsonAdvanceHost(*jsonTable_, jsonStates_[(size_t)slots[i]], out[i]);
         if (req >= 1)
             logprobsHost(raw.data(), vocab, out[i], std::min(req - 1, kMaxTopLogprobs),
                          &logprobs_[(size_t)i * kLogprobEntries]);

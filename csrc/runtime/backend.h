@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "../core/json_grammar.h"
 #include "../core/model_file.h"
 #include "../core/plan.h"
 
@@ -104,6 +105,11 @@ struct LogitProc {
     bool filter(float temperature, int vocab) const {
         return active && temperature > 0.f && ((topK >= 1 && topK < vocab) || minP > 0.f);
     }
+    // JSON mode (jsonMaskHost): the row's draw is confined to the tokens that keep its sequence's
+    // generated text a prefix of a JSON object; acts on every drawn row (greedy too), between the
+    // bias and the candidate filter. The backend keeps the automaton's state per KV slot: a fresh
+    // row restarts it, every drawn token advances it. Needs Backend::setJsonTable.
+    bool json = false;
 };
 // Host implementation (the CPU path and the reference for the device kernel); out may be logits.
 void logitProcHost(const float *logits, int vocab, const u32 *counts, float presence, float frequency,
@@ -120,6 +126,27 @@ void logitProcHost(const float *logits, int vocab, const u32 *counts, float pres
 // place a logarithm is taken.
 float minPDelta(float T, float minP);
 void logitFilterHost(float *x, int vocab, int topK, float delta);
+
+// JSON mode (`response_format: json_object`, csrc/core/json_grammar.h). The table holds every
+// token's bytes (the vocabulary piece, as the logprobs `bytes` field reports it) zero-padded to
+// 4-byte words, its offset in words and its length | class << 16: ids below bosId are regular
+// pieces, eosIds are EOS, every other special token is banned. A token is allowed in state s iff
+// jsonStepToken does not reject: a regular piece of >= 1 byte whose bytes all step, or an EOS in DONE.
+struct JsonTokenTable {
+    std::vector<u32> off, info, words;
+    int vocab() const { return (int)info.size(); }
+    size_t bytes() const { return (off.size() + info.size() + words.size()) * sizeof(u32); }
+};
+JsonTokenTable makeJsonTokenTable(const std::vector<std::string> &pieces, int bosId, const std::vector<int> &eosIds);
+// x[t] = -inf for the tokens that are not allowed in `state`; the others pass bit for bit.
+void jsonMaskHost(float *x, int vocab, const JsonTokenTable &table, const JsonState &state);
+// The state behind a drawn token; a token that is not allowed (or no token: id outside the table)
+// leaves the state as it is.
+JsonState jsonAdvanceHost(const JsonTokenTable &table, const JsonState &state, int token);
+// Startup check: in every lexer state, with the whitespace run and the depth at their caps and
+// under both container kinds, some single-byte regular token must be allowed (in DONE: an EOS must
+// exist). Returns the first state without one as text, empty when the vocabulary cannot dead-end.
+std::string jsonDeadEnd(const JsonTokenTable &table);
 
 // Embeddings: the pooled, L2-normalised final hidden state of a request's prompt rows. For a request
 // whose prompt is N >= 1 rows at positions 0 .. N - 1, with x[i] row i's final residual:
@@ -178,6 +205,8 @@ class Backend {
     // the counts of the tokens drawn by active rows since the slot's last `fresh` row, and the bias
     // that row brought. Root only (the root draws); without a call, forwards run as they always did.
     virtual void setLogitProcs(int n, const LogitProc *procs);
+    // The token table of JSON mode (LogitProc::json), once, before the first such row. Root only.
+    virtual void setJsonTable(std::shared_ptr<const JsonTokenTable> table);
     // Log-probabilities of the last forwardSample / collectIds: [n][kLogprobEntries] when a row of
     // that forward asked for them (SampleSpec::logprobs; rows that did not hold id -1 throughout),
     // empty otherwise and on ranks other than the root. Valid until the next forward is launched.
@@ -245,6 +274,8 @@ class Backend {
     // host state of the default forwardSample, per slot (allocated at a slot's first fresh row)
     std::vector<std::vector<u32>> procCounts_;
     std::vector<std::vector<LogitBias>> procBias_;
+    std::shared_ptr<const JsonTokenTable> jsonTable_;
+    std::vector<JsonState> jsonStates_;  // host state of the default forwardSample, per slot
     std::vector<PoolSpec> pendingPool_;  // setPooling, until the next forward takes it
     PooledSlots pooled_;
     // takes pendingPool_ for a forward of n rows (empty: none set, or no row takes part); checks the

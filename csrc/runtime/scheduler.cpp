@@ -553,6 +553,7 @@ bool Scheduler::step() {
                     if (lp.fresh) lp.bias = gp.logitBias;
                     lp.topK = gp.topK;
                     lp.minP = gp.minP;
+                    lp.json = gp.jsonObject;
                 }
                 sess_.setLogitProcs(next.n, procs.data());
             }
@@ -622,6 +623,7 @@ bool Scheduler::step() {
             stats_.completed++;
             if (r->params.penalized()) stats_.logitProcRequests++;
             if (r->params.logitFilter()) stats_.logitFilterRequests++;
+            if (r->params.jsonObject) stats_.jsonRequests++;
             stats_.generatedTokens += r->generated.size();
             finishRequest(rp, reason);
         }

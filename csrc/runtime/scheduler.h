@@ -46,10 +46,13 @@ struct GenParams {
     int topK = 0;
     float minP = 0.f;
     EmbedMode embed = EmbedMode::OFF;
+    // JSON mode (response_format json_object): every drawn token keeps the generated text a prefix of
+    // a JSON object (jsonMaskHost), between the bias and the candidate filter; greedy requests too
+    bool jsonObject = false;
     bool penalized() const { return presencePenalty != 0.f || frequencyPenalty != 0.f || !logitBias.empty(); }
     bool logitFilter() const { return temperature != 0.f && (topK > 0 || minP > 0.f); }
     // the request's drawn rows carry a LogitProc
-    bool logitProc() const { return penalized() || logitFilter(); }
+    bool logitProc() const { return penalized() || logitFilter() || jsonObject; }
 };
 
 // One generated token's log-probability record (GenParams::logprobs).
@@ -110,6 +113,7 @@ struct SchedulerStats {
     u64 prefixHits = 0, prefixTokens = 0, prefixCopies = 0, prefixEvictions = 0;
     u64 logitProcRequests = 0;  // finished requests that used penalties or a logit bias
     u64 logitFilterRequests = 0;  // finished requests with top_k or min_p on
+    u64 jsonRequests = 0;         // finished requests in JSON mode
     u64 embeddingRequests = 0;  // finished embedding requests
 };
 

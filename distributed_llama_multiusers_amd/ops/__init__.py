@@ -329,6 +329,32 @@ def ref_pool(x, norm_w, eps, mode="mean", add=None) -> np.ndarray:
     return p / np.sqrt(ss) if ss > 0 else np.zeros_like(p)
 
 
+def json_mask(logits, temperatures, on, table, states, fill=None):
+    """Device JSON token mask (launchJsonMask) of [B, vocab] logits. `table` is a `JsonTable` of the
+    vocabulary, states[b] row b's automaton state (4 words, as `cpu_ops.json_walk` returns). For a
+    row b with on[b] and temperatures[b] >= 0 every token that is not allowed in states[b] becomes
+    -inf; the others keep their bits. The kernel works in place and neither reads nor writes any
+    other row: with `fill`, those rows hold `fill` instead of their logits when the kernel runs, and
+    must hold it afterwards. Returns float32 [B, vocab], the buffer after the launch."""
+    x = _np(logits)
+    x = (x.reshape(1, -1) if x.ndim == 1 else x).copy()
+    temps = [float(t) for t in temperatures]
+    flags = [int(bool(a)) for a in on]
+    if fill is not None:
+        for b in range(x.shape[0]):
+            if not (flags[b] and temps[b] >= 0):
+                x[b] = fill
+    return native().ops.json_mask(x, temps, flags, table, [[int(w) for w in s] for s in states])
+
+
+def json_advance(temperatures, on, ids, table, states):
+    """Device automaton advance (launchJsonAdvance): states[b] stepped by the bytes of token ids[b]
+    for every row with on[b] and temperatures[b] >= 0; a token that is not allowed, and every other
+    row, leaves the state as it is. Returns the states after the launch (lists of 4 words)."""
+    return native().ops.json_advance([float(t) for t in temperatures], [int(bool(a)) for a in on],
+                                     [int(i) for i in ids], table, [[int(w) for w in s] for s in states])
+
+
 def argmax(logits) -> list:
     x = _np(logits)
     return native().ops.argmax(x, x.shape[0] if x.ndim == 2 else 1)

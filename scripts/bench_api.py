@@ -6,7 +6,7 @@ connection per request), and reports the aggregate completion tokens/s for tempe
 and temperature 0.8 / top_p 0.9 with per-request seeds (device sampling: only token ids come back
 to the host). One untimed round first captures the graphs.
 
-  python scripts/bench_api.py [--n 64] [--max-tokens 64] [--port 0] [--logprobs K] [--penalties] [--filters]
+  python scripts/bench_api.py [--n 64] [--max-tokens 64] [--port 0] [--logprobs K] [--penalties] [--filters] [--json]
                               [--embeddings]
 
 --embeddings: after the chat rounds, one /v1/embeddings request of N inputs of token ids (about 48
@@ -60,7 +60,7 @@ def _embed_round(port, n, tokens_each=48):
     return data["usage"]["prompt_tokens"], time.perf_counter() - t0
 
 
-EXTRA = {}  # request fields added to every body (--logprobs, --penalties, --filters)
+EXTRA = {}  # request fields added to every body (--logprobs, --penalties, --filters, --json)
 
 
 def _round(port, n, max_tokens, temperature, seed0):
@@ -100,11 +100,15 @@ def main():
     ap.add_argument("--filters", action="store_true",
                     help="every request sends top_k 40 and min_p 0.05: they act in the sampled round "
                          "(temperature 0.8), the greedy round ignores them")
+    ap.add_argument("--json", action="store_true",
+                    help="every request sends response_format json_object (JSON mode: both rounds are masked)")
     ap.add_argument("--embeddings", action="store_true",
                     help="also time one /v1/embeddings request of --n inputs, alone and next to a greedy chat round")
     args = ap.parse_args()
     if args.filters:
         EXTRA.update(top_k=40, min_p=0.05)
+    if args.json:
+        EXTRA.update(response_format={"type": "json_object"})
     if args.penalties:
         EXTRA.update(frequency_penalty=0.5, presence_penalty=0.5, logit_bias={str(1000 + 37 * i): (i % 5) - 2 for i in range(16)})
     if args.logprobs >= 0:
@@ -160,6 +164,7 @@ def main():
         res["top_logprobs"] = args.logprobs if args.logprobs >= 0 else None
         res["penalties"] = bool(args.penalties)
         res["filters"] = bool(args.filters)
+        res["json"] = bool(args.json)
         if args.embeddings:
             _embed_round(port, args.n)  # untimed: graph capture
             toks, dt = _embed_round(port, args.n)
