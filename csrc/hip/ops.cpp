@@ -9,107 +9,13 @@
 
 #include "../core/quant.h"
 #include "device_comm.h"
+#include "host_harness.h"
 #include "kernels.h"
 
 namespace dl {
 namespace ops {
 
 namespace {
-
-// Device allocations of one op call, released on scope exit.
-class Scratch {
-  public:
-    Scratch() { DL_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
-    ~Scratch() {
-        for (void *p : mem_) (void)hipFree(p);
-        (void)hipStreamDestroy(s);
-    }
-    template <typename T>
-    T *alloc(size_t count) {
-        void *p = nullptr;
-        const size_t bytes = count * sizeof(T) < 16 ? 16 : count * sizeof(T);
-        DL_HIP(hipMalloc(&p, bytes));
-        DL_HIP(hipMemsetAsync(p, 0, bytes, s));
-        mem_.push_back(p);
-        return static_cast<T *>(p);
-    }
-    template <typename T>
-    T *upload(const std::vector<T> &v) {
-        if (v.empty()) return nullptr;
-        T *p = alloc<T>(v.size());
-        DL_HIP(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
-        return p;
-    }
-    template <typename T>
-    std::vector<T> download(const T *p, size_t count) {
-        std::vector<T> v(count);
-        DL_HIP(hipMemcpyAsync(v.data(), p, count * sizeof(T), hipMemcpyDeviceToHost, s));
-        DL_HIP(hipStreamSynchronize(s));
-        return v;
-    }
-    void sync() {
-        DL_HIP(hipGetLastError());
-        DL_HIP(hipStreamSynchronize(s));
-    }
-    // Output buffer of `rows` rows of `ld` elements of which the first `valid` are results and the
-    // rest (ld - valid >= one workgroup's rows) guard, every byte preset to kGuardByte (a result
-    // the launch never wrote reads back as NaN). checkGuards() throws when a launch changed a
-    // guard byte: a store past the last valid row of an op is an error, not silent corruption.
-    static constexpr uint8_t kGuardByte = 0xFF;
-    template <typename T>
-    T *allocGuarded(size_t rows, size_t valid, size_t ld, const char *what) {
-        DL_CHECK(ld > valid && rows > 0, "guarded buffer needs a guard region");
-        void *p = nullptr;
-        const size_t bytes = rows * ld * sizeof(T);
-        DL_HIP(hipMalloc(&p, bytes));
-        mem_.push_back(p);
-        DL_HIP(hipMemsetAsync(p, kGuardByte, bytes, s));
-        guards_.push_back({static_cast<uint8_t *>(p), rows, valid * sizeof(T), ld * sizeof(T), what});
-        return static_cast<T *>(p);
-    }
-    // ... followed by `tail` whole guard rows (a store to a row past the last valid one); here the
-    // rows may be all valid (ld == valid: no room for a guard inside the row)
-    template <typename T>
-    T *allocGuardedTail(size_t rows, size_t valid, size_t ld, size_t tail, const char *what) {
-        DL_CHECK(ld >= valid && rows > 0 && tail > 0, "guarded buffer needs a guard region");
-        void *p = nullptr;
-        const size_t bytes = (rows + tail) * ld * sizeof(T);
-        DL_HIP(hipMalloc(&p, bytes));
-        mem_.push_back(p);
-        DL_HIP(hipMemsetAsync(p, kGuardByte, bytes, s));
-        guards_.push_back({static_cast<uint8_t *>(p), rows, valid * sizeof(T), ld * sizeof(T), what});
-        guards_.push_back({static_cast<uint8_t *>(p) + rows * ld * sizeof(T), tail, 0, ld * sizeof(T), what});
-        return static_cast<T *>(p);
-    }
-    void checkGuards() {
-        for (const Guard &g : guards_) {
-            const std::vector<uint8_t> v = download(g.p, g.rows * g.ld);
-            for (size_t r = 0; r < g.rows; r++)
-                for (size_t i = g.valid; i < g.ld; i++)
-                    DL_CHECK(v[r * g.ld + i] == kGuardByte,
-                             std::string("ops: the launch wrote past the valid part of ") + g.what + " (row " +
-                                 std::to_string(r) + ", byte " + std::to_string(i - g.valid) + " of its guard)");
-        }
-    }
-    // the valid part of a guarded buffer, rows packed
-    template <typename T>
-    std::vector<T> downloadRows(const T *p, size_t rows, size_t valid, size_t ld) {
-        const std::vector<T> all = download(p, rows * ld);
-        std::vector<T> v(rows * valid);
-        for (size_t r = 0; r < rows; r++) std::copy(all.begin() + r * ld, all.begin() + r * ld + valid, v.begin() + r * valid);
-        return v;
-    }
-    hipStream_t s = nullptr;
-
-  private:
-    struct Guard {
-        uint8_t *p;
-        size_t rows, valid, ld;  // bytes
-        const char *what;
-    };
-    std::vector<void *> mem_;
-    std::vector<Guard> guards_;
-};
 
 // File-layout Q40 blocks -> the engine's tiled device layout (csrc/hip/kernels.h Q40Tiling).
 struct DevQ40 {
@@ -1145,16 +1051,62 @@ AttnLaunchResult attentionLaunch(const AttnLaunchArgs &l) {
     return res;
 }
 
-std::vector<int> argmax(const std::vector<float> &logits, int B, int vocab) {
-    DL_CHECK(B >= 1 && vocab >= 1 && logits.size() == (size_t)B * vocab, "argmax sizes");
-    Scratch sc;
+namespace {
+
+// ids, partials and (zeroed) counters of an argmax over the device rows `logits`
+hipk::ArgmaxArgs argmaxArgs(Scratch &sc, const float *logits, int B, int vocab) {
     hipk::ArgmaxArgs g;
-    g.logits = sc.upload(logits);
+    g.logits = logits;
     g.vocab = vocab;
     g.ids = sc.alloc<int>(B);
     g.partV = sc.alloc<float>((size_t)B * 64);
     g.partI = sc.alloc<int>((size_t)B * 64);
     g.counters = sc.alloc<int>(B);
+    return g;
+}
+
+// The sampler of the filter and mask benches on the device rows `logits`: temperature 0.8, top-p
+// 0.9 and a fixed draw per row.
+hipk::SampleArgs benchSampleArgs(Scratch &sc, const float *logits, int B, int vocab) {
+    hipk::SampleArgs g;
+    g.logits = logits;
+    g.vocab = vocab;
+    std::vector<float> spec((size_t)B * 4, 0.f);
+    for (int b = 0; b < B; b++) {
+        spec[(size_t)b * 4] = 0.8f;
+        spec[(size_t)b * 4 + 1] = 0.9f;
+        spec[(size_t)b * 4 + 2] = (float)((b * 37 + 11) % 100) * 0.01f;
+    }
+    g.spec = reinterpret_cast<const float4 *>(sc.upload(spec));
+    g.ids = sc.alloc<int>(B);
+    g.scratch.carve(sc.alloc<uint8_t>(hipk::SampleScratch::bytes(B)), B);  // (alloc zero-fills)
+    return g;
+}
+
+// The logits of the filter and mask benches: sums of 4 uniform draws, a bell shape over about [-8, 8].
+std::vector<float> bellLogits(int B, int vocab) {
+    std::vector<float> logits((size_t)B * vocab);
+    uint32_t r = 12345u;
+    for (size_t i = 0; i < logits.size(); i++) {
+        float v = 0.f;
+        for (int j = 0; j < 4; j++) {
+            r = r * 1664525u + 1013904223u;
+            v += (float)(r >> 8) * (1.f / 16777216.f);
+        }
+        logits[i] = (v - 2.f) * 4.f;
+    }
+    return logits;
+}
+
+constexpr int kBenchWarmups = 5;  // untimed launches before each timeEagerUs window of the row benches
+constexpr size_t kRowTailGuard = 256;  // guard elements behind the last row of a row op's logits
+
+}  // namespace
+
+std::vector<int> argmax(const std::vector<float> &logits, int B, int vocab) {
+    DL_CHECK(B >= 1 && vocab >= 1 && logits.size() == (size_t)B * vocab, "argmax sizes");
+    Scratch sc;
+    const hipk::ArgmaxArgs g = argmaxArgs(sc, sc.upload(logits), B, vocab);
     hipk::launchArgmax(g, B, sc.s);
     sc.sync();
     return sc.download(g.ids, B);
@@ -1225,32 +1177,11 @@ void benchLogprobs(const std::vector<float> &logits, int B, int vocab, int k, in
     Scratch sc;
     hipk::LogprobArgs g = logprobArgs(sc, B, vocab, std::vector<int>(B, 1 + k));
     g.logits = sc.upload(logits);
-    hipk::ArgmaxArgs am;
-    am.logits = g.logits;
-    am.vocab = vocab;
-    am.ids = sc.alloc<int>(B);
-    am.partV = sc.alloc<float>((size_t)B * 64);
-    am.partI = sc.alloc<int>((size_t)B * 64);
-    am.counters = sc.alloc<int>(B);
+    const hipk::ArgmaxArgs am = argmaxArgs(sc, g.logits, B, vocab);
     g.ids = am.ids;
-    hipEvent_t e0, e1;
-    DL_HIP(hipEventCreate(&e0));
-    DL_HIP(hipEventCreate(&e1));
-    auto timed = [&](auto launch) {
-        for (int i = 0; i < 5; i++) launch();
-        DL_HIP(hipEventRecord(e0, sc.s));
-        for (int i = 0; i < iters; i++) launch();
-        DL_HIP(hipEventRecord(e1, sc.s));
-        DL_HIP(hipEventSynchronize(e1));
-        float ms = 0;
-        DL_HIP(hipEventElapsedTime(&ms, e0, e1));
-        return (double)ms * 1000.0 / iters;
-    };
-    argmaxUs = timed([&] { hipk::launchArgmax(am, B, sc.s); });
-    logprobsUs = timed([&] { hipk::launchLogprobs(g, B, sc.s); });
+    argmaxUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] { hipk::launchArgmax(am, B, sc.s); });
+    logprobsUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] { hipk::launchLogprobs(g, B, sc.s); });
     sc.sync();
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
 }
 
 namespace {
@@ -1305,16 +1236,11 @@ std::vector<float> logitProc(const std::vector<float> &logits, int B, int vocab,
     hipk::LogitProcArgs g =
         logitProcArgs(sc, B, vocab, temps, slots, active, presence, frequency, counts, nSlots, biasIds, biasVals, nBias);
     g.logits = sc.upload(logits);
-    constexpr size_t kPad = 256;  // guard elements behind the last row
-    const std::vector<float> filled((size_t)B * vocab + kPad, fill);
-    g.out = sc.upload(filled);
+    g.out = sc.uploadGuardedTail(std::vector<float>(logits.size(), fill), kRowTailGuard, "the processed logits");
     hipk::launchLogitProc(g, B, sc.s);
     sc.sync();
-    std::vector<float> out = sc.download(g.out, filled.size());
-    for (size_t i = (size_t)B * vocab; i < out.size(); i++)
-        DL_CHECK(std::memcmp(&out[i], &fill, sizeof(float)) == 0, "logit_proc: the launch wrote past the last row");
-    out.resize((size_t)B * vocab);
-    return out;
+    sc.checkGuards();
+    return sc.download(g.out, logits.size());
 }
 
 std::vector<uint32_t> logitProcCount(const std::vector<uint32_t> &counts, int nSlots, int vocab,
@@ -1369,24 +1295,9 @@ void benchLogitProc(int B, int vocab, int nBias, int iters, double &procUs, doub
     g.logits = sc.upload(logits);
     g.out = sc.alloc<float>((size_t)B * vocab);
     g.ids = sc.upload(ids);
-    hipEvent_t e0, e1;
-    DL_HIP(hipEventCreate(&e0));
-    DL_HIP(hipEventCreate(&e1));
-    auto timed = [&](auto launch) {
-        for (int i = 0; i < 5; i++) launch();
-        DL_HIP(hipEventRecord(e0, sc.s));
-        for (int i = 0; i < iters; i++) launch();
-        DL_HIP(hipEventRecord(e1, sc.s));
-        DL_HIP(hipEventSynchronize(e1));
-        float ms = 0;
-        DL_HIP(hipEventElapsedTime(&ms, e0, e1));
-        return (double)ms * 1000.0 / iters;
-    };
-    procUs = timed([&] { hipk::launchLogitProc(g, B, sc.s); });
-    countUs = timed([&] { hipk::launchLogitProcCount(g, B, sc.s); });
+    procUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] { hipk::launchLogitProc(g, B, sc.s); });
+    countUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] { hipk::launchLogitProcCount(g, B, sc.s); });
     sc.sync();
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
 }
 
 void pool(const std::vector<PoolLaunch> &launches, int dim, int nSlots, const std::vector<float> &normW, float eps,
@@ -1454,28 +1365,13 @@ void benchPool(int B, int dim, int slots, bool withAdd, int iters, double &poolU
     g.part = sc.alloc<float>((size_t)slots * hipk::kPoolMaxGroups);
     g.counters = sc.alloc<int>(slots);
     float *dst = sc.alloc<float>((size_t)B * dim * (withAdd ? 2 : 1));
-    hipEvent_t e0, e1;
-    DL_HIP(hipEventCreate(&e0));
-    DL_HIP(hipEventCreate(&e1));
-    auto timed = [&](auto launch) {
-        for (int i = 0; i < 5; i++) launch();
-        DL_HIP(hipEventRecord(e0, sc.s));
-        for (int i = 0; i < iters; i++) launch();
-        DL_HIP(hipEventRecord(e1, sc.s));
-        DL_HIP(hipEventSynchronize(e1));
-        float ms = 0;
-        DL_HIP(hipEventElapsedTime(&ms, e0, e1));
-        return (double)ms * 1000.0 / iters;
-    };
     const size_t bytes = (size_t)B * dim * sizeof(float);
-    copyUs = timed([&] {
+    copyUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] {
         DL_HIP(hipMemcpyAsync(dst, g.in, bytes, hipMemcpyDeviceToDevice, sc.s));
         if (withAdd) DL_HIP(hipMemcpyAsync(dst + (size_t)B * dim, g.add, bytes, hipMemcpyDeviceToDevice, sc.s));
     });
-    poolUs = timed([&] { hipk::launchPool(g, B, sc.s); });
+    poolUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] { hipk::launchPool(g, B, sc.s); });
     sc.sync();
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
 }
 
 namespace {
@@ -1509,77 +1405,35 @@ std::vector<float> logitFilter(const std::vector<float> &logits, int B, int voca
     DL_CHECK(B >= 1 && vocab >= 1 && logits.size() == (size_t)B * vocab, "logit_filter: logits is [B][vocab]");
     Scratch sc;
     hipk::LogitFilterArgs g = logitFilterArgs(sc, B, vocab, temps, topK, delta, active);
-    constexpr size_t kPad = 256;  // guard elements behind the last row
-    const float guard = -7.5f;
-    std::vector<float> padded(logits);
-    padded.resize(logits.size() + kPad, guard);
-    g.logits = sc.upload(padded);
+    g.logits = sc.uploadGuardedTail(logits, kRowTailGuard, "the filtered logits");
     hipk::launchLogitFilter(g, B, sc.s);
     sc.sync();
-    std::vector<float> out = sc.download(g.logits, padded.size());
-    for (size_t i = logits.size(); i < out.size(); i++)
-        DL_CHECK(std::memcmp(&out[i], &guard, sizeof(float)) == 0, "logit_filter: the launch wrote past the last row");
+    sc.checkGuards();
     const std::vector<uint32_t> state = sc.download(g.state, (size_t)B * hipk::kLogitFilterStateWords);
     for (int b = 0; b < B; b++)
         DL_CHECK(state[(size_t)b * hipk::kLogitFilterStateWords + 3] == 0, "logit_filter: a row's counter is not back to zero");
-    out.resize(logits.size());
-    return out;
+    return sc.download(g.logits, logits.size());
 }
 
 void benchLogitFilter(int B, int vocab, int topK, float delta, int iters, double &copyUs, double &copyFilterUs,
                       double &sampleUs) {
     DL_CHECK(B >= 1 && vocab >= 2 && iters >= 1, "bench_logit_filter arguments");
     Scratch sc;
-    std::vector<float> logits((size_t)B * vocab);
-    uint32_t r = 12345u;  // sums of 4 uniform draws: a bell shape over about [-8, 8]
-    for (size_t i = 0; i < logits.size(); i++) {
-        float v = 0.f;
-        for (int j = 0; j < 4; j++) {
-            r = r * 1664525u + 1013904223u;
-            v += (float)(r >> 8) * (1.f / 16777216.f);
-        }
-        logits[i] = (v - 2.f) * 4.f;
-    }
+    const std::vector<float> logits = bellLogits(B, vocab);
     hipk::LogitFilterArgs g = logitFilterArgs(sc, B, vocab, std::vector<float>(B, 0.8f), std::vector<int>(B, topK),
                                               std::vector<float>(B, delta), std::vector<int>(B, 1));
     const float *src = sc.upload(logits);
     g.logits = sc.alloc<float>(logits.size());
     const size_t bytes = logits.size() * sizeof(float);
-    hipk::SampleArgs sa;
-    sa.logits = g.logits;
-    sa.vocab = vocab;
-    std::vector<float> sspec((size_t)B * 4, 0.f);
-    for (int b = 0; b < B; b++) {
-        sspec[(size_t)b * 4] = 0.8f;
-        sspec[(size_t)b * 4 + 1] = 0.9f;
-        sspec[(size_t)b * 4 + 2] = (float)((b * 37 + 11) % 100) * 0.01f;
-    }
-    sa.spec = reinterpret_cast<const float4 *>(sc.upload(sspec));
-    sa.ids = sc.alloc<int>(B);
-    sa.scratch.carve(sc.alloc<uint8_t>(hipk::SampleScratch::bytes(B)), B);  // (alloc zero-fills)
-    hipEvent_t e0, e1;
-    DL_HIP(hipEventCreate(&e0));
-    DL_HIP(hipEventCreate(&e1));
-    auto timed = [&](auto launch) {
-        for (int i = 0; i < 5; i++) launch();
-        DL_HIP(hipEventRecord(e0, sc.s));
-        for (int i = 0; i < iters; i++) launch();
-        DL_HIP(hipEventRecord(e1, sc.s));
-        DL_HIP(hipEventSynchronize(e1));
-        float ms = 0;
-        DL_HIP(hipEventElapsedTime(&ms, e0, e1));
-        return (double)ms * 1000.0 / iters;
-    };
+    const hipk::SampleArgs sa = benchSampleArgs(sc, g.logits, B, vocab);
     auto copy = [&] { DL_HIP(hipMemcpyAsync(g.logits, src, bytes, hipMemcpyDeviceToDevice, sc.s)); };
-    copyUs = timed(copy);
-    copyFilterUs = timed([&] {
+    copyUs = timeEagerUs(sc.s, iters, kBenchWarmups, copy);
+    copyFilterUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] {
         copy();
         hipk::launchLogitFilter(g, B, sc.s);
     });
-    sampleUs = timed([&] { hipk::launchSample(sa, B, sc.s); });  // on the filtered rows
+    sampleUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] { hipk::launchSample(sa, B, sc.s); });  // on the filtered rows
     sc.sync();
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
 }
 
 namespace {
@@ -1625,20 +1479,13 @@ std::vector<float> jsonMask(const std::vector<float> &logits, int B, int vocab, 
     DL_CHECK(B >= 1 && vocab >= 1 && logits.size() == (size_t)B * vocab, "json_mask: logits is [B][vocab]");
     Scratch sc;
     hipk::JsonMaskArgs g = jsonMaskArgs(sc, B, vocab, temps, on, off, info, words, states);
-    constexpr size_t kPad = 256;  // guard elements behind the last row
-    const float guard = -7.5f;
-    std::vector<float> padded(logits);
-    padded.resize(logits.size() + kPad, guard);
-    g.logits = sc.upload(padded);
+    g.logits = sc.uploadGuardedTail(logits, kRowTailGuard, "the masked logits");
     hipk::launchJsonMask(g, B, sc.s);
     sc.sync();
-    std::vector<float> out = sc.download(g.logits, padded.size());
-    for (size_t i = logits.size(); i < out.size(); i++)
-        DL_CHECK(std::memcmp(&out[i], &guard, sizeof(float)) == 0, "json_mask: the launch wrote past the last row");
+    sc.checkGuards();
     const std::vector<uint32_t> after = sc.download(reinterpret_cast<const uint32_t *>(g.states), states.size());
     DL_CHECK(after == states, "json_mask: the launch changed a state");
-    out.resize(logits.size());
-    return out;
+    return sc.download(g.logits, logits.size());
 }
 
 std::vector<uint32_t> jsonAdvance(int vocab, const std::vector<float> &temps, const std::vector<int> &on,
@@ -1660,16 +1507,7 @@ void benchJsonMask(int B, int vocab, const std::vector<uint32_t> &off, const std
                    double &copyMaskUs, double &advanceUs, double &copyFilterUs, double &sampleUs) {
     DL_CHECK(B >= 1 && vocab >= 2 && iters >= 1 && state.size() == 4, "bench_json_mask arguments");
     Scratch sc;
-    std::vector<float> logits((size_t)B * vocab);
-    uint32_t r = 12345u;  // sums of 4 uniform draws: a bell shape over about [-8, 8]
-    for (size_t i = 0; i < logits.size(); i++) {
-        float v = 0.f;
-        for (int j = 0; j < 4; j++) {
-            r = r * 1664525u + 1013904223u;
-            v += (float)(r >> 8) * (1.f / 16777216.f);
-        }
-        logits[i] = (v - 2.f) * 4.f;
-    }
+    const std::vector<float> logits = bellLogits(B, vocab);
     std::vector<uint32_t> states;
     for (int b = 0; b < B; b++) states.insert(states.end(), state.begin(), state.end());
     hipk::JsonMaskArgs g = jsonMaskArgs(sc, B, vocab, std::vector<float>(B, 0.8f), std::vector<int>(B, 1), off, info, words, states);
@@ -1683,46 +1521,20 @@ void benchJsonMask(int B, int vocab, const std::vector<uint32_t> &off, const std
     adv.states = reinterpret_cast<uint4 *>(sc.upload(states));
     adv.ids = sc.alloc<int>(B);  // (alloc zero-fills)
     const size_t bytes = logits.size() * sizeof(float);
-    hipk::SampleArgs sa;
-    sa.logits = g.logits;
-    sa.vocab = vocab;
-    std::vector<float> sspec((size_t)B * 4, 0.f);
-    for (int b = 0; b < B; b++) {
-        sspec[(size_t)b * 4] = 0.8f;
-        sspec[(size_t)b * 4 + 1] = 0.9f;
-        sspec[(size_t)b * 4 + 2] = (float)((b * 37 + 11) % 100) * 0.01f;
-    }
-    sa.spec = reinterpret_cast<const float4 *>(sc.upload(sspec));
-    sa.ids = sc.alloc<int>(B);
-    sa.scratch.carve(sc.alloc<uint8_t>(hipk::SampleScratch::bytes(B)), B);  // (alloc zero-fills)
-    hipEvent_t e0, e1;
-    DL_HIP(hipEventCreate(&e0));
-    DL_HIP(hipEventCreate(&e1));
-    auto timed = [&](auto launch) {
-        for (int i = 0; i < 5; i++) launch();
-        DL_HIP(hipEventRecord(e0, sc.s));
-        for (int i = 0; i < iters; i++) launch();
-        DL_HIP(hipEventRecord(e1, sc.s));
-        DL_HIP(hipEventSynchronize(e1));
-        float ms = 0;
-        DL_HIP(hipEventElapsedTime(&ms, e0, e1));
-        return (double)ms * 1000.0 / iters;
-    };
+    const hipk::SampleArgs sa = benchSampleArgs(sc, g.logits, B, vocab);
     auto copy = [&] { DL_HIP(hipMemcpyAsync(g.logits, src, bytes, hipMemcpyDeviceToDevice, sc.s)); };
-    copyUs = timed(copy);
-    copyFilterUs = timed([&] {
+    copyUs = timeEagerUs(sc.s, iters, kBenchWarmups, copy);
+    copyFilterUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] {
         copy();
         hipk::launchLogitFilter(f, B, sc.s);
     });
-    copyMaskUs = timed([&] {
+    copyMaskUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] {
         copy();
         hipk::launchJsonMask(g, B, sc.s);
     });
-    sampleUs = timed([&] { hipk::launchSample(sa, B, sc.s); });  // on the masked rows
-    advanceUs = timed([&] { hipk::launchJsonAdvance(adv, B, sc.s); });
+    sampleUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] { hipk::launchSample(sa, B, sc.s); });  // on the masked rows
+    advanceUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] { hipk::launchJsonAdvance(adv, B, sc.s); });
     sc.sync();
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
 }
 
 std::vector<float> embedding(const std::vector<float> &table, int vocab, int dim, const std::vector<int> &tokens) {

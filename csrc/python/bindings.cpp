@@ -11,6 +11,7 @@
 #include "../core/quant.h"
 #include "../cpu/cpu_ops.h"
 #include "../hip/engine.h"
+#include "../hip/host_harness.h"
 #include "../hip/ops.h"
 #include "../runtime/backend.h"
 #include "../runtime/weight_stream.h"
@@ -305,6 +306,21 @@ py::array_t<T> arr(const std::vector<T> &v, std::vector<py::ssize_t> shape) {
     DL_CHECK((size_t)a.size() == v.size(), "result shape");
     std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(T));
     return a;
+}
+
+// Test helper of the collectives: x goes to the device, run(in, out, stream) gets it next to
+// `outFloats` zeros and returns the device vector (in or out) of `outFloats` floats to hand back.
+template <typename Run>
+py::array_t<float> hostCollective(const py::array_t<float, py::array::c_style | py::array::forcecast> &x, size_t outFloats,
+                                  Run run) {
+    std::vector<float> h(x.data(), x.data() + x.size());
+    {
+        py::gil_scoped_release rel;
+        Scratch sc;
+        float *in = sc.upload(h);
+        h = sc.download(run(in, sc.alloc<float>(outFloats), sc.s), outFloats);
+    }
+    return arr(h, {(py::ssize_t)outFloats});
 }
 
 void bindOps(py::module_ &m) {
@@ -1251,7 +1267,7 @@ PYBIND11_MODULE(_C, m) {
           },
           py::arg("rows"), py::arg("n"), py::arg("pro"), py::arg("epi"), py::arg("batch") = 1, py::arg("lanes") = 0,
           py::arg("passes") = 0, py::arg("copies") = 8, py::arg("iters") = 20,
-          "bench_gemv_q40 with per-workgroup s_memrealtime stamps: (us, u64[iters*grid*4])");
+          "bench_gemv_q40 with per-workgroup s_memrealtime stamps: (us, u64[iters*grid*8])");
     m.def("bench_gemm_q40", [](int rows, int n, int M, int epi, int copies, int iters) {
               return benchGemmQ40(rows, n, M, epi, copies, iters);
           }, py::arg("rows"), py::arg("n"), py::arg("tokens"), py::arg("epi") = 0,
@@ -1371,94 +1387,36 @@ PYBIND11_MODULE(_C, m) {
         .def("bench_all_reduce",
              [](PyComm &c, size_t n, int iters) {
                  py::gil_scoped_release rel;
-                 float *d;
-                 hipStream_t s;
-                 DL_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-                 DL_HIP(hipMalloc(&d, n * 4));
-                 DL_HIP(hipMemset(d, 0, n * 4));
-                 hipGraph_t g;
-                 hipGraphExec_t ge;
-                 DL_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                 for (int i = 0; i < iters; i++) c.comm->allReduceSum(d, n, s);
-                 DL_HIP(hipStreamEndCapture(s, &g));
-                 DL_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-                 DL_HIP(hipGraphLaunch(ge, s));
-                 DL_HIP(hipStreamSynchronize(s));
-                 hipEvent_t e0, e1;
-                 DL_HIP(hipEventCreate(&e0));
-                 DL_HIP(hipEventCreate(&e1));
-                 DL_HIP(hipEventRecord(e0, s));
-                 DL_HIP(hipGraphLaunch(ge, s));
-                 DL_HIP(hipEventRecord(e1, s));
-                 DL_HIP(hipEventSynchronize(e1));
-                 float ms = 0;
-                 DL_HIP(hipEventElapsedTime(&ms, e0, e1));
-                 (void)hipGraphExecDestroy(ge);
-                 (void)hipGraphDestroy(g);
-                 (void)hipFree(d);
-                 (void)hipStreamDestroy(s);
-                 return (double)ms * 1000.0 / iters;
+                 Scratch sc;
+                 float *d = sc.alloc<float>(n);
+                 return timeGraphUs(sc.s, iters, [&](int) { c.comm->allReduceSum(d, n, sc.s); });
              },
              py::arg("n"), py::arg("iters") = 200)
         .def_property_readonly("rank", [](PyComm &c) { return c.comm->rank(); })
         .def_property_readonly("world", [](PyComm &c) { return c.comm->size(); })
-        // test helpers: host vector in, collective result out (device round trip on the null stream)
+        // test helpers: host vector in, collective result out (device round trip on a stream of its own)
         .def("all_reduce",
              [](PyComm &c, py::array_t<float, py::array::c_style | py::array::forcecast> x) {
                  const size_t n = (size_t)x.size();
-                 py::array_t<float> out((py::ssize_t)n);
-                 std::vector<float> h(x.data(), x.data() + n);
-                 {
-                     py::gil_scoped_release rel;
-                     float *d;
-                     DL_HIP(hipMalloc(&d, n * 4));
-                     DL_HIP(hipMemcpy(d, h.data(), n * 4, hipMemcpyHostToDevice));
-                     c.comm->allReduceSum(d, n, nullptr);
-                     DL_HIP(hipMemcpy(h.data(), d, n * 4, hipMemcpyDeviceToHost));
-                     DL_HIP(hipFree(d));
-                 }
-                 std::memcpy(out.mutable_data(), h.data(), n * 4);
-                 return out;
+                 return hostCollective(x, n, [&](float *in, float *, hipStream_t s) {
+                     c.comm->allReduceSum(in, n, s);
+                     return in;
+                 });
              })
         .def("all_gather", [](PyComm &c, py::array_t<float, py::array::c_style | py::array::forcecast> x) {
             const size_t n = (size_t)x.size();
-            const int w = c.comm->size();
-            py::array_t<float> out((py::ssize_t)(n * w));
-            std::vector<float> h(x.data(), x.data() + n), r(n * w);
-            {
-                py::gil_scoped_release rel;
-                float *d, *o;
-                DL_HIP(hipMalloc(&d, n * 4));
-                DL_HIP(hipMalloc(&o, n * w * 4));
-                DL_HIP(hipMemcpy(d, h.data(), n * 4, hipMemcpyHostToDevice));
-                c.comm->allGather(d, o, n, nullptr);
-                DL_HIP(hipMemcpy(r.data(), o, n * w * 4, hipMemcpyDeviceToHost));
-                DL_HIP(hipFree(d));
-                DL_HIP(hipFree(o));
-            }
-            std::memcpy(out.mutable_data(), r.data(), n * w * 4);
-            return out;
+            return hostCollective(x, n * c.comm->size(), [&](float *in, float *out, hipStream_t s) {
+                c.comm->allGather(in, out, n, s);
+                return out;
+            });
         })
         // rank 0 gets every rank's x in rank order (other ranks: zeros)
         .def("gather_to_root", [](PyComm &c, py::array_t<float, py::array::c_style | py::array::forcecast> x) {
             const size_t n = (size_t)x.size();
-            const int w = c.comm->size();
-            py::array_t<float> out((py::ssize_t)(n * w));
-            std::vector<float> h(x.data(), x.data() + n), r(n * w);
-            {
-                py::gil_scoped_release rel;
-                float *d, *o;
-                DL_HIP(hipMalloc(&d, n * 4));
-                DL_HIP(hipMalloc(&o, n * w * 4));
-                DL_HIP(hipMemset(o, 0, n * w * 4));
-                DL_HIP(hipMemcpy(d, h.data(), n * 4, hipMemcpyHostToDevice));
-                c.comm->gatherToRoot(d, o, n, nullptr);
-                DL_HIP(hipMemcpy(r.data(), o, n * w * 4, hipMemcpyDeviceToHost));
-                DL_HIP(hipFree(d));
-                DL_HIP(hipFree(o));
-            }
-            std::memcpy(out.mutable_data(), r.data(), n * w * 4);
-            return out;
+            return hostCollective(x, n * c.comm->size(), [&](float *in, float *out, hipStream_t s) {
+                c.comm->gatherToRoot(in, out, n, s);
+                return out;
+            });
         })
         .def("broadcast_ints", [](PyComm &c, std::vector<int> v, int root) {
             py::gil_scoped_release rel;
