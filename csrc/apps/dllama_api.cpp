@@ -8,6 +8,12 @@
 //           "stream": true -> server-sent events with chat.completion.chunk objects + [DONE]
 //           "logprobs": true (+ "top_logprobs": 0..20) -> choices[0].logprobs.content, one entry
 //           per generated token: log_softmax of the raw logits, whatever temperature / top_p
+//   POST /v1/completions       {"prompt": <string | [strings] | [token ids] | [[token ids]]>, "max_tokens",
+//                               "echo", "logprobs": null | 0..20, and the sampling fields of the chat endpoint}
+//        -> {"object":"text_completion","choices":[{"text","index","logprobs","finish_reason"}...],"usage"};
+//           "echo": true returns the prompt with the completion and, with "logprobs", scores the
+//           prompt's tokens too (OpenAI's legacy arrays plus "token_ids" / "top_ids"); "max_tokens": 0
+//           then scores without generating; "stream": true -> text_completion chunks + [DONE]
 //   POST /v1/embeddings        {"input": <string | [strings] | [token ids] | [[token ids]]>, "model",
 //                               "encoding_format": "float"|"base64", "pooling": "mean"|"last"}
 //        -> {"object":"list","data":[{"object":"embedding","index":i,"embedding":[...]}...],
@@ -130,6 +136,84 @@ struct Api {
         return lp;
     }
 
+    // The request fields that /v1/chat/completions and /v1/completions share: temperature, top_p,
+    // seed, stop, stream, max_tokens (taken when a number; each endpoint has its own rule for it),
+    // the penalties, logit_bias, top_k, min_p and response_format. Returns what the 400 says (empty: fine).
+    std::string sharedParams(const Value &body, GenParams &p, bool &stream) {
+        p.temperature = args.temperature;
+        p.topp = args.topp;
+        p.seed = args.seed + counter.fetch_add(1);
+        if (body["max_tokens"].isNumber()) p.maxTokens = (int)body["max_tokens"].asNumber();
+        if (body["temperature"].isNumber()) p.temperature = (float)body["temperature"].asNumber();
+        if (body["top_p"].isNumber()) p.topp = (float)body["top_p"].asNumber();
+        if (body["seed"].isNumber()) p.seed = (u64)body["seed"].asNumber();
+        if (body["stop"].isString()) p.stop.push_back(body["stop"].asString());
+        if (body["stop"].isArray())
+            for (const Value &s : body["stop"].items())
+                if (s.isString()) p.stop.push_back(s.asString());
+        stream = body["stream"].isBool() && body["stream"].asBool();
+        std::string bad;
+        auto penalty = [&](const char *name, float &dst) {
+            const Value &v = body[name];
+            if (v.isNull() || !bad.empty()) return;
+            if (!v.isNumber() || !(v.asNumber() >= -2.0 && v.asNumber() <= 2.0))
+                bad = std::string(name) + " must be a number from -2 to 2";
+            else
+                dst = (float)v.asNumber();
+        };
+        penalty("frequency_penalty", p.frequencyPenalty);
+        penalty("presence_penalty", p.presencePenalty);
+        const Value &tk = body["top_k"], &mp = body["min_p"];
+        if (bad.empty() && !tk.isNull()) {
+            if (!tk.isNumber() || tk.asNumber() != std::floor(tk.asNumber()) || tk.asNumber() < 0)
+                bad = "top_k must be an integer >= 0";
+            else  // the whole vocabulary or more: off
+                p.topK = tk.asNumber() >= (double)sess->header().vocabSize ? 0 : (int)tk.asNumber();
+        }
+        if (bad.empty() && !mp.isNull()) {
+            if (!mp.isNumber() || !(mp.asNumber() >= 0.0 && mp.asNumber() <= 1.0))
+                bad = "min_p must be a number from 0 to 1";
+            else
+                p.minP = (float)mp.asNumber();
+        }
+        const Value &rf = body["response_format"];
+        if (bad.empty() && !rf.isNull()) {
+            const std::string type = rf.isObject() && rf["type"].isString() ? rf["type"].asString() : "";
+            if (type == "json_object") {
+                if (jsonUnavailable.empty())
+                    p.jsonObject = true;
+                else
+                    bad = "response_format json_object is unavailable with this tokenizer: " + jsonUnavailable;
+            } else if (type != "text") {
+                bad = "response_format must be {\"type\": \"text\"} or {\"type\": \"json_object\"}";
+            }
+        }
+        const Value &lb = body["logit_bias"];
+        if (bad.empty() && !lb.isNull()) {
+            const int vocab = (int)sess->header().vocabSize;
+            if (!lb.isObject())
+                bad = "logit_bias must be an object of token id: bias";
+            else if (lb.size() > (size_t)kMaxLogitBias)
+                bad = "logit_bias holds at most " + std::to_string(kMaxLogitBias) + " entries";
+            for (size_t e = 0; bad.empty() && e < lb.size(); e++) {
+                const auto &kv = lb.members()[e];
+                const std::string &k = kv.first;
+                const bool digits = !k.empty() && k.size() <= 9 && k.find_first_not_of("0123456789") == std::string::npos;
+                const int id = digits ? std::atoi(k.c_str()) : -1;
+                if (!digits || id >= vocab)
+                    bad = "logit_bias keys must be token ids from 0 to " + std::to_string(vocab - 1);
+                else if (!kv.second.isNumber() || !(kv.second.asNumber() >= -100.0 && kv.second.asNumber() <= 100.0))
+                    bad = "logit_bias values must be numbers from -100 to 100";
+                else {
+                    for (const LogitBias &e : p.logitBias)
+                        if (e.id == id) bad = "logit_bias names token " + std::to_string(id) + " twice";
+                    p.logitBias.push_back(LogitBias{id, (float)kv.second.asNumber()});
+                }
+            }
+        }
+        return bad;
+    }
+
     void complete(const HttpRequest &req, HttpConnection &conn) {
         Value body;
         try {
@@ -142,19 +226,9 @@ struct Api {
             return;
         }
         GenParams p;
-        p.temperature = args.temperature;
-        p.topp = args.topp;
-        p.seed = args.seed + counter.fetch_add(1);
-        if (body["max_tokens"].isNumber()) p.maxTokens = (int)body["max_tokens"].asNumber();
-        if (body["temperature"].isNumber()) p.temperature = (float)body["temperature"].asNumber();
-        if (body["top_p"].isNumber()) p.topp = (float)body["top_p"].asNumber();
-        if (body["seed"].isNumber()) p.seed = (u64)body["seed"].asNumber();
-        if (body["stop"].isString()) p.stop.push_back(body["stop"].asString());
-        if (body["stop"].isArray())
-            for (const Value &s : body["stop"].items())
-                if (s.isString()) p.stop.push_back(s.asString());
-        const bool stream = body["stream"].isBool() && body["stream"].asBool();
+        bool stream = false;
         {
+            const std::string shared = sharedParams(body, p, stream);
             const Value &lp = body["logprobs"], &top = body["top_logprobs"];
             std::string bad;
             if (!lp.isNull() && !lp.isBool()) bad = "logprobs must be a boolean";
@@ -168,73 +242,7 @@ struct Api {
                 else
                     p.topLogprobs = (int)top.asNumber();
             }
-            if (!bad.empty()) {
-                Value err = Value::object();
-                err.set("error", "Invalid request: " + bad);
-                conn.writeJson(400, err.dump());
-                return;
-            }
-        }
-        {
-            std::string bad;
-            auto penalty = [&](const char *name, float &dst) {
-                const Value &v = body[name];
-                if (v.isNull() || !bad.empty()) return;
-                if (!v.isNumber() || !(v.asNumber() >= -2.0 && v.asNumber() <= 2.0))
-                    bad = std::string(name) + " must be a number from -2 to 2";
-                else
-                    dst = (float)v.asNumber();
-            };
-            penalty("frequency_penalty", p.frequencyPenalty);
-            penalty("presence_penalty", p.presencePenalty);
-            const Value &tk = body["top_k"], &mp = body["min_p"];
-            if (bad.empty() && !tk.isNull()) {
-                if (!tk.isNumber() || tk.asNumber() != std::floor(tk.asNumber()) || tk.asNumber() < 0)
-                    bad = "top_k must be an integer >= 0";
-                else  // the whole vocabulary or more: off
-                    p.topK = tk.asNumber() >= (double)sess->header().vocabSize ? 0 : (int)tk.asNumber();
-            }
-            if (bad.empty() && !mp.isNull()) {
-                if (!mp.isNumber() || !(mp.asNumber() >= 0.0 && mp.asNumber() <= 1.0))
-                    bad = "min_p must be a number from 0 to 1";
-                else
-                    p.minP = (float)mp.asNumber();
-            }
-            const Value &rf = body["response_format"];
-            if (bad.empty() && !rf.isNull()) {
-                const std::string type = rf.isObject() && rf["type"].isString() ? rf["type"].asString() : "";
-                if (type == "json_object") {
-                    if (jsonUnavailable.empty())
-                        p.jsonObject = true;
-                    else
-                        bad = "response_format json_object is unavailable with this tokenizer: " + jsonUnavailable;
-                } else if (type != "text") {
-                    bad = "response_format must be {\"type\": \"text\"} or {\"type\": \"json_object\"}";
-                }
-            }
-            const Value &lb = body["logit_bias"];
-            if (bad.empty() && !lb.isNull()) {
-                const int vocab = (int)sess->header().vocabSize;
-                if (!lb.isObject())
-                    bad = "logit_bias must be an object of token id: bias";
-                else if (lb.size() > (size_t)kMaxLogitBias)
-                    bad = "logit_bias holds at most " + std::to_string(kMaxLogitBias) + " entries";
-                for (size_t e = 0; bad.empty() && e < lb.size(); e++) {
-                    const auto &kv = lb.members()[e];
-                    const std::string &k = kv.first;
-                    const bool digits = !k.empty() && k.size() <= 9 && k.find_first_not_of("0123456789") == std::string::npos;
-                    const int id = digits ? std::atoi(k.c_str()) : -1;
-                    if (!digits || id >= vocab)
-                        bad = "logit_bias keys must be token ids from 0 to " + std::to_string(vocab - 1);
-                    else if (!kv.second.isNumber() || !(kv.second.asNumber() >= -100.0 && kv.second.asNumber() <= 100.0))
-                        bad = "logit_bias values must be numbers from -100 to 100";
-                    else {
-                        for (const LogitBias &e : p.logitBias)
-                            if (e.id == id) bad = "logit_bias names token " + std::to_string(id) + " twice";
-                        p.logitBias.push_back(LogitBias{id, (float)kv.second.asNumber()});
-                    }
-                }
-            }
+            if (bad.empty()) bad = shared;  // (reported in the order they always were)
             if (!bad.empty()) {
                 Value err = Value::object();
                 err.set("error", "Invalid request: " + bad);
@@ -350,10 +358,11 @@ struct Api {
         return out;
     }
 
-    // One item of "input" as token ids: a string is tokenised as a raw prompt (BOS as for any
-    // prompt, no chat template), a list of token ids is taken as it is. Throws what the 400 says.
-    std::vector<int> embeddingInput(const Value &item, size_t index) {
-        const std::string at = "input[" + std::to_string(index) + "]";
+    // One item of "input" (embeddings) or "prompt" (completions) as token ids: a string is tokenised
+    // as a raw prompt (BOS as for any prompt, no chat template), a list of token ids is taken as it
+    // is. Throws what the 400 says.
+    std::vector<int> embeddingInput(const Value &item, size_t index, const char *field = "input") {
+        const std::string at = std::string(field) + "[" + std::to_string(index) + "]";
         const int vocab = (int)sess->header().vocabSize;
         std::vector<int> ids;
         if (item.isString()) {
@@ -379,7 +388,6 @@ struct Api {
     // POST /v1/embeddings: every item of "input" becomes one embedding request; they are submitted
     // together, so they batch with each other and with the chat traffic.
     void embeddings(const HttpRequest &req, HttpConnection &conn) {
-        constexpr size_t kMaxItems = 2048;
         std::vector<std::vector<int>> inputs;
         GenParams p;
         p.embed = EmbedMode::MEAN;
@@ -388,24 +396,7 @@ struct Api {
         try {
             const Value body = Value::parse(req.body);
             if (!body.isObject()) throw std::runtime_error("a JSON object is required");
-            const Value &in = body["input"];
-            if (in.isString()) {
-                inputs.push_back(embeddingInput(in, 0));
-            } else if (in.isArray()) {
-                if (in.size() == 0) throw std::runtime_error("input is empty");
-                if (in.items()[0].isNumber()) {  // one list of token ids
-                    inputs.push_back(embeddingInput(in, 0));
-                } else {
-                    if (in.size() > kMaxItems) throw std::runtime_error("input holds at most " + std::to_string(kMaxItems) + " items");
-                    const bool strings = in.items()[0].isString();
-                    for (size_t i = 0; i < in.size(); i++) {
-                        if (in.items()[i].isString() != strings) throw std::runtime_error("input mixes strings and token lists");
-                        inputs.push_back(embeddingInput(in.items()[i], i));
-                    }
-                }
-            } else {
-                throw std::runtime_error("input required: a string, a list of strings, a list of token ids or a list of such lists");
-            }
+            inputs = tokenItems(body["input"], "input");
             if (!body["dimensions"].isNull()) throw std::runtime_error("dimensions is not supported");
             const Value &ef = body["encoding_format"], &pl = body["pooling"];
             if (!ef.isNull()) {
@@ -473,6 +464,254 @@ struct Api {
         }
     }
 
+    // The items of "input" / "prompt": a string, a list of token ids, a non-empty list of strings or a
+    // list of token-id lists, at most kMaxItems of them. Throws what the 400 says.
+    static constexpr size_t kMaxItems = 2048;
+    std::vector<std::vector<int>> tokenItems(const Value &in, const char *field, std::vector<std::string> *texts = nullptr) {
+        const std::string f = field;
+        std::vector<std::vector<int>> items;
+        auto take = [&](const Value &item, size_t i) {
+            items.push_back(embeddingInput(item, i, field));
+            if (texts) texts->push_back(item.isString() ? item.asString() : decodeIds(items.back()));
+        };
+        if (in.isString()) {
+            take(in, 0);
+        } else if (in.isArray()) {
+            if (in.size() == 0) throw std::runtime_error(f + " is empty");
+            if (in.items()[0].isNumber()) {  // one list of token ids
+                take(in, 0);
+            } else {
+                if (in.size() > kMaxItems) throw std::runtime_error(f + " holds at most " + std::to_string(kMaxItems) + " items");
+                const bool strings = in.items()[0].isString();
+                for (size_t i = 0; i < in.size(); i++) {
+                    if (in.items()[i].isString() != strings) throw std::runtime_error(f + " mixes strings and token lists");
+                    take(in.items()[i], i);
+                }
+            }
+        } else {
+            throw std::runtime_error(f + " required: a string, a list of strings, a list of token ids or a list of such lists");
+        }
+        return items;
+    }
+
+    // The tokenizer's decode of a token-id prompt (what `echo` returns for it).
+    std::string decodeIds(const std::vector<int> &ids) {
+        TokenDecoder dec(sess->tokenizer());
+        std::string text, piece;
+        for (int t : ids)
+            if (dec.decode(t, piece)) text += piece;
+        return text;
+    }
+
+    // choices[i].logprobs of /v1/completions, OpenAI's legacy arrays, for records [0, recs.size()) of
+    // tokens `ids`: "tokens" (the piece as a JSON string), "token_logprobs", "top_logprobs" (one
+    // {token string: logprob} object per token; on a string collision the better entry wins),
+    // "text_offset" (bytes of the preceding tokens' pieces, special tokens counting 0; `offset` moves
+    // on) and, because token strings are ambiguous, "token_ids" and "top_ids" ([id, logprob] pairs in
+    // (logit descending, id ascending) order). A record without a token (the first echoed token, which
+    // has no context) gives null in the three logprob arrays.
+    Value legacyLogprobsJson(const std::vector<int> &ids, const std::vector<TokenRecord> &recs, size_t &offset) {
+        Tokenizer &tok = sess->tokenizer();
+        auto pieceOf = [&](int id) { return id >= 0 && id < tok.vocabSize() ? tok.piece(id) : std::string(); };
+        Value tokens = Value::array(), tlp = Value::array(), top = Value::array(), offs = Value::array(),
+              tids = Value::array(), topIds = Value::array();
+        for (size_t i = 0; i < recs.size() && i < ids.size(); i++) {
+            const TokenRecord &rec = recs[i];
+            const std::string piece = pieceOf(ids[i]);
+            tokens.push(validUtf8(piece));
+            tids.push(ids[i]);
+            offs.push((double)offset);
+            if (ids[i] < tok.bosId()) offset += piece.size();
+            if (rec.chosen.id < 0) {
+                tlp.push(Value());
+                top.push(Value());
+                topIds.push(Value());
+                continue;
+            }
+            tlp.push((double)rec.chosen.logprob);
+            Value o = Value::object(), l = Value::array();
+            for (const TokenLogprob &t : rec.top) {
+                const std::string key = validUtf8(pieceOf(t.id));
+                if (!o.contains(key)) o.set(key, (double)t.logprob);
+                Value pair = Value::array();
+                pair.push(t.id);
+                pair.push((double)t.logprob);
+                l.push(pair);
+            }
+            top.push(o);
+            topIds.push(l);
+        }
+        Value lp = Value::object();
+        lp.set("tokens", tokens);
+        lp.set("token_logprobs", tlp);
+        lp.set("top_logprobs", top);
+        lp.set("text_offset", offs);
+        lp.set("token_ids", tids);
+        lp.set("top_ids", topIds);
+        return lp;
+    }
+
+    // The records of a completions request not yet written: the prompt's (echo with logprobs) from
+    // `promptSent`, then the generated tokens' from `genSent`; both move on, with the byte offset.
+    struct LegacyCursor {
+        size_t promptSent = 0, genSent = 0, offset = 0;
+    };
+    Value legacyLogprobsJson(GenRequest &r, LegacyCursor &c) {
+        std::vector<int> ids;
+        std::vector<TokenRecord> recs;
+        {
+            std::lock_guard<std::mutex> lk(r.mu);
+            for (size_t i = c.promptSent; i < r.promptLogprobs.size() && i < r.prompt.size(); i++) {
+                ids.push_back(r.prompt[i]);
+                recs.push_back(r.promptLogprobs[i]);
+            }
+            c.promptSent = std::max(c.promptSent, r.promptLogprobs.size());
+            for (size_t i = c.genSent; i < r.logprobs.size(); i++) {
+                ids.push_back(r.logprobs[i].chosen.id);
+                recs.push_back(r.logprobs[i]);
+            }
+            c.genSent = std::max(c.genSent, r.logprobs.size());
+        }
+        return legacyLogprobsJson(ids, recs, c.offset);
+    }
+
+    // POST /v1/completions: every item of "prompt" becomes one scheduler request; they are submitted
+    // together, so they batch with each other and with the chat traffic. `echo` returns the prompt
+    // with the completion; with `logprobs` the prompt's tokens are scored too (row i scores token
+    // i + 1), and `max_tokens: 0` then scores without generating.
+    void completions(const HttpRequest &req, HttpConnection &conn) {
+        std::vector<std::vector<int>> prompts;
+        std::vector<std::string> texts;
+        GenParams p;
+        p.completion = true;
+        p.maxTokens = 16;
+        bool stream = false;
+        try {
+            const Value body = Value::parse(req.body);
+            if (!body.isObject()) throw std::runtime_error("a JSON object is required");
+            const std::string bad = sharedParams(body, p, stream);
+            if (!bad.empty()) throw std::runtime_error(bad);
+            auto integer = [](const Value &v, double lo, double hi) {
+                return v.isNumber() && v.asNumber() == std::floor(v.asNumber()) && v.asNumber() >= lo && v.asNumber() <= hi;
+            };
+            const Value &echo = body["echo"], &lp = body["logprobs"], &mt = body["max_tokens"];
+            if (!echo.isNull() && !echo.isBool()) throw std::runtime_error("echo must be a boolean");
+            p.echo = echo.isBool() && echo.asBool();
+            if (!mt.isNull() && !integer(mt, 0, 2147483647.0)) throw std::runtime_error("max_tokens must be an integer >= 0");
+            if (p.maxTokens == 0 && !p.echo) throw std::runtime_error("max_tokens: 0 requires echo: true");
+            if (!lp.isNull()) {
+                if (!integer(lp, 0, kMaxTopLogprobs))
+                    throw std::runtime_error("logprobs must be null or an integer from 0 to " + std::to_string(kMaxTopLogprobs));
+                p.logprobs = true;
+                p.topLogprobs = (int)lp.asNumber();
+            }
+            p.promptLogprobs = p.echo && p.logprobs;
+            for (const char *one : {"n", "best_of"})
+                if (!body[one].isNull() && !(body[one].isNumber() && body[one].asNumber() == 1.0))
+                    throw std::runtime_error(std::string(one) + " other than 1 is not supported");
+            if (!body["suffix"].isNull()) throw std::runtime_error("suffix is not supported");
+            if (!body["top_logprobs"].isNull())
+                throw std::runtime_error("top_logprobs belongs to /v1/chat/completions; here logprobs is the count");
+            prompts = tokenItems(body["prompt"], "prompt", &texts);
+            const size_t seqLen = sess->header().seqLen;
+            for (size_t i = 0; i < prompts.size(); i++)  // (one that generates leaves room for a token)
+                if (!p.drawsNothing() && prompts[i].size() >= seqLen)
+                    throw std::runtime_error("prompt[" + std::to_string(i) + "] has " + std::to_string(prompts[i].size()) +
+                                             " tokens, the context holds " + std::to_string(seqLen) + " with the completion");
+        } catch (const std::exception &e) {
+            Value err = Value::object();
+            err.set("error", std::string("Invalid request: ") + e.what());
+            conn.writeJson(400, err.dump());
+            return;
+        }
+        std::vector<std::shared_ptr<GenRequest>> reqs;
+        struct CancelOnExit {  // the client went away, or one item failed: drop the rest
+            std::vector<std::shared_ptr<GenRequest>> &rs;
+            ~CancelOnExit() {
+                for (auto &r : rs) r->cancel();
+            }
+        } cancelGuard{reqs};
+        size_t promptTokens = 0;
+        for (size_t i = 0; i < prompts.size(); i++) {
+            GenParams pi = p;
+            pi.seed = p.seed + i;  // (items of one request draw from their own generators)
+            promptTokens += prompts[i].size();
+            reqs.push_back(sched->submit(prompts[i], pi));
+        }
+        const std::string id = "cmpl-" + std::to_string(reqs[0]->id);
+        const long created = (long)std::time(nullptr);
+        auto envelope = [&]() {
+            Value v = Value::object();
+            v.set("id", id);
+            v.set("object", "text_completion");
+            v.set("created", created);
+            v.set("model", model);
+            return v;
+        };
+        if (stream) {
+            conn.beginSse();
+            for (size_t i = 0; i < reqs.size(); i++) {
+                GenRequest &r = *reqs[i];
+                LegacyCursor cur;
+                auto send = [&](const std::string &text, bool last) {
+                    Value chunk = envelope();
+                    Value ch = Value::object();
+                    ch.set("text", text);
+                    ch.set("index", (int)i);
+                    ch.set("logprobs", p.logprobs ? legacyLogprobsJson(r, cur) : Value());
+                    ch.set("finish_reason", last ? Value(r.finishReason) : Value());
+                    chunk.set("choices", Value::array()).push(ch);
+                    conn.writeSse(chunk.dump());
+                };
+                if (p.echo) {  // the prompt and, once every row was scored, its records
+                    if (p.promptLogprobs) r.waitPromptLogprobs();
+                    send(texts[i], false);
+                }
+                std::string d;
+                while (r.nextDelta(d)) send(d, false);
+                send("", true);  // the records not sent yet
+            }
+            conn.writeSse("[DONE]");
+            return;
+        }
+        Value choices = Value::array();
+        int completionTokens = 0, cachedTokens = 0;
+        for (size_t i = 0; i < reqs.size(); i++) {
+            GenRequest &r = *reqs[i];
+            const std::string text = r.wait();
+            if (r.finishReason == "error") {
+                Value err = Value::object();
+                err.set("error", r.error.empty() ? "generation failed" : r.error);
+                conn.writeJson(500, err.dump());
+                return;
+            }
+            LegacyCursor cur;
+            Value ch = Value::object();
+            ch.set("text", p.echo ? texts[i] + text : text);
+            ch.set("index", (int)i);
+            ch.set("logprobs", p.logprobs ? legacyLogprobsJson(r, cur) : Value());
+            ch.set("finish_reason", r.finishReason);
+            choices.push(ch);
+            completionTokens += r.completionTokens;
+            cachedTokens += r.cachedTokens;
+        }
+        Value resp = envelope();
+        resp.set("choices", choices);
+        Value usage = Value::object();
+        usage.set("prompt_tokens", (double)promptTokens);
+        usage.set("completion_tokens", completionTokens);
+        usage.set("total_tokens", (double)promptTokens + completionTokens);
+        Value details = Value::object();
+        details.set("cached_tokens", cachedTokens);
+        usage.set("prompt_tokens_details", details);
+        resp.set("usage", usage);
+        conn.writeJson(200, resp.dump());
+        if (logLevel() >= 1) {
+            std::printf("🔶 %s: %zu prompts, %zu prompt + %d completion tokens\n", id.c_str(), reqs.size(), promptTokens, completionTokens);
+            std::fflush(stdout);
+        }
+    }
+
     void models(const HttpRequest &, HttpConnection &conn) {
         Value m = Value::object();
         m.set("id", model);
@@ -516,6 +755,10 @@ struct Api {
                (double)s.logitFilterRequests);
         metric("dllama_embedding_requests_total", "counter", "Finished embedding requests.", (double)s.embeddingRequests);
         metric("dllama_json_requests_total", "counter", "Finished requests in JSON mode.", (double)s.jsonRequests);
+        metric("dllama_completion_requests_total", "counter", "Finished /v1/completions requests (one per prompt item).",
+               (double)s.completionRequests);
+        metric("dllama_scored_prompt_tokens_total", "counter", "Prompt tokens scored (echo with logprobs).",
+               (double)s.scoredPromptTokens);
         metric("dllama_active_requests", "gauge", "Requests holding a KV slot.", (double)s.active);
         metric("dllama_queued_requests", "gauge", "Requests waiting for a KV slot.", (double)s.queued);
         metric("dllama_kv_slots", "gauge", "KV-cache slots (max concurrent sequences).", (double)sess->nSlots());
@@ -550,6 +793,8 @@ struct Api {
         v.set("logit_filter_requests", (double)s.logitFilterRequests);
         v.set("json_requests", (double)s.jsonRequests);
         v.set("embedding_requests", (double)s.embeddingRequests);
+        v.set("completion_requests", (double)s.completionRequests);
+        v.set("scored_prompt_tokens", (double)s.scoredPromptTokens);
         conn.writeJson(200, v.dump());
     }
 };
@@ -624,6 +869,7 @@ int main(int argc, char **argv) {
         api.sched = &sched;
         HttpServer server(args.port);
         server.route("POST", "/v1/chat/completions", [&](const HttpRequest &r, HttpConnection &c) { api.complete(r, c); });
+        server.route("POST", "/v1/completions", [&](const HttpRequest &r, HttpConnection &c) { api.completions(r, c); });
         server.route("POST", "/v1/embeddings", [&](const HttpRequest &r, HttpConnection &c) { api.embeddings(r, c); });
         server.route("GET", "/v1/models", [&](const HttpRequest &r, HttpConnection &c) { api.models(r, c); });
         server.route("GET", "/health", [&](const HttpRequest &r, HttpConnection &c) { api.health(r, c); });

@@ -194,6 +194,7 @@ void HipEngineImpl::collectIds(int *out) {
 // stream - not inside the graph, like launchLogprobs.
 void HipEngineImpl::enqueueSampled(int n, const int *tokens, const int *positions, const int *slots,
                                    const SampleSpec *specs) {
+    const std::vector<int> targets = takeLogprobTargets(n, specs);  // (checked before anything is enqueued)
     std::vector<LogitProc> procs;
     GraphKind kind = beginProcs(n, slots, specs, procs);
     const std::vector<PoolSpec> pool = beginPooling(n, positions, slots);
@@ -214,7 +215,7 @@ void HipEngineImpl::enqueueSampled(int n, const int *tokens, const int *position
         logprobReq_.clear();
         DL_HIP(hipMemsetAsync(dIds_, 0xff, n * sizeof(int), stream_));  // no row drew: ids -1
     } else {
-        enqueueLogprobs(n, specs);
+        enqueueLogprobs(n, specs, targets);
         if (poolStaged_) {
             enqueuePool(n);
             DL_HIP(hipGetLastError());
@@ -437,7 +438,7 @@ hipk::LogitProcArgs HipEngineImpl::logitProcArgs(const float *raw) const {
 // replay exactly the graphs they always did - over the full logits and the ids the sampler wrote,
 // and the (1 + 20) pairs per row copied to pinned memory with the ids. Root only: the other ranks
 // of a tensor-parallel forward neither hold the full logits nor draw.
-void HipEngineImpl::enqueueLogprobs(int n, const SampleSpec *specs) {
+void HipEngineImpl::enqueueLogprobs(int n, const SampleSpec *specs, const std::vector<int> &targets) {
     logprobReq_.clear();
     if (!specs || rank() != 0) return;
     bool any = false;
@@ -452,6 +453,11 @@ void HipEngineImpl::enqueueLogprobs(int n, const SampleSpec *specs) {
     g.spec = dSpec_;
     g.scratch = logprobScratch_;
     g.out = dLogprobs_;
+    if (!targets.empty()) {  // (the pinned staging is free: the previous forward was collected)
+        std::memcpy(hLogprobTargets_, targets.data(), (size_t)n * sizeof(int));
+        DL_HIP(hipMemcpyAsync(dLogprobTargets_, hLogprobTargets_, (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream_));
+        g.target = dLogprobTargets_;
+    }
     hipk::launchLogprobs(g, n, stream_);
     DL_HIP(hipGetLastError());
     DL_HIP(hipMemcpyAsync(hLogprobs_, dLogprobs_, (size_t)n * hipk::kLogprobSlots * sizeof(hipk::LogprobEntry),

@@ -426,7 +426,9 @@ class HipEngineImpl : public HipEngine {
     hipk::LogprobScratch logprobScratch_;
     hipk::LogprobEntry *dLogprobs_ = nullptr, *hLogprobs_ = nullptr;
     std::vector<int> logprobReq_;  // per row of the forward in flight (empty: no row asked)
-    void enqueueLogprobs(int n, const SampleSpec *specs);
+    // given tokens to score (Backend::setLogprobTargets): staged next to the specs when a row has one
+    int *dLogprobTargets_ = nullptr, *hLogprobTargets_ = nullptr;  // [maxBatch]
+    void enqueueLogprobs(int n, const SampleSpec *specs, const std::vector<int> &targets);
     void enqueueSampled(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs);
     void readLogprobs();
     // logit processors (Backend::setLogitProcs), root rank only: per slot the dense token counts and

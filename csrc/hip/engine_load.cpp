@@ -237,6 +237,8 @@ void HipEngineImpl::allocBuffers() {
         logprobScratch_.carve(ls, (int)MB);
         dLogprobs_ = dalloc<hipk::LogprobEntry>((size_t)MB * hipk::kLogprobSlots);
         hLogprobs_ = halloc<hipk::LogprobEntry>((size_t)MB * hipk::kLogprobSlots);
+        dLogprobTargets_ = dalloc<int>(MB);
+        hLogprobTargets_ = halloc<int>(MB);
     }
     dArgCnt_ = dalloc<int>(MB);
     DL_HIP(hipMemsetAsync(dArgCnt_, 0, sizeof(int) * MB, stream_));

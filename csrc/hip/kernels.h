@@ -555,8 +555,9 @@ void launchSample(const SampleArgs &a, int B, hipStream_t s);
 
 // Log-probabilities of B rows of full-vocabulary logits: log_softmax of the raw logits (whatever
 // the row's temperature / top-p). spec[b].w is the row's request (SampleSpec::logprobs): 0 = none
-// (the row's output is left untouched), 1 + k = the token ids[b] plus the k <= kLogprobTop best
-// tokens, ordered by (logit descending, id ascending) on the f32 logits. out[b] holds 1 + kLogprobTop
+// (the row's output is left untouched), 1 + k = the token ids[b] (or the given token target[b] of
+// a row that draws none: prompt scoring) plus the k <= kLogprobTop best tokens, ordered by
+// (logit descending, id ascending) on the f32 logits. out[b] holds 1 + kLogprobTop
 // {logprob, id} pairs: slot 0 the chosen token (id -1 when ids[b] is no token), slots 1..k the best,
 // the rest id -1. One launch of logprobGroups(vocab) workgroups per row - a count that does not
 // depend on B, so a row's result is bitwise the same whatever else is in the launch: every
@@ -592,6 +593,7 @@ struct LogprobArgs {
     int vocab = 0;
     const int *ids = nullptr;       // [B] the tokens just written by the sampler / argmax on this stream
     const float4 *spec = nullptr;   // [B] (temperature, topp, coin, request)
+    const int *target = nullptr;    // [B] or null: target[b] >= 0 is the token slot 0 scores instead of ids[b]
     LogprobScratch scratch;
     LogprobEntry *out = nullptr;    // [B][kLogprobSlots]
 };

@@ -150,7 +150,8 @@ __global__ __launch_bounds__(kRowWg) void logprobsKernel(LogprobArgs a) {
         const float lz = logf(z);
         lse[0] = gm;
         lse[1] = lz;
-        const int id = a.ids[b];
+        const int tg = a.target ? a.target[b] : -1;  // a row that scores a given token draws none
+        const int id = tg >= 0 ? tg : a.ids[b];
         const bool ok = id >= 0 && id < V;
         LogprobEntry e;
         e.logprob = ok ? (x[ok ? id : 0] - gm) - lz : 0.f;

@@ -1145,9 +1145,9 @@ hipk::LogprobArgs logprobArgs(Scratch &sc, int B, int vocab, const std::vector<i
 
 void logprobs(const std::vector<float> &logits, int B, int vocab, const std::vector<int> &ids,
               const std::vector<int> &requests, std::vector<float> &outLogprobs, std::vector<int> &outIds,
-              const std::vector<float> *warmLogits, const std::vector<int> *warmIds) {
+              const std::vector<float> *warmLogits, const std::vector<int> *warmIds, const std::vector<int> *targets) {
     DL_CHECK(B >= 1 && vocab >= 1 && logits.size() == (size_t)B * vocab && ids.size() == (size_t)B &&
-                 requests.size() == (size_t)B, "logprobs sizes");
+                 requests.size() == (size_t)B && (!targets || targets->size() == (size_t)B), "logprobs sizes");
     for (int r : requests) DL_CHECK(r >= 0 && r <= hipk::kLogprobSlots, "logprobs request out of range");
     Scratch sc;
     hipk::LogprobArgs g = logprobArgs(sc, B, vocab, requests);
@@ -1159,6 +1159,7 @@ void logprobs(const std::vector<float> &logits, int B, int vocab, const std::vec
     }
     g.logits = sc.upload(logits);
     g.ids = sc.upload(ids);
+    if (targets) g.target = sc.upload(*targets);
     hipk::launchLogprobs(g, B, sc.s);
     sc.sync();
     const std::vector<hipk::LogprobEntry> out = sc.download(g.out, (size_t)B * hipk::kLogprobSlots);
@@ -1171,7 +1172,7 @@ void logprobs(const std::vector<float> &logits, int B, int vocab, const std::vec
 }
 
 void benchLogprobs(const std::vector<float> &logits, int B, int vocab, int k, int iters, double &logprobsUs,
-                   double &argmaxUs) {
+                   double &argmaxUs, bool targets) {
     DL_CHECK(B >= 1 && vocab >= 1 && logits.size() == (size_t)B * vocab && k >= 0 && k <= hipk::kLogprobTop && iters >= 1,
              "bench_logprobs arguments");
     Scratch sc;
@@ -1179,6 +1180,11 @@ void benchLogprobs(const std::vector<float> &logits, int B, int vocab, int k, in
     g.logits = sc.upload(logits);
     const hipk::ArgmaxArgs am = argmaxArgs(sc, g.logits, B, vocab);
     g.ids = am.ids;
+    if (targets) {
+        std::vector<int> tg(B);
+        for (int b = 0; b < B; b++) tg[b] = (int)((long long)b * 7919 % vocab);
+        g.target = sc.upload(tg);
+    }
     argmaxUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] { hipk::launchArgmax(am, B, sc.s); });
     logprobsUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] { hipk::launchLogprobs(g, B, sc.s); });
     sc.sync();

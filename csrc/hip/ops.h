@@ -217,14 +217,17 @@ std::vector<int> sample(const std::vector<float> &logits, int B, int vocab, cons
 // launchLogprobs over [B][vocab] logits: ids[b] the row's chosen token, requests[b] = 0 (none) or
 // 1 + k (SampleSpec::logprobs). Returns [B][21] (logprob, id) pairs as two arrays; the output is
 // pre-filled with (0, -2), which rows without a request keep. `warm` (optional): logits and ids of
-// an earlier call with the same requests, run first on the same scratch and output buffer.
+// an earlier call with the same requests, run first on the same scratch and output buffer (without
+// targets). `targets` (optional, [B]): LogprobArgs::target, the given token a row scores (< 0: ids[b]).
 void logprobs(const std::vector<float> &logits, int B, int vocab, const std::vector<int> &ids,
               const std::vector<int> &requests, std::vector<float> &outLogprobs, std::vector<int> &outIds,
-              const std::vector<float> *warmLogits = nullptr, const std::vector<int> *warmIds = nullptr);
+              const std::vector<float> *warmLogits = nullptr, const std::vector<int> *warmIds = nullptr,
+              const std::vector<int> *targets = nullptr);
 // Device microseconds per launch of launchLogprobs (request 1 + k on every row) and of launchArgmax
 // on the same [B][vocab] logits: `iters` launches of each between two events, after a warm-up.
+// targets: every row scores a given token (b * 7919 % vocab) instead of the argmax kernel's id.
 void benchLogprobs(const std::vector<float> &logits, int B, int vocab, int k, int iters, double &logprobsUs,
-                   double &argmaxUs);
+                   double &argmaxUs, bool targets = false);
 
 // launchLogitProc over [B][vocab] logits. Row b: temps[b] (< 0: the row is not drawn and its output
 // keeps `fill`), slots[b] in [0, nSlots), active[b], presence[b], frequency[b]. counts is the

@@ -186,12 +186,15 @@ std::vector<int> runSample(Backend &b, const std::vector<int> &tokens, const std
 }
 
 // forward_sample plus per-row log-probabilities: top[i] = -1 (no request) or k in 0..20. Returns
-// (ids, float32 [n][21] logprobs, int32 [n][21] token ids); see Backend::lastLogprobs.
+// (ids, float32 [n][21] logprobs, int32 [n][21] token ids); see Backend::lastLogprobs. targets: None
+// or one token id per row (Backend::setLogprobTargets: >= 0 scores that token on a row that draws none).
 py::tuple runLogprobs(Backend &b, const std::vector<int> &tokens, const std::vector<int> &positions,
                       const std::vector<int> &slots, const std::vector<float> &temps, const std::vector<float> &topps,
                       const std::vector<float> &coins, const std::vector<int> &top,
-                      const py::object &logitProcs = py::none()) {
+                      const py::object &logitProcs = py::none(), const py::object &targets = py::none()) {
     const size_t n = tokens.size();
+    const std::vector<int> tg = targets.is_none() ? std::vector<int>() : targets.cast<std::vector<int>>();
+    DL_CHECK(targets.is_none() || tg.size() == n, "targets: one token id (or -1) per row");
     DL_CHECK(positions.size() == n && slots.size() == n && temps.size() == n && topps.size() == n &&
                  coins.size() == n && top.size() == n, "one (temperature, topp, coin, top_logprobs) per row");
     std::vector<SampleSpec> specs(n);
@@ -205,6 +208,7 @@ py::tuple runLogprobs(Backend &b, const std::vector<int> &tokens, const std::vec
     {
         py::gil_scoped_release rel;
         if (!procs.empty()) b.setLogitProcs((int)n, procs.data());
+        if (!tg.empty()) b.setLogprobTargets((int)n, tg.data());
         b.forwardSample((int)n, tokens.data(), positions.data(), slots.data(), specs.data(), out.data());
         lp = b.lastLogprobs();
     }
@@ -637,9 +641,9 @@ void bindOps(py::module_ &m) {
           });
     o.def("logprobs",
           [](py::object logits, std::vector<int> ids, std::vector<int> requests, py::object warmLogits,
-             py::object warmIds) {
+             py::object warmIds, py::object targets) {
               const std::vector<float> l = vec<float>(logits), wl = vec<float>(warmLogits);
-              const std::vector<int> wi = vec<int>(warmIds);
+              const std::vector<int> wi = vec<int>(warmIds), tg = vec<int>(targets);
               const int B = (int)ids.size();
               DL_CHECK(B >= 1 && l.size() % B == 0, "logprobs: one id per row");
               std::vector<float> v;
@@ -647,12 +651,12 @@ void bindOps(py::module_ &m) {
               {
                   py::gil_scoped_release rel;
                   ops::logprobs(l, B, (int)(l.size() / B), ids, requests, v, idx, wl.empty() ? nullptr : &wl,
-                                wl.empty() ? nullptr : &wi);
+                                wl.empty() ? nullptr : &wi, targets.is_none() ? nullptr : &tg);
               }
               return py::make_tuple(arr(v, {B, (py::ssize_t)kLogprobEntries}), arr(idx, {B, (py::ssize_t)kLogprobEntries}));
           },
           py::arg("logits"), py::arg("ids"), py::arg("requests"), py::arg("warm_logits") = py::none(),
-          py::arg("warm_ids") = py::none());
+          py::arg("warm_ids") = py::none(), py::arg("targets") = py::none());
     o.def("logit_proc",
           [](py::object logits, std::vector<float> temps, std::vector<int> slots, std::vector<int> active,
              std::vector<float> presence, std::vector<float> frequency, py::object counts, py::object biasIds,
@@ -817,16 +821,16 @@ void bindOps(py::module_ &m) {
           py::arg("rows"), py::arg("dim"), py::arg("slots") = 1, py::arg("add") = true, py::arg("iters") = 50,
           "(us per launchPool, us per device copy of the same rows)");
     o.def("bench_logprobs",
-          [](py::object logits, int B, int k, int iters) {
+          [](py::object logits, int B, int k, int iters, bool targets) {
               const std::vector<float> l = vec<float>(logits);
               double lp = 0, am = 0;
               {
                   py::gil_scoped_release rel;
-                  ops::benchLogprobs(l, B, (int)(l.size() / B), k, iters, lp, am);
+                  ops::benchLogprobs(l, B, (int)(l.size() / B), k, iters, lp, am, targets);
               }
               return py::make_tuple(lp, am);
           },
-          py::arg("logits"), py::arg("batch"), py::arg("k"), py::arg("iters") = 200,
+          py::arg("logits"), py::arg("batch"), py::arg("k"), py::arg("iters") = 200, py::arg("targets") = false,
           "(us per launchLogprobs, us per launchArgmax) on the same logits");
     o.def("argmax",
           [](py::object logits, int B) {
@@ -1149,7 +1153,7 @@ PYBIND11_MODULE(_C, m) {
              py::arg("temperatures"), py::arg("topps"), py::arg("coins"), py::arg("logit_procs") = py::none())
         .def("forward_logprobs", &runLogprobs, py::arg("tokens"), py::arg("positions"), py::arg("slots"),
              py::arg("temperatures"), py::arg("topps"), py::arg("coins"), py::arg("top_logprobs"),
-             py::arg("logit_procs") = py::none())
+             py::arg("logit_procs") = py::none(), py::arg("targets") = py::none())
         .def("forward_argmax", [](Backend &b, std::vector<int> t, std::vector<int> p, std::vector<int> s) { return runArgmax(b, t, p, s); },
              py::arg("tokens"), py::arg("positions"), py::arg("slots"))
         .def("forward_embed", &runEmbed, py::arg("tokens"), py::arg("positions"), py::arg("slots"), py::arg("pooling"),
@@ -1530,11 +1534,12 @@ PYBIND11_MODULE(_C, m) {
              py::arg("coins"), py::arg("logit_procs") = py::none())
         .def("forward_logprobs",
              [](PyHipEngine &e, std::vector<int> t, std::vector<int> p, std::vector<int> s, std::vector<float> temps,
-                std::vector<float> topps, std::vector<float> coins, std::vector<int> top, py::object procs) {
-                 return runLogprobs(*e.engine, t, p, s, temps, topps, coins, top, procs);
+                std::vector<float> topps, std::vector<float> coins, std::vector<int> top, py::object procs,
+                py::object targets) {
+                 return runLogprobs(*e.engine, t, p, s, temps, topps, coins, top, procs, targets);
              },
              py::arg("tokens"), py::arg("positions"), py::arg("slots"), py::arg("temperatures"), py::arg("topps"),
-             py::arg("coins"), py::arg("top_logprobs"), py::arg("logit_procs") = py::none())
+             py::arg("coins"), py::arg("top_logprobs"), py::arg("logit_procs") = py::none(), py::arg("targets") = py::none())
         .def("forward_argmax", [](PyHipEngine &e, std::vector<int> t, std::vector<int> p, std::vector<int> s) { return runArgmax(*e.engine, t, p, s); },
              py::arg("tokens"), py::arg("positions"), py::arg("slots"))
         .def("forward_embed",

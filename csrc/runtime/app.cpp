@@ -324,7 +324,7 @@ bool InferenceSession::sendEmbed(int n, const int *tokens, const int *positions,
                                  const SampleSpec *specs) {
     bool embed = poolPending_ && specs != nullptr;
     poolPending_ = false;
-    for (int i = 0; embed && i < n; i++) embed = specs[i].temperature < 0.f;
+    for (int i = 0; embed && i < n; i++) embed = specs[i].temperature < 0.f && !(specs[i].logprobs >= 1.f);  // (Backend::noRowDraws)
     if (embed) sendControl(Cmd::FORWARD_EMBED, n, tokens, positions, slots);
     return embed;
 }

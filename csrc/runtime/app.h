@@ -102,6 +102,9 @@ class InferenceSession {
     // logit processors of the next forwardSample / launchIds (Backend::setLogitProcs; the root
     // draws, so nothing goes to the workers)
     void setLogitProcs(int n, const LogitProc *procs) { backend_->setLogitProcs(n, procs); }
+    // given tokens to score in the next forwardSample / launchIds (Backend::setLogprobTargets; the
+    // root scores, so nothing goes to the workers)
+    void setLogprobTargets(int n, const int *targets) { backend_->setLogprobTargets(n, targets); }
     // JSON mode (LogitProc::json): builds the token table from the tokenizer, checks that the
     // vocabulary cannot dead-end (jsonDeadEnd) and hands the table to the backend. Returns an empty
     // string, or why JSON mode is unavailable (the backend then has no table).

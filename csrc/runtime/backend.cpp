@@ -218,7 +218,7 @@ std::vector<PoolSpec> Backend::takePooling(int n, const int *positions, const in
 bool Backend::noRowDraws(int n, const SampleSpec *specs) {
     if (!specs) return false;
     for (int i = 0; i < n; i++)
-        if (specs[i].temperature >= 0.f) return false;
+        if (specs[i].temperature >= 0.f || specs[i].logprobs >= 1.f) return false;
     return true;
 }
 
@@ -262,6 +262,32 @@ void Backend::forwardEmbed(int n, const int *tokens, const int *positions, const
 
 void Backend::setLogitProcs(int n, const LogitProc *procs) { pendingProcs_.assign(procs, procs + n); }
 
+void Backend::setLogprobTargets(int n, const int *targets) { pendingTargets_.assign(targets, targets + n); }
+
+std::vector<int> Backend::takeLogprobTargets(int n, const SampleSpec *specs) {
+    std::vector<int> targets;
+    targets.swap(pendingTargets_);
+    if (targets.empty()) return targets;
+    auto fail = [&](const char *what) {  // the forward does not run: what was handed over for it goes with it
+        pendingProcs_.clear();
+        pendingPool_.clear();
+        throw Error(std::string("setLogprobTargets: ") + what);
+    };
+    if (!specs) fail("targets need a sampled forward (specs)");
+    if ((int)targets.size() != n) fail("one target per row of the forward");
+    const int vocab = (int)header().vocabSize;
+    bool any = false;
+    for (int i = 0; i < n; i++) {
+        if (targets[i] < 0) continue;
+        any = true;
+        if (targets[i] >= vocab) fail("token id out of range");
+        if (specs[i].temperature >= 0.f) fail("a row with a target draws no token (temperature < 0)");
+        if (!(specs[i].logprobs >= 1.f)) fail("a row with a target asks for log-probabilities (SampleSpec::logprobs)");
+    }
+    if (!any) targets.clear();  // no row has one: the forward is the plain one
+    return targets;
+}
+
 void Backend::setJsonTable(std::shared_ptr<const JsonTokenTable> table) {
     if (table && table->vocab() != (int)header().vocabSize) throw Error("json mode: the token table is not the model's vocabulary");
     jsonTable_ = std::move(table);
@@ -297,6 +323,7 @@ std::vector<LogitProc> Backend::takeLogitProcs(int n) {
 void Backend::forwardSample(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs,
                             int *out) {
     const int vocab = (int)header().vocabSize;
+    const std::vector<int> targets = takeLogprobTargets(n, specs);
     const std::vector<LogitProc> procs = takeLogitProcs(n);
     if (plan().rank != 0) {  // workers take part in the forward; the root draws
         pendingPool_.clear();
@@ -353,7 +380,7 @@ void Backend::forwardSample(int n, const int *tokens, const int *positions, cons
         if (proc && out[i] >= 0 && out[i] < vocab) procCounts_[(size_t)slots[i]][out[i]]++;
         if (proc && procs[i].json) jsonStates_[(size_t)slots[i]] = jsonAdvanceHost(*jsonTable_, jsonStates_[(size_t)slots[i]], out[i]);
         if (req >= 1)
-            logprobsHost(raw.data(), vocab, out[i], std::min(req - 1, kMaxTopLogprobs),
+            logprobsHost(raw.data(), vocab, !targets.empty() && targets[i] >= 0 ? targets[i] : out[i], std::min(req - 1, kMaxTopLogprobs),
                          &logprobs_[(size_t)i * kLogprobEntries]);
     }
 }
@@ -371,6 +398,7 @@ void Backend::launchIds(int n, const int *tokens, const int *positions, const in
             pendingPool_.clear();
             throw Error("launchIds: pooling needs a sampled forward (specs)");
         }
+        takeLogprobTargets(n, nullptr);
         pooled_ = PooledSlots{};
         logprobs_.clear();
         forwardArgmax(n, tokens, positions, slots, pendingIds_.data());

@@ -211,6 +211,13 @@ class Backend {
     // that forward asked for them (SampleSpec::logprobs; rows that did not hold id -1 throughout),
     // empty otherwise and on ranks other than the root. Valid until the next forward is launched.
     virtual const std::vector<TokenLogprob> &lastLogprobs() const { return logprobs_; }
+    // Given tokens to score (prompt log-probabilities) in the next forwardSample / launchIds (with
+    // specs) of n rows, which consumes them: targets[i] >= 0 makes row i's entry 0 of lastLogprobs()
+    // (log_softmax[targets[i]], targets[i]) instead of the drawn token's; entries 1..k are as ever.
+    // Such a row draws nothing (temperature < 0) and asks for log-probabilities (SampleSpec::logprobs
+    // = 1 + k), else the forward throws. targets[i] < 0: the row behaves as without a call. Root only
+    // (the root scores the gathered logits): workers and the worker protocol take no part.
+    virtual void setLogprobTargets(int n, const int *targets);
     // Pooling of the next forwardSample / launchIds (with specs) / forwardEmbed of n rows, which
     // consumes it: pool[i] belongs to row i. Rows of one slot appear in a forward in ascending
     // position. Root only (the final residual is replicated: the root pools); without a call,
@@ -271,6 +278,10 @@ class Backend {
     std::vector<LogitProc> pendingProcs_;  // setLogitProcs, until the next sampled forward takes them
     // takes pendingProcs_ for a forward of n rows (empty: none set); checks sizes, bias ids and counts
     std::vector<LogitProc> takeLogitProcs(int n);
+    std::vector<int> pendingTargets_;  // setLogprobTargets, until the next sampled forward takes them
+    // takes pendingTargets_ for a forward of n rows (empty: none set, or no row has one); checks the
+    // size, the ids and that a target row neither draws nor lacks a request
+    std::vector<int> takeLogprobTargets(int n, const SampleSpec *specs);
     // host state of the default forwardSample, per slot (allocated at a slot's first fresh row)
     std::vector<std::vector<u32>> procCounts_;
     std::vector<std::vector<LogitBias>> procBias_;
@@ -281,7 +292,8 @@ class Backend {
     // takes pendingPool_ for a forward of n rows (empty: none set, or no row takes part); checks the
     // sizes and that each slot's taking-part rows come in ascending position
     std::vector<PoolSpec> takePooling(int n, const int *positions, const int *slots);
-    // every row of the forward is a non-drawing row (specs null: every row draws)
+    // no row of the forward needs logits: none draws (specs null: every row draws) and none asks for
+    // log-probabilities (a prompt row that scores a given token)
     static bool noRowDraws(int n, const SampleSpec *specs);
     std::vector<std::vector<float>> poolAcc_;  // default pooling: per slot
     void poolRowsHost(int n, const int *slots, const std::vector<PoolSpec> &pool, const float *hidden);

@@ -22,6 +22,11 @@ bool GenRequest::nextDelta(std::string &out) {
     return false;
 }
 
+void GenRequest::waitPromptLogprobs() {
+    std::unique_lock<std::mutex> lk(mu);
+    cv.wait(lk, [&] { return done || promptLogprobs.size() >= prompt.size(); });
+}
+
 void GenRequest::emit(const std::string &d) {
     if (d.empty()) return;
     std::lock_guard<std::mutex> lk(mu);
@@ -213,6 +218,28 @@ void Scheduler::finishRequest(const std::shared_ptr<GenRequest> &r, const char *
     active_.erase(std::remove(active_.begin(), active_.end(), r), active_.end());
 }
 
+// Scheduler thread. Row i of the prompt scored token i + 1: the record of position i + 1 comes from
+// the pick's batch row of position i; position 0 gets the empty record.
+void Scheduler::appendPromptRecords(const Pick &p, const std::vector<TokenLogprob> &logprobs) {
+    GenRequest *r = p.r.get();
+    const int N = (int)r->prompt.size(), k = r->params.topLogprobs;
+    std::vector<TokenRecord> recs;
+    if (p.start == 0) recs.push_back(TokenRecord{TokenLogprob{0.f, -1}, {}});
+    for (int i = 0; i < p.prefill && p.start + i + 1 < N; i++) {
+        const size_t row = (size_t)(p.firstRow() + i);
+        TokenRecord rec{TokenLogprob{0.f, -1}, {}};
+        if (logprobs.size() >= (row + 1) * kLogprobEntries) {
+            const TokenLogprob *e = &logprobs[row * kLogprobEntries];
+            rec.chosen = e[0];
+            for (int j = 1; j < kLogprobEntries && j <= k && e[j].id >= 0; j++) rec.top.push_back(e[j]);
+        }
+        recs.push_back(std::move(rec));
+    }
+    std::lock_guard<std::mutex> rl(r->mu);
+    for (auto &rec : recs) r->promptLogprobs.push_back(std::move(rec));
+    r->cv.notify_all();
+}
+
 // Under mu_. The request takes the slot and starts with its first `prefilled` prompt tokens' KV
 // already in place (0 without prefix reuse).
 void Scheduler::startRequest(const std::shared_ptr<GenRequest> &r, int slot, size_t prefilled) {
@@ -283,8 +310,9 @@ bool Scheduler::admitWithPrefix() {
             return true;
         }
         if (freeSlots_.empty()) return false;
-        // (an embedding request never takes a hit: mean pooling needs every row's hidden state)
-        const size_t cap = r->params.embed != EmbedMode::OFF ? 0 : r->prompt.size() - 1;
+        // (an embedding request never takes a hit: mean pooling needs every row's hidden state; nor
+        //  does one that scores its prompt: every row's logits are needed)
+        const size_t cap = r->params.embed != EmbedMode::OFF || r->params.promptLogprobs ? 0 : r->prompt.size() - 1;
         int idleBest = -1, lru = freeSlots_.back();
         size_t idleL = 0, activeL = 0;
         for (auto it = freeSlots_.rbegin(); it != freeSlots_.rend(); ++it) {
@@ -387,6 +415,7 @@ bool Scheduler::step() {
         for (auto &p : flight_.picks) {
             GenRequest *r = p.r.get();
             if (r->finished) continue;  // finished while its row was in flight: dropped
+            if (r->params.promptLogprobs && p.prefill > 0) appendPromptRecords(p, doneLogprobs);
             r->prefilled += p.prefill;
             if (p.sample) r->generated.push_back(ids[p.row]);
         }
@@ -415,6 +444,16 @@ bool Scheduler::step() {
             stats_.completed++;
             stats_.embeddingRequests++;
             finishRequest(p.r, "stop");
+        }
+        // so does an echo request with max_tokens 0: its last prompt row asked for nothing
+        for (auto &p : done) {
+            if (p.r->finished) continue;
+            if (p.r->params.promptLogprobs)  // (the last prompt row scores nothing)
+                stats_.scoredPromptTokens += (u64)std::max(0, std::min(p.prefill, (int)p.r->prompt.size() - 1 - p.start));
+            if (!p.scoreDone) continue;
+            stats_.completed++;
+            if (p.r->params.completion) stats_.completionRequests++;
+            finishRequest(p.r, "length");
         }
     }
     flushReleases();  // slots freed by the previous step's text work and by the collection above
@@ -479,7 +518,7 @@ bool Scheduler::step() {
     Flight next;
     for (auto &rp : active_) {
         GenRequest *r = rp.get();
-        if (r->prefilled < r->prompt.size() || r->params.embed != EmbedMode::OFF) continue;
+        if (r->prefilled < r->prompt.size() || r->params.drawsNothing()) continue;
         if ((int)tokens.size() >= sess_.maxBatch()) break;
         const int pos = (int)(r->prompt.size() + r->generated.size()) - 1;
         if ((r->params.maxTokens > 0 && (int)r->generated.size() >= r->params.maxTokens) || (u32)(pos + 1) >= seqLen)
@@ -502,8 +541,9 @@ bool Scheduler::step() {
             slots.push_back(r->slot);
         }
         const bool completes = r->prefilled + take == r->prompt.size();
-        const bool embed = r->params.embed != EmbedMode::OFF;  // draws no token
-        next.picks.push_back({rp, (int)tokens.size() - 1, completes && !embed, take, completes && embed});
+        const bool embed = r->params.embed != EmbedMode::OFF, none = r->params.drawsNothing();  // draws no token
+        next.picks.push_back({rp, (int)tokens.size() - 1, completes && !none, take, completes && embed,
+                              completes && none && !embed, (int)r->prefilled});
     }
     next.n = (int)tokens.size();
 
@@ -518,9 +558,11 @@ bool Scheduler::step() {
         //  with penalties or a logit bias, which act between the logits and the draw)
         // (a forward with rows of an embedding request takes the specs too: they say which rows draw,
         //  and a forward in which none does computes no logits at all)
-        bool allGreedy = true, anyProc = false, anyPool = false;
+        // (so does one with prompt rows that score their next token: only a sampled forward keeps logits)
+        bool allGreedy = true, anyProc = false, anyPool = false, anyTarget = false;
         for (auto &p : next.picks) {
             if (p.r->params.embed != EmbedMode::OFF) allGreedy = false, anyPool = true;
+            if (p.r->params.promptLogprobs && p.prefill > 0 && p.start + 1 < (int)p.r->prompt.size()) allGreedy = false, anyTarget = true;
             if (!p.sample) continue;
             if (p.r->params.temperature != 0.0f || p.r->params.logprobs || p.r->params.logitProc()) allGreedy = false;
             anyProc = anyProc || p.r->params.logitProc();
@@ -556,6 +598,19 @@ bool Scheduler::step() {
                     lp.json = gp.jsonObject;
                 }
                 sess_.setLogitProcs(next.n, procs.data());
+            }
+            if (anyTarget) {  // prompt row i scores token i + 1, which may lie in the next chunk: the host knows it
+                std::vector<int> targets(next.n, -1);
+                for (auto &p : next.picks) {
+                    const GenParams &gp = p.r->params;
+                    if (!gp.promptLogprobs) continue;
+                    const int N = (int)p.r->prompt.size();
+                    for (int i = 0; i < p.prefill && p.start + i + 1 < N; i++) {
+                        targets[p.firstRow() + i] = p.r->prompt[p.start + i + 1];
+                        specs[p.firstRow() + i].logprobs = 1.f + (float)std::min(std::max(gp.topLogprobs, 0), kMaxTopLogprobs);
+                    }
+                }
+                sess_.setLogprobTargets(next.n, targets.data());
             }
             if (anyPool) {  // the prompt rows of the embedding requests: their picks' last `prefill` rows
                 std::vector<PoolSpec> pool(next.n);
@@ -624,6 +679,7 @@ bool Scheduler::step() {
             if (r->params.penalized()) stats_.logitProcRequests++;
             if (r->params.logitFilter()) stats_.logitFilterRequests++;
             if (r->params.jsonObject) stats_.jsonRequests++;
+            if (r->params.completion) stats_.completionRequests++;
             stats_.generatedTokens += r->generated.size();
             finishRequest(rp, reason);
         }

@@ -49,6 +49,15 @@ struct GenParams {
     // JSON mode (response_format json_object): every drawn token keeps the generated text a prefix of
     // a JSON object (jsonMaskHost), between the bias and the candidate filter; greedy requests too
     bool jsonObject = false;
+    // POST /v1/completions: `echo` returns the prompt with the completion and makes maxTokens == 0
+    // legal (the request then draws nothing: it ends with the forward that carries its last prompt
+    // row, finish_reason "length"); promptLogprobs (echo && logprobs) scores the prompt too: row i of
+    // the prompt scores token i + 1 (Backend::setLogprobTargets), with topLogprobs alternatives
+    bool completion = false;  // the request came through /v1/completions (SchedulerStats)
+    bool echo = false;
+    bool promptLogprobs = false;
+    // the request never goes beyond its prompt: an embedding, or an echo with max_tokens 0
+    bool drawsNothing() const { return embed != EmbedMode::OFF || (echo && maxTokens == 0); }
     bool penalized() const { return presencePenalty != 0.f || frequencyPenalty != 0.f || !logitBias.empty(); }
     bool logitFilter() const { return temperature != 0.f && (topK > 0 || minP > 0.f); }
     // the request's drawn rows carry a LogitProc
@@ -77,6 +86,9 @@ class GenRequest {
     bool done = false;
     int completionTokens = 0;
     std::vector<TokenRecord> logprobs;  // one per generated token (params.logprobs), the last one included
+    // params.promptLogprobs: one per prompt token, appended in position order as the forwards that
+    // carry the prompt are collected; entry 0 is empty (chosen.id -1: the first token has no context)
+    std::vector<TokenRecord> promptLogprobs;
     int cachedTokens = 0;  // prompt tokens whose KV was reused instead of prefilled (--prefix-cache)
     std::vector<float> embedding;  // params.embed: the pooled, L2-normalised vector [dim]
 
@@ -89,6 +101,8 @@ class GenRequest {
     std::string wait();
     // Pops the next delta (blocking); returns false once the request is done and drained.
     bool nextDelta(std::string &out);
+    // Blocks until every prompt token has its record (params.promptLogprobs) or the request is done.
+    void waitPromptLogprobs();
 
   private:
     friend class Scheduler;
@@ -115,6 +129,8 @@ struct SchedulerStats {
     u64 logitFilterRequests = 0;  // finished requests with top_k or min_p on
     u64 jsonRequests = 0;         // finished requests in JSON mode
     u64 embeddingRequests = 0;  // finished embedding requests
+    u64 completionRequests = 0;  // finished /v1/completions requests (one per prompt item)
+    u64 scoredPromptTokens = 0;  // prompt tokens scored for them (echo with logprobs)
 };
 
 class Scheduler {
@@ -130,11 +146,16 @@ class Scheduler {
     // decodes, EOS-checks and streams the previous forward's tokens.
     struct Pick {
         std::shared_ptr<GenRequest> r;
-        int row;      // batch row whose id belongs to the request
-        bool sample;  // the row yields the request's next token
-        int prefill;  // prompt tokens consumed by this forward
+        int row;      // the request's last batch row in the forward: the row whose id belongs to it
+        bool sample;  // that row yields the request's next token
+        int prefill;  // prompt tokens consumed by this forward: batch rows [row - prefill + 1, row]
         bool embedDone = false;  // the row is an embedding request's last prompt row
+        bool scoreDone = false;  // the row is the last prompt row of an echo request with max_tokens 0
+        int start = 0;           // prompt position of the first of the prefill rows
+        int firstRow() const { return prefill > 0 ? row - prefill + 1 : row; }
     };
+    // the records of the prompt rows of a collected pick, in position order (params.promptLogprobs)
+    void appendPromptRecords(const Pick &p, const std::vector<TokenLogprob> &logprobs);
     struct Flight {
         std::vector<Pick> picks;
         int n = 0, nDecode = 0;
@@ -177,14 +198,14 @@ class Scheduler {
     std::vector<size_t> slotReach_;  // positions launched into each slot (its mapped pages, paged)
     u64 useStamp_ = 0;
     std::vector<int> residentOf(const GenRequest &r) const;
-    // positions a request may reach: an embedding request never goes beyond its prompt
+    // positions a request may reach: one that draws nothing never goes beyond its prompt
     static u64 spanOf(const GenRequest &r, u32 seqLen) {
-        if (r.params.embed != EmbedMode::OFF) return r.prompt.size();
+        if (r.params.drawsNothing()) return r.prompt.size();
         return r.params.maxTokens > 0 ? (u64)r.prompt.size() + (u64)r.params.maxTokens + 1 : seqLen;
     }
-    // (a chat prompt leaves room for one generated token; an embedding input may fill the context)
+    // (a chat prompt leaves room for one generated token; one that draws nothing may fill the context)
     static bool promptTooLong(const GenRequest &r, u32 seqLen) {
-        return r.params.embed != EmbedMode::OFF ? r.prompt.size() > seqLen : r.prompt.size() >= seqLen;
+        return r.params.drawsNothing() ? r.prompt.size() > seqLen : r.prompt.size() >= seqLen;
     }
     int pagesFor(size_t positions) const { return (int)((positions + pageSize_ - 1) / pageSize_); }
     bool admitWithPrefix();  // one request from the head of the queue; false: nothing admitted

@@ -213,18 +213,20 @@ def sample(logits, temperatures, topps, coins) -> list:
     return native().ops.sample(x, B, spec)
 
 
-def logprobs(logits, ids, top_logprobs, warm=None):
+def logprobs(logits, ids, top_logprobs, targets=None, warm=None):
     """Device log-probabilities (launchLogprobs) of [B, vocab] logits: log_softmax of the raw logits.
     ids[b] is the row's chosen token, top_logprobs[b] = -1 (no request) or k in 0..20. Returns
     (float32 [B, 21] logprobs, int32 [B, 21] token ids): slot 0 the chosen token, slots 1..k the k
     best by (logit descending, id ascending), unused slots id -1. Rows without a request are not
     written and keep the fill (0, -2). warm=(logits, ids): an earlier call of the same shape and
-    requests run first on the same scratch and output buffers."""
+    requests run first on the same scratch and output buffers. targets[b] >= 0: the row scores that
+    given token in slot 0 instead of ids[b] (prompt scoring); None or -1: ids[b]."""
     x = _np(logits)
     x = x.reshape(1, -1) if x.ndim == 1 else x
     req = [0 if int(k) < 0 else 1 + int(k) for k in top_logprobs]
     wl, wi = (None, None) if warm is None else (_np(warm[0]), np.asarray(warm[1], np.int32))
-    return native().ops.logprobs(x, [int(i) for i in ids], req, wl, wi)
+    tg = None if targets is None else np.asarray(targets, np.int32)
+    return native().ops.logprobs(x, [int(i) for i in ids], req, wl, wi, tg)
 
 
 MAX_LOGIT_BIAS = 300

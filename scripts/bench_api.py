@@ -7,10 +7,14 @@ and temperature 0.8 / top_p 0.9 with per-request seeds (device sampling: only to
 to the host). One untimed round first captures the graphs.
 
   python scripts/bench_api.py [--n 64] [--max-tokens 64] [--port 0] [--logprobs K] [--penalties] [--filters] [--json]
-                              [--embeddings]
+                              [--embeddings] [--score]
 
 --embeddings: after the chat rounds, one /v1/embeddings request of N inputs of token ids (about 48
 tokens each), alone and next to a greedy chat round: inputs/s and prompt tokens/s.
+
+--score: after the chat rounds, N /v1/completions scoring requests (echo, max_tokens 0, logprobs 5;
+prompts of token ids, about 48 tokens each) sent together, next to the same prompts sent as
+max_tokens 1 requests without logprobs: prompt tokens/s of both, on the same server.
 """
 import argparse
 import http.client
@@ -60,6 +64,38 @@ def _embed_round(port, n, tokens_each=48):
     return data["usage"]["prompt_tokens"], time.perf_counter() - t0
 
 
+def _completions_round(port, n, score, tokens_each=48):
+    """n concurrent /v1/completions requests over the same token-id prompts: scoring (echo, max_tokens
+    0, logprobs 5) or plain max_tokens 1 without logprobs. Returns (prompt tokens, seconds)."""
+    out = [None] * n
+
+    def one(i):
+        body = {"prompt": [1000 + (37 * i + 11 * j) % 100000 for j in range(tokens_each)], "temperature": 0}
+        body.update(dict(echo=True, max_tokens=0, logprobs=5) if score else dict(max_tokens=1))
+        try:
+            c = http.client.HTTPConnection("127.0.0.1", port, timeout=300)
+            c.request("POST", "/v1/completions", json.dumps(body), {"Content-Type": "application/json"})
+            r = c.getresponse()
+            data = json.loads(r.read())
+            if score and len(data["choices"][0]["logprobs"]["token_logprobs"]) != tokens_each:
+                raise RuntimeError("a scoring response without its records")
+            out[i] = data["usage"]["prompt_tokens"]
+        except Exception as e:  # noqa: BLE001 - counted as a failed request
+            out[i] = e
+
+    th = [threading.Thread(target=one, args=(i,)) for i in range(n)]
+    t0 = time.perf_counter()
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    dt = time.perf_counter() - t0
+    bad = [o for o in out if not isinstance(o, int)]
+    if bad:
+        raise RuntimeError(f"{len(bad)} completions requests failed: {bad[:3]}")
+    return sum(out), dt
+
+
 EXTRA = {}  # request fields added to every body (--logprobs, --penalties, --filters, --json)
 
 
@@ -104,6 +140,9 @@ def main():
                     help="every request sends response_format json_object (JSON mode: both rounds are masked)")
     ap.add_argument("--embeddings", action="store_true",
                     help="also time one /v1/embeddings request of --n inputs, alone and next to a greedy chat round")
+    ap.add_argument("--score", action="store_true",
+                    help="also time --n /v1/completions scoring requests (echo, max_tokens 0, logprobs 5) next to "
+                         "the same prompts as max_tokens 1 requests without logprobs")
     args = ap.parse_args()
     if args.filters:
         EXTRA.update(top_k=40, min_p=0.05)
@@ -177,6 +216,14 @@ def main():
             th.join()
             res["embeddings_next_to_chat"] = {"embed_s": round(box["e"][1], 3), "chat_tok_s": round(ctoks / cdt, 1)}
             print("embeddings", res["embeddings"], res["embeddings_next_to_chat"], flush=True)
+        if args.score:
+            for score in (False, True):  # untimed: graph capture
+                _completions_round(port, args.n, score)
+            for name, score in (("score_plain_max_tokens_1", False), ("score", True), ("score_plain_max_tokens_1_again", False),
+                                ("score_again", True)):
+                toks, dt = _completions_round(port, args.n, score)
+                res[name] = {"requests": args.n, "prompt_tokens": toks, "s": round(dt, 3), "tok_s": round(toks / dt, 1)}
+                print(name, res[name], flush=True)
         print(json.dumps(res), flush=True)
     finally:
         srv.terminate()
