@@ -275,7 +275,7 @@ __device__ __forceinline__ uint64_t ldWT64(const void *p) {
 // pins the result of many splits across XCDs bitwise against one split.
 // Two sites keep a cheaper form of their own on purpose, argmaxKernel (sample.hip) and the argmax
 // tail of the logits GEMV (gemv_dev.h): only thread 0 stores there, so only thread 0 waits and
-// there is no first barrier. The counters of the attention block / FFN block are other protocols.
+// there is no first barrier. The counters of the attention block are another protocol.
 template <typename T>
 __device__ __forceinline__ void wtStore(T *p, T v) {  // T: float, int, uint32_t
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -335,9 +335,7 @@ __device__ __forceinline__ void qkvPairStore(const GemvArgs &a, int r0, float v0
 }
 
 // Quantize a workgroup's `halfR` hidden units (multiple of 32, in LDS) to Q80 blocks in global.
-// WT: the hidden rows are consumed in this launch (fused FFN block): 4 lanes' bytes packed into one
-// write-through 32-bit store, the scale pair one write-through 64-bit store.
-template <int B, bool WT = false>
+template <int B>
 __device__ __forceinline__ void storeHiddenQ80(const GemvArgs &a, const float *hbuf, int halfR, int hBase) {
     for (int i = threadIdx.x; i < B * halfR; i += kThreads) {  // 32-lane groups = one block
         const int b = i / halfR, k = i % halfR;
@@ -348,18 +346,10 @@ __device__ __forceinline__ void storeHiddenQ80(const GemvArgs &a, const float *h
         const float id = d != 0.f ? 1.0f / d : 0.f;
         int q = (int)rintf(h * id);
         q = q > 127 ? 127 : (q < -127 ? -127 : q);
-        int8_t *dst = a.oq + (size_t)b * a.ldOut + hBase + k;
-        if constexpr (WT) {
-            const uint32_t u = (uint32_t)(uint8_t)q;
-            const uint32_t w = u | ((uint32_t)__shfl_down((int)u, 1, 32) << 8) |
-                               ((uint32_t)__shfl_down((int)u, 2, 32) << 16) | ((uint32_t)__shfl_down((int)u, 3, 32) << 24);
-            if ((k & 3) == 0) st32<true>(dst, w);
-        } else {
-            *dst = (int8_t)q;
-        }
+        a.oq[(size_t)b * a.ldOut + hBase + k] = (int8_t)q;
         const float qs = groupSum<32>((float)q);
-        if ((k & 31) == 0) stF2<WT>(reinterpret_cast<float *>(a.os + (size_t)b * (a.ldOut >> 5) + ((hBase + k) >> 5)),
-                                    roundF16(d), qs);
+        if ((k & 31) == 0) stF2<false>(reinterpret_cast<float *>(a.os + (size_t)b * (a.ldOut >> 5) + ((hBase + k) >> 5)),
+                                       roundF16(d), qs);
     }
 }
 
@@ -381,29 +371,6 @@ __device__ __forceinline__ void stageQ80(const GemvArgs &a, int8_t *sq, float2 *
             int4 *dst = reinterpret_cast<int4 *>(sq + (size_t)b * n);
             for (int i = threadIdx.x; i < (n >> 4); i += kThreads) dst[i] = src[i];
             for (int i = threadIdx.x; i < nb; i += kThreads) ssc[b * nb + i] = a.as[(size_t)b * nb + i];
-        }
-    }
-    __syncthreads();
-}
-
-// B rows of f32 activations produced in this launch (write-through loads) quantized into the LDS
-// Q80 image: the fused FFN block's w2 role when w13 hands the hidden rows off in f32. Same values
-// as resNormPrologue without a norm (n % 32 == 0: the quads of a block stay together).
-template <int B>
-__device__ __forceinline__ void stageF32WT(const GemvArgs &a, int8_t *sq, float2 *ssc) {
-    const int n = a.n, nChunks = n >> 3;
-#pragma unroll
-    for (int b = 0; b < B; b++) {
-        const float *xi = a.in + (size_t)b * a.ldIn;
-        for (int c = threadIdx.x; c < nChunks; c += kThreads) {
-            float v[8];
-#pragma unroll
-            for (int i = 0; i < 8; i += 2) {
-                const uint64_t u = ldWT64(xi + c * 8 + i);
-                v[i] = __uint_as_float((uint32_t)u);
-                v[i + 1] = __uint_as_float((uint32_t)(u >> 32));
-            }
-            stageChunk<true>(v, b, c, n, sq, ssc, nullptr);
         }
     }
     __syncthreads();

@@ -337,38 +337,6 @@ void HipEngineImpl::setupPrenorm() {
     prenormOn_ = true;
 }
 
-hipk::FfnBlockArgs HipEngineImpl::ffnBlockArgs(const hipk::GemvArgs &w13, const hipk::GemvArgs &w2, u32 l) {
-    hipk::FfnBlockArgs f;
-    f.w13 = w13;
-    f.w2 = w2;
-    f.hQ80 = hQ80_ ? 1 : 0;
-    f.layer = (int)l;
-    f.nLayers = (int)h_.nLayers;
-    f.epoch = dEpoch_ + 1;
-    f.cnt = dBlockCnt_ + kFfnCntOff;
-    f.flag = dBlockCnt_ + kFfnCntOff + 64;
-    f.error = dBlockErr_;
-    return f;
-}
-
-// Fused FFN block (kernels.h FfnBlockArgs) for the pre-normalized single rows of a TP rank: a
-// compiled (w13 lanes, w2 lanes) instance and the whole w13 + w2 grid co-resident, shared with the
-// other ranks on this GPU. DL_FFN_BLOCK=0 keeps the two launches.
-void HipEngineImpl::setupFfnBlock() {
-    ffnOn_ = false;
-    const char *e = std::getenv("DL_FFN_BLOCK");
-    if (!prenormOn_ || !(e && *e == '1')) return;
-    const hipk::FfnBlockArgs f = ffnBlockArgs(w13ConsumerArgs(layers_[0]), w2ProducerArgs(layers_[0]), 0);
-    if (!hipk::ffnBlockPlan(f).fn) return;
-    const hipk::GemvResidency r = hipk::ffnBlockResidency(f);
-    if (!fitsResident(r)) {
-        std::fprintf(stderr, "ℹ️  fused FFN block off: grid %d > %d co-resident workgroups per rank\n", r.grid,
-                     residentLimit(r));
-        return;
-    }
-    ffnOn_ = true;
-}
-
 // The logits GEMV `a` of one greedy decode row, ending in the row's argmax (EPI_ARGMAX; under TP the
 // winners trade over the fused exchange's region; CHAIN also feeds the token back, as ArgmaxArgs).
 void HipEngineImpl::launchArgmaxTail(hipk::GemvArgs a, int pro, GraphKind kind) {
@@ -432,14 +400,11 @@ void HipEngineImpl::enqueuePrenormLayers(const FwdPath &f, GraphKind kind) {
         xSlot_ = 2 * (int)l + 1;
         const hipk::GemvArgs a13 = consumer(w13ConsumerArgs(L));
         const hipk::GemvArgs a2 = producer(w2ProducerArgs(L), nextNormW(l));
-        if (ffnOn_) {  // one launch: w13 role + w2 role (weights prefetched before the hand-off wait)
-            ProfScope ps(this, "ffn_block");
-            hipk::launchFfnBlock(ffnBlockArgs(a13, a2, l), stream_);
-        } else {
-            {
-                ProfScope ps(this, "gemv_w13");
-                hipk::launchGemv(a13, 1, hipk::PRO_PRENORM, w13Epi(), true, stream_);
-            }
+        {
+            ProfScope ps(this, "gemv_w13");
+            hipk::launchGemv(a13, 1, hipk::PRO_PRENORM, w13Epi(), true, stream_);
+        }
+        {
             ProfScope ps(this, "gemv_w2");
             hipk::launchGemv(a2, 1, w2Pro(), hipk::EPI_RESQ_TP, true, stream_);
         }
@@ -456,41 +421,11 @@ void HipEngineImpl::enqueuePrenormLayers(const FwdPath &f, GraphKind kind) {
         hipk::launchGemv(a, 1, hipk::PRO_PRENORM, hipk::EPI_STORE, true, stream_);
 }
 
-// The wo GEMV with the layer's attention in its prologue (PRO_ATTN, gemv_dev.h): every wo workgroup
-// recomputes the rank's decode attention from the L2-resident cache instead of waiting for an
-// attention launch, which at a TP-N rank's few heads is a handful of workgroups and a whole kernel
-// boundary (TP8 rank of 8B: 4 heads, attention launch 5.8 us of a ~28 us layer, r5_decode_profile.md).
-// The redundant work grows with the heads and the context, so it is taken for <= DL_WO_ATTN_HEADS
-// (default 8) query heads per rank and context buckets of <= DL_WO_ATTN_LEN (256) positions; the
-// block (TP1) and batched rows keep their own attention. With the fused exchange the kernel spins
-// on peers, so its grid must be co-resident like the plain wo GEMV's.
-// Measured (8B TP8 rank, f32 KV, same box): 0.973 ms/token with it vs 0.894 without - one
-// workgroup computing all 4 heads of the rank serially (2 dependent key rounds, the per-key
-// softmax of 4 heads on 256 lanes, then the ring's HBM latency, which cannot be issued before the
-// attention: check_isa.py --hazards) costs more than the 4-workgroup attention launch it replaces.
-// Opt-in (DL_WO_ATTN=1) for that reason; profiles/r6_tp_rank.md.
-void HipEngineImpl::setupWoAttn() {
-    woAttnOn_ = false;
-    const char *e = std::getenv("DL_WO_ATTN");
-    if (!(e && *e == '1') || !q40_) return;
-    const char *hm = std::getenv("DL_WO_ATTN_HEADS");
-    const char *lm = std::getenv("DL_WO_ATTN_LEN");
-    const int maxHeads = hm && *hm ? std::atoi(hm) : 8;
-    woAttnMaxLen_ = lm && *lm ? std::atoi(lm) : 256;
-    if ((int)plan_.nHeads0 > maxHeads) return;
-    const int epi = woEpi();
-    const hipk::GemvArgs a = woRowArgs(layers_[0], epi);
-    const hipk::AttnArgs at = attnArgs(layers_[0], false);
-    if (!hipk::gemvAttnSupported(a, at, epi)) return;
-    if (epi == hipk::EPI_STORE_TP && !fitsResident(hipk::gemvAttnResidency(a, at, epi))) return;
-    woAttnOn_ = true;
-}
-
 // A fused-block wait gave up (a workgroup of the launch never arrived): reset the monotonic
 // counters and the epoch so the engine stays usable, then raise.
 void HipEngineImpl::resetAttnBlockState() {
-    DL_HIP(hipMemsetAsync(dBlockCnt_, 0, sizeof(unsigned) * kAllCntWords, stream_));
-    DL_HIP(hipMemsetAsync(dEpoch_, 0, 2 * sizeof(unsigned), stream_));
+    DL_HIP(hipMemsetAsync(dBlockCnt_, 0, sizeof(unsigned) * kBlockCntWords, stream_));
+    DL_HIP(hipMemsetAsync(dEpoch_, 0, sizeof(unsigned), stream_));
     DL_HIP(hipMemsetAsync(dBlockErr_, 0, sizeof(int), stream_));
     DL_HIP(hipStreamSynchronize(stream_));
 }
@@ -631,10 +566,7 @@ void HipEngineImpl::enqueueWo(const FwdPath &f, const DevLayer &L, int cur) {
         gemmBatched(L.wo, f.n, hipk::EPI_RES, {.xh = dAttH_, .ldOut = dim(), .rf = {dX_[cur], dX_[cur ^ 1], L.rmsFfn}});
     else if (f.bat)
         gemmBatched(L.wo, f.n, hipk::EPI_STORE, {.xh = dAttH_, .out = dY_, .ldOut = dim()});
-    else if (f.woAttn) {
-        xChunk_ = 0;
-        hipk::launchGemvAttn(woRowArgs(L, woEpi()), attnArgs(L, false), woEpi(), stream_);
-    } else
+    else
         gemv(L.wo, f.n, hipk::PRO_GLOBAL, hipk::EPI_STORE,
              {.in = q40_ ? nullptr : dAtt_, .ldIn = q0(), .aq = dAttQ_, .as = dAttS_, .out = dY_, .ldOut = dim(),
               .tp = fusedTp(false)});
@@ -810,7 +742,6 @@ void HipEngineImpl::enqueueForward(int n, GraphKind kind) {
     // (an all-embedding forward keeps the norm-prologue schedule, whose final residual is the
     //  dX_ / dY_ pair the pooling kernel reads; the pre-normalized hand-off holds Q80 images instead)
     f.pre = prenormOn_ && row && kind != GraphKind::EMBED;
-    f.woAttn = woAttnOn_ && row && buckets_[bucket_].maxLen <= woAttnMaxLen_;
     // one greedy decode row: the logits GEMV ends in the row's argmax (EPI_ARGMAX: no logits
     // written, no argmax launch; under TP the winners trade over the fused exchange's region)
     f.argTail = argTailOn_ && q40_ && !f.bat && !f.fz && n == 1 &&
@@ -818,9 +749,8 @@ void HipEngineImpl::enqueueForward(int n, GraphKind kind) {
                 (plan_.nRanks == 1 || (tpFused_ && tpArg_.stride >= 2));
     {
         ProfScope ps(this, "embedding");
-        // the epochs count the forwards that run the fused attention block / the FFN block (their
-        // counters' targets); the two never run in the same forward (FwdPath::pre excludes blk)
-        unsigned *ep = f.blk ? dEpoch_ : (f.pre && ffnOn_) ? dEpoch_ + 1 : nullptr;
+        // the epoch counts the forwards that run the fused attention block (its counters' targets)
+        unsigned *ep = f.blk ? dEpoch_ : nullptr;
         hipk::launchEmbedding(emb_, dTok_, dX_[0], dim(), n, stream_, ep,
                               plan_.nRanks > 1 ? dSync_ : nullptr, plan_.nRanks > 1 ? syncSlots() : 0);
     }
@@ -839,7 +769,7 @@ void HipEngineImpl::enqueueForward(int n, GraphKind kind) {
         } else {
             enqueueQkv(f, L, cur, hasDelta);
             if (hasDelta) cur ^= 1;
-            if (!f.woAttn) enqueueAttention(f, L);
+            enqueueAttention(f, L);
             enqueueWo(f, L, cur);
         }
         if (sepReduce) allReduce(dY_, (size_t)n * dim());

@@ -96,9 +96,7 @@ class HipEngineImpl : public HipEngine {
                                                  const SampleSpec *specs, const PoolSpec *pool) override;
     bool tpFused() const override { return tpFused_; }
     bool attnBlock() const override { return blockOn_; }
-    bool woAttn() const override { return woAttnOn_; }
     bool prenorm() const override { return prenormOn_; }
-    bool ffnBlock() const override { return ffnOn_; }
     std::vector<unsigned long long> traceAttnBlock(int token, int pos, int slot, int layer) override;
     int fusedGridMax() const override { return fusedGridMax_; }
     bool tpBatchedFused(int n) const override { return plan_.nRanks > 1 && batchedPath(n) && fuseNorm(n); }
@@ -294,15 +292,9 @@ class HipEngineImpl : public HipEngine {
     hipk::AttnBlockArgs attnBlockArgs(const DevLayer &L, u32 l, int cur) const;
     void setupAttnBlock();
     void resetAttnBlockState();
-    // the wo GEMV with the attention in its prologue (PRO_ATTN) for single decode rows of short
-    // contexts when a rank holds few heads: decided once (setupWoAttn), taken per forward (FwdPath::woAttn)
-    void setupWoAttn();
     // pre-normalized hand-off for single decode rows (EPI_RESQ_TP producers -> PRO_PRENORM
     // consumers): decided once (setupPrenorm), taken per forward (FwdPath::pre)
     void setupPrenorm();
-    // fused FFN block (w13 + w2 roles in one launch) inside the pre-normalized layers: setupFfnBlock
-    void setupFfnBlock();
-    hipk::FfnBlockArgs ffnBlockArgs(const hipk::GemvArgs &w13, const hipk::GemvArgs &w2, u32 l);
     bool batchedPath(int n) const {
         return n >= gemmMin_ && hipk::gemmSupported(h_.dim) && hipk::gemmSupported(plan_.q0) &&
                hipk::gemmSupported(plan_.hidden0);
@@ -319,7 +311,6 @@ class HipEngineImpl : public HipEngine {
         bool fz;       // batched: residual + norm in the GEMM epilogues
         bool blk;      // single row: qkv + attention + wo as the fused attention block
         bool pre;      // single row: pre-normalized Q80 hand-offs between the GEMVs
-        bool woAttn;   // single row: attention inside the wo GEMV's prologue
         bool argTail;  // single greedy row: the logits GEMV ends in the argmax
     };
     void enqueueQkv(const FwdPath &f, const DevLayer &L, int cur, bool hasDelta);
@@ -342,8 +333,6 @@ class HipEngineImpl : public HipEngine {
     // attention block counters: qkv counters per KV group | attention counter | 8 flags | qkv counter |
     // 8 flags | spare line (every word on its own 256-B line; attn_block_inst.h carves them)
     static constexpr int kBlockCntWords = kMaxKvGroups * 64 + 64 + 8 * 64 + 64 + 8 * 64 + 64;
-    // the FFN block's words after the attention block's: [64] arrivals, [8 * 64] per-XCD flags
-    static constexpr int kFfnCntOff = kBlockCntWords, kAllCntWords = kBlockCntWords + 64 + 8 * 64;
     static constexpr int kAttnMfmaMinPos = 1024;
     static constexpr int kAttnMfmaMinRows = 16;
 
@@ -498,11 +487,8 @@ class HipEngineImpl : public HipEngine {
     unsigned *dEpoch_ = nullptr, *dBlockCnt_ = nullptr, *dBlockExpect_ = nullptr;
     int *dBlockErr_ = nullptr;
     bool blockOn_ = false;   // decode rows may run the fused attention block (per bucket: CtxBucket::block)
-    bool woAttnOn_ = false;  // setupWoAttn
     bool prenormOn_ = false; // setupPrenorm
-    bool ffnOn_ = false;     // setupFfnBlock (prenorm forwards only)
     static constexpr int kMaxSsp = 256;  // producer workgroups of a pre-normalized hand-off
-    int woAttnMaxLen_ = 256; // DL_WO_ATTN_LEN: context buckets up to this length
     int blockPassMul_ = 1;   // qkv / wo passes multiplier of the block's roles (same-GPU rehearsals)
     int traceLayer_ = -1;    // traceAttnBlock: the layer whose block launch is traced
     unsigned long long *traceBuf_ = nullptr;

@@ -203,7 +203,7 @@ void HipEngineImpl::allocBuffers() {
         DL_HIP(hipMemsetAsync(dGemmCnt_, 0, sizeof(int) * maxTiles, stream_));
     }
     {  // fused attention block: epoch, monotonic counters, expected counts, timeout flag
-        dEpoch_ = dalloc<unsigned>(4);
+        dEpoch_ = dalloc<unsigned>(1);
         // measured-sync slots (hipk::syncFoldWords: folded and cleared by the embedding kernel of
         // every forward) and their host copies (the last forward + one per chain step in flight)
         const size_t sw = hipk::syncFoldWords(syncSlots());
@@ -211,11 +211,11 @@ void HipEngineImpl::allocBuffers() {
         hSync_ = halloc<unsigned>(sw * (1 + kChainDepth));
         DL_HIP(hipMemsetAsync(dSync_, 0, sw * sizeof(unsigned), stream_));
         std::memset(hSync_, 0, sw * (1 + kChainDepth) * sizeof(unsigned));
-        dBlockCnt_ = dalloc<unsigned>(kAllCntWords);
+        dBlockCnt_ = dalloc<unsigned>(kBlockCntWords);
         dBlockExpect_ = dalloc<unsigned>(kMaxKvGroups);
         dBlockErr_ = dalloc<int>(4);
-        DL_HIP(hipMemsetAsync(dEpoch_, 0, 4 * sizeof(unsigned), stream_));
-        DL_HIP(hipMemsetAsync(dBlockCnt_, 0, kAllCntWords * sizeof(unsigned), stream_));
+        DL_HIP(hipMemsetAsync(dEpoch_, 0, sizeof(unsigned), stream_));
+        DL_HIP(hipMemsetAsync(dBlockCnt_, 0, kBlockCntWords * sizeof(unsigned), stream_));
         DL_HIP(hipMemsetAsync(dBlockExpect_, 0, kMaxKvGroups * sizeof(unsigned), stream_));
         DL_HIP(hipMemsetAsync(dBlockErr_, 0, 4 * sizeof(int), stream_));
     }

@@ -75,8 +75,6 @@ struct BlockSync {
     unsigned attnTarget = 0;             // s * head groups
     int *error = nullptr;                // set when a wait gave up (the engine raises)
     long long timeoutTicks = 0;
-    int codeBase = 0;                    // added to the GEMV waits' error codes (3 data, 4 ring start)
-    bool ringEarly = false;              // consumer: issue the weight ring at entry (no ring-start wait)
 };
 __device__ __forceinline__ int xccId() { return (int)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 7u); }
 
@@ -130,16 +128,8 @@ __host__ __device__ inline unsigned long long qkvGroupMask(int r0, int r1, int q
     return m;
 }
 
-// attn_dev.h (included after this header): the decode attention task, used by PRO_ATTN
-template <int HG, int HS, int AT>
-__host__ __device__ constexpr int attnLocalOut();
-template <int HG, int HS, bool BF16, int AT, bool SYNC = false, bool LOCAL = false>
-__device__ __forceinline__ bool attnTask(const AttnArgs &a, int b, int hgIdx, int c, char *smem,
-                                         const BlockSync *bs = nullptr, unsigned long long *trace = nullptr);
-
-template <int L, int B, int PRO, int EPI, int MODE = GEMV_PLAIN, int AHG = 1, bool ABF16 = false>
-__device__ __forceinline__ void gemvQ40Body(const GemvArgs &a, const int blk, char *smem, const BlockSync *bs = nullptr,
-                                            const AttnArgs *at = nullptr) {
+template <int L, int B, int PRO, int EPI, int MODE = GEMV_PLAIN>
+__device__ __forceinline__ void gemvQ40Body(const GemvArgs &a, const int blk, char *smem, const BlockSync *bs = nullptr) {
     constexpr int RG = 2, NG = kThreads / L, RP = NG * RG, D = kRing;
     const int n = a.n, nb = n >> 5, K = (nb + L - 1) / L, P = a.passes, T = P * K;
     const int R = RP * P;
@@ -361,8 +351,7 @@ __device__ __forceinline__ void gemvQ40Body(const GemvArgs &a, const int blk, ch
     auto latePath = [&]() {
         // consumer: the weight ring is issued once the qkv phase of the launch is done, so it streams
         // while HBM would idle during attention instead of competing with the qkv weights
-        if constexpr (MODE == GEMV_CONSUMER)
-            if (!bs->ringEarly) blockWait(bs->qkvFlag + xccId() * kCntStride, bs->step, *bs, bs->codeBase + 4);
+        if constexpr (MODE == GEMV_CONSUMER) blockWait(bs->qkvFlag + xccId() * kCntStride, bs->step, *bs, 4);
         // sched_barrier keeps issue order == slot order, so each step waits for exactly its own
         // slot (vmcnt = loads of the other kRing-1 slots) instead of the scheduler batching the ring.
 #pragma unroll
@@ -380,9 +369,8 @@ __device__ __forceinline__ void gemvQ40Body(const GemvArgs &a, const int blk, ch
         if constexpr (MODE == GEMV_CONSUMER) {
             // the activations are produced in this launch: wait for every producer (the ring's
             // weight loads are already in flight), then read them write-through
-            tWaited = blockWait(bs->attnFlag + xccId() * kCntStride, bs->step, *bs, bs->codeBase + 3);
-            if constexpr (PRO == PRO_RESNORM) stageF32WT<B>(a, sq, ssc);  // f32 rows (FFN block, skinny w13)
-            else stageQ80<B, true>(a, sq, ssc);
+            tWaited = blockWait(bs->attnFlag + xccId() * kCntStride, bs->step, *bs, 3);
+            stageQ80<B, true>(a, sq, ssc);
         } else if constexpr (PRO == PRO_RESNORM)
             resNormPrologue<B, true>(a, scratch, sq, ssc, nullptr);
         else {
@@ -390,43 +378,6 @@ __device__ __forceinline__ void gemvQ40Body(const GemvArgs &a, const int blk, ch
         }
         waitAll();
         if (a.trace) tReady = wall_clock64();
-    };
-
-    // PRO_ATTN: the rank's attention heads, one KV group at a time (AHG query heads sharing its
-    // keys), computed into this workgroup's LDS from the L2-resident cache and quantized to the Q80
-    // image the main loop reads (32-lane groups = one block, the attention kernel's own rounding);
-    // then the weight ring. The ring is NOT issued first: under the attention's register pressure
-    // the compiler moved pending ring registers to AGPRs before their s_waitcnt (stale copies,
-    // scripts/check_isa.py --hazards), so no inline-asm load is in flight during the attention.
-    auto attnPath = [&]() {
-      if constexpr (PRO == PRO_ATTN && B == 1) {
-        char *asmem = smem + alignUp(lay.total, 16);
-        const float *o = reinterpret_cast<const float *>(asmem) + attnLocalOut<AHG, 128, kThreads>();
-        const int groups = at->nHeads0 / AHG;
-        for (int g = 0; g < groups; g++) {
-            attnTask<AHG, 128, ABF16, kThreads, false, true>(*at, 0, g, 0, asmem);
-            for (int i = tid; i < AHG * 128; i += kThreads) {  // AHG * 128 is a multiple of 256
-                const float v = o[i];
-                const float amax = groupMax<32>(fabsf(v));
-                const float d = amax / 127.0f;
-                const float id = d != 0.f ? 1.0f / d : 0.f;
-                int q = (int)rintf(v * id);
-                q = q > 127 ? 127 : (q < -127 ? -127 : q);
-                const int col = g * AHG * 128 + i;
-                sq[col] = (int8_t)q;
-                const float qs = groupSum<32>((float)q);
-                if ((i & 31) == 0) ssc[col >> 5] = make_float2(roundF16(d), qs);
-            }
-            __syncthreads();  // the next group's task reuses the scratch
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s = 0; s < D; s++) {
-            issue(w[s], dh[s]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (a.trace) tReady = wall_clock64();
-      }
     };
 
     // The ring's consume loop. Each prologue path below inlines its own copy, so no ring register
@@ -469,10 +420,7 @@ __device__ __forceinline__ void gemvQ40Body(const GemvArgs &a, const int blk, ch
                     if (r0 + 1 < a.rows) o[1] = v1;
                 } else if constexpr (EPI == EPI_ACT) {
                     float *o = a.out + (size_t)b * a.ldOut + (r0 >> 1);
-                    if constexpr (MODE == GEMV_PRODUCER)  // read by the FFN block's w2 role in this launch
-                        __hip_atomic_store(o, gateAct(a, v0) * v1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    else
-                        *o = gateAct(a, v0) * v1;
+                    *o = gateAct(a, v0) * v1;
                 } else if constexpr (EPI == EPI_ACT_Q80) {
                     hbuf[b * (R >> 1) + ((r0 - rowBase) >> 1)] = gateAct(a, v0) * v1;
                 } else {
@@ -517,14 +465,10 @@ __device__ __forceinline__ void gemvQ40Body(const GemvArgs &a, const int blk, ch
     staticFor<D>(lastSlot);
     };
 
-    const int unitsPerThread = (PRO != PRO_GLOBAL && PRO != PRO_PRENORM) ? (n + 8 * kThreads - 1) / (8 * kThreads)
-                                                                         : (n + 16 * kThreads - 1) / (16 * kThreads);
-    static_assert(MODE != GEMV_CONSUMER || PRO == PRO_GLOBAL || PRO == PRO_RESNORM,
-                  "a consumer GEMV reads Q80 activations (or un-normalized f32 rows: PRO_RESNORM, no norm)");
-    if constexpr (PRO == PRO_ATTN) {
-        attnPath();
-        mainLoop();
-    } else if constexpr (MODE == GEMV_CONSUMER) {
+    const int unitsPerThread = PRO == PRO_RESNORM ? (n + 8 * kThreads - 1) / (8 * kThreads)
+                                                  : (n + 16 * kThreads - 1) / (16 * kThreads);
+    static_assert(MODE != GEMV_CONSUMER || PRO == PRO_GLOBAL, "a consumer GEMV reads Q80 activations");
+    if constexpr (MODE == GEMV_CONSUMER) {
         latePath();
         mainLoop();
     } else if (B == 1 && unitsPerThread <= 1) {
@@ -543,7 +487,7 @@ __device__ __forceinline__ void gemvQ40Body(const GemvArgs &a, const int blk, ch
     const unsigned long long tLoop = a.trace ? wall_clock64() : 0ull;  // main loop done (this wave)
     if constexpr (EPI == EPI_ACT_Q80) {
         __syncthreads();
-        storeHiddenQ80<B, MODE == GEMV_PRODUCER>(a, hbuf, R >> 1, rowBase >> 1);
+        storeHiddenQ80<B>(a, hbuf, R >> 1, rowBase >> 1);
     }
     if constexpr (MODE == GEMV_PRODUCER) {  // rows published write-through: drain, then count in
         blockDrain();
@@ -558,7 +502,7 @@ __device__ __forceinline__ void gemvQ40Body(const GemvArgs &a, const int blk, ch
             }
             // the last producer workgroup of the step raises the per-XCD "phase done" flags: the
             // attention block's wo role starts its weight ring (so the wo weights stream while
-            // attention runs instead of competing with qkv's), the FFN block's w2 role its ring + reads
+            // attention runs instead of competing with qkv's)
             if (__hip_atomic_fetch_add(bs->qkvAll, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == bs->qkvAllTarget)
                 raiseFlags(bs->qkvFlag, bs->step);
         }

@@ -27,16 +27,13 @@ namespace hipk {
 //             Q40 weights, f32 for F32 weights) - no prologue, no LDS, no barrier.
 // PRO_RESNORM: (x + delta) -> RMS norm -> Q80 (or f32) staged once per workgroup in LDS
 //             (normW == null: no norm, plain quantization of `in`).
-// PRO_ATTN (Q40 ring GEMV, one row: the wo GEMV of a short-context decode step): the layer's
-//             decode attention for every head of the rank is computed in the prologue of EVERY
-//             workgroup (redundantly, from L2) and quantized to Q80 into LDS - no attention
-//             launch and no hand-off (launchGemvAttn; the engine takes it for few heads per rank).
 // PRO_PRENORM (Q40 ring GEMV, one row): the producer of this input (EPI_RESQ_TP, or the embedding)
 //             already applied the residual update and the RMS norm's weights and quantized
 //             x * normW to Q80 blocks (aq / as, unrounded block scale d' = amax / 127); the
 //             workgroup only sums the producer's per-workgroup sums of squares (sspIn, nSsp, in
 //             order) and folds 1 / rms into each block scale (d = f16(d' / rms)) while copying.
-enum Prologue : int { PRO_GLOBAL = 0, PRO_RESNORM = 1, PRO_ATTN = 2, PRO_PRENORM = 3 };
+// The values are passed as integers by Python callers and scripts: 2 is retired, not reused.
+enum Prologue : int { PRO_GLOBAL = 0, PRO_RESNORM = 1, PRO_PRENORM = 3 };
 // EPI_ACT_Q80: act(w1 x) * (w3 x), quantized to Q80 blocks for the next GEMV (32 hidden units/block).
 // EPI_STORE_TP: EPI_STORE whose rows are first all-reduced over the tensor-parallel ranks (GemvArgs::tp).
 // EPI_RES (batched GEMMs): residual update fused with the next RMS norm's elementwise half - see
@@ -320,13 +317,6 @@ void launchNormF16(const GemvArgs &a, _Float16 *out, int M, hipStream_t s);
 
 // B = batch rows in this launch (1, 2 or 4); q40 = weight format.
 void launchGemv(const GemvArgs &a, int B, int pro, int epi, bool q40, hipStream_t s);
-// The wo GEMV of one decode row with the layer's attention in its prologue (PRO_ATTN): `at` is the
-// row's attention (every head of the rank, one chunk over the whole context); epi EPI_STORE or
-// EPI_STORE_TP. Supported: gemvAttnSupported (Q40, head size 128, query heads per KV head 1/2/4/8).
-bool gemvAttnSupported(const GemvArgs &a, const AttnArgs &at, int epi);
-void launchGemvAttn(const GemvArgs &a, const AttnArgs &at, int epi, hipStream_t s);
-struct GemvResidency;
-GemvResidency gemvAttnResidency(const GemvArgs &a, const AttnArgs &at, int epi);
 // Co-residency of one GEMV launch on the current device: its grid and the most workgroups of that
 // kernel (at its LDS size) the device holds at once (occupancy per CU x CUs). A kernel whose
 // workgroups spin on peers (EPI_STORE_TP) is deadlock-free only if grid <= maxResident.
@@ -404,34 +394,6 @@ AttnBlockPlan attnBlockPlan(const AttnBlockArgs &a, bool tp);
 void attnBlockExpect(const GemvArgs &qkv, int nKv, unsigned *out);
 GemvResidency attnBlockResidency(const AttnBlockArgs &a, bool tp);
 void launchAttnBlock(const AttnBlockArgs &a, bool tp, hipStream_t s);
-
-// Fused FFN block of one decode row at a tensor-parallel rank with the pre-normalized hand-off
-// (ffn_block.hip): w13 (PRO_PRENORM, SwiGLU epilogue, hidden rows stored write-through as f32 or
-// Q80) and w2 (EPI_RESQ_TP exchange tail) in ONE launch as two workgroup roles
-//   [0, g13) w13 rows | [g13, g13 + g2) w2 rows.
-// The w2 workgroups issue their weight ring at entry - it streams while w13 runs - then wait for
-// every w13 workgroup (a monotonic counter, per-XCD "phase done" flags as the attention block's)
-// and read the hidden rows write-through. Removes a kernel boundary and w2's start-up latency per
-// layer. Requires the whole grid co-resident (ffnBlockResidency); waits are bounded (error word).
-struct FfnBlockArgs {
-    GemvArgs w13;                 // PRO_PRENORM + EPI_ACT (f32 hidden) or EPI_ACT_Q80 (hQ80)
-    GemvArgs w2;                  // EPI_RESQ_TP: PRO_RESNORM (f32 hidden, no norm) or PRO_GLOBAL (Q80)
-    int hQ80 = 0;
-    int layer = 0, nLayers = 1;
-    const unsigned *epoch = nullptr;  // per-forward epoch of the FFN block (incremented by launchEmbedding)
-    unsigned *cnt = nullptr;          // [1] monotonic w13 arrivals (zeroed once)
-    unsigned *flag = nullptr;         // [8 * 64] per-XCD "w13 phase done" step flags (zeroed once)
-    int *error = nullptr;             // wait timeout flag (codes 7 data, 8 ring start)
-    long long timeoutTicks = 200LL * 1000 * 1000;
-};
-struct FfnBlockPlan {
-    const void *fn = nullptr;
-    int g13 = 0, g2 = 0;
-    size_t lds = 0;
-};
-FfnBlockPlan ffnBlockPlan(const FfnBlockArgs &a);
-GemvResidency ffnBlockResidency(const FfnBlockArgs &a);
-void launchFfnBlock(const FfnBlockArgs &a, hipStream_t s);
 
 // Fused-exchange self-test (tp_check.hip): out[el] = sum over ranks of (val_rank + el % 1024) for
 // el < n (n <= x.stride), through the transport of the fused exchange; every rank must call it.

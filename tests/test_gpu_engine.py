@@ -403,13 +403,17 @@ def test_attn_block_matches_separate_kernels(C, assets, medium, monkeypatch, kv_
         assert list(ca) == list(cb)
 
 
+@pytest.mark.parametrize("hq80", ["1", "0"])
 @pytest.mark.parametrize("sync", ["q80", "f32"])
-def test_prenorm_handoff_matches_norm_prologue(C, medium, monkeypatch, sync):
+def test_prenorm_handoff_matches_norm_prologue(C, medium, monkeypatch, sync, hq80):
     """A TP rank's single decode rows with the pre-normalized hand-off (wo / w2 exchange tails apply
     the residual update and the next norm's weights and emit Q80 blocks + sums of squares; qkv,
     w13 and the logits GEMV only copy them and fold in 1 / rms) vs the norm prologues: the same
     shard logits up to Q80 rounding ties and the same greedy chain (rank in loopback). The f32
-    exchange keeps 16-row workgroups, so the hand-off stays off there (same results both ways)."""
+    exchange keeps 16-row workgroups, so the hand-off stays off there (same results both ways).
+    Both w13 -> w2 hand-off types (DL_H_Q80: Q80 blocks / f32 rows that w2 quantizes): the default
+    depends on the shard shape, so the pre-normalized rows run under either."""
+    monkeypatch.setenv("DL_H_Q80", hq80)
     out = {}
     for on in ("1", "0"):
         monkeypatch.setenv("DL_PRENORM", on)
@@ -427,53 +431,6 @@ def test_prenorm_handoff_matches_norm_prologue(C, medium, monkeypatch, sync):
     assert _rel(out["1"][0], out["0"][0]) < 2e-3
     assert sum(a == b for a, b in zip(out["1"][1], out["0"][1])) >= 10, (out["1"][1], out["0"][1])
     assert out["1"][2] == [int(i) for i in out["1"][0].argmax(-1)]
-
-
-@pytest.mark.parametrize("hq80", ["1", "0"])
-def test_ffn_block_matches_two_launches(C, medium, monkeypatch, hq80):
-    """DL_FFN_BLOCK=1: a TP rank's pre-normalized single rows run w13 and w2 as two workgroup roles of
-    one launch (w2 prefetches its weights, waits on the w13 arrival counter, reads the hidden rows
-    write-through: Q80 blocks or f32 rows) - bitwise the same logits and greedy chain as the two
-    launches (same arithmetic, only the hand-off changes), rank in loopback, over several forwards
-    (the monotonic step targets) and a decode chain."""
-    monkeypatch.setenv("DL_H_Q80", hq80)
-    out = {}
-    for on in ("1", "0"):
-        monkeypatch.setenv("DL_FFN_BLOCK", on)
-        e = C.HipEngine(medium, "q80", max_batch=8, rank=0, world=2, comm=C.ComputeOnlyComm(0, 2, 0),
-                        sync_type="q80", kv_bf16=False)
-        assert e.prenorm and bool(e.ffn_block) == (on == "1")
-        v0 = e.header["vocab_size"] // 2
-        toks = [3, 17, 101, 7, 250, 9]
-        lg = np.stack([e.forward([t], [p], [0])[0][:v0] for p, t in enumerate(toks)])
-        _, ch = e.decode_greedy(12, [int(lg[-1].argmax())], [len(toks)], [0])
-        ids = [e.forward_argmax([t], [p], [0])[0] for p, t in enumerate(toks)]
-        out[on] = (lg, list(ch), ids)
-        del e
-    assert np.isfinite(out["1"][0]).all()
-    assert np.array_equal(out["1"][0], out["0"][0])
-    assert out["1"][1] == out["0"][1] and out["1"][2] == out["0"][2]
-
-
-@pytest.mark.parametrize("world", [2])
-def test_wo_attention_prologue_matches_attention_launch(C, medium, monkeypatch, world):
-    """DL_WO_ATTN=1: a TP rank's wo GEMV computes the layer's decode attention in every workgroup's
-    prologue (PRO_ATTN, no attention launch): same shard logits as the attention launch + wo GEMV
-    (another reduction order: tolerance) and the same greedy chain, rank in loopback."""
-    out = {}
-    for on in ("1", "0"):
-        monkeypatch.setenv("DL_WO_ATTN", on)
-        e = C.HipEngine(medium, "q80", max_batch=8, rank=0, world=world, comm=C.ComputeOnlyComm(0, world, 0),
-                        sync_type="f32", kv_bf16=False)
-        assert bool(e.wo_attn) == (on == "1")
-        v0 = e.header["vocab_size"] // world
-        toks = [3, 17, 101, 7, 250, 9]
-        lg = np.stack([e.forward([t], [p], [0])[0][:v0] for p, t in enumerate(toks)])
-        _, ch = e.decode_greedy(12, [int(lg[-1].argmax())], [len(toks)], [0])
-        out[on] = (lg, list(ch))
-        del e
-    assert _rel(out["1"][0], out["0"][0]) < 1e-3
-    assert out["1"][1] == out["0"][1]
 
 
 def test_engine_8b_shape_matches_cpu(C, tmp_path):
