@@ -34,9 +34,9 @@ ifneq ($(SAN),)
 endif
 LDROCM     := -L$(ROCM)/lib -Wl,-rpath,$(ROCM)/lib -lamdhip64 -lrccl
 
-HOST_SRCS  := csrc/core/quant.cpp csrc/core/model_file.cpp csrc/core/plan.cpp csrc/text/tokenizer.cpp \
+HOST_SRCS  := csrc/core/quant.cpp csrc/core/model_file.cpp csrc/core/plan.cpp csrc/core/schema_dfa.cpp csrc/text/tokenizer.cpp \
               csrc/cpu/thread_pool.cpp csrc/cpu/cpu_ops.cpp csrc/cpu/cpu_backend.cpp $(wildcard csrc/net/*.cpp) $(wildcard csrc/runtime/*.cpp)
-HIP_SRCS   := csrc/hip/kernels.hip csrc/hip/attn_prefill.hip csrc/hip/sample.hip csrc/hip/logprobs.hip csrc/hip/logit_proc.hip csrc/hip/logit_filter.hip csrc/hip/json_mask.hip csrc/hip/pool.hip csrc/hip/tp_check.hip csrc/hip/kv_copy.hip csrc/hip/gemm.hip csrc/hip/gemm_wide.hip csrc/hip/attn_mfma.hip csrc/hip/gemv.hip csrc/hip/gemv_l16.hip csrc/hip/gemv_l32.hip csrc/hip/gemv_l64.hip csrc/hip/attn_block.hip csrc/hip/attn_block_16_16_128.hip csrc/hip/attn_block_16_32_128.hip csrc/hip/attn_block_32_32_128.hip csrc/hip/attn_block_64_32_128.hip csrc/hip/attn_block_64_16_128.hip csrc/hip/attn_block_64_64_128.hip csrc/hip/attn_block_32_64_128.hip csrc/hip/attn_block_64_64_64.hip csrc/hip/engine.cpp csrc/hip/engine_load.cpp csrc/hip/engine_kv.cpp csrc/hip/engine_forward.cpp csrc/hip/engine_bench.cpp csrc/hip/rccl_comm.cpp csrc/hip/sim_comm.cpp csrc/hip/xgmi_comm.cpp csrc/hip/ops.cpp
+HIP_SRCS   := csrc/hip/kernels.hip csrc/hip/attn_prefill.hip csrc/hip/sample.hip csrc/hip/logprobs.hip csrc/hip/logit_proc.hip csrc/hip/logit_filter.hip csrc/hip/json_mask.hip csrc/hip/grammar_mask.hip csrc/hip/pool.hip csrc/hip/tp_check.hip csrc/hip/kv_copy.hip csrc/hip/gemm.hip csrc/hip/gemm_wide.hip csrc/hip/attn_mfma.hip csrc/hip/gemv.hip csrc/hip/gemv_l16.hip csrc/hip/gemv_l32.hip csrc/hip/gemv_l64.hip csrc/hip/attn_block.hip csrc/hip/attn_block_16_16_128.hip csrc/hip/attn_block_16_32_128.hip csrc/hip/attn_block_32_32_128.hip csrc/hip/attn_block_64_32_128.hip csrc/hip/attn_block_64_16_128.hip csrc/hip/attn_block_64_64_128.hip csrc/hip/attn_block_32_64_128.hip csrc/hip/attn_block_64_64_64.hip csrc/hip/engine.cpp csrc/hip/engine_load.cpp csrc/hip/engine_kv.cpp csrc/hip/engine_forward.cpp csrc/hip/engine_bench.cpp csrc/hip/rccl_comm.cpp csrc/hip/sim_comm.cpp csrc/hip/xgmi_comm.cpp csrc/hip/ops.cpp
 HOST_OBJS  := $(patsubst csrc/%.cpp,$(BUILD)/obj/%.o,$(HOST_SRCS))
 HIP_OBJS   := $(patsubst csrc/%,$(BUILD)/obj/%.o,$(HIP_SRCS))
 HDRS       := $(wildcard csrc/*/*.h)
@@ -89,6 +89,15 @@ $(BUILD)/unit_tests: tests/cpp/unit_tests.cpp $(LIB) $(HDRS)
 test-cpp: $(BUILD)/unit_tests
 	$(BUILD)/unit_tests
 
+# the schema compiler under host AddressSanitizer / UBSan: a stand-alone program (its own main, the
+# compiler's sources compiled in, no GPU code), fed the test schemas and fixed-seed mutations of them
+$(BUILD)/schema_fuzz: tests/cpp/schema_fuzz.cpp csrc/core/schema_dfa.cpp $(HDRS)
+	@mkdir -p $(BUILD)
+	$(CXX) -std=c++17 -O1 -g -Wall -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -o $@ tests/cpp/schema_fuzz.cpp csrc/core/schema_dfa.cpp
+
+schema-fuzz: $(BUILD)/schema_fuzz
+	$(BUILD)/schema_fuzz
+
 # ring GEMV / attention block instances compile without scratch (inline-asm ring registers are never spilled)
 check-isa:
 	python3 scripts/check_isa.py
@@ -96,4 +105,4 @@ check-isa:
 clean:
 	rm -rf $(BUILD) $(LIB) $(EXT)
 
-.PHONY: all lib clean test-cpp check-isa
+.PHONY: all lib clean test-cpp check-isa schema-fuzz

@@ -57,6 +57,29 @@ struct Api {
     std::atomic<u64> counter{0};
     std::string jsonUnavailable;  // why response_format json_object cannot be served (empty: it can)
 
+    SchemaDfaCache schemaCache{32};  // compiled grammars of response_format json_schema, by schema text
+
+    // response_format {"type": "json_schema", "json_schema": {"name", "schema", "strict", "description"}}:
+    // the schema is compiled here, in the handler's thread (or taken from the cache), never in the
+    // scheduler loop. Returns what is wrong with the request, empty when p carries the grammar.
+    std::string schemaParams(const Value &rf, GenParams &p) {
+        const Value &js = rf["json_schema"];
+        if (!js.isObject()) return "response_format json_schema needs a json_schema object";
+        for (auto &m : js.members())
+            if (m.first != "name" && m.first != "schema" && m.first != "strict" && m.first != "description")
+                return "response_format json_schema: the member '" + m.first + "' is not supported";
+        if (js.contains("name") && !js["name"].isString()) return "response_format json_schema: name must be a string";
+        if (js.contains("strict") && !js["strict"].isBool()) return "response_format json_schema: strict must be a boolean";
+        if (!js["schema"].isObject()) return "response_format json_schema needs json_schema.schema, an object";
+        if (!sess->grammarVocab()) return "response_format json_schema is unavailable: no tokenizer";
+        try {
+            p.grammar = schemaCache.get(js["schema"], sess->grammarVocab());
+        } catch (const SchemaError &e) {
+            return e.what();
+        }
+        return "";
+    }
+
     std::vector<int> buildPrompt(const Value &messages) {
         std::vector<ChatItem> items;
         for (const Value &m : messages.items()) items.push_back(ChatItem{m["role"].asString(), m["content"].asString()});
@@ -184,8 +207,10 @@ struct Api {
                     p.jsonObject = true;
                 else
                     bad = "response_format json_object is unavailable with this tokenizer: " + jsonUnavailable;
+            } else if (type == "json_schema") {
+                bad = schemaParams(rf, p);
             } else if (type != "text") {
-                bad = "response_format must be {\"type\": \"text\"} or {\"type\": \"json_object\"}";
+                bad = "response_format must be {\"type\": \"text\"}, {\"type\": \"json_object\"} or {\"type\": \"json_schema\", \"json_schema\": {...}}";
             }
         }
         const Value &lb = body["logit_bias"];
@@ -755,6 +780,7 @@ struct Api {
                (double)s.logitFilterRequests);
         metric("dllama_embedding_requests_total", "counter", "Finished embedding requests.", (double)s.embeddingRequests);
         metric("dllama_json_requests_total", "counter", "Finished requests in JSON mode.", (double)s.jsonRequests);
+        metric("dllama_schema_requests_total", "counter", "Finished requests constrained by a JSON schema.", (double)s.schemaRequests);
         metric("dllama_completion_requests_total", "counter", "Finished /v1/completions requests (one per prompt item).",
                (double)s.completionRequests);
         metric("dllama_scored_prompt_tokens_total", "counter", "Prompt tokens scored (echo with logprobs).",
@@ -792,6 +818,7 @@ struct Api {
         v.set("logit_proc_requests", (double)s.logitProcRequests);
         v.set("logit_filter_requests", (double)s.logitFilterRequests);
         v.set("json_requests", (double)s.jsonRequests);
+        v.set("schema_requests", (double)s.schemaRequests);
         v.set("embedding_requests", (double)s.embeddingRequests);
         v.set("completion_requests", (double)s.completionRequests);
         v.set("scored_prompt_tokens", (double)s.scoredPromptTokens);

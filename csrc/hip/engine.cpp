@@ -329,7 +329,7 @@ HipEngineImpl::GraphKind HipEngineImpl::beginProcs(int n, const int *slots, cons
     std::vector<int> seen;
     procRows_.assign((size_t)n * 4, 0.f);
     filterRows_.assign((size_t)n, hipk::LogitFilterRow{0, -INFINITY, 0, 0});
-    bool any = false, anyFilter = false, anyJson = false;
+    bool any = false, anyFilter = false, anyJson = false, anyGrammar = false;
     for (int b = 0; b < n; b++) {
         const LogitProc &p = procs[b];
         if (!p.active || specs[b].temperature < 0.f) continue;
@@ -345,14 +345,23 @@ HipEngineImpl::GraphKind HipEngineImpl::beginProcs(int n, const int *slots, cons
         }
         if (p.json) {
             DL_CHECK(dJsonMeta_ != nullptr, "json mode: no token table (setJsonTable)");
-            procRows_[(size_t)b * 4 + 3] = 1.f;
+            procRows_[(size_t)b * 4 + 3] = hipk::kRowKindJson;
             anyJson = true;
+        }
+        if (p.grammar) {  // (takeLogitProcs: never next to json; a fresh row's tables are checked)
+            DL_CHECK(dJsonMeta_ != nullptr, "json_schema: no token table (setJsonTable)");
+            DL_CHECK(p.fresh || slotGrammar_[(size_t)slots[b]] == p.grammar,
+                     "json_schema: a row that is not fresh carries another grammar than its slot's");
+            procRows_[(size_t)b * 4 + 3] = hipk::kRowKindGrammar;
+            anyGrammar = true;
         }
     }
     std::sort(seen.begin(), seen.end());
     DL_CHECK(std::adjacent_find(seen.begin(), seen.end()) == seen.end(),
              "logit processors: two drawn rows of one forward share a slot");
     if (!any) return GraphKind::SAMPLE;
+    if (anyGrammar && anyJson) return anyFilter ? GraphKind::SAMPLE_PROC_FILTER_JSON_GRAMMAR : GraphKind::SAMPLE_PROC_JSON_GRAMMAR;
+    if (anyGrammar) return anyFilter ? GraphKind::SAMPLE_PROC_FILTER_GRAMMAR : GraphKind::SAMPLE_PROC_GRAMMAR;
     if (anyJson) return anyFilter ? GraphKind::SAMPLE_PROC_FILTER_JSON : GraphKind::SAMPLE_PROC_JSON;
     return anyFilter ? GraphKind::SAMPLE_PROC_FILTER : GraphKind::SAMPLE_PROC;
 }
@@ -367,6 +376,7 @@ void HipEngineImpl::enqueueProcState(int n, const int *slots, const std::vector<
         if (procRows_[(size_t)b * 4 + 2] == 0.f || !p.fresh) continue;
         const size_t s = (size_t)slots[b], nb = p.bias.size();
         if (p.json) DL_HIP(hipMemsetAsync(dJsonStates_ + s, 0, sizeof(uint4), stream_));  // START is all zero bits
+        if (p.grammar) enqueueGrammarInstall(s, p.grammar);
         DL_HIP(hipMemsetAsync(dProcCounts_ + s * h_.vocabSize, 0, (size_t)h_.vocabSize * sizeof(uint32_t), stream_));
         hProcNBias_[s] = (int)nb;
         DL_HIP(hipMemcpyAsync(dProcNBias_ + s, hProcNBias_ + s, sizeof(int), hipMemcpyHostToDevice, stream_));
@@ -399,6 +409,38 @@ void HipEngineImpl::setJsonTable(std::shared_ptr<const JsonTokenTable> table) {
     dJsonWords_ = dalloc<uint32_t>(table->words.size());
     DL_HIP(hipMemcpy(dJsonMeta_, meta.data(), V * sizeof(uint2), hipMemcpyHostToDevice));
     DL_HIP(hipMemcpy(dJsonWords_, table->words.data(), table->words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+}
+
+// A fresh row's grammar goes to its slot's table block, and the slot's state to the start state, in
+// stream order ahead of the forward. The copies read the grammar's own arrays: slotGrammar_ keeps
+// them alive until the slot's next fresh row, whose forward is launched after this one was
+// collected. Every part a walk can index is rewritten (next up to nStates * nClasses, the class
+// map, the accept words up to nStates, the head), so a slot never serves an earlier request's tables.
+void HipEngineImpl::enqueueGrammarInstall(size_t slot, const std::shared_ptr<const GrammarDfa> &g) {
+    static_assert(kGrammarMaxEntries * sizeof(uint16_t) <= hipk::kGrammarClassOff && kGrammarMaxStates / 8 <= 512, "table block layout");
+    static_assert(offsetof(GrammarDfa, nStates) == offsetof(GrammarDfa, nClasses) + sizeof(uint32_t), "the head is (nClasses, nStates)");
+    slotGrammar_[slot] = g;
+    uint8_t *base = dGrammarTables_ + slot * hipk::kGrammarSlotBytes;
+    DL_HIP(hipMemcpyAsync(base, g->next.data(), g->next.size() * sizeof(uint16_t), hipMemcpyHostToDevice, stream_));
+    DL_HIP(hipMemcpyAsync(base + hipk::kGrammarClassOff, g->classOf, 256, hipMemcpyHostToDevice, stream_));
+    DL_HIP(hipMemcpyAsync(base + hipk::kGrammarAcceptOff, g->accept.data(), g->accept.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+    DL_HIP(hipMemcpyAsync(base + hipk::kGrammarHeadOff, &g->nClasses, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+    DL_HIP(hipMemcpyAsync(dGrammarStates_ + slot, &g->start, sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+}
+
+hipk::GrammarMaskArgs HipEngineImpl::grammarMaskArgs() const {
+    hipk::GrammarMaskArgs g;
+    g.logits = dProcLogits_;
+    g.vocab = h_.vocabSize;
+    g.spec = dSpec_;
+    g.proc = dProc_;
+    g.slots = dSlot_;
+    g.table.meta = dJsonMeta_;
+    g.table.words = dJsonWords_;
+    g.tables = dGrammarTables_;
+    g.states = dGrammarStates_;
+    g.ids = dIds_;
+    return g;
 }
 
 hipk::JsonMaskArgs HipEngineImpl::jsonMaskArgs() const {

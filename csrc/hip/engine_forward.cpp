@@ -631,7 +631,7 @@ void HipEngineImpl::enqueueTokenPick(int n, GraphKind kind) {
     // logits for the host (LOGITS) and sampled rows (SAMPLE) are needed on the root only: the
     // vocab slices are gathered to rank 0 (the reference's SYNC_NODE_SLICES_EXCEPT_ROOT), the
     // other ranks publish theirs and skip the unshard and the draw (the root's ids are used)
-    const bool filtered = kindFilter(kind), json = kindJson(kind);
+    const bool filtered = kindFilter(kind), json = kindJson(kind), grammar = kindGrammar(kind);
     const bool sampled = kind == GraphKind::SAMPLE || kindProc(kind);
     const bool rootOnly = kind == GraphKind::LOGITS || sampled;
     if (p.nRanks > 1 && !distArgmax) {
@@ -665,6 +665,10 @@ void HipEngineImpl::enqueueTokenPick(int n, GraphKind kind) {
                 ProfScope ps(this, "json_mask");
                 hipk::launchJsonMask(jsonMaskArgs(), n, stream_);
             }
+            if (grammar) {  // ..._GRAMMAR: the same for rows that follow a compiled grammar (each mask takes its own rows)
+                ProfScope ps(this, "grammar_mask");
+                hipk::launchGrammarMask(grammarMaskArgs(), n, stream_);
+            }
             if (filtered) {
                 ProfScope ps(this, "logit_filter");
                 hipk::LogitFilterArgs f;
@@ -694,6 +698,10 @@ void HipEngineImpl::enqueueTokenPick(int n, GraphKind kind) {
             if (json) {
                 ProfScope ps(this, "json_mask");
                 hipk::launchJsonAdvance(jsonMaskArgs(), n, stream_);
+            }
+            if (grammar) {
+                ProfScope ps(this, "grammar_mask");
+                hipk::launchGrammarAdvance(grammarMaskArgs(), n, stream_);
             }
         }
     } else if (kind != GraphKind::LOGITS) {

@@ -112,11 +112,21 @@ class HipEngineImpl : public HipEngine {
     // and the automaton's advance behind the draw (a forward with a drawn row in JSON mode)
     enum class GraphKind {
         LOGITS = 0, ARGMAX = 1, CHAIN = 2, SAMPLE = 3, SAMPLE_PROC = 4, SAMPLE_PROC_FILTER = 5, EMBED = 6,
-        SAMPLE_PROC_JSON = 7, SAMPLE_PROC_FILTER_JSON = 8
+        SAMPLE_PROC_JSON = 7, SAMPLE_PROC_FILTER_JSON = 8,
+        // ..._GRAMMAR: with the grammar token mask and advance (a forward with a drawn row that follows
+        // a compiled schema); ..._JSON_GRAMMAR: a forward that has rows of both kinds runs both masks
+        SAMPLE_PROC_GRAMMAR = 9, SAMPLE_PROC_FILTER_GRAMMAR = 10, SAMPLE_PROC_JSON_GRAMMAR = 11, SAMPLE_PROC_FILTER_JSON_GRAMMAR = 12
     };
-    static bool kindJson(GraphKind k) { return k == GraphKind::SAMPLE_PROC_JSON || k == GraphKind::SAMPLE_PROC_FILTER_JSON; }
-    static bool kindFilter(GraphKind k) { return k == GraphKind::SAMPLE_PROC_FILTER || k == GraphKind::SAMPLE_PROC_FILTER_JSON; }
-    static bool kindProc(GraphKind k) { return k == GraphKind::SAMPLE_PROC || kindFilter(k) || kindJson(k); }
+    static bool kindJson(GraphKind k) {
+        return k == GraphKind::SAMPLE_PROC_JSON || k == GraphKind::SAMPLE_PROC_FILTER_JSON || k == GraphKind::SAMPLE_PROC_JSON_GRAMMAR ||
+               k == GraphKind::SAMPLE_PROC_FILTER_JSON_GRAMMAR;
+    }
+    static bool kindGrammar(GraphKind k) { return (int)k >= (int)GraphKind::SAMPLE_PROC_GRAMMAR && (int)k <= (int)GraphKind::SAMPLE_PROC_FILTER_JSON_GRAMMAR; }
+    static bool kindFilter(GraphKind k) {
+        return k == GraphKind::SAMPLE_PROC_FILTER || k == GraphKind::SAMPLE_PROC_FILTER_JSON || k == GraphKind::SAMPLE_PROC_FILTER_GRAMMAR ||
+               k == GraphKind::SAMPLE_PROC_FILTER_JSON_GRAMMAR;
+    }
+    static bool kindProc(GraphKind k) { return k == GraphKind::SAMPLE_PROC || kindFilter(k) || kindJson(k) || kindGrammar(k); }
 
     // engine.cpp
     void syncAndCheckComm();
@@ -443,6 +453,16 @@ class HipEngineImpl : public HipEngine {
     uint32_t *dJsonWords_ = nullptr;
     uint4 *dJsonStates_ = nullptr;                 // [nSlots]
     hipk::JsonMaskArgs jsonMaskArgs() const;
+    // structured outputs (LogitProc::grammar), root rank only: per KV slot a table block
+    // (hipk::kGrammarSlotBytes: the transition table, the class map, the accept bits, the head) and
+    // a u32 state, installed by a fresh row ahead of its forward (enqueueGrammarInstall) and advanced
+    // behind the draw; slotGrammar_ is the grammar each slot holds (it owns the bytes the install
+    // copies from). The token table is JSON mode's.
+    uint8_t *dGrammarTables_ = nullptr;            // [nSlots][kGrammarSlotBytes]
+    uint32_t *dGrammarStates_ = nullptr;           // [nSlots]
+    std::vector<std::shared_ptr<const GrammarDfa>> slotGrammar_;
+    void enqueueGrammarInstall(size_t slot, const std::shared_ptr<const GrammarDfa> &g);
+    hipk::GrammarMaskArgs grammarMaskArgs() const;
     size_t procBytes() const;
     // pooling (Backend::setPooling), root rank only: the forward's pool rows and their per-slot run
     // index (hipk::poolPlan) behind one pinned staging block (free once the previous forward was

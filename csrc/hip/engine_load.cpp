@@ -93,7 +93,9 @@ size_t HipEngineImpl::procBytes() const {
            (size_t)cfg_.maxBatch * (h_.vocabSize * sizeof(float) + hipk::kLogitFilterStateWords * sizeof(uint32_t)) +
            // JSON mode: the states, and the token table that setJsonTable uploads later (its entries and
            // an estimate of 16 padded bytes per piece; setJsonTable checks the real size)
-           (size_t)cfg_.nSlots * sizeof(uint4) + (size_t)h_.vocabSize * (sizeof(uint2) + 16);
+           (size_t)cfg_.nSlots * sizeof(uint4) + (size_t)h_.vocabSize * (sizeof(uint2) + 16) +
+           // structured outputs: a table block and a state per slot
+           (size_t)cfg_.nSlots * (hipk::kGrammarSlotBytes + sizeof(uint32_t));
 }
 
 // Device state of the pooling kernel (root rank): per slot the accumulator, the output, the norm's
@@ -138,6 +140,12 @@ void HipEngineImpl::allocBuffers() {
         DL_HIP(hipMemsetAsync(dProcNBias_, 0, S * sizeof(int), stream_));
         dJsonStates_ = dalloc<uint4>(S);
         DL_HIP(hipMemsetAsync(dJsonStates_, 0, S * sizeof(uint4), stream_));
+        // (zeroed: a block that was never installed has no states, so nothing is allowed in it)
+        dGrammarTables_ = dalloc<uint8_t>(S * hipk::kGrammarSlotBytes);
+        DL_HIP(hipMemsetAsync(dGrammarTables_, 0, S * hipk::kGrammarSlotBytes, stream_));
+        dGrammarStates_ = dalloc<uint32_t>(S);
+        DL_HIP(hipMemsetAsync(dGrammarStates_, 0, S * sizeof(uint32_t), stream_));
+        slotGrammar_.assign(S, nullptr);
         dFilterState_ = dalloc<uint32_t>((size_t)MB * hipk::kLogitFilterStateWords);
         DL_HIP(hipMemsetAsync(dFilterState_, 0, (size_t)MB * hipk::kLogitFilterStateWords * sizeof(uint32_t), stream_));
     }

@@ -6,10 +6,7 @@
 // 16-byte state, the workgroup takes it from LDS. A thread loads its token's (offset, length | class)
 // and walks the piece's bytes, one 4-byte word of the table per four bytes, through jsonStep until a
 // byte rejects or the piece ends, so a wave runs as long as its longest surviving token. The
-// verdicts of four neighbouring lanes meet through a ballot in the lane of the vector's first
-// element: all allowed - nothing is touched; none - one 16-byte store of -inf; mixed - the vector is
-// loaded, the rejected elements replaced and the vector stored. The vocab % 4 tail is stored per
-// element. Nothing is shared between workgroups.
+// verdicts are stored by maskStoreTail (row_dev.h). Nothing is shared between workgroups.
 #include "../core/json_grammar.h"
 #include "row_dev.h"
 
@@ -37,7 +34,7 @@ __device__ __forceinline__ uint4 jsonPack(const JsonState &s) {
 }
 
 __device__ __forceinline__ bool jsonRowOn(const JsonMaskArgs &a, int b) {
-    return a.spec[b].x >= 0.f && a.proc[b].w != 0.f;
+    return a.spec[b].x >= 0.f && a.proc[b].w == kRowKindJson;
 }
 
 __global__ __launch_bounds__(kRowWg) void jsonMaskKernel(JsonMaskArgs a) {
@@ -55,23 +52,7 @@ __global__ __launch_bounds__(kRowWg) void jsonMaskKernel(JsonMaskArgs a) {
         ok = !jsonRejected(jsonStepToken(st, a.table.words, m.x, m.y));
     }
     float *row = a.logits + (size_t)b * vocab;
-    const int lane = (int)threadIdx.x & 63;
-    const unsigned long long verdicts = __ballot(ok);
-    if ((t | 3) < vocab) {  // the whole vector lies in the row: its first lane stores it
-        if ((lane & 3) != 0) return;
-        const unsigned keep = (unsigned)(verdicts >> lane) & 0xfu;
-        if (keep == 0xfu) return;
-        RowVec4<float> *p = reinterpret_cast<RowVec4<float> *>(row + t);
-        RowVec4<float> v;
-        if (keep != 0u) v = *p;
-        if (!(keep & 1u)) v.x = -INFINITY;
-        if (!(keep & 2u)) v.y = -INFINITY;
-        if (!(keep & 4u)) v.z = -INFINITY;
-        if (!(keep & 8u)) v.w = -INFINITY;
-        *p = v;
-    } else if (t < vocab && !ok) {
-        row[t] = -INFINITY;
-    }
+    maskStoreTail(row, t, vocab, ok);
 }
 
 // One thread per row.

@@ -679,8 +679,8 @@ struct PoolArgs {
 void launchPool(const PoolArgs &a, int B, hipStream_t s);
 
 // JSON mode (csrc/core/json_grammar.h): the token mask between the logit processors and the candidate
-// filter, and the automaton's advance behind the draw. A row b takes part when proc[b].w != 0 (its
-// request is constrained) and spec[b].x >= 0 (it draws); its state is states[slots[b]].
+// filter, and the automaton's advance behind the draw. A row b takes part when proc[b].w == kRowKindJson (its
+// request is in JSON mode) and spec[b].x >= 0 (it draws); its state is states[slots[b]].
 // launchJsonMask, in place on [B][vocab] logits: x[t] = -inf for every token t that is not allowed
 // in the row's state (jsonStepToken rejects), the others keep their bits; every other row is neither
 // read nor written. Grid (ceil(vocab / 256), B), one thread per token, which walks the token's bytes
@@ -707,6 +707,46 @@ struct JsonMaskArgs {
 };
 void launchJsonMask(const JsonMaskArgs &a, int B, hipStream_t s);
 void launchJsonAdvance(const JsonMaskArgs &a, int B, hipStream_t s);
+// What constrains a drawn row is the 4th float of its proc entry: 0 nothing, kRowKindJson the JSON
+// automaton (the kernels above), kRowKindGrammar a compiled grammar (the kernels below). Each pair
+// of kernels takes its own kind only and neither reads nor writes the other's rows.
+constexpr float kRowKindJson = 1.f;
+constexpr float kRowKindGrammar = 2.f;
+
+// Structured outputs (csrc/core/grammar_dfa.h): the token mask of rows that follow a compiled byte
+// DFA, in the JSON mask's place, and the state's advance behind the draw. A row b takes part when
+// proc[b].w == kRowKindGrammar and spec[b].x >= 0; its DFA is the table block of slot slots[b] and
+// its state is states[slots[b]] (one u32).
+// A slot's table block is kGrammarSlotBytes: next[nStates][nClasses] (u16) from byte 0, classOf[256]
+// at kGrammarClassOff, the accept bits at kGrammarAcceptOff and (nClasses, nStates) as two u32 at
+// kGrammarHeadOff. The host installs only checked tables (grammarCheck): every entry of next is
+// < nStates or dead, so a walk stays inside the block; a state >= nStates allows nothing.
+// launchGrammarMask, in place on [B][vocab] logits: x[t] = -inf for every token that
+// grammarStepToken rejects in the row's state, the others keep their bits; every other row is
+// neither read nor written. Grid (ceil(vocab / 256), B), one thread per token. Once per workgroup:
+// the state, the table's head, the class map (256 B) and the state's transition row (nClasses u16)
+// go to LDS. A token's first byte is decided from LDS, and so is every later byte that is still in
+// the row's state (the loop of a free string); the others follow next[] through global loads of
+// the read-only table. The store tail is the JSON mask's (maskStoreTail). No atomics, no scratch.
+// launchGrammarAdvance, behind the draw: one thread per row steps states[slots[b]] by ids[b]; a
+// token that is not allowed, or an id outside [0, vocab), leaves the state as it is.
+constexpr size_t kGrammarClassOff = 262144;
+constexpr size_t kGrammarAcceptOff = kGrammarClassOff + 256;
+constexpr size_t kGrammarHeadOff = kGrammarAcceptOff + 512;
+constexpr size_t kGrammarSlotBytes = kGrammarHeadOff + 256;
+struct GrammarMaskArgs {
+    float *logits = nullptr;        // [B][vocab], masked in place
+    int vocab = 0;
+    const float4 *spec = nullptr;   // [B] (temperature, -, -, -)
+    const float4 *proc = nullptr;   // [B] (-, -, -, row kind)
+    const int *slots = nullptr;     // [B]
+    JsonTable table;
+    const uint8_t *tables = nullptr;  // [nSlots][kGrammarSlotBytes]
+    uint32_t *states = nullptr;       // [nSlots]
+    const int *ids = nullptr;         // [B] the drawn tokens (launchGrammarAdvance)
+};
+void launchGrammarMask(const GrammarMaskArgs &a, int B, hipStream_t s);
+void launchGrammarAdvance(const GrammarMaskArgs &a, int B, hipStream_t s);
 
 // Round-trip f32 partial sums through Q80 blocks in place (the reference's ZQ cast before the
 // exchange) - used ahead of a plain all-reduce when the fused exchange is not available.

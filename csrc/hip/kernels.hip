@@ -433,6 +433,7 @@ const void *sampleModuleKernel();
 const void *logitProcModuleKernel();
 const void *logitFilterModuleKernel();
 const void *jsonMaskModuleKernel();
+const void *grammarMaskModuleKernel();
 const void *attnPrefillModuleKernel();
 const void *tpCheckModuleKernel();
 const void *gemvFnL16(bool q40, int B, int pro, int epi);
@@ -451,7 +452,7 @@ void preloadModules() {
     typedef const void *(*BlockFn)(int, bool, int);
     const BlockFn blocks[] = {attnBlockFn_16_16_128, attnBlockFn_16_32_128, attnBlockFn_32_32_128, attnBlockFn_64_32_128, attnBlockFn_64_16_128,
                               attnBlockFn_64_64_128, attnBlockFn_32_64_128, attnBlockFn_64_64_64};
-    std::vector<const void *> fns = {sampleModuleKernel(), logitProcModuleKernel(), logitFilterModuleKernel(), jsonMaskModuleKernel(), attnPrefillModuleKernel(), tpCheckModuleKernel(),
+    std::vector<const void *> fns = {sampleModuleKernel(), logitProcModuleKernel(), logitFilterModuleKernel(), jsonMaskModuleKernel(), grammarMaskModuleKernel(), attnPrefillModuleKernel(), tpCheckModuleKernel(),
                                      gemmModuleKernel(),   gemmWideModuleKernel(),    attnMfmaModuleKernel(),
                                      xgmiModuleKernel(),   gemvFnL16(true, 1, 0, 0),
                                      gemvFnL32(true, 1, 0, 0), gemvFnL64(true, 1, 0, 0)};

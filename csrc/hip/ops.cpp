@@ -1543,6 +1543,137 @@ void benchJsonMask(int B, int vocab, const std::vector<uint32_t> &off, const std
     sc.sync();
 }
 
+namespace {
+// table, spec / proc rows, slots, the slots' table blocks and states of a GrammarMaskArgs
+hipk::GrammarMaskArgs grammarMaskArgs(Scratch &sc, int B, int vocab, const std::vector<float> &temps,
+                                      const std::vector<int> &kinds, const std::vector<int> &slots,
+                                      const std::vector<uint32_t> &off, const std::vector<uint32_t> &info,
+                                      const std::vector<uint32_t> &words, const std::vector<const GrammarDfa *> &grammars,
+                                      const std::vector<uint32_t> &states) {
+    const size_t S = grammars.size();
+    DL_CHECK(B >= 1 && vocab >= 1 && S >= 1, "grammar_mask sizes");
+    DL_CHECK(temps.size() == (size_t)B && kinds.size() == (size_t)B && slots.size() == (size_t)B && states.size() == S,
+             "grammar_mask: one temperature, kind and slot per row, one state per slot");
+    DL_CHECK(off.size() == (size_t)vocab && info.size() == (size_t)vocab && !words.empty(), "grammar_mask: the table is [vocab]");
+    std::vector<uint32_t> meta((size_t)vocab * 2);
+    for (int t = 0; t < vocab; t++) {
+        const uint32_t len = info[t] & 0xffffu;
+        DL_CHECK((size_t)off[t] + (len + 3) / 4 <= words.size(), "grammar_mask: a piece lies outside the table's words");
+        meta[(size_t)t * 2] = off[t];
+        meta[(size_t)t * 2 + 1] = info[t];
+    }
+    std::vector<float> spec((size_t)B * 4, 0.f), proc((size_t)B * 4, 0.f);
+    for (int b = 0; b < B; b++) {
+        DL_CHECK(slots[b] >= 0 && (size_t)slots[b] < S, "grammar_mask: slot out of range");
+        DL_CHECK(kinds[b] >= 0 && kinds[b] <= 2, "grammar_mask: a row's kind is 0 (none), 1 (json) or 2 (grammar)");
+        DL_CHECK(kinds[b] != 2 || grammars[slots[b]], "grammar_mask: a grammar row's slot holds no grammar");
+        spec[(size_t)b * 4] = temps[b];
+        proc[(size_t)b * 4 + 3] = (float)kinds[b];
+    }
+    static_assert(hipk::kRowKindJson == 1.f && hipk::kRowKindGrammar == 2.f, "row kinds");
+    uint8_t *blocks = sc.alloc<uint8_t>(S * hipk::kGrammarSlotBytes);  // (zero-filled: an empty slot allows nothing)
+    for (size_t s = 0; s < S; s++) {
+        const GrammarDfa *g = grammars[s];
+        if (!g) continue;
+        const std::string bad = grammarCheck(*g);
+        DL_CHECK(bad.empty(), "grammar_mask: malformed tables: " + bad);
+        uint8_t *base = blocks + s * hipk::kGrammarSlotBytes;
+        const uint32_t head[2] = {g->nClasses, g->nStates};
+        DL_HIP(hipMemcpyAsync(base, g->next.data(), g->next.size() * sizeof(uint16_t), hipMemcpyHostToDevice, sc.s));
+        DL_HIP(hipMemcpyAsync(base + hipk::kGrammarClassOff, g->classOf, 256, hipMemcpyHostToDevice, sc.s));
+        DL_HIP(hipMemcpyAsync(base + hipk::kGrammarAcceptOff, g->accept.data(), g->accept.size() * sizeof(uint32_t), hipMemcpyHostToDevice, sc.s));
+        DL_HIP(hipMemcpyAsync(base + hipk::kGrammarHeadOff, head, sizeof(head), hipMemcpyHostToDevice, sc.s));
+        DL_HIP(hipStreamSynchronize(sc.s));  // (head is a local)
+    }
+    hipk::GrammarMaskArgs g;
+    g.vocab = vocab;
+    g.spec = reinterpret_cast<const float4 *>(sc.upload(spec));
+    g.proc = reinterpret_cast<const float4 *>(sc.upload(proc));
+    g.slots = sc.upload(slots);
+    g.table.meta = reinterpret_cast<const uint2 *>(sc.upload(meta));
+    g.table.words = sc.upload(words);
+    g.tables = blocks;
+    g.states = sc.upload(states);
+    return g;
+}
+}  // namespace
+
+std::vector<float> grammarMask(const std::vector<float> &logits, int B, int vocab, const std::vector<float> &temps,
+                               const std::vector<int> &kinds, const std::vector<int> &slots,
+                               const std::vector<uint32_t> &off, const std::vector<uint32_t> &info,
+                               const std::vector<uint32_t> &words, const std::vector<const GrammarDfa *> &grammars,
+                               const std::vector<uint32_t> &states) {
+    DL_CHECK(B >= 1 && vocab >= 1 && logits.size() == (size_t)B * vocab, "grammar_mask: logits is [B][vocab]");
+    Scratch sc;
+    hipk::GrammarMaskArgs g = grammarMaskArgs(sc, B, vocab, temps, kinds, slots, off, info, words, grammars, states);
+    g.logits = sc.uploadGuardedTail(logits, kRowTailGuard, "the masked logits");
+    hipk::launchGrammarMask(g, B, sc.s);
+    sc.sync();
+    sc.checkGuards();
+    const std::vector<uint32_t> after = sc.download(g.states, states.size());
+    DL_CHECK(after == states, "grammar_mask: the launch changed a state");
+    return sc.download(g.logits, logits.size());
+}
+
+std::vector<uint32_t> grammarAdvance(int vocab, const std::vector<float> &temps, const std::vector<int> &kinds,
+                                     const std::vector<int> &slots, const std::vector<int> &ids,
+                                     const std::vector<uint32_t> &off, const std::vector<uint32_t> &info,
+                                     const std::vector<uint32_t> &words, const std::vector<const GrammarDfa *> &grammars,
+                                     const std::vector<uint32_t> &states) {
+    const int B = (int)temps.size();
+    DL_CHECK(ids.size() == (size_t)B, "grammar_advance: one drawn id per row");
+    std::vector<int> seen;
+    for (int b = 0; b < B; b++)
+        if (b < (int)kinds.size() && kinds[b] == 2 && temps[b] >= 0.f) seen.push_back(slots[b]);
+    std::sort(seen.begin(), seen.end());
+    DL_CHECK(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "grammar_advance: two drawn rows share a slot");
+    Scratch sc;
+    hipk::GrammarMaskArgs g = grammarMaskArgs(sc, B, vocab, temps, kinds, slots, off, info, words, grammars, states);
+    g.ids = sc.upload(ids);
+    hipk::launchGrammarAdvance(g, B, sc.s);
+    sc.sync();
+    return sc.download(g.states, states.size());
+}
+
+void benchGrammarMask(int B, int vocab, const std::vector<uint32_t> &off, const std::vector<uint32_t> &info,
+                      const std::vector<uint32_t> &words, const GrammarDfa &grammar, uint32_t state, int iters,
+                      double &copyUs, double &copyMaskUs, double &advanceUs, double &copyJsonUs, double &sampleUs) {
+    DL_CHECK(B >= 1 && vocab >= 2 && iters >= 1, "bench_grammar_mask arguments");
+    Scratch sc;
+    const std::vector<float> logits = bellLogits(B, vocab);
+    std::vector<int> slots(B);
+    for (int b = 0; b < B; b++) slots[b] = b;
+    const std::vector<const GrammarDfa *> grammars(B, &grammar);
+    const std::vector<uint32_t> states(B, state);
+    hipk::GrammarMaskArgs g = grammarMaskArgs(sc, B, vocab, std::vector<float>(B, 0.8f), std::vector<int>(B, 2), slots, off, info,
+                                              words, grammars, states);
+    // the JSON mask on the same rows, every row at START
+    hipk::JsonMaskArgs j = jsonMaskArgs(sc, B, vocab, std::vector<float>(B, 0.8f), std::vector<int>(B, 1), off, info, words,
+                                        std::vector<uint32_t>((size_t)B * 4, 0u));
+    const float *src = sc.upload(logits);
+    g.logits = sc.alloc<float>(logits.size());
+    j.logits = g.logits;
+    // the advance steps a scratch copy of the states (so that the mask's stay put) by token 0's bytes
+    hipk::GrammarMaskArgs adv = g;
+    adv.states = sc.upload(states);
+    adv.ids = sc.alloc<int>(B);  // (alloc zero-fills)
+    const size_t bytes = logits.size() * sizeof(float);
+    const hipk::SampleArgs sa = benchSampleArgs(sc, g.logits, B, vocab);
+    auto copy = [&] { DL_HIP(hipMemcpyAsync(g.logits, src, bytes, hipMemcpyDeviceToDevice, sc.s)); };
+    copyUs = timeEagerUs(sc.s, iters, kBenchWarmups, copy);
+    copyJsonUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] {
+        copy();
+        hipk::launchJsonMask(j, B, sc.s);
+    });
+    copyMaskUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] {
+        copy();
+        hipk::launchGrammarMask(g, B, sc.s);
+    });
+    sampleUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] { hipk::launchSample(sa, B, sc.s); });  // on the masked rows
+    advanceUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] { hipk::launchGrammarAdvance(adv, B, sc.s); });
+    sc.sync();
+}
+
 std::vector<float> embedding(const std::vector<float> &table, int vocab, int dim, const std::vector<int> &tokens) {
     const int B = (int)tokens.size();
     DL_CHECK(dim % 4 == 0 && table.size() == (size_t)vocab * dim, "embedding sizes");

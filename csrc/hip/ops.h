@@ -10,6 +10,8 @@
 #include <string>
 #include <vector>
 
+#include "../core/grammar_dfa.h"
+
 namespace dl {
 namespace ops {
 
@@ -296,6 +298,29 @@ std::vector<uint32_t> jsonAdvance(int vocab, const std::vector<float> &temps, co
 void benchJsonMask(int B, int vocab, const std::vector<uint32_t> &off, const std::vector<uint32_t> &info,
                    const std::vector<uint32_t> &words, const std::vector<uint32_t> &state, int iters, double &copyUs,
                    double &copyMaskUs, double &advanceUs, double &copyFilterUs, double &sampleUs);
+
+// The structured-output kernels on their own. The token table is JsonTokenTable's three arrays;
+// slot s holds grammars[s] (null: an empty table block) in state states[s]; row b is of kind
+// kinds[b] (0 none, 1 JSON mode, 2 grammar), sits in slot slots[b] and takes part when its kind is 2
+// and temps[b] >= 0. grammarMask: launchGrammarMask over a copy of [B][vocab] logits, returns the
+// buffer after the launch; a write behind its last row, or a state that changed, is an error.
+// grammarAdvance: launchGrammarAdvance with the drawn ids, returns the slots' states after it.
+std::vector<float> grammarMask(const std::vector<float> &logits, int B, int vocab, const std::vector<float> &temps,
+                               const std::vector<int> &kinds, const std::vector<int> &slots,
+                               const std::vector<uint32_t> &off, const std::vector<uint32_t> &info,
+                               const std::vector<uint32_t> &words, const std::vector<const GrammarDfa *> &grammars,
+                               const std::vector<uint32_t> &states);
+std::vector<uint32_t> grammarAdvance(int vocab, const std::vector<float> &temps, const std::vector<int> &kinds,
+                                     const std::vector<int> &slots, const std::vector<int> &ids,
+                                     const std::vector<uint32_t> &off, const std::vector<uint32_t> &info,
+                                     const std::vector<uint32_t> &words, const std::vector<const GrammarDfa *> &grammars,
+                                     const std::vector<uint32_t> &states);
+// Device microseconds as in benchJsonMask, on B grammar rows (one slot each) that all sit in `state`:
+// a device copy of the logits; the copy + launchGrammarMask; launchGrammarAdvance (by token 0); the
+// copy + launchJsonMask on the same rows at START; launchSample on the masked rows.
+void benchGrammarMask(int B, int vocab, const std::vector<uint32_t> &off, const std::vector<uint32_t> &info,
+                      const std::vector<uint32_t> &words, const GrammarDfa &grammar, uint32_t state, int iters,
+                      double &copyUs, double &copyMaskUs, double &advanceUs, double &copyJsonUs, double &sampleUs);
 
 // Embedding row gather: table [vocab][dim] -> [B][dim].
 std::vector<float> embedding(const std::vector<float> &table, int vocab, int dim, const std::vector<int> &tokens);

@@ -136,6 +136,31 @@ static constexpr int kRowU = 4;  // vectors in flight per thread per round
 template <typename T>
 using RowVec4 = T __attribute__((ext_vector_type(4), aligned(4)));
 
+// Store tail of the token masks (json_mask.hip, grammar_mask.hip), one thread per token t of `row`
+// with verdict ok (lanes behind the row pass true), called by every lane of the wave: the verdicts of
+// four neighbouring lanes meet through a ballot in the lane of the vector's first element: all
+// allowed - nothing is touched; none - one 16-byte store of -inf; mixed - the vector is loaded, the
+// rejected elements replaced and the vector stored. The vocab % 4 tail is stored per element.
+__device__ __forceinline__ void maskStoreTail(float *row, int t, int vocab, bool ok) {
+    const int lane = (int)threadIdx.x & 63;
+    const unsigned long long verdicts = __ballot(ok);
+    if ((t | 3) < vocab) {  // the whole vector lies in the row: its first lane stores it
+        if ((lane & 3) != 0) return;
+        const unsigned keep = (unsigned)(verdicts >> lane) & 0xfu;
+        if (keep == 0xfu) return;
+        RowVec4<float> *p = reinterpret_cast<RowVec4<float> *>(row + t);
+        RowVec4<float> v;
+        if (keep != 0u) v = *p;
+        if (!(keep & 1u)) v.x = -INFINITY;
+        if (!(keep & 2u)) v.y = -INFINITY;
+        if (!(keep & 4u)) v.z = -INFINITY;
+        if (!(keep & 8u)) v.w = -INFINITY;
+        *p = v;
+    } else if (t < vocab && !ok) {
+        row[t] = -INFINITY;
+    }
+}
+
 struct RowShare {
     int v0, v1;  // vectors
     int nvec, vocab;

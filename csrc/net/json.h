@@ -58,6 +58,11 @@ class Value {
         if (t_ != NUMBER) throw std::runtime_error("json: not a number");
         return n_;
     }
+    // a parsed number's source text (empty for a number that was not parsed from text)
+    const std::string &numberText() const {
+        if (t_ != NUMBER) throw std::runtime_error("json: not a number");
+        return s_;
+    }
     const std::string &asString() const {
         if (t_ != STRING) throw std::runtime_error("json: not a string");
         return s_;
@@ -319,9 +324,10 @@ class Value {
                                   s[end] == 'e' || s[end] == 'E'))
             end++;
         if (end == i) throw std::runtime_error("json: unexpected character");
-        const double v = std::stod(s.substr(i, end - i));
+        Value num(std::stod(s.substr(i, end - i)));
+        num.s_ = s.substr(i, end - i);
         i = end;
-        return Value(v);
+        return num;
     }
 
     Type t_;

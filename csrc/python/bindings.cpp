@@ -9,6 +9,7 @@
 #include "../core/model_file.h"
 #include "../core/plan.h"
 #include "../core/quant.h"
+#include "../core/schema_dfa.h"
 #include "../cpu/cpu_ops.h"
 #include "../hip/engine.h"
 #include "../hip/host_harness.h"
@@ -139,11 +140,21 @@ std::vector<uint32_t> stateToWords(const JsonState &s) {
 struct PyJsonTable {
     std::shared_ptr<JsonTokenTable> t;
 };
+// A compiled grammar (structured outputs) and the token table its masks walk.
+struct PyGrammar {
+    std::shared_ptr<const GrammarDfa> g;
+    std::shared_ptr<JsonTokenTable> t;  // may be null (from_table without one): no mask_host / advance_host
+};
+SchemaDfaCache &schemaCache() {
+    static SchemaDfaCache cache;
+    return cache;
+}
 
 // Per-row logit processors (Backend LogitProc) from Python: None (no row has one) or a sequence
 // of n entries, each None (the row has none) or a dict with the optional keys "presence",
 // "frequency", "fresh", "bias" (a dict token id -> value, read when fresh), "top_k", "min_p" and
-// "json" (the row is in JSON mode: set_json_table first).
+// "json" (the row is in JSON mode: set_json_table first) and "grammar" (a Grammar the row follows:
+// structured outputs; set_json_table first as well).
 std::vector<LogitProc> parseProcs(const py::object &o, size_t n) {
     std::vector<LogitProc> procs;
     if (o.is_none()) return procs;
@@ -162,6 +173,7 @@ std::vector<LogitProc> parseProcs(const py::object &o, size_t n) {
         if (d.contains("top_k") && !d["top_k"].is_none()) p.topK = d["top_k"].cast<int>();
         if (d.contains("min_p") && !d["min_p"].is_none()) p.minP = d["min_p"].cast<float>();
         if (d.contains("json") && !d["json"].is_none()) p.json = d["json"].cast<bool>();
+        if (d.contains("grammar") && !d["grammar"].is_none()) p.grammar = d["grammar"].cast<const PyGrammar &>().g;
         if (d.contains("bias") && !d["bias"].is_none())
             for (auto kv : d["bias"].cast<py::dict>()) p.bias.push_back(LogitBias{kv.first.cast<int>(), kv.second.cast<float>()});
     }
@@ -779,6 +791,46 @@ void bindOps(py::module_ &m) {
           py::arg("batch"), py::arg("table"), py::arg("state"), py::arg("iters") = 200,
           "(us per device copy of the logits, per copy + launchJsonMask, per launchJsonAdvance, per copy + "
           "launchLogitFilter with top_k 40, per launchSample on the masked rows), every row in `state`");
+    o.def("grammar_mask",
+          [](py::object logits, std::vector<float> temps, std::vector<int> kinds, std::vector<int> slots, const PyJsonTable &tb,
+             std::vector<py::object> grammars, std::vector<uint32_t> states) {
+              const std::vector<float> l = vec<float>(logits);
+              const int B = (int)temps.size();
+              DL_CHECK(B >= 1 && l.size() % B == 0, "grammar_mask: one temperature per row");
+              const int vocab = (int)(l.size() / B);
+              std::vector<const GrammarDfa *> gs;
+              for (auto &g : grammars) gs.push_back(g.is_none() ? nullptr : g.cast<const PyGrammar &>().g.get());
+              std::vector<float> out;
+              {
+                  py::gil_scoped_release rel;
+                  out = ops::grammarMask(l, B, vocab, temps, kinds, slots, tb.t->off, tb.t->info, tb.t->words, gs, states);
+              }
+              return arr(out, {B, vocab});
+          },
+          py::arg("logits"), py::arg("temperatures"), py::arg("kinds"), py::arg("slots"), py::arg("table"), py::arg("grammars"),
+          py::arg("states"));
+    o.def("grammar_advance",
+          [](std::vector<float> temps, std::vector<int> kinds, std::vector<int> slots, std::vector<int> ids, const PyJsonTable &tb,
+             std::vector<py::object> grammars, std::vector<uint32_t> states) {
+              std::vector<const GrammarDfa *> gs;
+              for (auto &g : grammars) gs.push_back(g.is_none() ? nullptr : g.cast<const PyGrammar &>().g.get());
+              py::gil_scoped_release rel;
+              return ops::grammarAdvance(tb.t->vocab(), temps, kinds, slots, ids, tb.t->off, tb.t->info, tb.t->words, gs, states);
+          },
+          py::arg("temperatures"), py::arg("kinds"), py::arg("slots"), py::arg("ids"), py::arg("table"), py::arg("grammars"),
+          py::arg("states"));
+    o.def("bench_grammar_mask",
+          [](int B, const PyJsonTable &tb, const PyGrammar &g, uint32_t state, int iters) {
+              double cu = 0, mu = 0, au = 0, ju = 0, su = 0;
+              {
+                  py::gil_scoped_release rel;
+                  ops::benchGrammarMask(B, tb.t->vocab(), tb.t->off, tb.t->info, tb.t->words, *g.g, state, iters, cu, mu, au, ju, su);
+              }
+              return py::make_tuple(cu, mu, au, ju, su);
+          },
+          py::arg("batch"), py::arg("table"), py::arg("grammar"), py::arg("state"), py::arg("iters") = 200,
+          "(us per device copy of the logits, per copy + launchGrammarMask, per launchGrammarAdvance, per copy + "
+          "launchJsonMask at START, per launchSample on the masked rows), every row in `state`");
     o.def("pool",
           [](py::list launches, int dim, int nSlots, py::array_t<float, py::array::c_style | py::array::forcecast> normW,
              float eps, py::array_t<float, py::array::c_style | py::array::forcecast> outInit,
@@ -1142,6 +1194,113 @@ PYBIND11_MODULE(_C, m) {
              },
              py::arg("state"), py::arg("token"))
         .def("dead_end", [](const PyJsonTable &t) { return jsonDeadEnd(*t.t); });
+
+    py::class_<PyGrammar>(m, "Grammar")
+        .def_static("from_schema",
+                    [](const std::string &text, py::object table, bool cache) {
+                        PyGrammar g;
+                        GrammarVocab vocab;
+                        if (!table.is_none()) {
+                            g.t = table.cast<const PyJsonTable &>().t;
+                            vocab = makeGrammarVocab(g.t->off, g.t->info, g.t->words);
+                        }
+                        json::Value schema;
+                        try {
+                            schema = json::Value::parse(text);
+                        } catch (const std::runtime_error &e) {
+                            throw SchemaError(std::string("json_schema: the schema is not JSON: ") + e.what());
+                        }
+                        const GrammarVocab *vp = g.t ? &vocab : nullptr;
+                        g.g = cache ? schemaCache().get(schema, vp) : compileSchemaDfa(schema, vp);
+                        return g;
+                    },
+                    py::arg("text"), py::arg("json_table") = py::none(), py::arg("cache") = false,
+                    "Compiles a JSON schema (text). With a JsonTable the dead-end check runs against its vocabulary and "
+                    "mask_host / advance_host work; cache=True goes through the process-wide LRU cache of 32 grammars.")
+        .def_static("from_table",
+                    [](py::array_t<uint8_t, py::array::c_style | py::array::forcecast> classOf,
+                       py::array_t<uint16_t, py::array::c_style | py::array::forcecast> next, uint32_t start,
+                       std::vector<int> accept, py::object table) {
+                        DL_CHECK(classOf.size() == 256, "from_table: class_of is 256 bytes");
+                        auto d = std::make_shared<GrammarDfa>();
+                        std::memcpy(d->classOf, classOf.data(), 256);
+                        DL_CHECK(next.ndim() == 2, "from_table: next is [n_states][n_classes]");
+                        d->nStates = (uint32_t)next.shape(0);
+                        d->nClasses = (uint32_t)next.shape(1);
+                        d->next.assign(next.data(), next.data() + next.size());
+                        d->start = start;
+                        d->accept.assign((d->nStates + 31) / 32, 0);
+                        for (int s : accept) {
+                            DL_CHECK(s >= 0 && (uint32_t)s < d->nStates, "from_table: an accepting state that is no state");
+                            d->accept[s >> 5] |= 1u << (s & 31);
+                        }
+                        const std::string bad = grammarCheck(*d);
+                        if (!bad.empty()) throw Error("from_table: " + bad);
+                        PyGrammar g;
+                        g.g = d;
+                        if (!table.is_none()) g.t = table.cast<const PyJsonTable &>().t;
+                        return g;
+                    },
+                    py::arg("class_of"), py::arg("next"), py::arg("start"), py::arg("accept"), py::arg("json_table") = py::none(),
+                    "A grammar from raw tables: class_of uint8[256], next uint16[n_states][n_classes] (0xFFFF: dead), the "
+                    "start state and the list of accepting states.")
+        .def_property_readonly("n_states", [](const PyGrammar &g) { return g.g->nStates; })
+        .def_property_readonly("n_classes", [](const PyGrammar &g) { return g.g->nClasses; })
+        .def_property_readonly("start", [](const PyGrammar &g) { return g.g->start; })
+        .def("tables",
+             [](const PyGrammar &g) {
+                 py::array_t<uint8_t> c(256);
+                 std::memcpy(c.mutable_data(), g.g->classOf, 256);
+                 py::array_t<uint16_t> n({(py::ssize_t)g.g->nStates, (py::ssize_t)g.g->nClasses});
+                 std::memcpy(n.mutable_data(), g.g->next.data(), g.g->next.size() * sizeof(uint16_t));
+                 std::vector<int> acc;
+                 for (uint32_t s = 0; s < g.g->nStates; s++)
+                     if (g.g->accepting(s)) acc.push_back((int)s);
+                 return py::make_tuple(c, n, g.g->start, acc);
+             },
+             "(class_of uint8[256], next uint16[n_states][n_classes], start, the accepting states)")
+        .def("table_bytes", [](const PyGrammar &g) { return py::bytes(g.g->tableBytes()); })
+        .def("same_object", [](const PyGrammar &a, const PyGrammar &b) { return a.g == b.g; }, py::arg("other"))
+        .def("walk",
+             [](const PyGrammar &g, py::bytes data, py::object state) -> py::object {
+                 uint32_t s = state.is_none() ? g.g->start : state.cast<uint32_t>();
+                 for (unsigned char c : std::string(data)) {
+                     s = g.g->stepByte(s, c);
+                     if (s == kGrammarDead) return py::none();
+                 }
+                 return py::int_(s);
+             },
+             py::arg("data"), py::arg("state") = py::none(),
+             "The state behind `data` from `state` (None: start); None when a byte has no transition.")
+        .def("is_accepting", [](const PyGrammar &g, uint32_t s) { return g.g->accepting(s); }, py::arg("state"))
+        .def("accepts",
+             [](const PyGrammar &g, py::bytes data) {
+                 uint32_t s = g.g->start;
+                 for (unsigned char c : std::string(data)) {
+                     s = g.g->stepByte(s, c);
+                     if (s == kGrammarDead) return false;
+                 }
+                 return g.g->accepting(s);
+             },
+             py::arg("data"))
+        .def("mask_host",
+             [](const PyGrammar &g, py::array_t<float, py::array::c_style | py::array::forcecast> logits, uint32_t state) {
+                 DL_CHECK(g.t != nullptr, "mask_host: the grammar was made without a JsonTable");
+                 py::array_t<float> out((py::ssize_t)logits.size());
+                 std::copy(logits.data(), logits.data() + logits.size(), out.mutable_data());
+                 grammarMaskHost(out.mutable_data(), (int)logits.size(), *g.t, *g.g, state);
+                 return out;
+             },
+             py::arg("logits"), py::arg("state"), "One row through grammarMaskHost.")
+        .def("advance_host",
+             [](const PyGrammar &g, uint32_t state, int token) {
+                 DL_CHECK(g.t != nullptr, "advance_host: the grammar was made without a JsonTable");
+                 return grammarAdvanceHost(*g.t, *g.g, state, token);
+             },
+             py::arg("state"), py::arg("token"));
+    m.def("schema_cache_stats", [] { return py::make_tuple(schemaCache().size(), schemaCache().hits()); },
+          "(entries, hits) of the process-wide schema cache that Grammar.from_schema(cache=True) uses");
+    py::register_exception<SchemaError>(m, "SchemaError", PyExc_ValueError);
 
     py::class_<Backend>(m, "Backend")
         .def("set_json_table", [](Backend &b, const PyJsonTable &t) { b.setJsonTable(t.t); }, py::arg("table"))

@@ -263,10 +263,11 @@ std::string InferenceSession::enableJsonMode() {
     std::vector<std::string> pieces(V);
     for (int t = 0; t < V; t++) pieces[t] = tokenizer_->piece(t);
     auto table = std::make_shared<JsonTokenTable>(makeJsonTokenTable(pieces, tokenizer_->bosId(), tokenizer_->eosTokenIds()));
-    const std::string why = jsonDeadEnd(*table);
-    if (!why.empty()) return why;
+    // structured outputs walk the same table and check dead ends per schema, so the backend gets it
+    // whether or not JSON mode itself can be served
+    grammarVocab_ = std::make_unique<GrammarVocab>(makeGrammarVocab(table->off, table->info, table->words));
     backend_->setJsonTable(table);
-    return "";
+    return jsonDeadEnd(*table);
 }
 
 InferenceSession::~InferenceSession() {

@@ -11,6 +11,7 @@
 
 #include "../net/tcp.h"
 #include "../text/tokenizer.h"
+#include "../core/schema_dfa.h"
 #include "backend.h"
 
 namespace dl {
@@ -107,8 +108,12 @@ class InferenceSession {
     void setLogprobTargets(int n, const int *targets) { backend_->setLogprobTargets(n, targets); }
     // JSON mode (LogitProc::json): builds the token table from the tokenizer, checks that the
     // vocabulary cannot dead-end (jsonDeadEnd) and hands the table to the backend. Returns an empty
-    // string, or why JSON mode is unavailable (the backend then has no table).
+    // string, or why JSON mode is unavailable. The backend gets the table either way: structured
+    // outputs (LogitProc::grammar) walk it too and check dead ends per schema.
     std::string enableJsonMode();
+    // what a schema's dead-end check needs of the vocabulary (compileSchemaDfa); null before
+    // enableJsonMode or without a tokenizer: structured outputs are unavailable
+    const GrammarVocab *grammarVocab() const { return grammarVocab_.get(); }
     // pooling of the next forwardSample / launchIds (Backend::setPooling; the root pools). When no
     // row of that forward draws, the workers get a FORWARD_EMBED instead of the FORWARD_SAMPLE.
     void setPooling(int n, const PoolSpec *pool);
@@ -134,6 +139,7 @@ class InferenceSession {
     std::unique_ptr<HostComm> hostComm_;
     std::unique_ptr<class DeviceComm> devComm_;
     std::unique_ptr<Backend> backend_;
+    std::unique_ptr<GrammarVocab> grammarVocab_;
     std::unique_ptr<Tokenizer> tokenizer_;
     std::unique_ptr<Sampler> sampler_;
     bool finished_ = false;

@@ -113,6 +113,19 @@ JsonState jsonAdvanceHost(const JsonTokenTable &table, const JsonState &state, i
     return jsonRejected(next) ? state : next;
 }
 
+void grammarMaskHost(float *x, int vocab, const JsonTokenTable &table, const GrammarDfa &dfa, u32 state) {
+    if (vocab != table.vocab()) throw Error("json_schema: the token table is not the model's vocabulary");
+    const GrammarView v = dfa.view();
+    for (int t = 0; t < vocab; t++)
+        if (grammarStepToken(v, state, table.words.data(), table.off[t], table.info[t]) == kGrammarReject) x[t] = -INFINITY;
+}
+
+u32 grammarAdvanceHost(const JsonTokenTable &table, const GrammarDfa &dfa, u32 state, int token) {
+    if (token < 0 || token >= table.vocab()) return state;
+    const u32 next = grammarStepToken(dfa.view(), state, table.words.data(), table.off[token], table.info[token]);
+    return next == kGrammarReject ? state : next;
+}
+
 std::string jsonDeadEnd(const JsonTokenTable &table) {
     bool eos = false;
     std::vector<u8> single;  // the bytes that some regular one-byte piece spells
@@ -306,6 +319,14 @@ std::vector<LogitProc> Backend::takeLogitProcs(int n) {
         if (p.topK < 0) throw Error("top_k: a count >= 0");
         if (!(p.minP >= 0.f && p.minP <= 1.f)) throw Error("min_p: a number from 0 to 1");
         if (p.json && plan().rank == 0 && !jsonTable_) throw Error("json mode: no token table (setJsonTable)");
+        if (p.grammar) {
+            if (p.json) throw Error("logit processors: a row is either in JSON mode or follows a grammar, not both");
+            if (plan().rank == 0 && !jsonTable_) throw Error("json_schema: no token table (setJsonTable)");
+            if (p.fresh) {  // (the slot keeps the grammar its fresh row brought: checked once)
+                const std::string bad = grammarCheck(*p.grammar);
+                if (!bad.empty()) throw Error("json_schema: malformed grammar tables: " + bad);
+            }
+        }
         if (!p.fresh) continue;
         if (p.bias.size() > (size_t)kMaxLogitBias) throw Error("logit_bias: at most 300 entries");
         std::vector<int> seen;
@@ -373,10 +394,21 @@ void Backend::forwardSample(int n, const int *tokens, const int *positions, cons
                 if (p.fresh) jsonStates_[s] = jsonStart();
                 jsonMaskHost(row, vocab, *jsonTable_, jsonStates_[s]);
             }
+            if (p.grammar) {  // in the JSON mask's place
+                if (grammarSlots_.size() <= s) grammarSlots_.resize(s + 1);
+                GrammarSlot &gs = grammarSlots_[s];
+                if (p.fresh) gs = GrammarSlot{p.grammar, p.grammar->start};
+                if (gs.dfa != p.grammar) throw Error("json_schema: a row that is not fresh carries another grammar than its slot's");
+                grammarMaskHost(row, vocab, *jsonTable_, *gs.dfa, gs.state);
+            }
             if (p.filter(specs[i].temperature, vocab))
                 logitFilterHost(row, vocab, p.topK, minPDelta(specs[i].temperature, p.minP));
         }
         out[i] = sampleHost(row, vocab, specs[i]);
+        if (proc && procs[i].grammar) {
+            GrammarSlot &gs = grammarSlots_[(size_t)slots[i]];
+            gs.state = grammarAdvanceHost(*jsonTable_, *gs.dfa, gs.state, out[i]);
+        }
         if (proc && out[i] >= 0 && out[i] < vocab) procCounts_[(size_t)slots[i]][out[i]]++;
         if (proc && procs[i].json) jsonStates_[(size_t)slots[i]] = jsonAdvanceHost(*jsonTable_, jsonStates_[(size_t)slots[i]], out[i]);
         if (req >= 1)

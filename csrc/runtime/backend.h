@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "../core/grammar_dfa.h"
 #include "../core/json_grammar.h"
 #include "../core/model_file.h"
 #include "../core/plan.h"
@@ -110,6 +111,12 @@ struct LogitProc {
     // bias and the candidate filter. The backend keeps the automaton's state per KV slot: a fresh
     // row restarts it, every drawn token advances it. Needs Backend::setJsonTable.
     bool json = false;
+    // Structured outputs (grammarMaskHost): the draw is confined to the tokens that keep the generated
+    // text a prefix of a document of the compiled schema; sits where the JSON mask sits and acts on
+    // every drawn row. Every row of the request carries the grammar; a fresh row installs it in its
+    // KV slot (tables and start state), every drawn token advances the slot's state. Needs
+    // Backend::setJsonTable (the token table is shared). Exclusive with `json`.
+    std::shared_ptr<const GrammarDfa> grammar;
 };
 // Host implementation (the CPU path and the reference for the device kernel); out may be logits.
 void logitProcHost(const float *logits, int vocab, const u32 *counts, float presence, float frequency,
@@ -147,6 +154,13 @@ JsonState jsonAdvanceHost(const JsonTokenTable &table, const JsonState &state, i
 // under both container kinds, some single-byte regular token must be allowed (in DONE: an EOS must
 // exist). Returns the first state without one as text, empty when the vocabulary cannot dead-end.
 std::string jsonDeadEnd(const JsonTokenTable &table);
+
+// Structured outputs (`response_format: json_schema`, csrc/core/grammar_dfa.h), over the same token
+// table. x[t] = -inf for the tokens that grammarStepToken rejects in `state`; the others pass bit
+// for bit. grammarAdvanceHost: the state behind a drawn token; a token that is not allowed, or an id
+// outside the table, leaves the state as it is.
+void grammarMaskHost(float *x, int vocab, const JsonTokenTable &table, const GrammarDfa &dfa, u32 state);
+u32 grammarAdvanceHost(const JsonTokenTable &table, const GrammarDfa &dfa, u32 state, int token);
 
 // Embeddings: the pooled, L2-normalised final hidden state of a request's prompt rows. For a request
 // whose prompt is N >= 1 rows at positions 0 .. N - 1, with x[i] row i's final residual:
@@ -287,6 +301,11 @@ class Backend {
     std::vector<std::vector<LogitBias>> procBias_;
     std::shared_ptr<const JsonTokenTable> jsonTable_;
     std::vector<JsonState> jsonStates_;  // host state of the default forwardSample, per slot
+    struct GrammarSlot {
+        std::shared_ptr<const GrammarDfa> dfa;
+        u32 state = 0;
+    };
+    std::vector<GrammarSlot> grammarSlots_;  // the same for structured outputs
     std::vector<PoolSpec> pendingPool_;  // setPooling, until the next forward takes it
     PooledSlots pooled_;
     // takes pendingPool_ for a forward of n rows (empty: none set, or no row takes part); checks the

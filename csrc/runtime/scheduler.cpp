@@ -596,6 +596,7 @@ bool Scheduler::step() {
                     lp.topK = gp.topK;
                     lp.minP = gp.minP;
                     lp.json = gp.jsonObject;
+                    lp.grammar = gp.grammar;
                 }
                 sess_.setLogitProcs(next.n, procs.data());
             }
@@ -679,6 +680,7 @@ bool Scheduler::step() {
             if (r->params.penalized()) stats_.logitProcRequests++;
             if (r->params.logitFilter()) stats_.logitFilterRequests++;
             if (r->params.jsonObject) stats_.jsonRequests++;
+            if (r->params.grammar) stats_.schemaRequests++;
             if (r->params.completion) stats_.completionRequests++;
             stats_.generatedTokens += r->generated.size();
             finishRequest(rp, reason);

@@ -49,6 +49,9 @@ struct GenParams {
     // JSON mode (response_format json_object): every drawn token keeps the generated text a prefix of
     // a JSON object (jsonMaskHost), between the bias and the candidate filter; greedy requests too
     bool jsonObject = false;
+    // structured outputs (response_format json_schema): the compiled schema every drawn token follows
+    // (grammarMaskHost), in the JSON mask's place; never set together with jsonObject
+    std::shared_ptr<const GrammarDfa> grammar;
     // POST /v1/completions: `echo` returns the prompt with the completion and makes maxTokens == 0
     // legal (the request then draws nothing: it ends with the forward that carries its last prompt
     // row, finish_reason "length"); promptLogprobs (echo && logprobs) scores the prompt too: row i of
@@ -61,7 +64,7 @@ struct GenParams {
     bool penalized() const { return presencePenalty != 0.f || frequencyPenalty != 0.f || !logitBias.empty(); }
     bool logitFilter() const { return temperature != 0.f && (topK > 0 || minP > 0.f); }
     // the request's drawn rows carry a LogitProc
-    bool logitProc() const { return penalized() || logitFilter() || jsonObject; }
+    bool logitProc() const { return penalized() || logitFilter() || jsonObject || grammar != nullptr; }
 };
 
 // One generated token's log-probability record (GenParams::logprobs).
@@ -128,6 +131,7 @@ struct SchedulerStats {
     u64 logitProcRequests = 0;  // finished requests that used penalties or a logit bias
     u64 logitFilterRequests = 0;  // finished requests with top_k or min_p on
     u64 jsonRequests = 0;         // finished requests in JSON mode
+    u64 schemaRequests = 0;       // finished requests constrained by a JSON schema
     u64 embeddingRequests = 0;  // finished embedding requests
     u64 completionRequests = 0;  // finished /v1/completions requests (one per prompt item)
     u64 scoredPromptTokens = 0;  // prompt tokens scored for them (echo with logprobs)

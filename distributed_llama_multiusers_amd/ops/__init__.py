@@ -357,6 +357,39 @@ def json_advance(temperatures, on, ids, table, states):
                                      [int(i) for i in ids], table, [[int(w) for w in s] for s in states])
 
 
+ROW_KINDS = {"none": 0, "json": 1, "grammar": 2}
+
+
+def grammar_mask(logits, temperatures, kinds, table, grammars, states, slots=None, fill=None):
+    """Device grammar token mask (launchGrammarMask) of [B, vocab] logits. `table` is the `JsonTable`
+    of the vocabulary; slot s holds `grammars[s]` (a `Grammar`, or None for an empty slot) in state
+    `states[s]`; row b is of kind `kinds[b]` ("none", "json" or "grammar") and sits in slot
+    `slots[b]` (default: b). For a grammar row with temperatures[b] >= 0 every token that is not
+    allowed in its slot's state becomes -inf; the others keep their bits. The kernel works in place
+    and neither reads nor writes any other row, a JSON-mode row included: with `fill`, those rows hold
+    `fill` instead of their logits when the kernel runs, and must hold it afterwards. Returns float32
+    [B, vocab], the buffer after the launch."""
+    x = _np(logits)
+    x = (x.reshape(1, -1) if x.ndim == 1 else x).copy()
+    temps = [float(t) for t in temperatures]
+    codes = [ROW_KINDS[k] for k in kinds]
+    slots = list(range(x.shape[0])) if slots is None else [int(s) for s in slots]
+    if fill is not None:
+        for b in range(x.shape[0]):
+            if not (codes[b] == 2 and temps[b] >= 0):
+                x[b] = fill
+    return native().ops.grammar_mask(x, temps, codes, slots, table, list(grammars), [int(s) for s in states])
+
+
+def grammar_advance(temperatures, kinds, ids, table, grammars, states, slots=None):
+    """Device grammar advance (launchGrammarAdvance): the state of slot slots[b] stepped by token
+    ids[b] for every grammar row with temperatures[b] >= 0; a token that is not allowed, an id
+    outside the vocabulary and every other row leave the state as it is. Returns the slots' states."""
+    slots = list(range(len(ids))) if slots is None else [int(s) for s in slots]
+    return native().ops.grammar_advance([float(t) for t in temperatures], [ROW_KINDS[k] for k in kinds], slots,
+                                        [int(i) for i in ids], table, list(grammars), [int(s) for s in states])
+
+
 def argmax(logits) -> list:
     x = _np(logits)
     return native().ops.argmax(x, x.shape[0] if x.ndim == 2 else 1)

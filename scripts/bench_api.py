@@ -6,7 +6,7 @@ connection per request), and reports the aggregate completion tokens/s for tempe
 and temperature 0.8 / top_p 0.9 with per-request seeds (device sampling: only token ids come back
 to the host). One untimed round first captures the graphs.
 
-  python scripts/bench_api.py [--n 64] [--max-tokens 64] [--port 0] [--logprobs K] [--penalties] [--filters] [--json]
+  python scripts/bench_api.py [--n 64] [--max-tokens 64] [--port 0] [--logprobs K] [--penalties] [--filters] [--json] [--schema]
                               [--embeddings] [--score]
 
 --embeddings: after the chat rounds, one /v1/embeddings request of N inputs of token ids (about 48
@@ -96,7 +96,7 @@ def _completions_round(port, n, score, tokens_each=48):
     return sum(out), dt
 
 
-EXTRA = {}  # request fields added to every body (--logprobs, --penalties, --filters, --json)
+EXTRA = {}  # request fields added to every body (--logprobs, --penalties, --filters, --json, --schema)
 
 
 def _round(port, n, max_tokens, temperature, seed0):
@@ -138,6 +138,9 @@ def main():
                          "(temperature 0.8), the greedy round ignores them")
     ap.add_argument("--json", action="store_true",
                     help="every request sends response_format json_object (JSON mode: both rounds are masked)")
+    ap.add_argument("--schema", action="store_true",
+                    help="every request sends response_format json_schema with a small object schema (structured "
+                         "outputs: both rounds are masked by the compiled grammar)")
     ap.add_argument("--embeddings", action="store_true",
                     help="also time one /v1/embeddings request of --n inputs, alone and next to a greedy chat round")
     ap.add_argument("--score", action="store_true",
@@ -148,6 +151,11 @@ def main():
         EXTRA.update(top_k=40, min_p=0.05)
     if args.json:
         EXTRA.update(response_format={"type": "json_object"})
+    if args.schema:
+        props = {"name": {"type": "string"}, "age": {"type": "integer"}, "tags": {"type": "array", "items": {"type": "string"}, "maxItems": 8},
+                 "role": {"enum": ["admin", "user", "guest"]}, "active": {"type": "boolean"}}
+        EXTRA.update(response_format={"type": "json_schema", "json_schema": {"name": "person", "strict": True, "schema": {
+            "type": "object", "properties": props, "required": list(props), "additionalProperties": False}}})
     if args.penalties:
         EXTRA.update(frequency_penalty=0.5, presence_penalty=0.5, logit_bias={str(1000 + 37 * i): (i % 5) - 2 for i in range(16)})
     if args.logprobs >= 0:
@@ -204,6 +212,7 @@ def main():
         res["penalties"] = bool(args.penalties)
         res["filters"] = bool(args.filters)
         res["json"] = bool(args.json)
+        res["schema"] = bool(args.schema)
         if args.embeddings:
             _embed_round(port, args.n)  # untimed: graph capture
             toks, dt = _embed_round(port, args.n)
