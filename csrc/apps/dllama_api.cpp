@@ -2,12 +2,16 @@
 // (reference: src/dllama-api.cpp:250-410, src/api-types.hpp).
 //
 //   POST /v1/chat/completions  {"messages":[...], "max_tokens", "temperature", "top_p", "seed",
-//                               "stop", "stream", "logprobs", "top_logprobs"}
+//                               "stop", "stream", "logprobs", "top_logprobs", "n"}
 //        -> {"generated_text": ...} (the reference/web-ui shape) plus the OpenAI
 //           {"id","object","created","model","choices":[...],"usage":{...}} fields;
 //           "stream": true -> server-sent events with chat.completion.chunk objects + [DONE]
 //           "logprobs": true (+ "top_logprobs": 0..20) -> choices[0].logprobs.content, one entry
 //           per generated token: log_softmax of the raw logits, whatever temperature / top_p
+//           "n": 1..--slots -> that many choices over one prompt, choice i drawn with seed + i; the
+//           prompt is prefilled once and its KV forked to the siblings (Scheduler::submitGroup);
+//           usage counts the prompt once and sums the completions; streamed chunks carry their
+//           choice's index, each index ends with its own finish_reason chunk, one [DONE] closes all
 //   POST /v1/completions       {"prompt": <string | [strings] | [token ids] | [[token ids]]>, "max_tokens",
 //                               "echo", "logprobs": null | 0..20, and the sampling fields of the chat endpoint}
 //        -> {"object":"text_completion","choices":[{"text","index","logprobs","finish_reason"}...],"usage"};
@@ -252,6 +256,7 @@ struct Api {
         }
         GenParams p;
         bool stream = false;
+        int choices = 1;  // "n"
         {
             const std::string shared = sharedParams(body, p, stream);
             const Value &lp = body["logprobs"], &top = body["top_logprobs"];
@@ -268,6 +273,13 @@ struct Api {
                     p.topLogprobs = (int)top.asNumber();
             }
             if (bad.empty()) bad = shared;  // (reported in the order they always were)
+            const Value &nv = body["n"];
+            if (bad.empty() && !nv.isNull()) {
+                if (!nv.isNumber() || nv.asNumber() != std::floor(nv.asNumber()) || nv.asNumber() < 1 || nv.asNumber() > sess->nSlots())
+                    bad = "n must be an integer from 1 to the number of KV slots (--slots " + std::to_string(sess->nSlots()) + ")";
+                else
+                    choices = (int)nv.asNumber();
+            }
             if (!bad.empty()) {
                 Value err = Value::object();
                 err.set("error", "Invalid request: " + bad);
@@ -282,6 +294,10 @@ struct Api {
             Value err = Value::object();
             err.set("error", std::string("Invalid messages: ") + e.what());
             conn.writeJson(400, err.dump());
+            return;
+        }
+        if (choices > 1) {
+            completeGroup(conn, std::move(prompt), p, choices, stream);
             return;
         }
         const int promptTokens = (int)prompt.size();
@@ -365,6 +381,123 @@ struct Api {
         if (logLevel() >= 1) {
             std::printf("🔶 %s: %d prompt + %d completion tokens (%s)\n", id.c_str(), promptTokens, r->completionTokens,
                         r->finishReason.c_str());
+            std::fflush(stdout);
+        }
+    }
+
+    // "n" > 1: the choices are the members of one scheduler group (one prefill, the prompt's KV forked
+    // to the siblings); member i draws with seed p.seed + i and answers as choice i.
+    void completeGroup(HttpConnection &conn, std::vector<int> prompt, const GenParams &p, int n, bool stream) {
+        const int promptTokens = (int)prompt.size();
+        std::vector<std::shared_ptr<GenRequest>> reqs = sched->submitGroup(std::move(prompt), p, n);
+        struct CancelOnExit {  // the client went away, or one choice failed: drop every member
+            std::vector<std::shared_ptr<GenRequest>> &rs;
+            ~CancelOnExit() {
+                for (auto &r : rs) r->cancel();
+            }
+        } cancelGuard{reqs};
+        const std::string id = "chatcmpl-" + std::to_string(reqs[0]->id);
+        const long created = (long)std::time(nullptr);
+        auto envelope = [&](const char *object) {
+            Value v = Value::object();
+            v.set("id", id);
+            v.set("object", object);
+            v.set("created", created);
+            v.set("model", model);
+            return v;
+        };
+        if (stream) {
+            conn.beginSse();
+            std::vector<size_t> lpSent(n, 0);
+            std::vector<char> started(n, 0), closed(n, 0);
+            GroupSignal &sig = *reqs[0]->signal;
+            int open = n;
+            while (open > 0) {
+                u64 seen;
+                {
+                    std::lock_guard<std::mutex> lk(sig.mu);
+                    seen = sig.events;
+                }
+                for (int i = 0; i < n; i++) {
+                    if (closed[i]) continue;
+                    GenRequest &r = *reqs[i];
+                    std::string d;
+                    bool ended = false;
+                    while (r.tryNextDelta(d, ended)) {
+                        Value chunk = envelope("chat.completion.chunk");
+                        Value ch = Value::object();
+                        ch.set("index", i);
+                        Value delta = Value::object();
+                        if (!started[i]) delta.set("role", "assistant");
+                        delta.set("content", d);
+                        ch.set("delta", delta);
+                        ch.set("logprobs", p.logprobs ? logprobsJson(r, lpSent[i]) : Value());
+                        ch.set("finish_reason", Value());
+                        chunk.set("choices", Value::array()).push(ch);
+                        conn.writeSse(chunk.dump());
+                        started[i] = 1;
+                    }
+                    if (!ended) continue;
+                    Value chunk = envelope("chat.completion.chunk");
+                    Value ch = Value::object();
+                    ch.set("index", i);
+                    Value delta = Value::object();
+                    if (!started[i]) delta.set("role", "assistant");  // (a choice that produced no text)
+                    ch.set("delta", delta);
+                    ch.set("logprobs", p.logprobs ? logprobsJson(r, lpSent[i]) : Value());  // the records not sent yet
+                    ch.set("finish_reason", r.finishReason);
+                    chunk.set("choices", Value::array()).push(ch);
+                    conn.writeSse(chunk.dump());
+                    closed[i] = 1;
+                    open--;
+                }
+                if (open > 0) {
+                    std::unique_lock<std::mutex> lk(sig.mu);
+                    sig.cv.wait(lk, [&] { return sig.events != seen; });
+                }
+            }
+            conn.writeSse("[DONE]");
+            return;
+        }
+        Value choices = Value::array();
+        int completionTokens = 0;
+        std::string first;
+        for (int i = 0; i < n; i++) {
+            GenRequest &r = *reqs[i];
+            const std::string text = r.wait();
+            if (r.finishReason == "error") {
+                Value err = Value::object();
+                err.set("error", r.error.empty() ? "generation failed" : r.error);
+                conn.writeJson(500, err.dump());
+                return;
+            }
+            if (i == 0) first = text;
+            size_t lpSent = 0;
+            Value choice = Value::object();
+            choice.set("index", i);
+            Value msg = Value::object();
+            msg.set("role", "assistant");
+            msg.set("content", text);
+            choice.set("message", msg);
+            choice.set("logprobs", p.logprobs ? logprobsJson(r, lpSent) : Value());
+            choice.set("finish_reason", r.finishReason);
+            choices.push(choice);
+            completionTokens += r.completionTokens;
+        }
+        Value resp = envelope("chat.completion");
+        resp.set("choices", choices);
+        Value usage = Value::object();
+        usage.set("prompt_tokens", promptTokens);  // the prompt counts once, the completions add up
+        usage.set("completion_tokens", completionTokens);
+        usage.set("total_tokens", promptTokens + completionTokens);
+        Value details = Value::object();
+        details.set("cached_tokens", reqs[0]->cachedTokens);  // the leader's: forked siblings are no cache hits
+        usage.set("prompt_tokens_details", details);
+        resp.set("usage", usage);
+        resp.set("generated_text", first);  // choice 0, as the web UI reads it
+        conn.writeJson(200, resp.dump());
+        if (logLevel() >= 1) {
+            std::printf("🔶 %s: %d choices, %d prompt + %d completion tokens\n", id.c_str(), n, promptTokens, completionTokens);
             std::fflush(stdout);
         }
     }
@@ -774,6 +907,11 @@ struct Api {
                (double)s.prefixCopies);
         metric("dllama_prefix_evictions_total", "counter", "Idle slots evicted to free KV pages.",
                (double)s.prefixEvictions);
+        metric("dllama_fork_groups_total", "counter", "Request groups (n > 1) whose siblings were forked from one prefill.",
+               (double)s.forkGroups);
+        metric("dllama_forked_requests_total", "counter", "Sibling requests that started behind a forked prompt KV.",
+               (double)s.forkedRequests);
+        metric("dllama_fork_tokens_total", "counter", "Prompt tokens the forked siblings did not prefill.", (double)s.forkTokens);
         metric("dllama_logit_proc_requests_total", "counter", "Finished requests that used penalties or a logit bias.",
                (double)s.logitProcRequests);
         metric("dllama_logit_filter_requests_total", "counter", "Finished requests with top_k or min_p on.",
@@ -815,6 +953,9 @@ struct Api {
         v.set("prefix_tokens", (double)s.prefixTokens);
         v.set("prefix_copies", (double)s.prefixCopies);
         v.set("prefix_evictions", (double)s.prefixEvictions);
+        v.set("fork_groups", (double)s.forkGroups);
+        v.set("forked_requests", (double)s.forkedRequests);
+        v.set("fork_tokens", (double)s.forkTokens);
         v.set("logit_proc_requests", (double)s.logitProcRequests);
         v.set("logit_filter_requests", (double)s.logitFilterRequests);
         v.set("json_requests", (double)s.jsonRequests);
@@ -861,6 +1002,7 @@ void usage() {
                  "        [--nthreads <n>] [--gpu-index <i>]\n"
                  "        [--workers <ip:port> ...]\n"
                  "        [--temperature <temp>] [--topp <t>] [--seed <s>] [--chat-template <t>]\n"
+                 "        (chat requests may ask for \"n\": 1..slots choices: one prefill, forked to the siblings)\n"
                  "        [--web-ui <dir>] [--metrics <file|->]\n");
 }
 

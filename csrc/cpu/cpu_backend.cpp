@@ -147,6 +147,7 @@ class CpuBackend : public Backend {
     const ModelHeader &header() const override { return h_; }
     const ShardPlan &plan() const override { return plan_; }
     std::string name() const override { return "cpu"; }
+    int kvSlots() const override { return (int)cfg_.nSlots; }
 
     void forward(int n, const int *tokens, const int *positions, const int *slots, float *logits) override {
         std::vector<float> full;

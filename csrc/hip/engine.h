@@ -57,6 +57,7 @@ class HipEngine : public Backend {
 // comm may be null (single GPU). The engine does not own comm.
 std::unique_ptr<HipEngine> makeHipEngine(const EngineConfig &cfg, DeviceComm *comm);
 int hipDeviceCount();
+int hipMaxForkDst();  // destinations per fork launch (hipk::kMaxForkDst): a forkPrefix of more takes several
 
 // Micro-benchmark of one Q40 GEMV configuration: `copies` weight matrices (to defeat the 256 MB
 // infinity cache) are cycled through a graph of `iters` launches. Returns microseconds per launch.

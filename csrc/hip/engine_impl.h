@@ -66,6 +66,7 @@ class HipEngineImpl : public HipEngine {
     const ModelHeader &header() const override { return h_; }
     const ShardPlan &plan() const override { return plan_; }
     std::string name() const override { return "hip"; }
+    int kvSlots() const override { return (int)cfg_.nSlots; }
     LoadStats loadStats() const override { return load_; }
     void forward(int n, const int *tokens, const int *positions, const int *slots, float *logits) override;
     void forwardArgmax(int n, const int *tokens, const int *positions, const int *slots, int *out) override;
@@ -82,6 +83,7 @@ class HipEngineImpl : public HipEngine {
     int kvPageSize() const override { return paged() ? (int)cfg_.kvPageSize : 0; }
     void releaseSlot(int slot) override;
     void copyPrefix(int src, int dst, int n) override;
+    void forkPrefix(int src, const int *dsts, int m, int n) override;
 
     // HipEngine
     double decodeGreedy(int steps, int token, int pos, int slot, int *outTokens) override {

@@ -147,5 +147,63 @@ void HipEngineImpl::copyPrefix(int src, int dst, int n) {
     hipk::launchKvCopyPrefix(a, stream_);
 }
 
+// forkPrefix(src, dsts, m, n): copyPrefix(src, dsts[i], n) for every i, the source read once per
+// launch of up to hipk::kMaxForkDst destinations (hipk::launchKvForkPrefix). Paged: every
+// destination gives its pages back and maps ceil(n / pageSize) fresh ones; the pool is checked for
+// all m before any destination is touched, so a refusal leaves every slot as it was. One table upload,
+// then ceil(m / kMaxForkDst) launches.
+void HipEngineImpl::forkPrefix(int src, const int *dsts, int m, int n) {
+    DL_CHECK(m >= 1 && dsts != nullptr, "forkPrefix: no destination slot");
+    DL_CHECK(src >= 0 && (u32)src < cfg_.nSlots, "forkPrefix: slot out of range");
+    for (int i = 0; i < m; i++) {
+        DL_CHECK(dsts[i] >= 0 && (u32)dsts[i] < cfg_.nSlots, "forkPrefix: slot out of range");
+        DL_CHECK(dsts[i] != src, "forkPrefix: source and destination slot are the same");
+        for (int j = 0; j < i; j++) DL_CHECK(dsts[i] != dsts[j], "forkPrefix: a destination slot is named twice");
+    }
+    DL_CHECK(n >= 1 && (u32)n < h_.seqLen, "forkPrefix: prefix length out of range");
+    DL_CHECK(pendingN_ == 0, "forkPrefix: a launchIds forward was not collected");
+    DL_CHECK(chainInFlight() == 0, "forkPrefix: a chained decode step is still in flight");
+    if (paged()) {
+        DL_CHECK(n <= slotPages_[src] << pageShift_, "forkPrefix: the source slot never reached that position");
+        const int need = (n + (int)cfg_.kvPageSize - 1) >> pageShift_;
+        size_t avail = freePages_.size();
+        for (int i = 0; i < m; i++) avail += (size_t)slotPages_[dsts[i]];
+        if ((size_t)need * (size_t)m > avail)
+            throw Error("KV page pool exhausted: " + std::to_string(cfg_.kvPages) + " pages of " +
+                        std::to_string(cfg_.kvPageSize) + " positions cannot hold " + std::to_string(m) +
+                        " prefix copies of " + std::to_string(n) + " positions; raise --kv-pages or lower the concurrent context");
+        for (int i = 0; i < m; i++) releaseSlot(dsts[i]);
+        for (int i = 0; i < m; i++) {
+            const int dst = dsts[i];
+            while (slotPages_[dst] < need) {
+                hostTable_[(size_t)dst * pagesPerSlot_ + slotPages_[dst]++] = freePages_.back();
+                freePages_.pop_back();
+            }
+        }
+        tableDirty_ = false;
+        uploadTable();
+        inputsInFlight_ = true;  // the upload reads pinned staging: the next one waits for it
+    }
+    hipk::KvForkArgs a;
+    a.bases = dKvBases_;
+    a.kvMap = kvMap();
+    a.nLayers = (int)h_.nLayers;
+    a.nKv = (int)(plan_.kv0 / plan_.headSize);
+    a.hs = (int)plan_.headSize;
+    a.seqLen = (int)h_.seqLen;
+    a.elemBytes = kvBf16_ ? 2 : 4;
+    a.srcSlot = src;
+    a.n = n;
+    a.chunkPos = hipk::kvCopyChunkPos(a.hs, a.elemBytes, paged() ? pageShift_ : 0);
+    for (int i0 = 0; i0 < m; i0 += hipk::kMaxForkDst) {
+        a.nDst = std::min(hipk::kMaxForkDst, m - i0);
+        for (int d = 0; d < hipk::kMaxForkDst; d++) a.dstSlots[d] = dsts[i0 + (d < a.nDst ? d : 0)];
+        hipk::launchKvForkPrefix(a, stream_);
+    }
+}
+
 }  // namespace engine_detail
+
+int hipMaxForkDst() { return hipk::kMaxForkDst; }
+
 }  // namespace dl

@@ -114,6 +114,21 @@ struct KvCopyArgs {
 int kvCopyChunkPos(int hs, int elemBytes, int pageShift);
 void launchKvCopyPrefix(const KvCopyArgs &a, hipStream_t s);
 
+// One-to-many prefix copy (kv_fork.hip): positions [0, n) of srcSlot to each of dstSlots[0 .. nDst),
+// the source read once per launch. The fields and the geometry are KvCopyArgs'; the destinations are
+// distinct, none is the source, and all have their pages mapped.
+constexpr int kMaxForkDst = 8;  // destinations per launch
+struct KvForkArgs {
+    void *const *bases = nullptr;  // as KvCopyArgs
+    KvMap kvMap;
+    int nLayers = 0, nKv = 0, hs = 0, seqLen = 0, elemBytes = 0;
+    int srcSlot = 0, n = 0;
+    int dstSlots[kMaxForkDst] = {};
+    int nDst = 0;
+    int chunkPos = 0;  // kvCopyChunkPos
+};
+void launchKvForkPrefix(const KvForkArgs &a, hipStream_t s);
+
 struct AttnArgs {
     const float *q = nullptr;   // [B][ldq], rotated queries
     int ldq = 0;

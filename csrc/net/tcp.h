@@ -94,7 +94,7 @@ void exchangeAll(const std::vector<Socket *> &peers, const void *send, u64 n, co
 // ---- control protocol ------------------------------------------------------------------------
 constexpr u32 kProtoMagic = 0xD11A3355;  // "dllama MI355"
 constexpr u32 kMeshMagic = 0xD11A3356;   // worker -> worker data-plane connection
-constexpr u32 kProtoVersion = 3;         // 2: Cmd::COPY_PREFIX, 3: Cmd::FORWARD_EMBED (an older worker would ignore them)
+constexpr u32 kProtoVersion = 4;         // 2: Cmd::COPY_PREFIX, 3: Cmd::FORWARD_EMBED, 4: Cmd::FORK_PREFIX (an older worker would ignore them)
 constexpr u32 kAck = 23571114;           // same ACK value as the reference (nn-network.cpp:23)
 
 // RELEASE: the first n ints of the payload are KV slots whose sequences ended (paged KV cache:
@@ -104,6 +104,9 @@ constexpr u32 kAck = 23571114;           // same ACK value as the reference (nn-
 // before any other command.
 // COPY_PREFIX: a control-only command like RELEASE (Backend::copyPrefix on every rank), n = 1:
 // tokens[0] = source slot, positions[0] = positions to copy, slots[0] = destination slot.
+// FORK_PREFIX: COPY_PREFIX to n destinations (Backend::forkPrefix on every rank, so every rank does the
+// same launches): tokens[0] = source slot, positions[0] = positions to copy, slots[0 .. n) = the
+// destination slots; the other entries of tokens and positions are zero.
 // FORWARD_EMBED: an all-embedding forward (Backend::forwardEmbed): the row arrays like FORWARD_ARGMAX,
 // nothing behind them. Every rank runs the layers and skips wcls and the logits exchange; the root
 // pools. A forward that mixes pooled rows with drawn ones goes out as the FORWARD_SAMPLE it is.
@@ -116,7 +119,8 @@ enum class Cmd : u32 {
     RELEASE = 6,
     CHAIN = 7,
     COPY_PREFIX = 8,
-    FORWARD_EMBED = 9
+    FORWARD_EMBED = 9,
+    FORK_PREFIX = 10
 };
 
 struct ControlHeader {

@@ -306,6 +306,7 @@ struct PyComputeOnlyComm : PyComm {};
 struct PyHipEngine {
     std::shared_ptr<DeviceComm> comm;
     std::unique_ptr<HipEngine> engine;
+    int launched = 0;  // rows of the launch_ids forward not collected yet
 };
 
 
@@ -915,6 +916,7 @@ PYBIND11_MODULE(_C, m) {
     bindOps(m);
     m.def("set_log_level", &setLogLevel);
     m.def("hip_device_count", &hipDeviceCount);
+    m.def("hip_max_fork_dst", &hipMaxForkDst);
 
     m.def("f32_to_f16", &f32ToF16);
     m.def("f16_to_f32", &f16ToF32);
@@ -1338,7 +1340,10 @@ PYBIND11_MODULE(_C, m) {
             ForwardStats s = b.lastStats();
             return py::make_tuple(s.computeMs, s.syncMs, s.sentBytes, s.recvBytes, s.xchgMs);
         })
-        .def("copy_prefix", &Backend::copyPrefix, py::arg("src"), py::arg("dst"), py::arg("n"));
+        .def("copy_prefix", &Backend::copyPrefix, py::arg("src"), py::arg("dst"), py::arg("n"))
+        .def("fork_prefix",
+             [](Backend &b, int src, const std::vector<int> &dsts, int n) { b.forkPrefix(src, dsts.data(), (int)dsts.size(), n); },
+             py::arg("src"), py::arg("dsts"), py::arg("n"));
 
     m.def("cpu_backend",
           [](const std::string &model, const std::string &bufferType, int nThreads, u32 maxSeqLen, u32 maxBatch,
@@ -1744,6 +1749,25 @@ PYBIND11_MODULE(_C, m) {
              py::arg("pooling") = py::none())
         .def("copy_prefix", [](PyHipEngine &e, int src, int dst, int n) { e.engine->copyPrefix(src, dst, n); },
              py::arg("src"), py::arg("dst"), py::arg("n"))
+        .def("fork_prefix",
+             [](PyHipEngine &e, int src, const std::vector<int> &dsts, int n) {
+                 e.engine->forkPrefix(src, dsts.data(), (int)dsts.size(), n);
+             },
+             py::arg("src"), py::arg("dsts"), py::arg("n"))
+        // a greedy forward launched and left in flight until collect_ids (Backend::launchIds / collectIds)
+        .def("launch_ids",
+             [](PyHipEngine &e, const std::vector<int> &t, const std::vector<int> &p, const std::vector<int> &s) {
+                 DL_CHECK(t.size() == p.size() && t.size() == s.size() && !t.empty(), "launch_ids: one position and slot per token");
+                 e.engine->launchIds((int)t.size(), t.data(), p.data(), s.data(), nullptr);
+                 e.launched = (int)t.size();
+             },
+             py::arg("tokens"), py::arg("positions"), py::arg("slots"))
+        .def("collect_ids", [](PyHipEngine &e) {
+            std::vector<int> ids((size_t)e.launched);
+            e.engine->collectIds(ids.data());
+            e.launched = 0;
+            return ids;
+        })
         .def("synchronize", [](PyHipEngine &e) { e.engine->synchronize(); });
 
 }

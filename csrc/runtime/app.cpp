@@ -299,6 +299,15 @@ void InferenceSession::copyPrefix(int src, int dst, int n) {
     backend_->copyPrefix(src, dst, n);
 }
 
+void InferenceSession::forkPrefix(int src, const int *dsts, int m, int n) {
+    DL_CHECK(m >= 1, "forkPrefix: no destination slot");
+    std::vector<int> srcs(m, 0), lens(m, 0);
+    srcs[0] = src;
+    lens[0] = n;
+    sendControl(Cmd::FORK_PREFIX, m, srcs.data(), lens.data(), dsts);
+    backend_->forkPrefix(src, dsts, m, n);
+}
+
 void InferenceSession::forward(int n, const int *tokens, const int *positions, const int *slots, float *logits) {
     TraceRange tr("dllama.forward");
     Timer t;
@@ -546,6 +555,8 @@ void runWorker(const AppArgs &args) {
                     for (int i = 0; i < n; i++) backend->releaseSlot(buf[i]);
                 } else if (cmd == Cmd::COPY_PREFIX) {
                     backend->copyPrefix(buf[0], buf[2 * n], buf[n]);
+                } else if (cmd == Cmd::FORK_PREFIX) {
+                    backend->forkPrefix(buf[0], &buf[2 * n], n, buf[n]);
                 } else if (cmd == Cmd::FORWARD_EMBED) {
                     backend->forwardEmbed(n, &buf[0], &buf[n], &buf[2 * n]);
                 } else if (cmd == Cmd::FORWARD_SAMPLE) {

@@ -84,6 +84,8 @@ class InferenceSession {
     // KV positions [0, n) of slot src copied to slot dst on every rank (Backend::copyPrefix; each
     // rank copies its own heads, nothing crosses the data plane)
     void copyPrefix(int src, int dst, int n);
+    // the same to m destination slots at once (Backend::forkPrefix; a FORK_PREFIX to every worker)
+    void forkPrefix(int src, const int *dsts, int m, int n);
     const AppArgs &args() const { return args_; }
     bool isGpu() const { return gpu_; }
     int nNodes() const { return 1 + (int)workers_.size(); }

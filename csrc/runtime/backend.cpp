@@ -446,4 +446,17 @@ void Backend::chainLaunch(int, int, int) { throw Error(name() + " backend: no ch
 int Backend::chainCollect() { throw Error(name() + " backend: no chained decode"); }
 void Backend::copyPrefix(int, int, int) { throw Error(name() + " backend: prefix copy not supported"); }
 
+void Backend::forkPrefix(int src, const int *dsts, int m, int n) {
+    const int nSlots = kvSlots();  // every check before the first copy
+    DL_CHECK(m >= 1 && dsts != nullptr, "forkPrefix: no destination slot");
+    DL_CHECK(src >= 0 && src < nSlots, "forkPrefix: slot out of range");
+    for (int i = 0; i < m; i++) {
+        DL_CHECK(dsts[i] >= 0 && dsts[i] < nSlots, "forkPrefix: slot out of range");
+        DL_CHECK(dsts[i] != src, "forkPrefix: source and destination slot are the same");
+        for (int j = 0; j < i; j++) DL_CHECK(dsts[i] != dsts[j], "forkPrefix: a destination slot is named twice");
+    }
+    DL_CHECK(n >= 1 && (u32)n < header().seqLen, "forkPrefix: prefix length out of range");
+    for (int i = 0; i < m; i++) copyPrefix(src, dsts[i], n);
+}
+
 }  // namespace dl

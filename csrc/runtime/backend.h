@@ -276,6 +276,12 @@ class Backend {
     // seqLen, src != dst, no forward launched and not collected. The copy is ordered after the
     // forwards already issued and before the next one. Default: not supported.
     virtual void copyPrefix(int src, int dst, int n);
+    // Parallel sampling (Scheduler::submitGroup): copyPrefix(src, dsts[i], n) for every i < m, ordered
+    // like copyPrefix. m >= 1, every dst in range, distinct and != src, 1 <= n < seqLen. Default: a
+    // loop over copyPrefix (a backend without it throws); the HIP engine reads the source once per
+    // launch and, paged, checks the pool for all m destinations before it touches any.
+    virtual void forkPrefix(int src, const int *dsts, int m, int n);
+    virtual int kvSlots() const = 0;  // EngineConfig::nSlots
     virtual std::string name() const = 0;
 
     // Host backends, for the default pooling: the forward with the rows' final residual (before the

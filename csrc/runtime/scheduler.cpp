@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <limits>
 
 namespace dl {
 
@@ -22,6 +23,25 @@ bool GenRequest::nextDelta(std::string &out) {
     return false;
 }
 
+bool GenRequest::tryNextDelta(std::string &out, bool &ended) {
+    std::lock_guard<std::mutex> lk(mu);
+    ended = false;
+    if (!deltas.empty()) {
+        out = std::move(deltas.front());
+        deltas.pop_front();
+        return true;
+    }
+    ended = done;
+    return false;
+}
+
+void GenRequest::signalGroup() {
+    if (!signal) return;
+    std::lock_guard<std::mutex> lk(signal->mu);
+    signal->events++;
+    signal->cv.notify_all();
+}
+
 void GenRequest::waitPromptLogprobs() {
     std::unique_lock<std::mutex> lk(mu);
     cv.wait(lk, [&] { return done || promptLogprobs.size() >= prompt.size(); });
@@ -29,17 +49,23 @@ void GenRequest::waitPromptLogprobs() {
 
 void GenRequest::emit(const std::string &d) {
     if (d.empty()) return;
-    std::lock_guard<std::mutex> lk(mu);
-    text += d;
-    deltas.push_back(d);
-    cv.notify_all();
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        text += d;
+        deltas.push_back(d);
+        cv.notify_all();
+    }
+    signalGroup();
 }
 
 void GenRequest::finish(const std::string &reason) {
-    std::lock_guard<std::mutex> lk(mu);
-    finishReason = reason;
-    done = true;
-    cv.notify_all();
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        finishReason = reason;
+        done = true;
+        cv.notify_all();
+    }
+    signalGroup();
 }
 
 Scheduler::Scheduler(InferenceSession &sess) : sess_(sess), tok_(sess.tokenizer()) {
@@ -68,6 +94,8 @@ void Scheduler::stop() {
     // fail anything still pending
     for (auto &r : queue_) r->finish("error");
     for (auto &r : active_) r->finish("error");
+    for (auto &g : groups_)
+        for (auto &r : g->waiting) r->finish("error");
 }
 
 std::shared_ptr<GenRequest> Scheduler::submit(std::vector<int> prompt, const GenParams &params) {
@@ -88,10 +116,51 @@ std::shared_ptr<GenRequest> Scheduler::submit(std::vector<int> prompt, const Gen
     return r;
 }
 
+std::vector<std::shared_ptr<GenRequest>> Scheduler::submitGroup(std::vector<int> prompt, const GenParams &params,
+                                                                int count) {
+    DL_CHECK(count >= 1, "submitGroup: a group has at least one member");
+    std::vector<std::shared_ptr<GenRequest>> members;
+    auto signal = count > 1 ? std::make_shared<GroupSignal>() : nullptr;
+    for (int i = 0; i < count; i++) {
+        auto r = std::make_shared<GenRequest>();
+        r->signal = signal;
+        r->prompt = prompt;
+        r->params = params;
+        r->params.seed = params.seed + (u64)i;
+        members.push_back(r);
+    }
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        for (auto &r : members) r->id = nextId_++;
+        if (stop_) {
+            for (auto &r : members) {
+                r->error = "scheduler stopped";
+                r->finish("error");
+            }
+            return members;
+        }
+        queue_.push_back(members[0]);
+        // nothing to fork from a one-token prompt, nor for requests that need every prompt row
+        // themselves (embeddings, prompt scores: they take no prefix hit either)
+        const bool fork = count > 1 && prompt.size() > 1 && params.embed == EmbedMode::OFF && !params.promptLogprobs;
+        if (fork) {
+            auto g = std::make_shared<Group>();
+            g->members = members;
+            g->waiting.assign(members.begin() + 1, members.end());
+            groups_.push_back(g);
+        } else {
+            for (int i = 1; i < count; i++) queue_.push_back(members[i]);
+        }
+    }
+    cv_.notify_all();
+    return members;
+}
+
 SchedulerStats Scheduler::stats() {
     std::lock_guard<std::mutex> lk(mu_);
     SchedulerStats s = stats_;
     s.queued = (int)queue_.size();
+    for (auto &g : groups_) s.queued += (int)g->waiting.size();
     return s;
 }
 
@@ -99,7 +168,7 @@ void Scheduler::loop() {
     while (true) {
         {
             std::unique_lock<std::mutex> lk(mu_);
-            cv_.wait(lk, [&] { return stop_ || !queue_.empty() || !active_.empty() || inflight_; });
+            cv_.wait(lk, [&] { return stop_ || !queue_.empty() || !active_.empty() || inflight_ || !groups_.empty(); });
             if (stop_) break;
         }
         try {
@@ -185,6 +254,12 @@ void Scheduler::failAll(const std::string &what) {
         for (auto &r : draining_) returnSlot(r->slot);
         active_.clear();
         draining_.clear();
+        for (auto &g : groups_)  // followers that waited for a fork from the failed members
+            for (auto &r : g->waiting) {
+                r->error = what;
+                r->finish("error");
+            }
+        groups_.clear();
         if (prefixOn_) {  // the device state is unknown after a failed forward: forget every record
             for (auto &rec : resident_) rec.clear();
             std::vector<int> keep;
@@ -395,6 +470,131 @@ bool Scheduler::admitWithPrefix() {
     return true;
 }
 
+// ---------------------------------------------------------------- request groups (submitGroup)
+GenRequest *Scheduler::forkSource(const Group &g) const {
+    for (auto &m : g.members)
+        if (m->slot >= 0 && !m->finished && m->prefilled + 1 >= m->prompt.size()) return m.get();
+    return nullptr;
+}
+
+// Under mu_. The followers that could join now, slots permitting. Cancelled followers are dropped; a
+// group whose members have all ended (none active, the leader no longer queued) hands its followers
+// to the queue as ordinary requests.
+int Scheduler::readyFollowers() {
+    int ready = 0;
+    for (size_t gi = 0; gi < groups_.size();) {
+        Group &g = *groups_[gi];
+        for (auto it = g.waiting.begin(); it != g.waiting.end();) {
+            if ((*it)->isCancelled()) {
+                (*it)->finish("cancelled");
+                stats_.cancelled++;
+                it = g.waiting.erase(it);
+            } else {
+                ++it;
+            }
+        }
+        bool alive = false;
+        for (auto &m : g.members)
+            alive = alive || (m->slot >= 0 ? !m->finished : std::find(queue_.begin(), queue_.end(), m) != queue_.end());
+        if (!alive)
+            for (auto &r : g.waiting) queue_.push_back(r);
+        if (!alive || g.waiting.empty()) {
+            groups_.erase(groups_.begin() + gi);
+            continue;
+        }
+        if (forkSource(g)) ready += (int)g.waiting.size();
+        gi++;
+    }
+    return ready;
+}
+
+// Scheduler thread, between the collection of a forward and the next launch, after the queue's
+// admission. Every waiting follower of a group with a fork source takes an idle slot (the least
+// recently used one under --prefix-cache, its record dropped, as a copyPrefix target's is) while
+// slots and, paged, unreserved pages last; idle slots are evicted for pages in LRU order as in
+// admitWithPrefix. One forkPrefix per group serves all that joined. Decided under mu_, the device
+// work runs after it.
+void Scheduler::admitFollowers() {
+    const u32 seqLen = sess_.header().seqLen;
+    struct Fork {
+        int src;
+        size_t L;
+        std::vector<int> dsts;
+    };
+    std::vector<Fork> forks;
+    std::vector<int> evict;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        for (auto &gp : groups_) {
+            Group &g = *gp;
+            const GenRequest *s = forkSource(g);
+            if (!s) continue;
+            Fork f{s->slot, s->prompt.size() - 1, {}};
+            while (!g.waiting.empty() && !freeSlots_.empty()) {
+                auto r = g.waiting.front();
+                if (r->isCancelled()) {
+                    g.waiting.pop_front();
+                    r->finish("cancelled");
+                    stats_.cancelled++;
+                    continue;
+                }
+                int target = freeSlots_.back();
+                if (prefixOn_)
+                    for (auto it = freeSlots_.rbegin(); it != freeSlots_.rend(); ++it)
+                        if (lastUse_[*it] < lastUse_[target]) target = *it;
+                if (pagesTotal_ >= 0) {
+                    const int need = pagesFor(std::min<u64>(spanOf(*r, seqLen), seqLen));
+                    if (need > pagesTotal_) {
+                        g.waiting.pop_front();
+                        r->error = "request needs more KV pages than the pool holds";
+                        r->finish("error");
+                        continue;
+                    }
+                    int held = 0, idleHeld = 0;
+                    for (int p : slotPages_) held += p;
+                    for (int fs : freeSlots_) idleHeld += slotPages_[fs];
+                    if (need > pagesTotal_ - (held - idleHeld)) break;  // wait for pages
+                    // the target gives its pages back first (forkPrefix does)
+                    std::vector<int> order(freeSlots_);
+                    std::sort(order.begin(), order.end(), [&](int a, int b) { return lastUse_[a] < lastUse_[b]; });
+                    for (int e : order) {
+                        if (held - slotPages_[target] + need <= pagesTotal_) break;
+                        if (e == target || slotPages_[e] == 0) continue;
+                        held -= slotPages_[e];
+                        slotPages_[e] = 0;
+                        slotReach_[e] = 0;
+                        resident_[e].clear();
+                        evict.push_back(e);
+                        stats_.prefixEvictions++;
+                    }
+                    slotPages_[target] = need;
+                }
+                slotReach_[target] = f.L;  // the fork maps the pages of [0, L)
+                resident_[target].clear();
+                g.waiting.pop_front();
+                freeSlots_.erase(std::find(freeSlots_.begin(), freeSlots_.end(), target));
+                startRequest(r, target, f.L);
+                f.dsts.push_back(target);
+                stats_.forkedRequests++;
+                stats_.forkTokens += f.L;
+            }
+            if (f.dsts.empty()) continue;
+            if (!g.counted) stats_.forkGroups++;
+            g.counted = true;
+            forks.push_back(std::move(f));
+        }
+        groups_.erase(std::remove_if(groups_.begin(), groups_.end(), [](const std::shared_ptr<Group> &g) { return g->waiting.empty(); }),
+                      groups_.end());
+    }
+    for (int s : evict) {
+        try {
+            sess_.releaseSlot(s);
+        } catch (const std::exception &) {  // a lost worker surfaces on the next forward
+        }
+    }
+    for (auto &f : forks) sess_.forkPrefix(f.src, f.dsts.data(), (int)f.dsts.size(), (int)f.L);  // a failure fails the step (failAll)
+}
+
 bool Scheduler::step() {
     const u32 seqLen = sess_.header().seqLen;
 
@@ -461,12 +661,28 @@ bool Scheduler::step() {
     // 1) admission: one free KV slot per request (and, with a paged KV cache, the pages its prompt +
     //    max_tokens can reach; FIFO: the head waits until enough pages are free); cancelled requests
     //    give their slot back
-    if (prefixOn_)
-        while (admitWithPrefix()) {
-        }
+    //    Followers of request groups join behind it (admitFollowers). When they and the queue together
+    //    want more slots than are free, the queue takes its share of them (scheduler.h: dealt one
+    //    at a time, the side served second goes first next time) and the followers the rest.
+    int queueQuota = std::numeric_limits<int>::max();
+    bool anyGroups;
     {
         std::lock_guard<std::mutex> lk(mu_);
-        while (!prefixOn_ && !queue_.empty() && !freeSlots_.empty()) {
+        anyGroups = !groups_.empty();
+        const int F = anyGroups ? readyFollowers() : 0, Q = (int)queue_.size(), S = (int)freeSlots_.size();
+        if (F > 0 && Q > 0 && S > 0 && F + Q > S) {
+            const int forkShare = std::min(F, forkFirst_ ? (S + 1) / 2 : S / 2);
+            queueQuota = S - forkShare;
+            forkFirst_ = !forkFirst_;
+        }
+    }
+    if (prefixOn_)
+        for (int k = 0; k < queueQuota && admitWithPrefix(); k++) {
+        }
+    {
+        std::unique_lock<std::mutex> lk(mu_);
+        int admitted = 0;
+        while (!prefixOn_ && !queue_.empty() && !freeSlots_.empty() && admitted < queueQuota) {
             auto r = queue_.front();
             if (r->isCancelled()) {
                 queue_.pop_front();
@@ -497,6 +713,12 @@ bool Scheduler::step() {
             queue_.pop_front();
             freeSlots_.pop_back();
             startRequest(r, slot, 0);
+            admitted++;
+        }
+        if (anyGroups) {
+            lk.unlock();
+            admitFollowers();
+            lk.lock();
         }
         // the cancel flag is read ONCE per request (cancel() runs on HTTP threads without mu_)
         std::vector<std::shared_ptr<GenRequest>> cancelled;

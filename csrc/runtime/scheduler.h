@@ -73,6 +73,14 @@ struct TokenRecord {
     std::vector<TokenLogprob> top;  // (logit descending, id ascending)
 };
 
+// Wakes a reader that waits on several requests at once (the members of a Scheduler::submitGroup
+// group streamed into one response): every emit / finish of a member counts one event.
+struct GroupSignal {
+    std::mutex mu;
+    std::condition_variable cv;
+    u64 events = 0;
+};
+
 class GenRequest {
   public:
     u64 id = 0;
@@ -104,6 +112,9 @@ class GenRequest {
     std::string wait();
     // Pops the next delta (blocking); returns false once the request is done and drained.
     bool nextDelta(std::string &out);
+    // The same without blocking: false when no delta is ready; `ended` then says done and drained.
+    bool tryNextDelta(std::string &out, bool &ended);
+    std::shared_ptr<GroupSignal> signal;  // set for the members of a group of more than one
     // Blocks until every prompt token has its record (params.promptLogprobs) or the request is done.
     void waitPromptLogprobs();
 
@@ -119,6 +130,7 @@ class GenRequest {
     std::unique_ptr<EosDetector> eos;
     void emit(const std::string &d);
     void finish(const std::string &reason);
+    void signalGroup();
 };
 
 struct SchedulerStats {
@@ -135,6 +147,10 @@ struct SchedulerStats {
     u64 embeddingRequests = 0;  // finished embedding requests
     u64 completionRequests = 0;  // finished /v1/completions requests (one per prompt item)
     u64 scoredPromptTokens = 0;  // prompt tokens scored for them (echo with logprobs)
+    // parallel sampling (submitGroup): groups of more than one whose followers were forked at least
+    // once, the followers that started behind a fork, the prompt tokens those skipped (no prefix-cache
+    // hits: the prefix* counters and the followers' cachedTokens do not move)
+    u64 forkGroups = 0, forkedRequests = 0, forkTokens = 0;
 };
 
 class Scheduler {
@@ -142,6 +158,18 @@ class Scheduler {
     explicit Scheduler(InferenceSession &sess);
     ~Scheduler();
     std::shared_ptr<GenRequest> submit(std::vector<int> prompt, const GenParams &params);
+    // Parallel sampling (the chat API's n): `count` requests over one prompt that share one prefill.
+    // Member i is an ordinary GenRequest with seed params.seed + i. Member 0, the leader, goes through
+    // the queue like any request; the followers wait in a group record and, once a member's collected
+    // prefill has reached L = prompt - 1 (one row runs in every member for its own logits), take free
+    // slots behind one Backend::forkPrefix(srcSlot, dsts, L) per admission step, each starting at
+    // prefilled = L. Followers that find no slot (or, paged, no pages) wait and fork later from any
+    // member still active; when none is left they enter the queue as ordinary requests, as they do
+    // at submission when L == 0. A cancelled follower that has not joined is dropped.
+    // Fairness: when ready followers and queued requests together want more slots than are free, the
+    // free slots are dealt to the two sides one at a time, and the side that was served second at one
+    // contended admission is served first at the next, so neither starves the other.
+    std::vector<std::shared_ptr<GenRequest>> submitGroup(std::vector<int> prompt, const GenParams &params, int count);
     void stop();
     SchedulerStats stats();
 
@@ -213,6 +241,19 @@ class Scheduler {
     }
     int pagesFor(size_t positions) const { return (int)((positions + pageSize_ - 1) / pageSize_); }
     bool admitWithPrefix();  // one request from the head of the queue; false: nothing admitted
+
+    // Request groups (submitGroup) that still have followers waiting to join.
+    struct Group {
+        std::vector<std::shared_ptr<GenRequest>> members;  // all of them, the leader first
+        std::deque<std::shared_ptr<GenRequest>> waiting;   // followers that have not joined
+        bool counted = false;                              // in stats_.forkGroups
+    };
+    std::vector<std::shared_ptr<Group>> groups_;
+    bool forkFirst_ = false;  // the side served first at the next contended admission
+    // a member whose slot holds [0, L) of the group's prompt (active, prefill collected up to L)
+    GenRequest *forkSource(const Group &g) const;
+    int readyFollowers();  // under mu_: drops cancelled followers, dissolves groups without a member left
+    void admitFollowers();
     Flight flight_;
     bool inflight_ = false;
     bool stop_ = false;

@@ -7,8 +7,14 @@
          copies are asynchronous; a paged copy also uploads the page table, which is part of its cost).
   ttft   time to the first streamed token through dllama-api for a ~2048-token shared prefix plus a
          short distinct suffix, with and without --prefix-cache 1 (same box, same run).
+  fork   HipEngine.fork_prefix(0, [1..m], n) against m back-to-back copy_prefix(0, i, n) calls
+         (profiles/parallel_sampling.md): the same shapes, n = 512 / 4096, m = 1 / 3 / 7, timed like
+         `copy`, the two alternating `reps` times in one process; the copies' spread is reported.
+  chat   one n = 4 chat request with a ~1k-token prompt against four concurrent single requests on
+         the 8B synthetic model: wall time and the /health prefill_rows delta (--api: the server
+         binary, so that another build can be measured by the same script).
 
-  python scripts/bench_prefix.py [copy] [ttft] [--iters 20] [--reps 5]
+  python scripts/bench_prefix.py [copy] [ttft] [fork] [chat] [--iters 20] [--reps 5] [--api build/dllama-api]
 """
 import argparse
 import http.client
@@ -55,6 +61,56 @@ def bench_copy(iters):
                            memcpy_us=round(ref, 1), memcpy_gbs=round(2 * nbytes / ref / 1e3, 1))
                 rows.append(row)
                 print(json.dumps(row), flush=True)
+            del eng
+    return rows
+
+
+def bench_fork(iters, reps):
+    import distributed_llama_multiusers_amd as dl
+    C = dl.native()
+    rows = []
+    for kv_bf16 in (False, True):
+        for page in (0, 256):
+            kw = dict(synthetic=H8B, max_seq_len=4224, n_slots=8, max_batch=8, kv_bf16=kv_bf16)
+            if page:
+                kw.update(kv_pages=8 * 4352 // page, kv_page_size=page)
+            eng = C.HipEngine("", "q80", **kw)
+            eng.forward([1], [4095], [0])  # slot 0 reaches 4096 positions (paged: its pages are mapped)
+            for n in (512, 4096):
+                nbytes = 32 * 2 * 8 * 128 * (2 if kv_bf16 else 4) * n
+                for m in (1, 3, 7):
+                    dsts = list(range(1, m + 1))
+
+                    def fork():
+                        eng.fork_prefix(0, dsts, n)
+
+                    def copies():
+                        for d in dsts:
+                            eng.copy_prefix(0, d, n)
+
+                    def timed(f):
+                        for _ in range(3):
+                            f()
+                        eng.synchronize()
+                        t0 = time.perf_counter()
+                        for _ in range(iters):
+                            f()
+                        eng.synchronize()
+                        return (time.perf_counter() - t0) / iters * 1e6
+
+                    fk, cp = [], []
+                    for _ in range(reps):  # alternating, so that both see the same neighbours
+                        cp.append(timed(copies))
+                        fk.append(timed(fork))
+                    f_us, c_us = statistics.median(fk), statistics.median(cp)
+                    row = dict(kv="bf16" if kv_bf16 else "f32", layout=f"paged{page}" if page else "contiguous", n=n, m=m,
+                               mib=round(nbytes / 2**20, 1), copies_us=round(c_us, 1),
+                               copies_spread_us=round(max(cp) - min(cp), 1), fork_us=round(f_us, 1),
+                               fork_spread_us=round(max(fk) - min(fk), 1), ratio=round(f_us / c_us, 3),
+                               by_bytes=round((1 + m) / (2 * m), 3), fork_gbs=round((1 + m) * nbytes / f_us / 1e3, 1),
+                               copies_gbs=round(2 * m * nbytes / c_us / 1e3, 1))
+                    rows.append(row)
+                    print(json.dumps(row), flush=True)
             del eng
     return rows
 
@@ -141,17 +197,92 @@ def bench_ttft(reps):
     return out
 
 
+def bench_chat(api, reps):
+    """Wall ms and prefill rows of one n = 4 request, and of four concurrent single requests."""
+    import concurrent.futures
+    from distributed_llama_multiusers_amd.models.synthetic import make_tokenizer
+    tmp = tempfile.mkdtemp()
+    tok = os.path.join(tmp, "tok.t")
+    make_tokenizer(tok, 128256)
+    port = _port()
+    cmd = [api, "--synthetic", "llama3_1_8b", "--tokenizer", tok, "--gpu-index", "0", "--port", str(port), "--slots", "4",
+           "--max-seq-len", "2048", "--buffer-float-type", "q80"]
+    log = open(os.path.join(tmp, "chat.log"), "w")
+    srv = subprocess.Popen(cmd, stdout=log, stderr=subprocess.STDOUT)
+
+    def post(content, **kw):
+        body = {"messages": [{"role": "user", "content": content}], "max_tokens": 16, "temperature": 0.8, "seed": 1}
+        body.update(kw)
+        c = http.client.HTTPConnection("127.0.0.1", port, timeout=300)
+        c.request("POST", "/v1/chat/completions", json.dumps(body), {"Content-Type": "application/json"})
+        return json.loads(c.getresponse().read())
+
+    def health():
+        c = http.client.HTTPConnection("127.0.0.1", port, timeout=10)
+        c.request("GET", "/health")
+        return json.loads(c.getresponse().read())
+
+    out = {}
+    try:
+        for _ in range(900):
+            try:
+                health()
+                break
+            except OSError:
+                pass
+            if srv.poll() is not None:
+                raise RuntimeError("dllama-api exited: " + open(log.name).read()[-2000:])
+            time.sleep(0.2)
+        shared = " hello world the" * 170  # ~1k tokens with the synthetic merges
+        for i in range(2):  # untimed: code objects, graphs
+            post(shared + f" warm {i}")
+        with concurrent.futures.ThreadPoolExecutor(4) as ex:
+            list(ex.map(lambda i: post(shared + " warm", seed=i), range(4)))
+        for name in ("four_singles", "n4"):
+            ms, rows, choices, ptoks = [], [], 0, 0
+            for i in range(reps):
+                content = shared + f" run {name} {i} and the end of the world"
+                h0 = health()
+                t0 = time.perf_counter()
+                if name == "n4":
+                    d = post(content, n=4)
+                    choices = len(d["choices"])
+                else:
+                    with concurrent.futures.ThreadPoolExecutor(4) as ex:
+                        ds = list(ex.map(lambda k: post(content, seed=1 + k), range(4)))
+                    d, choices = ds[0], sum(len(x["choices"]) for x in ds)
+                ms.append((time.perf_counter() - t0) * 1e3)
+                rows.append(health()["prefill_rows"] - h0["prefill_rows"])
+                ptoks = d["usage"]["prompt_tokens"]
+            out[name] = dict(wall_ms=[round(x, 1) for x in ms], median_ms=round(statistics.median(ms), 1),
+                             prefill_rows=rows, prompt_tokens=ptoks, choices=choices)
+            print(name, json.dumps(out[name]), flush=True)
+    finally:
+        srv.terminate()
+        try:
+            srv.wait(timeout=30)
+        except subprocess.TimeoutExpired:
+            srv.kill()
+        log.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="*", default=["copy", "ttft"])
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--api", default=os.path.join(REPO, "build", "dllama-api"))
     args = ap.parse_args()
     res = {}
     if "copy" in args.what:
         res["copy"] = bench_copy(args.iters)
     if "ttft" in args.what:
         res["ttft"] = bench_ttft(args.reps)
+    if "fork" in args.what:
+        res["fork"] = bench_fork(args.iters, args.reps)
+    if "chat" in args.what:
+        res["chat"] = bench_chat(args.api, args.reps)
     print(json.dumps(res), flush=True)
 
 
