@@ -3,6 +3,7 @@
 #include "engine_impl.h"
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -41,6 +42,7 @@ HipEngineImpl::HipEngineImpl(const EngineConfig &cfg, DeviceComm *comm) : cfg_(c
     if (!q40_ && h_.weightType != FloatType::F32) throw Error("unsupported weight type");
     DL_CHECK(h_.headSize() == 64 || h_.headSize() == 128, "GPU kernels support head size 64 or 128");
     DL_CHECK(cfg.maxBatch >= 1 && cfg.nSlots >= 1, "maxBatch/nSlots");
+    DL_CHECK(cfg.maxBatch <= kKeyMaxRows, "maxBatch: more rows than a graph key holds");
     kvBf16_ = cfg.kvBf16;
     syncQ80_ = cfg.syncType == FloatType::Q80;
     decodeRows_ = (int)(cfg.maxDecode ? std::min(cfg.maxDecode, cfg.maxBatch) : cfg.maxBatch);
@@ -194,22 +196,21 @@ void HipEngineImpl::enqueueSampled(int n, const int *tokens, const int *position
                                    const SampleSpec *specs) {
     const std::vector<int> targets = takeLogprobTargets(n, specs);  // (checked before anything is enqueued)
     std::vector<LogitProc> procs;
-    GraphKind kind = beginProcs(n, slots, specs, procs);
+    FwdKind k(GraphKind::SAMPLE, beginProcs(n, slots, specs, procs));
     const std::vector<PoolSpec> pool = beginPooling(n, positions, slots);
     if (!pool.empty()) {
         if (!specs) throw Error("launchIds: pooling needs a sampled forward (specs)");
-        if (noRowDraws(n, specs))
-            kind = GraphKind::EMBED;
+        if (noRowDraws(n, specs))  // (no row draws: beginProcs found no active row either)
+            k = GraphKind::EMBED;
         else  // (a single row takes paths that keep the residual elsewhere: setupPrenorm)
             DL_CHECK(n >= 2, "pooling: a pooled row that draws needs a forward of its own kind with >= 2 rows");
     }
-    const bool proc = kindProc(kind);
-    setInputs(n, tokens, positions, slots, specs, 0, proc ? procRows_.data() : nullptr,
-              kindFilter(kind) ? filterRows_.data() : nullptr);
-    if (proc) enqueueProcState(n, slots, procs);
+    setInputs(n, tokens, positions, slots, specs, 0, k.has(PROC) ? procRows_.data() : nullptr,
+              k.has(FILTER) ? filterRows_.data() : nullptr);
+    if (k.has(PROC)) enqueueProcState(n, slots, procs);
     stagePooling(n, slots, pool);
-    runGraph(n, specs ? kind : GraphKind::ARGMAX);
-    if (kind == GraphKind::EMBED) {
+    runGraph(n, specs ? k : GraphKind::ARGMAX);
+    if (k.kind == GraphKind::EMBED) {
         logprobReq_.clear();
         DL_HIP(hipMemsetAsync(dIds_, 0xff, n * sizeof(int), stream_));  // no row drew: ids -1
     } else {
@@ -314,22 +315,21 @@ void HipEngineImpl::readPooled() {
 
 // The logit processors handed over for this forward (Backend::setLogitProcs). Ranks other than the
 // root drop them: they neither hold the full logits nor draw, and run their SAMPLE schedule with
-// the same collectives in the same order. Returns the sampled forward's graph kind: SAMPLE without an
-// active row, else SAMPLE_PROC with procRows_ filled, or SAMPLE_PROC_FILTER with filterRows_ filled
-// too when one of the active rows has top_k or min_p on.
-HipEngineImpl::GraphKind HipEngineImpl::beginProcs(int n, const int *slots, const SampleSpec *specs,
-                                                   std::vector<LogitProc> &procs) {
-    if (pendingProcs_.empty()) return GraphKind::SAMPLE;
+// the same collectives in the same order. Returns the sampled forward's draw stages: none without an
+// active row, else PROC with procRows_ filled, FILTER with filterRows_ filled too when one of the
+// active rows has top_k or min_p on, and JSON / GRAMMAR when one of them is constrained that way.
+unsigned HipEngineImpl::beginProcs(int n, const int *slots, const SampleSpec *specs, std::vector<LogitProc> &procs) {
+    if (pendingProcs_.empty()) return 0;
     if (!specs) {
         pendingProcs_.clear();
         throw Error("launchIds: logit processors need a sampled forward (specs)");
     }
     procs = takeLogitProcs(n);
-    if (procs.empty() || rank() != 0) return GraphKind::SAMPLE;
+    if (procs.empty() || rank() != 0) return 0;
     std::vector<int> seen;
     procRows_.assign((size_t)n * 4, 0.f);
     filterRows_.assign((size_t)n, hipk::LogitFilterRow{0, -INFINITY, 0, 0});
-    bool any = false, anyFilter = false, anyJson = false, anyGrammar = false;
+    unsigned stages = 0;
     for (int b = 0; b < n; b++) {
         const LogitProc &p = procs[b];
         if (!p.active || specs[b].temperature < 0.f) continue;
@@ -338,32 +338,28 @@ HipEngineImpl::GraphKind HipEngineImpl::beginProcs(int n, const int *slots, cons
         procRows_[(size_t)b * 4] = p.presence;
         procRows_[(size_t)b * 4 + 1] = p.frequency;
         procRows_[(size_t)b * 4 + 2] = 1.f;
-        any = true;
+        stages |= PROC;
         if (p.filter(specs[b].temperature, (int)h_.vocabSize)) {
             filterRows_[b] = hipk::LogitFilterRow{p.topK, minPDelta(specs[b].temperature, p.minP), 1, 0};
-            anyFilter = true;
+            stages |= FILTER;
         }
         if (p.json) {
             DL_CHECK(dJsonMeta_ != nullptr, "json mode: no token table (setJsonTable)");
             procRows_[(size_t)b * 4 + 3] = hipk::kRowKindJson;
-            anyJson = true;
+            stages |= JSON;
         }
         if (p.grammar) {  // (takeLogitProcs: never next to json; a fresh row's tables are checked)
             DL_CHECK(dJsonMeta_ != nullptr, "json_schema: no token table (setJsonTable)");
             DL_CHECK(p.fresh || slotGrammar_[(size_t)slots[b]] == p.grammar,
                      "json_schema: a row that is not fresh carries another grammar than its slot's");
             procRows_[(size_t)b * 4 + 3] = hipk::kRowKindGrammar;
-            anyGrammar = true;
+            stages |= GRAMMAR;
         }
     }
     std::sort(seen.begin(), seen.end());
     DL_CHECK(std::adjacent_find(seen.begin(), seen.end()) == seen.end(),
              "logit processors: two drawn rows of one forward share a slot");
-    if (!any) return GraphKind::SAMPLE;
-    if (anyGrammar && anyJson) return anyFilter ? GraphKind::SAMPLE_PROC_FILTER_JSON_GRAMMAR : GraphKind::SAMPLE_PROC_JSON_GRAMMAR;
-    if (anyGrammar) return anyFilter ? GraphKind::SAMPLE_PROC_FILTER_GRAMMAR : GraphKind::SAMPLE_PROC_GRAMMAR;
-    if (anyJson) return anyFilter ? GraphKind::SAMPLE_PROC_FILTER_JSON : GraphKind::SAMPLE_PROC_JSON;
-    return anyFilter ? GraphKind::SAMPLE_PROC_FILTER : GraphKind::SAMPLE_PROC;
+    return stages;
 }
 
 // Before the forward, in stream order: a fresh slot's counts are zeroed and its bias entries and
@@ -412,40 +408,18 @@ void HipEngineImpl::setJsonTable(std::shared_ptr<const JsonTokenTable> table) {
 }
 
 // A fresh row's grammar goes to its slot's table block, and the slot's state to the start state, in
-// stream order ahead of the forward. The copies read the grammar's own arrays: slotGrammar_ keeps
-// them alive until the slot's next fresh row, whose forward is launched after this one was
-// collected. Every part a walk can index is rewritten (next up to nStates * nClasses, the class
-// map, the accept words up to nStates, the head), so a slot never serves an earlier request's tables.
+// stream order ahead of the forward. The copies read the grammar's own arrays (installGrammarTables):
+// slotGrammar_ keeps them alive until the slot's next fresh row, whose forward is launched after this
+// one was collected.
 void HipEngineImpl::enqueueGrammarInstall(size_t slot, const std::shared_ptr<const GrammarDfa> &g) {
-    static_assert(kGrammarMaxEntries * sizeof(uint16_t) <= hipk::kGrammarClassOff && kGrammarMaxStates / 8 <= 512, "table block layout");
-    static_assert(offsetof(GrammarDfa, nStates) == offsetof(GrammarDfa, nClasses) + sizeof(uint32_t), "the head is (nClasses, nStates)");
     slotGrammar_[slot] = g;
-    uint8_t *base = dGrammarTables_ + slot * hipk::kGrammarSlotBytes;
-    DL_HIP(hipMemcpyAsync(base, g->next.data(), g->next.size() * sizeof(uint16_t), hipMemcpyHostToDevice, stream_));
-    DL_HIP(hipMemcpyAsync(base + hipk::kGrammarClassOff, g->classOf, 256, hipMemcpyHostToDevice, stream_));
-    DL_HIP(hipMemcpyAsync(base + hipk::kGrammarAcceptOff, g->accept.data(), g->accept.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
-    DL_HIP(hipMemcpyAsync(base + hipk::kGrammarHeadOff, &g->nClasses, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
+    hipk::installGrammarTables(dGrammarTables_ + slot * hipk::kGrammarSlotBytes, *g, stream_);
     DL_HIP(hipMemcpyAsync(dGrammarStates_ + slot, &g->start, sizeof(uint32_t), hipMemcpyHostToDevice, stream_));
 }
 
-hipk::GrammarMaskArgs HipEngineImpl::grammarMaskArgs() const {
-    hipk::GrammarMaskArgs g;
-    g.logits = dProcLogits_;
-    g.vocab = h_.vocabSize;
-    g.spec = dSpec_;
-    g.proc = dProc_;
-    g.slots = dSlot_;
-    g.table.meta = dJsonMeta_;
-    g.table.words = dJsonWords_;
-    g.tables = dGrammarTables_;
-    g.states = dGrammarStates_;
-    g.ids = dIds_;
-    return g;
-}
-
-hipk::JsonMaskArgs HipEngineImpl::jsonMaskArgs() const {
+hipk::ConstraintArgs HipEngineImpl::constraintArgs() const {
     static_assert(sizeof(JsonState) == sizeof(uint4), "device and host state layouts");
-    hipk::JsonMaskArgs g;
+    hipk::ConstraintArgs g;
     g.logits = dProcLogits_;
     g.vocab = h_.vocabSize;
     g.spec = dSpec_;
@@ -453,8 +427,10 @@ hipk::JsonMaskArgs HipEngineImpl::jsonMaskArgs() const {
     g.slots = dSlot_;
     g.table.meta = dJsonMeta_;
     g.table.words = dJsonWords_;
-    g.states = dJsonStates_;
     g.ids = dIds_;
+    g.jsonStates = dJsonStates_;
+    g.grammarTables = dGrammarTables_;
+    g.grammarStates = dGrammarStates_;
     return g;
 }
 
@@ -834,9 +810,9 @@ void HipEngineImpl::tpFusedSelfTest() {
     setupPrenorm();
 }
 
-void HipEngineImpl::runGraph(int n, GraphKind kind, unsigned *syncDst) {
+void HipEngineImpl::runGraph(int n, FwdKind kind, unsigned *syncDst) {
     if (!tpTested_) tpFusedSelfTest();
-    accountForward(n, kind, 1);
+    accountForward(n, kind.kind, 1);
     auto copySync = [&]() {  // the forward's measured-sync slots to the host (read after the sync)
         if (plan_.nRanks > 1 && syncDst)
             DL_HIP(hipMemcpyAsync(syncDst, dSync_, hipk::syncFoldWords(syncSlots()) * sizeof(unsigned),
@@ -847,7 +823,8 @@ void HipEngineImpl::runGraph(int n, GraphKind kind, unsigned *syncDst) {
         copySync();
         return;
     }
-    const int key = ((((n * 16 + (int)kind) * 2 + (prefillOk_ ? 1 : 0)) * 2 + (attnLong_ ? 1 : 0)) << 4) + bucket_;
+    const GraphKey key = graphKey({.bucket = (unsigned)bucket_, .attnLong = attnLong_, .prefillOk = prefillOk_,
+                                   .stages = kind.stages, .kind = kind.kind, .rows = (unsigned)n});
     auto it = graphs_.find(key);
     if (it == graphs_.end()) {
         // capture on the second use of a shape: a one-off row count (the tail chunk of a prompt,
@@ -873,7 +850,7 @@ void HipEngineImpl::runGraph(int n, GraphKind kind, unsigned *syncDst) {
     copySync();
 }
 
-hipGraphExec_t HipEngineImpl::captureForward(int n, GraphKind kind) {
+hipGraphExec_t HipEngineImpl::captureForward(int n, FwdKind kind) {
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
     if (hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal) != hipSuccess) return nullptr;
@@ -900,6 +877,16 @@ hipGraphExec_t HipEngineImpl::captureForward(int n, GraphKind kind) {
 }
 
 }  // namespace engine_detail
+
+// (kernels.h; host code, shared with ops.cpp)
+void hipk::installGrammarTables(uint8_t *block, const GrammarDfa &g, hipStream_t s) {
+    static_assert(kGrammarMaxEntries * sizeof(uint16_t) <= hipk::kGrammarClassOff && kGrammarMaxStates / 8 <= 512, "table block layout");
+    static_assert(offsetof(GrammarDfa, nStates) == offsetof(GrammarDfa, nClasses) + sizeof(uint32_t), "the head is (nClasses, nStates)");
+    DL_HIP(hipMemcpyAsync(block, g.next.data(), g.next.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    DL_HIP(hipMemcpyAsync(block + hipk::kGrammarClassOff, g.classOf, 256, hipMemcpyHostToDevice, s));
+    DL_HIP(hipMemcpyAsync(block + hipk::kGrammarAcceptOff, g.accept.data(), g.accept.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    DL_HIP(hipMemcpyAsync(block + hipk::kGrammarHeadOff, &g.nClasses, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+}
 
 std::unique_ptr<HipEngine> makeHipEngine(const EngineConfig &cfg, DeviceComm *comm) {
     return std::unique_ptr<HipEngine>(new engine_detail::HipEngineImpl(cfg, comm));

@@ -24,7 +24,7 @@ void HipEngineImpl::setupBuckets() {
     CtxBucket last;
     last.maxLen = (int)h_.seqLen;
     buckets_.push_back(last);
-    DL_CHECK(buckets_.size() <= 16, "too many context buckets");
+    DL_CHECK(buckets_.size() <= kKeyMaxBucket + 1, "too many context buckets");  // (the graph key's field)
     for (CtxBucket &b : buckets_) {
         b.splitGrid = hipk::attnSplitGrid(b.maxLen, true);
         b.splitGridBat = hipk::attnSplitGrid(b.maxLen, false);
@@ -618,9 +618,10 @@ void HipEngineImpl::enqueueLogits(const FwdPath &f, GraphKind kind, int cur) {
         gemv(wcls_, f.n, hipk::PRO_RESNORM, hipk::EPI_STORE, o);
 }
 
-// From the logits of n rows to their token ids: (gather) -> argmax / sample.
-void HipEngineImpl::enqueueTokenPick(int n, GraphKind kind) {
+// From the logits of n rows to their token ids: (gather) -> argmax / draw.
+void HipEngineImpl::enqueueTokenPick(int n, FwdKind k) {
     const ShardPlan &p = plan_;
+    const GraphKind kind = k.kind;
     const float *full = dLogits_;
     // greedy rows under tensor parallelism: each rank reduces its own vocab slice and only the
     // (value, index) winners cross the links (reference: logits gathered to the root,
@@ -631,9 +632,7 @@ void HipEngineImpl::enqueueTokenPick(int n, GraphKind kind) {
     // logits for the host (LOGITS) and sampled rows (SAMPLE) are needed on the root only: the
     // vocab slices are gathered to rank 0 (the reference's SYNC_NODE_SLICES_EXCEPT_ROOT), the
     // other ranks publish theirs and skip the unshard and the draw (the root's ids are used)
-    const bool filtered = kindFilter(kind), json = kindJson(kind), grammar = kindGrammar(kind);
-    const bool sampled = kind == GraphKind::SAMPLE || kindProc(kind);
-    const bool rootOnly = kind == GraphKind::LOGITS || sampled;
+    const bool rootOnly = kind == GraphKind::LOGITS || kind == GraphKind::SAMPLE;
     if (p.nRanks > 1 && !distArgmax) {
         ProfScope ps(this, "allgather");
         stamped([&] {
@@ -645,65 +644,8 @@ void HipEngineImpl::enqueueTokenPick(int n, GraphKind kind) {
         if (!rootOnly || rank() == 0) hipk::launchUnshardLogits(dLogitsAll_, dLogitsFull_, p.nRanks, n, p.vocab0, stream_);
         full = dLogitsFull_;
     }
-    if (sampled) {
-        if (p.nRanks == 1 || rank() == 0) {  // the other ranks' ids are not used (no draw, no argmax)
-            // SAMPLE_PROC (root only): the drawn rows' penalties and bias into the processed buffer,
-            // which the sampler reads instead; the raw logits stay for the log-probabilities; the
-            // drawn tokens are counted behind the draw
-            // SAMPLE_PROC_FILTER: top_k / min_p then mask the processed rows in place; the filter's
-            // partial histograms and maxima live in the sampler's scratch, which the sampler rewrites
-            // before it reads it
-            // SAMPLE_PROC_JSON / SAMPLE_PROC_FILTER_JSON: the JSON token mask on the processed rows
-            // ahead of the filter (top_k counts allowed tokens only), and the slots' automaton states
-            // advanced by the drawn tokens behind the draw
-            const bool proc = kindProc(kind);
-            if (proc) {
-                ProfScope ps(this, "logit_proc");
-                hipk::launchLogitProc(logitProcArgs(full), n, stream_);
-            }
-            if (json) {
-                ProfScope ps(this, "json_mask");
-                hipk::launchJsonMask(jsonMaskArgs(), n, stream_);
-            }
-            if (grammar) {  // ..._GRAMMAR: the same for rows that follow a compiled grammar (each mask takes its own rows)
-                ProfScope ps(this, "grammar_mask");
-                hipk::launchGrammarMask(grammarMaskArgs(), n, stream_);
-            }
-            if (filtered) {
-                ProfScope ps(this, "logit_filter");
-                hipk::LogitFilterArgs f;
-                f.logits = dProcLogits_;
-                f.vocab = h_.vocabSize;
-                f.spec = dSpec_;
-                f.rows = dFilter_;
-                f.hist = reinterpret_cast<uint32_t *>(sampleScratch_.hist);
-                f.part = sampleScratch_.part;
-                f.state = dFilterState_;
-                hipk::launchLogitFilter(f, n, stream_);
-            }
-            {
-                ProfScope ps(this, "sample");
-                hipk::SampleArgs g;
-                g.logits = proc ? dProcLogits_ : full;
-                g.vocab = h_.vocabSize;
-                g.spec = dSpec_;
-                g.ids = dIds_;
-                g.scratch = sampleScratch_;
-                hipk::launchSample(g, n, stream_);
-            }
-            if (proc) {
-                ProfScope ps(this, "logit_proc");
-                hipk::launchLogitProcCount(logitProcArgs(full), n, stream_);
-            }
-            if (json) {
-                ProfScope ps(this, "json_mask");
-                hipk::launchJsonAdvance(jsonMaskArgs(), n, stream_);
-            }
-            if (grammar) {
-                ProfScope ps(this, "grammar_mask");
-                hipk::launchGrammarAdvance(grammarMaskArgs(), n, stream_);
-            }
-        }
+    if (kind == GraphKind::SAMPLE) {
+        if (p.nRanks == 1 || rank() == 0) enqueueDraw(n, k.stages, full);  // the other ranks' ids are not used
     } else if (kind != GraphKind::LOGITS) {
         ProfScope ps(this, "argmax");
         hipk::ArgmaxArgs g;
@@ -737,12 +679,57 @@ void HipEngineImpl::enqueueTokenPick(int n, GraphKind kind) {
     }
 }
 
+// The draw of n sampled rows from their full logits, with the forward's stages around the sampler
+// (root only). PROC: the drawn rows' penalties and bias into the processed buffer, which every later
+// stage and the sampler read instead; the raw logits stay for the log-probabilities; the drawn tokens
+// are counted behind the draw. JSON, GRAMMAR: the token masks on the processed rows (each takes the
+// rows of its own kind) ahead of the filter, so top_k counts allowed tokens only, and the slots'
+// states advanced by the drawn tokens behind the draw. FILTER: top_k / min_p mask the processed rows
+// in place; the filter's partial histograms and maxima live in the sampler's scratch, which the
+// sampler rewrites before it reads it.
+void HipEngineImpl::enqueueDraw(int n, unsigned stages, const float *full) {
+    const bool proc = stages & PROC;
+    auto stage = [&](DrawStage st, const char *name, auto &&launch) {
+        if (!(stages & st)) return;
+        ProfScope ps(this, name);
+        launch();
+    };
+    stage(PROC, "logit_proc", [&] { hipk::launchLogitProc(logitProcArgs(full), n, stream_); });
+    stage(JSON, "json_mask", [&] { hipk::launchJsonMask(constraintArgs(), n, stream_); });
+    stage(GRAMMAR, "grammar_mask", [&] { hipk::launchGrammarMask(constraintArgs(), n, stream_); });
+    stage(FILTER, "logit_filter", [&] {
+        hipk::LogitFilterArgs f;
+        f.logits = dProcLogits_;
+        f.vocab = h_.vocabSize;
+        f.spec = dSpec_;
+        f.rows = dFilter_;
+        f.hist = reinterpret_cast<uint32_t *>(sampleScratch_.hist);
+        f.part = sampleScratch_.part;
+        f.state = dFilterState_;
+        hipk::launchLogitFilter(f, n, stream_);
+    });
+    {
+        ProfScope ps(this, "sample");
+        hipk::SampleArgs g;
+        g.logits = proc ? dProcLogits_ : full;
+        g.vocab = h_.vocabSize;
+        g.spec = dSpec_;
+        g.ids = dIds_;
+        g.scratch = sampleScratch_;
+        hipk::launchSample(g, n, stream_);
+    }
+    stage(PROC, "logit_proc", [&] { hipk::launchLogitProcCount(logitProcArgs(full), n, stream_); });
+    stage(JSON, "json_mask", [&] { hipk::launchJsonAdvance(constraintArgs(), n, stream_); });
+    stage(GRAMMAR, "grammar_mask", [&] { hipk::launchGrammarAdvance(constraintArgs(), n, stream_); });
+}
+
 // The forward of n rows: embedding -> nLayers x [qkv (+RoPE, KV append) -> attention -> wo
 // (-> all-reduce) -> w13 (SwiGLU) -> w2 (-> all-reduce)] -> logits -> (gather) -> argmax / sample.
 // Single decode rows (GEMV path) run qkv + attention + wo as one fused attention-block launch when
 // the context bucket allows it; batched rows run the MFMA GEMMs with residual + norm fused into
 // their epilogues (reference step list: llm.cpp:200-434, ~840 barrier steps per forward).
-void HipEngineImpl::enqueueForward(int n, GraphKind kind) {
+void HipEngineImpl::enqueueForward(int n, FwdKind k) {
+    const GraphKind kind = k.kind;
     FwdPath f{.n = n, .bat = batchedPath(n)};
     f.fz = f.bat && fuseNorm(n);
     f.blk = blockOn_ && buckets_[bucket_].block && n == 1 && !f.bat;
@@ -795,7 +782,7 @@ void HipEngineImpl::enqueueForward(int n, GraphKind kind) {
             enqueuePrenormLayers(f, kind);
         else
             enqueueLogits(f, kind, cur);
-        if (!f.argTail) enqueueTokenPick(n, kind);
+        if (!f.argTail) enqueueTokenPick(n, k);
     }
     DL_HIP(hipGetLastError());
 }

@@ -4,6 +4,7 @@
 //   engine_kv.cpp       paged KV cache (page table per slot over per-layer pools), prefix copy
 //   engine_forward.cpp  the per-forward kernel schedule (GEMV / GEMM / attention / block launches)
 //   engine_bench.cpp    kernel microbenchmarks (scripts/bench_*.py)
+// graph_key.h holds what a graph is captured for: the forward's kind, its draw stages, and the key.
 //
 // Weight residency: every rank repacks ITS shard of the mmapped `.m` file on the host into the
 // GPU layout and uploads it once (reference: root streams shards to workers over TCP,
@@ -27,6 +28,7 @@
 #include "../core/plan.h"
 #include "../runtime/metrics.h"
 #include "engine.h"
+#include "graph_key.h"
 #include "kernels.h"
 
 namespace dl {
@@ -104,31 +106,18 @@ class HipEngineImpl : public HipEngine {
     bool tpBatchedFused(int n) const override { return plan_.nRanks > 1 && batchedPath(n) && fuseNorm(n); }
 
     // ------------------------------------------------------------------ internals
-    // SAMPLE_PROC: SAMPLE with the logit processors between the logits and the draw (root rank of a
-    // forward with an active LogitProc row; every other forward takes the kinds it always took)
-    // SAMPLE_PROC_FILTER: SAMPLE_PROC with the candidate filter (top_k / min_p) between the processors
-    // and the draw (a forward with a row whose filter is on)
-    // EMBED: every row is a non-drawing row and one of them is pooled (Backend::setPooling): all the
-    // layers, then launchPool on the root; no wcls, no logits exchange, no token pick on any rank
-    // SAMPLE_PROC_JSON / SAMPLE_PROC_FILTER_JSON: the two with the JSON token mask behind the processors
-    // and the automaton's advance behind the draw (a forward with a drawn row in JSON mode)
-    enum class GraphKind {
-        LOGITS = 0, ARGMAX = 1, CHAIN = 2, SAMPLE = 3, SAMPLE_PROC = 4, SAMPLE_PROC_FILTER = 5, EMBED = 6,
-        SAMPLE_PROC_JSON = 7, SAMPLE_PROC_FILTER_JSON = 8,
-        // ..._GRAMMAR: with the grammar token mask and advance (a forward with a drawn row that follows
-        // a compiled schema); ..._JSON_GRAMMAR: a forward that has rows of both kinds runs both masks
-        SAMPLE_PROC_GRAMMAR = 9, SAMPLE_PROC_FILTER_GRAMMAR = 10, SAMPLE_PROC_JSON_GRAMMAR = 11, SAMPLE_PROC_FILTER_JSON_GRAMMAR = 12
+    // What a forward runs behind its layers (graph_key.h): its kind and, for SAMPLE, the draw stages.
+    // A forward that no stage asks for takes the plain kinds and replays the graphs it always did.
+    using GraphKind = engine_detail::GraphKind;
+    struct FwdKind {
+        GraphKind kind;
+        unsigned stages;
+        FwdKind(GraphKind k, unsigned st = 0) : kind(k), stages(st) {
+            DL_CHECK(st == 0 || (k == GraphKind::SAMPLE && (st & PROC) && st < kDrawStageSets),
+                     "draw stages: only with SAMPLE, and FILTER / JSON / GRAMMAR imply PROC");
+        }
+        bool has(DrawStage s) const { return (stages & s) != 0; }
     };
-    static bool kindJson(GraphKind k) {
-        return k == GraphKind::SAMPLE_PROC_JSON || k == GraphKind::SAMPLE_PROC_FILTER_JSON || k == GraphKind::SAMPLE_PROC_JSON_GRAMMAR ||
-               k == GraphKind::SAMPLE_PROC_FILTER_JSON_GRAMMAR;
-    }
-    static bool kindGrammar(GraphKind k) { return (int)k >= (int)GraphKind::SAMPLE_PROC_GRAMMAR && (int)k <= (int)GraphKind::SAMPLE_PROC_FILTER_JSON_GRAMMAR; }
-    static bool kindFilter(GraphKind k) {
-        return k == GraphKind::SAMPLE_PROC_FILTER || k == GraphKind::SAMPLE_PROC_FILTER_JSON || k == GraphKind::SAMPLE_PROC_FILTER_GRAMMAR ||
-               k == GraphKind::SAMPLE_PROC_FILTER_JSON_GRAMMAR;
-    }
-    static bool kindProc(GraphKind k) { return k == GraphKind::SAMPLE_PROC || kindFilter(k) || kindJson(k) || kindGrammar(k); }
 
     // engine.cpp
     void syncAndCheckComm();
@@ -136,8 +125,8 @@ class HipEngineImpl : public HipEngine {
     void checkErrorWords();
     int rank() const { return comm_ ? comm_->rank() : 0; }
     // syncDst: host copy of the forward's measured-sync slots (null: none, e.g. inside a decode chain)
-    void runGraph(int n, GraphKind kind, unsigned *syncDst);
-    void runGraph(int n, GraphKind kind) { runGraph(n, kind, hSync_); }
+    void runGraph(int n, FwdKind k, unsigned *syncDst);
+    void runGraph(int n, FwdKind k) { runGraph(n, k, hSync_); }
     void accountForward(int n, GraphKind kind, int times);
     // measured sync (ForwardStats::syncMs / xchgMs): one slot per (exchange, launch) of a forward
     // (exchange xSlot_: layer l's wo 2l, w2 2l + 1, the logits / argmax exchange 2L; launch xChunk_:
@@ -177,7 +166,7 @@ class HipEngineImpl : public HipEngine {
     }
     void launchStampAt(unsigned long long *p);
     void tpFusedSelfTest();
-    hipGraphExec_t captureForward(int n, GraphKind kind);
+    hipGraphExec_t captureForward(int n, FwdKind k);
     template <typename T>
     T *dalloc(size_t count) {
         void *p = nullptr;
@@ -234,8 +223,8 @@ class HipEngineImpl : public HipEngine {
     // engine_forward.cpp
     void setupBuckets();
     const CtxBucket &bucketFor(int maxPos) const;
-    // procRows: [n][4] (presence, frequency, active, -) of a SAMPLE_PROC / SAMPLE_PROC_FILTER forward,
-    // else null; filterRows: [n] of a SAMPLE_PROC_FILTER forward, else null
+    // procRows: [n][4] (presence, frequency, active, row kind) of a forward with the PROC stage, else
+    // null; filterRows: [n] of a forward with the FILTER stage, else null
     void setInputs(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs = nullptr,
                    int ahead = 0, const float *procRows = nullptr, const hipk::LogitFilterRow *filterRows = nullptr);
     int tpPasses(const DevMat &m, int bc) const;
@@ -333,8 +322,9 @@ class HipEngineImpl : public HipEngine {
     void enqueuePrenormLayers(const FwdPath &f, GraphKind kind);
     void enqueueLogits(const FwdPath &f, GraphKind kind, int cur);
     void launchArgmaxTail(hipk::GemvArgs a, int pro, GraphKind kind);
-    void enqueueTokenPick(int n, GraphKind kind);
-    void enqueueForward(int n, GraphKind kind);
+    void enqueueTokenPick(int n, FwdKind k);
+    void enqueueDraw(int n, unsigned stages, const float *full);
+    void enqueueForward(int n, FwdKind k);
 
     // timing hook for profileForward (eager only)
     struct ProfScope;
@@ -433,7 +423,7 @@ class HipEngineImpl : public HipEngine {
     void enqueueSampled(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs);
     void readLogprobs();
     // logit processors (Backend::setLogitProcs), root rank only: per slot the dense token counts and
-    // the bias entries, the processed logits the sampler of a SAMPLE_PROC forward reads, and pinned
+    // the bias entries, the processed logits the sampler of a PROC forward reads, and pinned
     // staging of the bias entries | counts per slot (free once the previous forward was collected)
     uint32_t *dProcCounts_ = nullptr;              // [nSlots][vocab]
     hipk::LogitBiasEntry *dProcBias_ = nullptr, *hProcBias_ = nullptr;  // [nSlots][kMaxLogitBias]
@@ -441,7 +431,7 @@ class HipEngineImpl : public HipEngine {
     float *dProcLogits_ = nullptr;                 // [maxBatch][vocab]
     float4 *dProc_ = nullptr;                      // [maxBatch] per row, behind dSpec_ in the input block
     std::vector<float> procRows_;                  // host copy of the forward being set up
-    // candidate filter (top_k / min_p) of a SAMPLE_PROC_FILTER forward: per row (topK, delta, on, -)
+    // candidate filter (top_k / min_p) of a FILTER forward: per row (topK, delta, on, -)
     // behind dProc_ in the input block, and the filter's per-row state (its partial histograms and
     // maxima use the sampler's scratch, which the sampler rewrites before it reads it)
     hipk::LogitFilterRow *dFilter_ = nullptr;      // [maxBatch]
@@ -454,7 +444,6 @@ class HipEngineImpl : public HipEngine {
     uint2 *dJsonMeta_ = nullptr;                   // [vocab]
     uint32_t *dJsonWords_ = nullptr;
     uint4 *dJsonStates_ = nullptr;                 // [nSlots]
-    hipk::JsonMaskArgs jsonMaskArgs() const;
     // structured outputs (LogitProc::grammar), root rank only: per KV slot a table block
     // (hipk::kGrammarSlotBytes: the transition table, the class map, the accept bits, the head) and
     // a u32 state, installed by a fresh row ahead of its forward (enqueueGrammarInstall) and advanced
@@ -464,7 +453,7 @@ class HipEngineImpl : public HipEngine {
     uint32_t *dGrammarStates_ = nullptr;           // [nSlots]
     std::vector<std::shared_ptr<const GrammarDfa>> slotGrammar_;
     void enqueueGrammarInstall(size_t slot, const std::shared_ptr<const GrammarDfa> &g);
-    hipk::GrammarMaskArgs grammarMaskArgs() const;
+    hipk::ConstraintArgs constraintArgs() const;  // both masks and both advances, over dProcLogits_
     size_t procBytes() const;
     // pooling (Backend::setPooling), root rank only: the forward's pool rows and their per-slot run
     // index (hipk::poolPlan) behind one pinned staging block (free once the previous forward was
@@ -488,10 +477,10 @@ class HipEngineImpl : public HipEngine {
     void enqueuePoolReadback();            // the finalised slots' vectors to pinned memory
     void readPooled();                     // after the stream sync: Backend::lastEmbeddings()
     hipk::LogitProcArgs logitProcArgs(const float *raw) const;
-    // takes the pending processors of a sampled forward and returns its graph kind (SAMPLE: no row is
+    // takes the pending processors of a sampled forward and returns its draw stages (0: no row is
     // active); beginProcs fills procRows_ / filterRows_, enqueueProcState resets / uploads fresh slots
     void setJsonTable(std::shared_ptr<const JsonTokenTable> table) override;
-    GraphKind beginProcs(int n, const int *slots, const SampleSpec *specs, std::vector<LogitProc> &procs);
+    unsigned beginProcs(int n, const int *slots, const SampleSpec *specs, std::vector<LogitProc> &procs);
     void enqueueProcState(int n, const int *slots, const std::vector<LogitProc> &procs);
     // measured-sync slots (syncSlots, hipk::syncFoldWords) and their host copies: [0] the last
     // forward / chain, [1 + k] chain step k % kChainDepth (chainLaunch / chainCollect)
@@ -524,8 +513,8 @@ class HipEngineImpl : public HipEngine {
     void **dKvBases_ = nullptr;  // copyPrefix: every layer's K and V base (hipk::KvCopyArgs::bases)
 
     // graphs
-    std::map<int, hipGraphExec_t> graphs_;
-    std::unordered_set<int> graphSeen_;  // graph keys used once (captured on the second use)
+    std::map<GraphKey, hipGraphExec_t> graphs_;
+    std::unordered_set<GraphKey> graphSeen_;  // graph keys used once (captured on the second use)
     bool graphsBroken_ = false;
     bool profile_ = false;
     std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> profTimes_;

@@ -1,4 +1,4 @@
-// Structured outputs on the device (GrammarMaskArgs in kernels.h): the token mask of rows that
+// Structured outputs on the device (ConstraintArgs in kernels.h): the token mask of rows that
 // follow a compiled byte DFA, ahead of the sampler, and the state's advance behind it. The walk is
 // grammarStepToken of csrc/core/grammar_dfa.h, the same function the host runs, over a view of the
 // tables.
@@ -27,8 +27,8 @@ struct GrammarSlotTables {
     uint32_t nClasses, nStates;
 };
 
-__device__ __forceinline__ GrammarSlotTables grammarSlotTables(const GrammarMaskArgs &a, int slot) {
-    const uint8_t *base = a.tables + (size_t)slot * kGrammarSlotBytes;
+__device__ __forceinline__ GrammarSlotTables grammarSlotTables(const ConstraintArgs &a, int slot) {
+    const uint8_t *base = a.grammarTables + (size_t)slot * kGrammarSlotBytes;
     GrammarSlotTables t;
     t.next = reinterpret_cast<const uint16_t *>(base);
     t.classOf = base + kGrammarClassOff;
@@ -41,7 +41,7 @@ __device__ __forceinline__ GrammarSlotTables grammarSlotTables(const GrammarMask
     return t;
 }
 
-__device__ __forceinline__ bool grammarRowOn(const GrammarMaskArgs &a, int b) {
+__device__ __forceinline__ bool grammarRowOn(const ConstraintArgs &a, int b) {
     return a.spec[b].x >= 0.f && a.proc[b].w == kRowKindGrammar;
 }
 
@@ -63,14 +63,14 @@ struct GrammarLdsView {
 
 }  // namespace
 
-__global__ __launch_bounds__(kRowWg) void grammarMaskKernel(GrammarMaskArgs a) {
+__global__ __launch_bounds__(kRowWg) void grammarMaskKernel(ConstraintArgs a) {
     const int b = blockIdx.y;
     if (!grammarRowOn(a, b)) return;  // (uniform over the workgroup) the row is neither read nor written
     __shared__ uint32_t shClass[64];
     __shared__ uint16_t shRow[256];
     const int slot = a.slots[b];
     const GrammarSlotTables tb = grammarSlotTables(a, slot);
-    const uint32_t state = a.states[slot];
+    const uint32_t state = a.grammarStates[slot];
     const bool inside = state < tb.nStates;
     const int tid = (int)threadIdx.x;
     if (tid < 64) shClass[tid] = reinterpret_cast<const uint32_t *>(tb.classOf)[tid];
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(kRowWg) void grammarMaskKernel(GrammarMaskArgs a) {
 }
 
 // One thread per row.
-__global__ __launch_bounds__(64) void grammarAdvanceKernel(GrammarMaskArgs a, int B) {
+__global__ __launch_bounds__(64) void grammarAdvanceKernel(ConstraintArgs a, int B) {
     const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (b >= B || !grammarRowOn(a, b)) return;
     const int id = a.ids[b];
@@ -109,16 +109,16 @@ __global__ __launch_bounds__(64) void grammarAdvanceKernel(GrammarMaskArgs a, in
     v.nClasses = tb.nClasses;
     v.nStates = tb.nStates;
     const uint2 m = a.table.meta[id];
-    const uint32_t next = grammarStepToken(v, a.states[slot], a.table.words, m.x, m.y);
+    const uint32_t next = grammarStepToken(v, a.grammarStates[slot], a.table.words, m.x, m.y);
     if (next == kGrammarReject) return;
-    a.states[slot] = next;
+    a.grammarStates[slot] = next;
 }
 
-void launchGrammarMask(const GrammarMaskArgs &a, int B, hipStream_t s) {
+void launchGrammarMask(const ConstraintArgs &a, int B, hipStream_t s) {
     hipLaunchKernelGGL(grammarMaskKernel, dim3((a.vocab + kRowWg - 1) / kRowWg, B), dim3(kRowWg), 0, s, a);
 }
 
-void launchGrammarAdvance(const GrammarMaskArgs &a, int B, hipStream_t s) {
+void launchGrammarAdvance(const ConstraintArgs &a, int B, hipStream_t s) {
     hipLaunchKernelGGL(grammarAdvanceKernel, dim3((B + 63) / 64), dim3(64), 0, s, a, B);
 }
 

@@ -1,4 +1,4 @@
-// JSON mode on the device (JsonMaskArgs in kernels.h): the token mask ahead of the sampler and the
+// JSON mode on the device (ConstraintArgs in kernels.h): the token mask ahead of the sampler and the
 // automaton's advance behind it, so that a constrained request still leaves the device as token ids
 // only. The automaton is csrc/core/json_grammar.h, the same functions the host runs.
 //
@@ -33,15 +33,15 @@ __device__ __forceinline__ uint4 jsonPack(const JsonState &s) {
     return v;
 }
 
-__device__ __forceinline__ bool jsonRowOn(const JsonMaskArgs &a, int b) {
+__device__ __forceinline__ bool jsonRowOn(const ConstraintArgs &a, int b) {
     return a.spec[b].x >= 0.f && a.proc[b].w == kRowKindJson;
 }
 
-__global__ __launch_bounds__(kRowWg) void jsonMaskKernel(JsonMaskArgs a) {
+__global__ __launch_bounds__(kRowWg) void jsonMaskKernel(ConstraintArgs a) {
     const int b = blockIdx.y;
     if (!jsonRowOn(a, b)) return;  // (uniform over the workgroup) the row is neither read nor written
     __shared__ uint4 shState;
-    if (threadIdx.x == 0) shState = a.states[a.slots[b]];
+    if (threadIdx.x == 0) shState = a.jsonStates[a.slots[b]];
     __syncthreads();
     const JsonState st = jsonUnpack(shState);
     const int vocab = a.vocab;
@@ -56,23 +56,23 @@ __global__ __launch_bounds__(kRowWg) void jsonMaskKernel(JsonMaskArgs a) {
 }
 
 // One thread per row.
-__global__ __launch_bounds__(64) void jsonAdvanceKernel(JsonMaskArgs a, int B) {
+__global__ __launch_bounds__(64) void jsonAdvanceKernel(ConstraintArgs a, int B) {
     const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (b >= B || !jsonRowOn(a, b)) return;
     const int id = a.ids[b];
     if (id < 0 || id >= a.vocab) return;
-    uint4 *sp = a.states + a.slots[b];
+    uint4 *sp = a.jsonStates + a.slots[b];
     const uint2 m = a.table.meta[id];
     const JsonState next = jsonStepToken(jsonUnpack(*sp), a.table.words, m.x, m.y);
     if (jsonRejected(next)) return;
     *sp = jsonPack(next);
 }
 
-void launchJsonMask(const JsonMaskArgs &a, int B, hipStream_t s) {
+void launchJsonMask(const ConstraintArgs &a, int B, hipStream_t s) {
     hipLaunchKernelGGL(jsonMaskKernel, dim3((a.vocab + kRowWg - 1) / kRowWg, B), dim3(kRowWg), 0, s, a);
 }
 
-void launchJsonAdvance(const JsonMaskArgs &a, int B, hipStream_t s) {
+void launchJsonAdvance(const ConstraintArgs &a, int B, hipStream_t s) {
     hipLaunchKernelGGL(jsonAdvanceKernel, dim3((B + 63) / 64), dim3(64), 0, s, a, B);
 }
 

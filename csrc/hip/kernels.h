@@ -21,6 +21,7 @@
 #include <vector>
 
 namespace dl {
+struct GrammarDfa;  // csrc/core/grammar_dfa.h
 namespace hipk {
 
 // PRO_GLOBAL: activations are read straight from global memory in the main loop (Q80 blocks for
@@ -693,9 +694,32 @@ struct PoolArgs {
 };
 void launchPool(const PoolArgs &a, int B, hipStream_t s);
 
+// Constrained rows: what constrains a drawn row is the 4th float of its proc entry: 0 nothing,
+// kRowKindJson the JSON automaton, kRowKindGrammar a compiled grammar. Each pair of kernels below
+// takes its own kind only and neither reads nor writes the other's rows; all four take the same
+// arguments and walk the same token table.
+constexpr float kRowKindJson = 1.f;
+constexpr float kRowKindGrammar = 2.f;
+struct TokenTable {
+    const uint2 *meta = nullptr;      // [vocab] (offset in words, length | class << 16)
+    const uint32_t *words = nullptr;  // the pieces' bytes, zero-padded to 4-byte words
+};
+struct ConstraintArgs {
+    float *logits = nullptr;        // [B][vocab], masked in place
+    int vocab = 0;
+    const float4 *spec = nullptr;   // [B] (temperature, -, -, -)
+    const float4 *proc = nullptr;   // [B] (-, -, -, row kind)
+    const int *slots = nullptr;     // [B]
+    TokenTable table;
+    const int *ids = nullptr;       // [B] the drawn tokens (the advances)
+    uint4 *jsonStates = nullptr;             // [nSlots] JsonState
+    const uint8_t *grammarTables = nullptr;  // [nSlots][kGrammarSlotBytes]
+    uint32_t *grammarStates = nullptr;       // [nSlots]
+};
+
 // JSON mode (csrc/core/json_grammar.h): the token mask between the logit processors and the candidate
 // filter, and the automaton's advance behind the draw. A row b takes part when proc[b].w == kRowKindJson (its
-// request is in JSON mode) and spec[b].x >= 0 (it draws); its state is states[slots[b]].
+// request is in JSON mode) and spec[b].x >= 0 (it draws); its state is jsonStates[slots[b]].
 // launchJsonMask, in place on [B][vocab] logits: x[t] = -inf for every token t that is not allowed
 // in the row's state (jsonStepToken rejects), the others keep their bits; every other row is neither
 // read nor written. Grid (ceil(vocab / 256), B), one thread per token, which walks the token's bytes
@@ -703,35 +727,16 @@ void launchPool(const PoolArgs &a, int B, hipStream_t s);
 // neighbouring lanes' verdicts meet in one lane that stores the 16-byte vector (loading it first
 // only when the verdicts differ), the vocab % 4 tail is stored per element. No atomics, no scratch:
 // a row's result does not depend on the rest of the launch.
-// launchJsonAdvance, behind the draw: one thread per row steps states[slots[b]] by the bytes of
+// launchJsonAdvance, behind the draw: one thread per row steps jsonStates[slots[b]] by the bytes of
 // ids[b]; a token that is not allowed leaves the state as it is (jsonAdvanceHost). A forward holds
 // at most one drawn row per slot.
-struct JsonTable {
-    const uint2 *meta = nullptr;      // [vocab] (offset in words, length | class << 16)
-    const uint32_t *words = nullptr;  // the pieces' bytes, zero-padded to 4-byte words
-};
-struct JsonMaskArgs {
-    float *logits = nullptr;        // [B][vocab], masked in place
-    int vocab = 0;
-    const float4 *spec = nullptr;   // [B] (temperature, -, -, -)
-    const float4 *proc = nullptr;   // [B] (-, -, -, constrained)
-    const int *slots = nullptr;     // [B]
-    JsonTable table;
-    uint4 *states = nullptr;        // [nSlots] JsonState
-    const int *ids = nullptr;       // [B] the drawn tokens (launchJsonAdvance)
-};
-void launchJsonMask(const JsonMaskArgs &a, int B, hipStream_t s);
-void launchJsonAdvance(const JsonMaskArgs &a, int B, hipStream_t s);
-// What constrains a drawn row is the 4th float of its proc entry: 0 nothing, kRowKindJson the JSON
-// automaton (the kernels above), kRowKindGrammar a compiled grammar (the kernels below). Each pair
-// of kernels takes its own kind only and neither reads nor writes the other's rows.
-constexpr float kRowKindJson = 1.f;
-constexpr float kRowKindGrammar = 2.f;
+void launchJsonMask(const ConstraintArgs &a, int B, hipStream_t s);
+void launchJsonAdvance(const ConstraintArgs &a, int B, hipStream_t s);
 
 // Structured outputs (csrc/core/grammar_dfa.h): the token mask of rows that follow a compiled byte
 // DFA, in the JSON mask's place, and the state's advance behind the draw. A row b takes part when
 // proc[b].w == kRowKindGrammar and spec[b].x >= 0; its DFA is the table block of slot slots[b] and
-// its state is states[slots[b]] (one u32).
+// its state is grammarStates[slots[b]] (one u32).
 // A slot's table block is kGrammarSlotBytes: next[nStates][nClasses] (u16) from byte 0, classOf[256]
 // at kGrammarClassOff, the accept bits at kGrammarAcceptOff and (nClasses, nStates) as two u32 at
 // kGrammarHeadOff. The host installs only checked tables (grammarCheck): every entry of next is
@@ -743,25 +748,19 @@ constexpr float kRowKindGrammar = 2.f;
 // go to LDS. A token's first byte is decided from LDS, and so is every later byte that is still in
 // the row's state (the loop of a free string); the others follow next[] through global loads of
 // the read-only table. The store tail is the JSON mask's (maskStoreTail). No atomics, no scratch.
-// launchGrammarAdvance, behind the draw: one thread per row steps states[slots[b]] by ids[b]; a
+// launchGrammarAdvance, behind the draw: one thread per row steps grammarStates[slots[b]] by ids[b]; a
 // token that is not allowed, or an id outside [0, vocab), leaves the state as it is.
 constexpr size_t kGrammarClassOff = 262144;
 constexpr size_t kGrammarAcceptOff = kGrammarClassOff + 256;
 constexpr size_t kGrammarHeadOff = kGrammarAcceptOff + 512;
 constexpr size_t kGrammarSlotBytes = kGrammarHeadOff + 256;
-struct GrammarMaskArgs {
-    float *logits = nullptr;        // [B][vocab], masked in place
-    int vocab = 0;
-    const float4 *spec = nullptr;   // [B] (temperature, -, -, -)
-    const float4 *proc = nullptr;   // [B] (-, -, -, row kind)
-    const int *slots = nullptr;     // [B]
-    JsonTable table;
-    const uint8_t *tables = nullptr;  // [nSlots][kGrammarSlotBytes]
-    uint32_t *states = nullptr;       // [nSlots]
-    const int *ids = nullptr;         // [B] the drawn tokens (launchGrammarAdvance)
-};
-void launchGrammarMask(const GrammarMaskArgs &a, int B, hipStream_t s);
-void launchGrammarAdvance(const GrammarMaskArgs &a, int B, hipStream_t s);
+void launchGrammarMask(const ConstraintArgs &a, int B, hipStream_t s);
+void launchGrammarAdvance(const ConstraintArgs &a, int B, hipStream_t s);
+// Host: g's tables to a slot's table block `block` (device), as copies on `s` that read g's own arrays,
+// so the caller keeps g alive until they ran. Every part a walk can index is rewritten (next up to
+// nStates * nClasses, the class map, the accept words up to nStates, the head), so a block never
+// serves an earlier grammar's tables. The slot's state stays with the caller.
+void installGrammarTables(uint8_t *block, const GrammarDfa &g, hipStream_t s);
 
 // Round-trip f32 partial sums through Q80 blocks in place (the reference's ZQ cast before the
 // exchange) - used ahead of a plain all-reduce when the fused exchange is not available.

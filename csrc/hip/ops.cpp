@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <tuple>
 
 #include "../core/quant.h"
 #include "device_comm.h"
@@ -1421,59 +1422,140 @@ std::vector<float> logitFilter(const std::vector<float> &logits, int B, int voca
     return sc.download(g.logits, logits.size());
 }
 
+namespace {
+// The skeleton of the filter and mask benches: fresh rows of bell logits by a D2D copy, one stage on
+// them, the sampler on what the stage left. Every figure is a timeEagerUs window of its own.
+struct StageBench {
+    Scratch &sc;
+    int B, iters;
+    const float *src;
+    float *rows;  // what the stages and the sampler work on
+    size_t bytes;
+    hipk::SampleArgs sa;
+    StageBench(Scratch &sc_, int B_, int vocab, int iters_) : sc(sc_), B(B_), iters(iters_) {
+        const std::vector<float> logits = bellLogits(B, vocab);
+        src = sc.upload(logits);
+        rows = sc.alloc<float>(logits.size());
+        bytes = logits.size() * sizeof(float);
+        sa = benchSampleArgs(sc, rows, B, vocab);
+    }
+    void copy() const { DL_HIP(hipMemcpyAsync(rows, src, bytes, hipMemcpyDeviceToDevice, sc.s)); }
+    template <typename Launch>
+    double launchUs(Launch launch) const { return timeEagerUs(sc.s, iters, kBenchWarmups, launch); }
+    double copyUs() const { return launchUs([&] { copy(); }); }
+    template <typename Launch>
+    double copyStageUs(Launch stage) const {
+        return launchUs([&] {
+            copy();
+            stage();
+        });
+    }
+    double sampleUs() const { return launchUs([&] { hipk::launchSample(sa, B, sc.s); }); }
+};
+}  // namespace
+
 void benchLogitFilter(int B, int vocab, int topK, float delta, int iters, double &copyUs, double &copyFilterUs,
                       double &sampleUs) {
     DL_CHECK(B >= 1 && vocab >= 2 && iters >= 1, "bench_logit_filter arguments");
     Scratch sc;
-    const std::vector<float> logits = bellLogits(B, vocab);
     hipk::LogitFilterArgs g = logitFilterArgs(sc, B, vocab, std::vector<float>(B, 0.8f), std::vector<int>(B, topK),
                                               std::vector<float>(B, delta), std::vector<int>(B, 1));
-    const float *src = sc.upload(logits);
-    g.logits = sc.alloc<float>(logits.size());
-    const size_t bytes = logits.size() * sizeof(float);
-    const hipk::SampleArgs sa = benchSampleArgs(sc, g.logits, B, vocab);
-    auto copy = [&] { DL_HIP(hipMemcpyAsync(g.logits, src, bytes, hipMemcpyDeviceToDevice, sc.s)); };
-    copyUs = timeEagerUs(sc.s, iters, kBenchWarmups, copy);
-    copyFilterUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] {
-        copy();
-        hipk::launchLogitFilter(g, B, sc.s);
-    });
-    sampleUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] { hipk::launchSample(sa, B, sc.s); });  // on the filtered rows
+    const StageBench sb(sc, B, vocab, iters);
+    g.logits = sb.rows;
+    copyUs = sb.copyUs();
+    copyFilterUs = sb.copyStageUs([&] { hipk::launchLogitFilter(g, B, sc.s); });
+    sampleUs = sb.sampleUs();  // on the filtered rows
     sc.sync();
 }
 
 namespace {
-// table, spec / proc rows, slots (row b's state is states[b]) and the states of a JsonMaskArgs
-hipk::JsonMaskArgs jsonMaskArgs(Scratch &sc, int B, int vocab, const std::vector<float> &temps,
-                                const std::vector<int> &on, const std::vector<uint32_t> &off,
-                                const std::vector<uint32_t> &info, const std::vector<uint32_t> &words,
-                                const std::vector<uint32_t> &states) {
-    DL_CHECK(B >= 1 && vocab >= 1, "json_mask sizes");
-    DL_CHECK(temps.size() == (size_t)B && on.size() == (size_t)B && states.size() == (size_t)B * 4,
-             "json_mask: one temperature, flag and 4-word state per row");
-    DL_CHECK(off.size() == (size_t)vocab && info.size() == (size_t)vocab && !words.empty(), "json_mask: the table is [vocab]");
+// The token table on the device: per token (offset in words, length | class << 16), and the words.
+// (`op` names the entry point in the errors)
+hipk::TokenTable uploadTokenTable(Scratch &sc, int vocab, const std::vector<uint32_t> &off, const std::vector<uint32_t> &info,
+                                  const std::vector<uint32_t> &words, const std::string &op) {
+    DL_CHECK(vocab >= 1 && off.size() == (size_t)vocab && info.size() == (size_t)vocab && !words.empty(), op + ": the table is [vocab]");
     std::vector<uint32_t> meta((size_t)vocab * 2);
     for (int t = 0; t < vocab; t++) {
         const uint32_t len = info[t] & 0xffffu;
-        DL_CHECK((size_t)off[t] + (len + 3) / 4 <= words.size(), "json_mask: a piece lies outside the table's words");
+        DL_CHECK((size_t)off[t] + (len + 3) / 4 <= words.size(), op + ": a piece lies outside the table's words");
         meta[(size_t)t * 2] = off[t];
         meta[(size_t)t * 2 + 1] = info[t];
     }
-    std::vector<float> spec((size_t)B * 4, 0.f), proc((size_t)B * 4, 0.f);
-    std::vector<int> slots(B);
-    for (int b = 0; b < B; b++) {
-        spec[(size_t)b * 4] = temps[b];
-        proc[(size_t)b * 4 + 3] = on[b] ? 1.f : 0.f;
-        slots[b] = b;
+    hipk::TokenTable t;
+    t.meta = reinterpret_cast<const uint2 *>(sc.upload(meta));
+    t.words = sc.upload(words);
+    return t;
+}
+
+// The rows' spec (temperature, -, -, -) and proc (-, -, -, row kind) entries on the device.
+std::pair<const float4 *, const float4 *> uploadDrawRows(Scratch &sc, const std::vector<float> &temps, const std::vector<int> &kinds,
+                                                         const std::string &op) {
+    static_assert(hipk::kRowKindJson == 1.f && hipk::kRowKindGrammar == 2.f, "row kinds");
+    std::vector<float> spec(temps.size() * 4, 0.f), proc(temps.size() * 4, 0.f);
+    for (size_t b = 0; b < temps.size(); b++) {
+        DL_CHECK(kinds[b] >= 0 && kinds[b] <= 2, op + ": a row's kind is 0 (none), 1 (json) or 2 (grammar)");
+        spec[b * 4] = temps[b];
+        proc[b * 4 + 3] = (float)kinds[b];
     }
-    hipk::JsonMaskArgs g;
+    return {reinterpret_cast<const float4 *>(sc.upload(spec)), reinterpret_cast<const float4 *>(sc.upload(proc))};
+}
+
+// The table, the rows and their slots of a ConstraintArgs. The states follow from the entry point:
+// jsonArgs, or installGrammars.
+hipk::ConstraintArgs constraintArgs(Scratch &sc, const std::string &op, int vocab, const std::vector<float> &temps,
+                                    const std::vector<int> &kinds, const std::vector<int> &slots,
+                                    const std::vector<uint32_t> &off, const std::vector<uint32_t> &info,
+                                    const std::vector<uint32_t> &words) {
+    DL_CHECK(!temps.empty() && kinds.size() == temps.size() && slots.size() == temps.size(), op + ": one temperature, kind and slot per row");
+    hipk::ConstraintArgs g;
     g.vocab = vocab;
-    g.spec = reinterpret_cast<const float4 *>(sc.upload(spec));
-    g.proc = reinterpret_cast<const float4 *>(sc.upload(proc));
+    std::tie(g.spec, g.proc) = uploadDrawRows(sc, temps, kinds, op);
     g.slots = sc.upload(slots);
-    g.table.meta = reinterpret_cast<const uint2 *>(sc.upload(meta));
-    g.table.words = sc.upload(words);
-    g.states = reinterpret_cast<uint4 *>(sc.upload(states));
+    g.table = uploadTokenTable(sc, vocab, off, info, words, op);
+    return g;
+}
+
+// The JSON entry points' arguments: kind 1 where `on`, row b's slot is b and its state states[4 b ..].
+hipk::ConstraintArgs jsonArgs(Scratch &sc, int vocab, const std::vector<float> &temps, const std::vector<int> &on,
+                              const std::vector<uint32_t> &off, const std::vector<uint32_t> &info,
+                              const std::vector<uint32_t> &words, const std::vector<uint32_t> &states) {
+    const size_t B = temps.size();
+    DL_CHECK(on.size() == B && states.size() == B * 4, "json_mask: one temperature, flag and 4-word state per row");
+    std::vector<int> kinds(B), slots(B);
+    for (size_t b = 0; b < B; b++) {
+        kinds[b] = on[b] ? 1 : 0;
+        slots[b] = (int)b;
+    }
+    hipk::ConstraintArgs g = constraintArgs(sc, "json_mask", vocab, temps, kinds, slots, off, info, words);
+    g.jsonStates = reinterpret_cast<uint4 *>(sc.upload(states));
+    return g;
+}
+
+// The grammar entry points' arguments: a table block and a state per slot (a null grammar leaves its
+// block zero-filled, which allows nothing). The grammars outlive the call's stream work.
+hipk::ConstraintArgs grammarArgs(Scratch &sc, int vocab, const std::vector<float> &temps, const std::vector<int> &kinds,
+                                 const std::vector<int> &slots, const std::vector<uint32_t> &off,
+                                 const std::vector<uint32_t> &info, const std::vector<uint32_t> &words,
+                                 const std::vector<const GrammarDfa *> &grammars, const std::vector<uint32_t> &states) {
+    const size_t S = grammars.size();
+    DL_CHECK(S >= 1 && states.size() == S, "grammar_mask: one grammar (or none) and one state per slot");
+    uint8_t *blocks = sc.alloc<uint8_t>(S * hipk::kGrammarSlotBytes);  // (ahead of the rows and the table, as ever)
+    for (size_t s = 0; s < S; s++) {
+        if (!grammars[s]) continue;
+        const std::string bad = grammarCheck(*grammars[s]);
+        DL_CHECK(bad.empty(), "grammar_mask: malformed tables: " + bad);
+        hipk::installGrammarTables(blocks + s * hipk::kGrammarSlotBytes, *grammars[s], sc.s);
+    }
+    // (once, for all slots: without it the bench's advance figure, which is the cost of enqueueing a
+    //  launch, was 2 to 3 times the parent's: profiles/draw_stages.md)
+    DL_HIP(hipStreamSynchronize(sc.s));
+    hipk::ConstraintArgs g = constraintArgs(sc, "grammar_mask", vocab, temps, kinds, slots, off, info, words);
+    for (size_t b = 0; b < slots.size(); b++) {
+        DL_CHECK(slots[b] >= 0 && (size_t)slots[b] < S, "grammar_mask: slot out of range");
+        DL_CHECK(kinds[b] != 2 || grammars[slots[b]], "grammar_mask: a grammar row's slot holds no grammar");
+    }
+    g.grammarTables = blocks;
+    g.grammarStates = sc.upload(states);
     return g;
 }
 }  // namespace
@@ -1482,15 +1564,14 @@ std::vector<float> jsonMask(const std::vector<float> &logits, int B, int vocab, 
                             const std::vector<int> &on, const std::vector<uint32_t> &off,
                             const std::vector<uint32_t> &info, const std::vector<uint32_t> &words,
                             const std::vector<uint32_t> &states) {
-    DL_CHECK(B >= 1 && vocab >= 1 && logits.size() == (size_t)B * vocab, "json_mask: logits is [B][vocab]");
+    DL_CHECK(B >= 1 && vocab >= 1 && temps.size() == (size_t)B && logits.size() == (size_t)B * vocab, "json_mask: logits is [B][vocab]");
     Scratch sc;
-    hipk::JsonMaskArgs g = jsonMaskArgs(sc, B, vocab, temps, on, off, info, words, states);
+    hipk::ConstraintArgs g = jsonArgs(sc, vocab, temps, on, off, info, words, states);
     g.logits = sc.uploadGuardedTail(logits, kRowTailGuard, "the masked logits");
     hipk::launchJsonMask(g, B, sc.s);
     sc.sync();
     sc.checkGuards();
-    const std::vector<uint32_t> after = sc.download(reinterpret_cast<const uint32_t *>(g.states), states.size());
-    DL_CHECK(after == states, "json_mask: the launch changed a state");
+    DL_CHECK(sc.download(reinterpret_cast<const uint32_t *>(g.jsonStates), states.size()) == states, "json_mask: the launch changed a state");
     return sc.download(g.logits, logits.size());
 }
 
@@ -1501,11 +1582,11 @@ std::vector<uint32_t> jsonAdvance(int vocab, const std::vector<float> &temps, co
     const int B = (int)temps.size();
     DL_CHECK(ids.size() == (size_t)B, "json_advance: one drawn id per row");
     Scratch sc;
-    hipk::JsonMaskArgs g = jsonMaskArgs(sc, B, vocab, temps, on, off, info, words, states);
+    hipk::ConstraintArgs g = jsonArgs(sc, vocab, temps, on, off, info, words, states);
     g.ids = sc.upload(ids);
     hipk::launchJsonAdvance(g, B, sc.s);
     sc.sync();
-    return sc.download(reinterpret_cast<const uint32_t *>(g.states), states.size());
+    return sc.download(reinterpret_cast<const uint32_t *>(g.jsonStates), states.size());
 }
 
 void benchJsonMask(int B, int vocab, const std::vector<uint32_t> &off, const std::vector<uint32_t> &info,
@@ -1513,104 +1594,38 @@ void benchJsonMask(int B, int vocab, const std::vector<uint32_t> &off, const std
                    double &copyMaskUs, double &advanceUs, double &copyFilterUs, double &sampleUs) {
     DL_CHECK(B >= 1 && vocab >= 2 && iters >= 1 && state.size() == 4, "bench_json_mask arguments");
     Scratch sc;
-    const std::vector<float> logits = bellLogits(B, vocab);
     std::vector<uint32_t> states;
     for (int b = 0; b < B; b++) states.insert(states.end(), state.begin(), state.end());
-    hipk::JsonMaskArgs g = jsonMaskArgs(sc, B, vocab, std::vector<float>(B, 0.8f), std::vector<int>(B, 1), off, info, words, states);
+    hipk::ConstraintArgs g = jsonArgs(sc, vocab, std::vector<float>(B, 0.8f), std::vector<int>(B, 1), off, info, words, states);
     hipk::LogitFilterArgs f = logitFilterArgs(sc, B, vocab, std::vector<float>(B, 0.8f), std::vector<int>(B, 40),
                                               std::vector<float>(B, -INFINITY), std::vector<int>(B, 1));
-    const float *src = sc.upload(logits);
-    g.logits = sc.alloc<float>(logits.size());
-    f.logits = g.logits;
+    const StageBench sb(sc, B, vocab, iters);
+    g.logits = f.logits = sb.rows;
     // the advance steps a scratch copy of the states (so that the mask's stay put) by token 0's bytes
-    hipk::JsonMaskArgs adv = g;
-    adv.states = reinterpret_cast<uint4 *>(sc.upload(states));
+    hipk::ConstraintArgs adv = g;
+    adv.jsonStates = reinterpret_cast<uint4 *>(sc.upload(states));
     adv.ids = sc.alloc<int>(B);  // (alloc zero-fills)
-    const size_t bytes = logits.size() * sizeof(float);
-    const hipk::SampleArgs sa = benchSampleArgs(sc, g.logits, B, vocab);
-    auto copy = [&] { DL_HIP(hipMemcpyAsync(g.logits, src, bytes, hipMemcpyDeviceToDevice, sc.s)); };
-    copyUs = timeEagerUs(sc.s, iters, kBenchWarmups, copy);
-    copyFilterUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] {
-        copy();
-        hipk::launchLogitFilter(f, B, sc.s);
-    });
-    copyMaskUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] {
-        copy();
-        hipk::launchJsonMask(g, B, sc.s);
-    });
-    sampleUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] { hipk::launchSample(sa, B, sc.s); });  // on the masked rows
-    advanceUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] { hipk::launchJsonAdvance(adv, B, sc.s); });
+    copyUs = sb.copyUs();
+    copyFilterUs = sb.copyStageUs([&] { hipk::launchLogitFilter(f, B, sc.s); });
+    copyMaskUs = sb.copyStageUs([&] { hipk::launchJsonMask(g, B, sc.s); });
+    sampleUs = sb.sampleUs();  // on the masked rows
+    advanceUs = sb.launchUs([&] { hipk::launchJsonAdvance(adv, B, sc.s); });
     sc.sync();
 }
-
-namespace {
-// table, spec / proc rows, slots, the slots' table blocks and states of a GrammarMaskArgs
-hipk::GrammarMaskArgs grammarMaskArgs(Scratch &sc, int B, int vocab, const std::vector<float> &temps,
-                                      const std::vector<int> &kinds, const std::vector<int> &slots,
-                                      const std::vector<uint32_t> &off, const std::vector<uint32_t> &info,
-                                      const std::vector<uint32_t> &words, const std::vector<const GrammarDfa *> &grammars,
-                                      const std::vector<uint32_t> &states) {
-    const size_t S = grammars.size();
-    DL_CHECK(B >= 1 && vocab >= 1 && S >= 1, "grammar_mask sizes");
-    DL_CHECK(temps.size() == (size_t)B && kinds.size() == (size_t)B && slots.size() == (size_t)B && states.size() == S,
-             "grammar_mask: one temperature, kind and slot per row, one state per slot");
-    DL_CHECK(off.size() == (size_t)vocab && info.size() == (size_t)vocab && !words.empty(), "grammar_mask: the table is [vocab]");
-    std::vector<uint32_t> meta((size_t)vocab * 2);
-    for (int t = 0; t < vocab; t++) {
-        const uint32_t len = info[t] & 0xffffu;
-        DL_CHECK((size_t)off[t] + (len + 3) / 4 <= words.size(), "grammar_mask: a piece lies outside the table's words");
-        meta[(size_t)t * 2] = off[t];
-        meta[(size_t)t * 2 + 1] = info[t];
-    }
-    std::vector<float> spec((size_t)B * 4, 0.f), proc((size_t)B * 4, 0.f);
-    for (int b = 0; b < B; b++) {
-        DL_CHECK(slots[b] >= 0 && (size_t)slots[b] < S, "grammar_mask: slot out of range");
-        DL_CHECK(kinds[b] >= 0 && kinds[b] <= 2, "grammar_mask: a row's kind is 0 (none), 1 (json) or 2 (grammar)");
-        DL_CHECK(kinds[b] != 2 || grammars[slots[b]], "grammar_mask: a grammar row's slot holds no grammar");
-        spec[(size_t)b * 4] = temps[b];
-        proc[(size_t)b * 4 + 3] = (float)kinds[b];
-    }
-    static_assert(hipk::kRowKindJson == 1.f && hipk::kRowKindGrammar == 2.f, "row kinds");
-    uint8_t *blocks = sc.alloc<uint8_t>(S * hipk::kGrammarSlotBytes);  // (zero-filled: an empty slot allows nothing)
-    for (size_t s = 0; s < S; s++) {
-        const GrammarDfa *g = grammars[s];
-        if (!g) continue;
-        const std::string bad = grammarCheck(*g);
-        DL_CHECK(bad.empty(), "grammar_mask: malformed tables: " + bad);
-        uint8_t *base = blocks + s * hipk::kGrammarSlotBytes;
-        const uint32_t head[2] = {g->nClasses, g->nStates};
-        DL_HIP(hipMemcpyAsync(base, g->next.data(), g->next.size() * sizeof(uint16_t), hipMemcpyHostToDevice, sc.s));
-        DL_HIP(hipMemcpyAsync(base + hipk::kGrammarClassOff, g->classOf, 256, hipMemcpyHostToDevice, sc.s));
-        DL_HIP(hipMemcpyAsync(base + hipk::kGrammarAcceptOff, g->accept.data(), g->accept.size() * sizeof(uint32_t), hipMemcpyHostToDevice, sc.s));
-        DL_HIP(hipMemcpyAsync(base + hipk::kGrammarHeadOff, head, sizeof(head), hipMemcpyHostToDevice, sc.s));
-        DL_HIP(hipStreamSynchronize(sc.s));  // (head is a local)
-    }
-    hipk::GrammarMaskArgs g;
-    g.vocab = vocab;
-    g.spec = reinterpret_cast<const float4 *>(sc.upload(spec));
-    g.proc = reinterpret_cast<const float4 *>(sc.upload(proc));
-    g.slots = sc.upload(slots);
-    g.table.meta = reinterpret_cast<const uint2 *>(sc.upload(meta));
-    g.table.words = sc.upload(words);
-    g.tables = blocks;
-    g.states = sc.upload(states);
-    return g;
-}
-}  // namespace
 
 std::vector<float> grammarMask(const std::vector<float> &logits, int B, int vocab, const std::vector<float> &temps,
                                const std::vector<int> &kinds, const std::vector<int> &slots,
                                const std::vector<uint32_t> &off, const std::vector<uint32_t> &info,
                                const std::vector<uint32_t> &words, const std::vector<const GrammarDfa *> &grammars,
                                const std::vector<uint32_t> &states) {
-    DL_CHECK(B >= 1 && vocab >= 1 && logits.size() == (size_t)B * vocab, "grammar_mask: logits is [B][vocab]");
+    DL_CHECK(B >= 1 && vocab >= 1 && temps.size() == (size_t)B && logits.size() == (size_t)B * vocab, "grammar_mask: logits is [B][vocab]");
     Scratch sc;
-    hipk::GrammarMaskArgs g = grammarMaskArgs(sc, B, vocab, temps, kinds, slots, off, info, words, grammars, states);
+    hipk::ConstraintArgs g = grammarArgs(sc, vocab, temps, kinds, slots, off, info, words, grammars, states);
     g.logits = sc.uploadGuardedTail(logits, kRowTailGuard, "the masked logits");
     hipk::launchGrammarMask(g, B, sc.s);
     sc.sync();
     sc.checkGuards();
-    const std::vector<uint32_t> after = sc.download(g.states, states.size());
+    const std::vector<uint32_t> after = sc.download(g.grammarStates, states.size());
     DL_CHECK(after == states, "grammar_mask: the launch changed a state");
     return sc.download(g.logits, logits.size());
 }
@@ -1628,11 +1643,11 @@ std::vector<uint32_t> grammarAdvance(int vocab, const std::vector<float> &temps,
     std::sort(seen.begin(), seen.end());
     DL_CHECK(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "grammar_advance: two drawn rows share a slot");
     Scratch sc;
-    hipk::GrammarMaskArgs g = grammarMaskArgs(sc, B, vocab, temps, kinds, slots, off, info, words, grammars, states);
+    hipk::ConstraintArgs g = grammarArgs(sc, vocab, temps, kinds, slots, off, info, words, grammars, states);
     g.ids = sc.upload(ids);
     hipk::launchGrammarAdvance(g, B, sc.s);
     sc.sync();
-    return sc.download(g.states, states.size());
+    return sc.download(g.grammarStates, states.size());
 }
 
 void benchGrammarMask(int B, int vocab, const std::vector<uint32_t> &off, const std::vector<uint32_t> &info,
@@ -1640,37 +1655,25 @@ void benchGrammarMask(int B, int vocab, const std::vector<uint32_t> &off, const 
                       double &copyUs, double &copyMaskUs, double &advanceUs, double &copyJsonUs, double &sampleUs) {
     DL_CHECK(B >= 1 && vocab >= 2 && iters >= 1, "bench_grammar_mask arguments");
     Scratch sc;
-    const std::vector<float> logits = bellLogits(B, vocab);
     std::vector<int> slots(B);
     for (int b = 0; b < B; b++) slots[b] = b;
-    const std::vector<const GrammarDfa *> grammars(B, &grammar);
+    const std::vector<float> temps(B, 0.8f);
     const std::vector<uint32_t> states(B, state);
-    hipk::GrammarMaskArgs g = grammarMaskArgs(sc, B, vocab, std::vector<float>(B, 0.8f), std::vector<int>(B, 2), slots, off, info,
-                                              words, grammars, states);
+    hipk::ConstraintArgs g = grammarArgs(sc, vocab, temps, std::vector<int>(B, 2), slots, off, info, words,
+                                         std::vector<const GrammarDfa *>(B, &grammar), states);
     // the JSON mask on the same rows, every row at START
-    hipk::JsonMaskArgs j = jsonMaskArgs(sc, B, vocab, std::vector<float>(B, 0.8f), std::vector<int>(B, 1), off, info, words,
-                                        std::vector<uint32_t>((size_t)B * 4, 0u));
-    const float *src = sc.upload(logits);
-    g.logits = sc.alloc<float>(logits.size());
-    j.logits = g.logits;
+    hipk::ConstraintArgs j = jsonArgs(sc, vocab, temps, std::vector<int>(B, 1), off, info, words, std::vector<uint32_t>((size_t)B * 4, 0u));
+    const StageBench sb(sc, B, vocab, iters);
+    g.logits = j.logits = sb.rows;
     // the advance steps a scratch copy of the states (so that the mask's stay put) by token 0's bytes
-    hipk::GrammarMaskArgs adv = g;
-    adv.states = sc.upload(states);
+    hipk::ConstraintArgs adv = g;
+    adv.grammarStates = sc.upload(states);
     adv.ids = sc.alloc<int>(B);  // (alloc zero-fills)
-    const size_t bytes = logits.size() * sizeof(float);
-    const hipk::SampleArgs sa = benchSampleArgs(sc, g.logits, B, vocab);
-    auto copy = [&] { DL_HIP(hipMemcpyAsync(g.logits, src, bytes, hipMemcpyDeviceToDevice, sc.s)); };
-    copyUs = timeEagerUs(sc.s, iters, kBenchWarmups, copy);
-    copyJsonUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] {
-        copy();
-        hipk::launchJsonMask(j, B, sc.s);
-    });
-    copyMaskUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] {
-        copy();
-        hipk::launchGrammarMask(g, B, sc.s);
-    });
-    sampleUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] { hipk::launchSample(sa, B, sc.s); });  // on the masked rows
-    advanceUs = timeEagerUs(sc.s, iters, kBenchWarmups, [&] { hipk::launchGrammarAdvance(adv, B, sc.s); });
+    copyUs = sb.copyUs();
+    copyJsonUs = sb.copyStageUs([&] { hipk::launchJsonMask(j, B, sc.s); });
+    copyMaskUs = sb.copyStageUs([&] { hipk::launchGrammarMask(g, B, sc.s); });
+    sampleUs = sb.sampleUs();  // on the masked rows
+    advanceUs = sb.launchUs([&] { hipk::launchGrammarAdvance(adv, B, sc.s); });
     sc.sync();
 }
 

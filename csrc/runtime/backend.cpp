@@ -318,10 +318,10 @@ std::vector<LogitProc> Backend::takeLogitProcs(int n) {
         any = true;
         if (p.topK < 0) throw Error("top_k: a count >= 0");
         if (!(p.minP >= 0.f && p.minP <= 1.f)) throw Error("min_p: a number from 0 to 1");
-        if (p.json && plan().rank == 0 && !jsonTable_) throw Error("json mode: no token table (setJsonTable)");
+        if ((p.json || p.grammar) && plan().rank == 0 && !jsonTable_)
+            throw Error(std::string(p.json ? "json mode" : "json_schema") + ": no token table (setJsonTable)");
         if (p.grammar) {
             if (p.json) throw Error("logit processors: a row is either in JSON mode or follows a grammar, not both");
-            if (plan().rank == 0 && !jsonTable_) throw Error("json_schema: no token table (setJsonTable)");
             if (p.fresh) {  // (the slot keeps the grammar its fresh row brought: checked once)
                 const std::string bad = grammarCheck(*p.grammar);
                 if (!bad.empty()) throw Error("json_schema: malformed grammar tables: " + bad);
@@ -339,6 +339,31 @@ std::vector<LogitProc> Backend::takeLogitProcs(int n) {
     }
     if (!any) procs.clear();  // no active row: the forward is the plain one
     return procs;
+}
+
+// (a request is of one kind throughout: a fresh row begins its own kind's state and leaves the other,
+//  and every row masks and advances by its own kind)
+void Backend::ConstraintSlot::begin(const LogitProc &p) {
+    if (p.grammar) {
+        dfa = p.grammar;
+        state = dfa->start;
+    } else {
+        json = jsonStart();
+    }
+}
+
+void Backend::ConstraintSlot::mask(float *row, int vocab, const JsonTokenTable &table, bool grammar) const {
+    if (grammar)
+        grammarMaskHost(row, vocab, table, *dfa, state);
+    else
+        jsonMaskHost(row, vocab, table, json);
+}
+
+void Backend::ConstraintSlot::advance(const JsonTokenTable &table, bool grammar, int id) {
+    if (grammar)
+        state = grammarAdvanceHost(table, *dfa, state, id);
+    else
+        json = jsonAdvanceHost(table, json, id);
 }
 
 void Backend::forwardSample(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs,
@@ -389,28 +414,18 @@ void Backend::forwardSample(int n, const int *tokens, const int *positions, cons
             if (p.fresh) procBias_[s] = p.bias;
             logitProcHost(row, vocab, procCounts_[s].data(), p.presence, p.frequency, procBias_[s].data(),
                           (int)procBias_[s].size(), row);
-            if (p.json) {  // behind the bias, ahead of the candidate filter: top_k counts allowed tokens
-                if (jsonStates_.size() <= s) jsonStates_.resize(s + 1, jsonStart());
-                if (p.fresh) jsonStates_[s] = jsonStart();
-                jsonMaskHost(row, vocab, *jsonTable_, jsonStates_[s]);
-            }
-            if (p.grammar) {  // in the JSON mask's place
-                if (grammarSlots_.size() <= s) grammarSlots_.resize(s + 1);
-                GrammarSlot &gs = grammarSlots_[s];
-                if (p.fresh) gs = GrammarSlot{p.grammar, p.grammar->start};
-                if (gs.dfa != p.grammar) throw Error("json_schema: a row that is not fresh carries another grammar than its slot's");
-                grammarMaskHost(row, vocab, *jsonTable_, *gs.dfa, gs.state);
+            if (p.json || p.grammar) {  // behind the bias, ahead of the candidate filter: top_k counts allowed tokens
+                if (constraintSlots_.size() <= s) constraintSlots_.resize(s + 1);
+                if (p.fresh) constraintSlots_[s].begin(p);
+                if (p.grammar && constraintSlots_[s].dfa != p.grammar) throw Error("json_schema: a row that is not fresh carries another grammar than its slot's");
+                constraintSlots_[s].mask(row, vocab, *jsonTable_, p.grammar != nullptr);
             }
             if (p.filter(specs[i].temperature, vocab))
                 logitFilterHost(row, vocab, p.topK, minPDelta(specs[i].temperature, p.minP));
         }
         out[i] = sampleHost(row, vocab, specs[i]);
-        if (proc && procs[i].grammar) {
-            GrammarSlot &gs = grammarSlots_[(size_t)slots[i]];
-            gs.state = grammarAdvanceHost(*jsonTable_, *gs.dfa, gs.state, out[i]);
-        }
         if (proc && out[i] >= 0 && out[i] < vocab) procCounts_[(size_t)slots[i]][out[i]]++;
-        if (proc && procs[i].json) jsonStates_[(size_t)slots[i]] = jsonAdvanceHost(*jsonTable_, jsonStates_[(size_t)slots[i]], out[i]);
+        if (proc && (procs[i].json || procs[i].grammar)) constraintSlots_[(size_t)slots[i]].advance(*jsonTable_, procs[i].grammar != nullptr, out[i]);
         if (req >= 1)
             logprobsHost(raw.data(), vocab, !targets.empty() && targets[i] >= 0 ? targets[i] : out[i], std::min(req - 1, kMaxTopLogprobs),
                          &logprobs_[(size_t)i * kLogprobEntries]);

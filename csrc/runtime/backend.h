@@ -306,12 +306,17 @@ class Backend {
     std::vector<std::vector<u32>> procCounts_;
     std::vector<std::vector<LogitBias>> procBias_;
     std::shared_ptr<const JsonTokenTable> jsonTable_;
-    std::vector<JsonState> jsonStates_;  // host state of the default forwardSample, per slot
-    struct GrammarSlot {
+    // what confines a slot's draws in the default forwardSample: the JSON automaton's state, or a
+    // grammar with its state; a fresh row begins its kind's, each row masks and advances by its kind
+    struct ConstraintSlot {
+        JsonState json = jsonStart();
         std::shared_ptr<const GrammarDfa> dfa;
         u32 state = 0;
+        void begin(const LogitProc &p);
+        void mask(float *row, int vocab, const JsonTokenTable &table, bool grammar) const;
+        void advance(const JsonTokenTable &table, bool grammar, int id);
     };
-    std::vector<GrammarSlot> grammarSlots_;  // the same for structured outputs
+    std::vector<ConstraintSlot> constraintSlots_;
     std::vector<PoolSpec> pendingPool_;  // setPooling, until the next forward takes it
     PooledSlots pooled_;
     // takes pendingPool_ for a forward of n rows (empty: none set, or no row takes part); checks the

@@ -16,6 +16,7 @@
 #include "../../csrc/core/plan.h"
 #include "../../csrc/core/quant.h"
 #include "../../csrc/cpu/cpu_ops.h"
+#include "../../csrc/hip/graph_key.h"
 #include "../../csrc/net/json.h"
 #include "../../csrc/text/tokenizer.h"
 
@@ -192,6 +193,53 @@ int main() {
             CHECK(threw);  // short read past the end of the file
         }
         ::unlink(path);
+        return ok;
+    });
+    run("graph key: every combination of fields has its own key, which decodes back; a wider value is refused", [] {
+        using namespace engine_detail;
+        bool ok = true;
+        // fields walked from the most to the least significant one: strictly increasing keys are distinct keys
+        long long count = 0, notAbove = 0, notBack = 0, last = -1;
+        for (unsigned rows = 1; rows <= kKeyMaxRows; rows++)
+            for (unsigned kind = 0; kind < kGraphKinds; kind++)
+                for (unsigned stages = 0; stages < kDrawStageSets; stages++)
+                    for (int prefillOk = 0; prefillOk < 2; prefillOk++)
+                        for (int attnLong = 0; attnLong < 2; attnLong++)
+                            for (unsigned bucket = 0; bucket <= kKeyMaxBucket; bucket++) {
+                                const GraphKey k = graphKey({bucket, attnLong != 0, prefillOk != 0, stages, (GraphKind)kind, rows});
+                                const GraphKeyFields f = graphKeyFields(k);
+                                notAbove += (long long)k <= last;
+                                notBack += !(f.bucket == bucket && f.attnLong == (attnLong != 0) && f.prefillOk == (prefillOk != 0) &&
+                                             f.stages == stages && (unsigned)f.kind == kind && f.rows == rows);
+                                last = k;
+                                count++;
+                            }
+        CHECK(count == (long long)kKeyMaxRows * kGraphKinds * kDrawStageSets * 4 * (kKeyMaxBucket + 1));
+        CHECK(notAbove == 0);
+        CHECK(notBack == 0);
+        const GraphKeyFields fits{kKeyMaxBucket, true, true, kDrawStageSets - 1, GraphKind::EMBED, kKeyMaxRows};
+        auto refused = [](GraphKeyFields f) {
+            try {
+                (void)graphKey(f);
+            } catch (const Error &) {
+                return true;
+            }
+            return false;
+        };
+        CHECK(!refused(fits));
+        GraphKeyFields f = fits;
+        f.bucket = kKeyMaxBucket + 1;
+        CHECK(refused(f));
+        f = fits;
+        f.stages = kDrawStageSets;
+        CHECK(refused(f));
+        f = fits;
+        f.kind = (GraphKind)kGraphKinds;
+        CHECK(refused(f));
+        f = fits;
+        f.rows = kKeyMaxRows + 1;
+        CHECK(refused(f));
+        static_assert(graphKeyFields(graphKey({3, false, true, PROC | JSON, GraphKind::SAMPLE, 7})).stages == (PROC | JSON), "constexpr");
         return ok;
     });
     std::printf("%d/%d native unit tests passed\n", gRun - gFailed, gRun);

@@ -179,6 +179,49 @@ def test_engine_grammar_rows_follow_the_host_pipeline(C, assets, synth_table, gr
     run_grammar_rows(_engine(C, assets, synth_table, use_graphs=graphs), C, synth_table, steps=6)
 
 
+@pytest.fixture(scope="module")
+def stage_backends(C, assets, synth_table):
+    """One HIP engine with graphs on and the CPU backend, for every stage set: f32 weights and f32 KV,
+    where the two backends' logits agree to 1e-4 of their range (test_gpu_engine.py)."""
+    gpu = C.HipEngine(assets["f32"], "f32", kv_bf16=False, max_batch=64, n_slots=4, use_graphs=True)
+    cpu = C.cpu_backend(assets["f32"], "f32", 2, 128, 64, 4)
+    gpu.set_json_table(synth_table)
+    cpu.set_json_table(synth_table)
+    return gpu, cpu
+
+
+@pytest.mark.parametrize("grammar", [False, True])
+@pytest.mark.parametrize("json_mode", [False, True])
+@pytest.mark.parametrize("filtered", [False, True])
+def test_engine_every_stage_set_draws_what_the_cpu_backend_draws(C, stage_backends, synth_table, filtered, json_mode, grammar):
+    """The 8 sets of draw stages that a forward with processors can have, each as the same 2-row forward
+    run three times from fresh slots on one engine: the eager first use of its graph key, the capture
+    and a replay. Every set has the rows, bucket and flags of the others, so only its stages keep its
+    graph apart from theirs; all three runs equal the CPU backend's draw for the same rows. Both rows
+    are drawn flat (T = 1.5, no top-p) with coins past the mass of their 3 best tokens, so top_k = 3
+    changes a draw in every set (the grammar's start state allows one token: there the other row's
+    draw moves), which the CPU backend's own ids must show."""
+    gpu, cpu = stage_backends
+
+    def procs(with_filter):
+        row0 = dict(presence=0.5, frequency=0.25, bias={34: 1.0}, fresh=True)
+        row1 = dict(bias={35: 0.5}, fresh=True)
+        if grammar:
+            row0["grammar"] = compile_case(C, "flat", synth_table)
+            row1["json"] = json_mode
+        else:
+            row0["json"] = json_mode
+        if with_filter:
+            row0["top_k"] = row1["top_k"] = 3
+        return [row0, row1]
+
+    args = ([65, 66], [0, 0], [0, 1], [1.5, 1.5], [1.0, 1.0], [0.9, 0.5])
+    want = cpu.forward_sample(*args, logit_procs=procs(filtered))
+    assert want != cpu.forward_sample(*args, logit_procs=procs(not filtered))  # the filter decides a draw
+    for use in ("eager", "capture", "replay"):
+        assert gpu.forward_sample(*args, logit_procs=procs(filtered)) == want, use
+
+
 def test_engine_mixed_forward_equals_each_row_on_its_own_path(C, assets, synth_table):
     """One forward with a schema row, a JSON-mode row, a penalties row and a plain row: every row draws
     what it draws in an engine whose forwards hold that row's processor only (the existing paths for
