@@ -133,7 +133,7 @@ class CpuBackend : public Backend {
         q80_ = cfg.bufferType == FloatType::Q80;
         DL_CHECK(cfg.syncType == FloatType::F32 || cfg.syncType == FloatType::Q80, "sync type must be f32 or q80");
         syncQ80_ = cfg.syncType == FloatType::Q80;
-        if (h_.weightType == FloatType::Q40 && !q80_)
+        if ((h_.weightType == FloatType::Q40 || h_.weightType == FloatType::Q80) && !q80_)
             throw Error("This version supports only Q40 weights with Q80 sync type");
         if (h_.weightType == FloatType::F32 && q80_)
             throw Error("F32 weights require --buffer-float-type f32");
@@ -252,9 +252,13 @@ class CpuBackend : public Backend {
             cpu::matmulF32((const float *)W.data, W.rows, W.cols, xf.data(), B, ys, pool_);
             return;
         }
-        DL_CHECK(W.type == FloatType::Q40 && q80_, "Q40 matmul needs Q80 activations");
+        DL_CHECK((W.type == FloatType::Q40 || W.type == FloatType::Q80) && q80_, "quantized matmul needs Q80 activations");
         std::vector<const BlockQ80 *> xq(B);
         for (int t = 0; t < B; t++) xq[t] = xs[t]->q.data();
+        if (W.type == FloatType::Q80) {
+            cpu::matmulQ80Q80((const BlockQ80 *)W.data, W.rows, W.cols, xq.data(), B, ys, pool_);
+            return;
+        }
         cpu::matmulQ40Q80((const BlockQ40 *)W.data, W.rows, W.cols, xq.data(), B, ys, pool_);
     }
 

@@ -44,6 +44,44 @@ static float hsum(__m256 v) {
     return _mm_cvtss_f32(s);
 }
 
+void matmulQ80Q80(const BlockQ80 *w, u32 rows, u32 cols, const BlockQ80 *const *xs, int B, float *const *ys,
+                  ThreadPool &pool) {
+    DL_CHECK(cols % kQBlock == 0, "matmulQ80Q80: cols % 32");
+    const u32 nb = cols / kQBlock;
+    std::vector<float> xd((size_t)B * nb);
+    for (int t = 0; t < B; t++)
+        for (u32 b = 0; b < nb; b++) xd[(size_t)t * nb + b] = f16ToF32(xs[t][b].d);
+    pool.parallelFor(rows, [&](long s, long e) {
+        const __m256i ones = _mm256_set1_epi16(1);
+        for (long r = s; r < e; r++) {
+            const BlockQ80 *wr = w + (u64)r * nb;
+            for (int t0 = 0; t0 < B; t0 += kGroup) {
+                const int g = std::min(kGroup, B - t0);
+                float acc[kGroup];
+                for (int t = 0; t < g; t++) acc[t] = 0.f;
+                for (u32 b = 0; b < nb; b++) {
+                    // |w| <= 128 as an unsigned byte times the sign-transferred x: pairs sum to at
+                    // most 2 * 128 * 127 < 2^15, so maddubs does not saturate
+                    const __m256i wq = _mm256_loadu_si256(reinterpret_cast<const __m256i *>(wr[b].qs));
+                    const __m256i aw = _mm256_sign_epi8(wq, wq);
+                    const float dw = f16ToF32(wr[b].d);
+                    for (int t = 0; t < g; t++) {
+                        const __m256i xq = _mm256_loadu_si256(reinterpret_cast<const __m256i *>(xs[t0 + t][b].qs));
+                        const __m256i p16 = _mm256_maddubs_epi16(aw, _mm256_sign_epi8(xq, wq));
+                        const __m256i p32 = _mm256_madd_epi16(p16, ones);
+                        // the eight lanes to one exact int32 block sum, then one scaled f32 term
+                        __m128i q = _mm_add_epi32(_mm256_castsi256_si128(p32), _mm256_extracti128_si256(p32, 1));
+                        q = _mm_add_epi32(q, _mm_shuffle_epi32(q, 0x4E));
+                        q = _mm_add_epi32(q, _mm_shuffle_epi32(q, 0xB1));
+                        acc[t] += (dw * xd[(size_t)(t0 + t) * nb + b]) * (float)_mm_cvtsi128_si32(q);
+                    }
+                }
+                for (int t = 0; t < g; t++) ys[t0 + t][r] = acc[t];
+            }
+        }
+    });
+}
+
 void matmulF32(const float *w, u32 rows, u32 n, const float *const *xs, int B, float *const *ys, ThreadPool &pool) {
     DL_CHECK(n % 8 == 0, "f32 matmul: columns must be a multiple of 8");
     pool.parallelFor(rows, [&](long s, long e) {

@@ -23,6 +23,9 @@ void ropeApply(float *v, u32 len, u32 pos, u32 headSize, const float *table);
 // ys[t][r] = W[r,:] . xs[t] for r < rows, t < B; every weight row is read once for all B rows
 void matmulQ40Q80(const BlockQ40 *w, u32 rows, u32 cols, const BlockQ80 *const *xs, int B, float *const *ys,
                   ThreadPool &pool);
+// The same on Q80 weight blocks: y = sum_j f32(dw) * dx * (sum_i qw * qx), the inner sum exact.
+void matmulQ80Q80(const BlockQ80 *w, u32 rows, u32 cols, const BlockQ80 *const *xs, int B, float *const *ys,
+                  ThreadPool &pool);
 void matmulF32(const float *w, u32 rows, u32 cols, const float *const *xs, int B, float *const *ys, ThreadPool &pool);
 
 }  // namespace cpu

@@ -36,10 +36,14 @@ HipEngineImpl::HipEngineImpl(const EngineConfig &cfg, DeviceComm *comm) : cfg_(c
         h_ = file_->header();
     }
     plan_ = ShardPlan::make(h_, nRanks, rank);
-    q40_ = h_.weightType == FloatType::Q40;
-    if (q40_ && cfg.bufferType != FloatType::Q80)
+    switch (h_.weightType) {
+        case FloatType::Q40: wkind_ = WeightKind::Q40; break;
+        case FloatType::Q80: wkind_ = WeightKind::Q80; break;
+        case FloatType::F32: wkind_ = WeightKind::F32; break;
+        default: throw Error("unsupported weight type");
+    }
+    if (blocks() && cfg.bufferType != FloatType::Q80)
         throw Error("This version supports only Q40 weights with Q80 sync type");
-    if (!q40_ && h_.weightType != FloatType::F32) throw Error("unsupported weight type");
     DL_CHECK(h_.headSize() == 64 || h_.headSize() == 128, "GPU kernels support head size 64 or 128");
     DL_CHECK(cfg.maxBatch >= 1 && cfg.nSlots >= 1, "maxBatch/nSlots");
     DL_CHECK(cfg.maxBatch <= kKeyMaxRows, "maxBatch: more rows than a graph key holds");

@@ -144,6 +144,91 @@ double benchGemmQ40(int rows, int n, int M, int epi, int copies, int iters, std:
     return us;
 }
 
+// Q80-weight GEMV (gemvQ80wKernel) on synthetic planes, timed as benchGemvQ40. depth > 0: the
+// depth-sweep instance (B = 1, PRO_GLOBAL, EPI_STORE).
+double benchGemvQ80w(int rows, int n, int pro, int epi, int B, int lanes, int passes, int depth, int copies, int iters) {
+    DL_CHECK(epi == hipk::EPI_STORE && rows > 0 && n % 32 == 0 && copies >= 1, "bad Q80 gemv bench shape");
+    Scratch sc;
+    hipStream_t s = sc.s;
+    const int L = lanes > 0 ? lanes : hipk::gemvLanesPerRow(n, rows, 1, true);
+    const hipk::Q80Tiling t = hipk::q80Tiling(rows, n, L);
+    std::vector<uint8_t *> q(copies);
+    std::vector<uint16_t *> d(copies);
+    for (int c = 0; c < copies; c++) {
+        q[c] = sc.allocRaw<uint8_t>(t.qBytes);
+        d[c] = sc.allocRaw<uint16_t>(t.dBytes / 2);
+        hipk::launchFillQ80w(q[c], d[c], t.qBytes / 16, t.dBytes / 2, 1e-3f, 77 + c, s);
+    }
+    float *x = sc.allocRaw<float>((size_t)B * n), *w = sc.allocRaw<float>(n);
+    hipk::launchFillF32Uniform(x, (size_t)B * n, 1.f, 1, s);
+    hipk::launchFillF32Const(w, n, 1.f, s);
+    int8_t *aq = sc.allocRaw<int8_t>((size_t)B * n);
+    DL_HIP(hipMemsetAsync(aq, 1, (size_t)B * n, s));
+    hipk::GemvArgs a;
+    a.rows = rows;
+    a.n = n;
+    a.lanes = L;
+    const int rp = 256 / L * 2, grid0 = (rows + rp - 1) / rp;
+    a.passes = passes > 0 ? passes : (grid0 + 511) / 512;
+    a.in = x;
+    a.ldIn = n;
+    a.normW = w;
+    a.aq = aq;
+    a.as = sc.alloc<float2>((size_t)B * n / 32);
+    a.out = sc.allocRaw<float>((size_t)B * rows);
+    a.ldOut = rows;
+    return timeGraphUs(s, iters, [&](int c) {
+        a.qs = q[c % copies];
+        a.wd = d[c % copies];
+        hipk::launchGemvQ80w(a, B, pro, epi, s, depth);
+    });
+}
+
+// Batched GEMM on Q80 (fetch 0 / 8 / 16: launchGemmQ80w) or F32 (f32 = true: gemmF32Kernel) weights, EPI_STORE.
+double benchGemmQ80w(int rows, int n, int M, bool f32, int fetch, int copies, int iters) {
+    DL_CHECK(M >= 1 && M <= hipk::kGemmF32MaxTokens && hipk::gemmSupported(n) && rows % 64 == 0 && copies >= 1,
+             "bad gemm bench shape");
+    Scratch sc;
+    hipStream_t s = sc.s;
+    const int L = hipk::gemvLanesPerRow(n, rows, 1, true);
+    const hipk::Q80Tiling t = hipk::q80Tiling(rows, n, L);
+    std::vector<uint8_t *> q(copies);
+    std::vector<uint16_t *> d(copies);
+    std::vector<float *> wf(copies);
+    for (int c = 0; c < copies; c++) {
+        if (f32) {
+            wf[c] = sc.allocRaw<float>((size_t)rows * n);
+            hipk::launchFillF32Uniform(wf[c], (size_t)rows * n, 1e-2f, 77 + c, s);
+        } else {
+            q[c] = sc.allocRaw<uint8_t>(t.qBytes);
+            d[c] = sc.allocRaw<uint16_t>(t.dBytes / 2);
+            hipk::launchFillQ80w(q[c], d[c], t.qBytes / 16, t.dBytes / 2, 1e-3f, 77 + c, s);
+        }
+    }
+    const int MP = hipk::gemmTokenPad(M);
+    _Float16 *x = sc.alloc<_Float16>((size_t)MP * n);
+    hipk::launchFillF32Uniform((float *)x, (size_t)MP * n / 2, 1e-3f, 3, s);  // small finite f16 pairs
+    const size_t part = hipk::gemmPartFloats(rows, n, M);
+    hipk::GemmArgs g;
+    g.e.rows = rows;
+    g.e.n = n;
+    g.e.lanes = L;
+    g.e.out = sc.alloc<float>((size_t)M * rows);
+    g.e.ldOut = rows;
+    g.x = x;
+    g.M = M;
+    g.splits = hipk::gemmSplits(rows, n, M);
+    g.part = part ? sc.alloc<float>(part) : nullptr;
+    g.counters = sc.alloc<int>((size_t)rows / 64 + 1);
+    return timeGraphUs(s, iters, [&](int c) {
+        g.e.qs = q[c % copies];
+        g.e.wd = d[c % copies];
+        g.e.wf = wf[c % copies];
+        if (f32) hipk::launchGemmF32(g, hipk::EPI_STORE, s);
+        else hipk::launchGemmQ80w(g, hipk::EPI_STORE, s, fetch);
+    });
+}
+
 double benchAttention(int nHeads0, int kvMul, int hs, int seqLen, int pos, int B, int copies, int iters,
                       std::vector<unsigned long long> *trace, bool kvBf16) {
     DL_CHECK(kvMul >= 1 && nHeads0 % kvMul == 0 && pos >= 0 && pos < seqLen && B >= 1, "bad attention bench shape");

@@ -106,9 +106,9 @@ int HipEngineImpl::batchChunk(const DevMat &m, int pro, int epi) const {
     // measured 2x slower than the MFMA GEMM: the GEMV's per-row int8 dots are VALU-bound there)
     int bc = 4;
     while (bc > 1) {
-        const int rp = q40_ ? 256 / m.lanes * hipk::gemvRowGroup(bc, true) : hipk::gemvRowsPerPass(m.n, m.rows, bc, false);
+        const int rp = blocks() ? 256 / m.lanes * hipk::gemvRowGroup(bc, true) : hipk::gemvRowsPerPass(m.n, m.rows, bc, false);
         const int rpw = rp * passesFor(m, epi, bc);
-        if (hipk::gemvLdsBytes(m.n, bc, q40_, rpw, pro) <= 64 * 1024) break;  // B > 1 only; B = 1 may use up to 160 KB
+        if (hipk::gemvLdsBytes(m.n, bc, blocks(), rpw, pro) <= 64 * 1024) break;  // B > 1 only; B = 1 may use up to 160 KB
         bc >>= 1;
     }
     return bc;
@@ -177,7 +177,10 @@ void HipEngineImpl::gemv(const DevMat &m, int n, int pro, int epi, const MatOper
         int bc = n - c0;
         if (bc > bcMax) bc = bcMax;
         while (bc & (bc - 1)) bc &= bc - 1;  // 1, 2 or 4 rows per launch
-        hipk::launchGemv(gemvArgs(m, c0, bc, epi, o), bc, pro, epi, q40_, stream_);
+        if (q80w())
+            hipk::launchGemvQ80w(gemvArgs(m, c0, bc, epi, o), bc, pro, epi, stream_);
+        else
+            hipk::launchGemv(gemvArgs(m, c0, bc, epi, o), bc, pro, epi, q40(), stream_);
         c0 += bc;
     }
     xChunk_ = 0;
@@ -228,8 +231,8 @@ hipk::AttnArgs HipEngineImpl::attnArgs(const DevLayer &L, bool bat) const {
     a.partO = dPartO_;
     a.partML = dPartML_;
     a.out = dAtt_;
-    a.outQ = q40_ && !bat ? dAttQ_ : nullptr;
-    a.outS = q40_ && !bat ? dAttS_ : nullptr;
+    a.outQ = blocks() && !bat ? dAttQ_ : nullptr;
+    a.outS = blocks() && !bat ? dAttS_ : nullptr;
     a.outH = bat ? dAttH_ : nullptr;
     a.ldOut = p.q0;
     a.kvBf16 = kvBf16_ ? 1 : 0;
@@ -269,7 +272,7 @@ hipk::AttnBlockArgs HipEngineImpl::attnBlockArgs(const DevLayer &L, u32 l, int c
 // DL_ATTN_BLOCK=0 keeps the three separate launches.
 void HipEngineImpl::setupAttnBlock() {
     const char *e = std::getenv("DL_ATTN_BLOCK");
-    if ((e && *e == '0') || !q40_ || plan_.nKvHeads0 > kMaxKvGroups) return;
+    if ((e && *e == '0') || !q40() || plan_.nKvHeads0 > kMaxKvGroups) return;
     // one KV group per rank (8 KV heads at TP8): the attention role is a handful of workgroups
     // the whole wo role waits on - measured 2x the three launches (8B TP8 rank: 38 vs ~18 us per
     // layer, profiles/r5_tp_rank.md); DL_ATTN_BLOCK=1 forces it
@@ -326,7 +329,7 @@ void HipEngineImpl::setupAttnBlock() {
 void HipEngineImpl::setupPrenorm() {
     prenormOn_ = false;
     const char *e = std::getenv("DL_PRENORM");
-    if ((e && *e == '0') || !q40_ || !fusedTp(false) || h_.dim % 32 || h_.dim > 16384) return;
+    if ((e && *e == '0') || !q40() || !fusedTp(false) || h_.dim % 32 || h_.dim > 16384) return;
     const hipk::GemvArgs producers[2] = {woRowArgs(layers_[0], hipk::EPI_RESQ_TP), w2ProducerArgs(layers_[0])};
     const int pros[2] = {hipk::PRO_GLOBAL, w2Pro()};
     for (int w = 0; w < 2; w++) {
@@ -444,7 +447,7 @@ bool HipEngineImpl::tpBatchedOk(int n) const {
         const char *e = std::getenv("DL_TP_BATCHED");
         return !(e && *e == '0');
     }();
-    return on && !invariant_ && tpFused_ && q40_ && !hipk::gemmUsesWide(n) &&
+    return on && !invariant_ && tpFused_ && q40() && !hipk::gemmUsesWide(n) &&
            (size_t)n * h_.dim <= (size_t)tpVec_.stride && hipk::gemmTpxFits(n, plan_.nRanks, tpVec_.q80 != 0);
 }
 
@@ -454,7 +457,7 @@ void HipEngineImpl::gemmBatched(const DevMat &m, int n, int epi, const MatOperan
     // pass per token tile, all tiles of a row tile on one XCD), the narrow one <= 128
     // (batch-invariant engines: narrow launches only, the split count of a 16-token launch for all)
     // (a width the wide kernel cannot split into its two-block stages: narrow launches too)
-    const int chunk = hipk::gemmChunkTokens(m.n, n, q40_, invariant_);
+    const int chunk = hipk::gemmChunkTokens(m.n, n, q40(), invariant_);
     for (int c0 = 0; c0 < n; c0 += chunk) {
         const int bc = std::min(chunk, n - c0);
         xChunk_ = c0 / chunk;  // each launch's tile exchange waits in a measured-sync slot of its own
@@ -504,13 +507,15 @@ void HipEngineImpl::gemmBatched(const DevMat &m, int n, int epi, const MatOperan
             g.ldSS = (int)cfg_.maxBatch;
         }
         g.M = bc;
-        g.splits = invariant_ ? hipk::gemmSplits(m.rows, m.n, 16, 0) : hipk::gemmSplits(m.rows, m.n, bc, q40_ ? m.lanes : 0);
+        g.splits = invariant_ ? hipk::gemmSplits(m.rows, m.n, 16, 0) : hipk::gemmSplits(m.rows, m.n, bc, q40() ? m.lanes : 0);
         g.fixed = invariant_ ? 1 : 0;
         g.part = dPart_;
         g.partFloats = partFloats_;
         g.counters = dGemmCnt_;
-        if (q40_)
+        if (q40())
             hipk::launchGemmQ40(g, epi, stream_);
+        else if (q80w())
+            hipk::launchGemmQ80w(g, epi, stream_);
         else
             hipk::launchGemmF32(g, epi, stream_);
     }
@@ -568,7 +573,7 @@ void HipEngineImpl::enqueueWo(const FwdPath &f, const DevLayer &L, int cur) {
         gemmBatched(L.wo, f.n, hipk::EPI_STORE, {.xh = dAttH_, .out = dY_, .ldOut = dim()});
     else
         gemv(L.wo, f.n, hipk::PRO_GLOBAL, hipk::EPI_STORE,
-             {.in = q40_ ? nullptr : dAtt_, .ldIn = q0(), .aq = dAttQ_, .as = dAttS_, .out = dY_, .ldOut = dim(),
+             {.in = blocks() ? nullptr : dAtt_, .ldIn = q0(), .aq = dAttQ_, .as = dAttS_, .out = dY_, .ldOut = dim(),
               .tp = fusedTp(false)});
 }
 
@@ -593,9 +598,9 @@ void HipEngineImpl::enqueueW2(const FwdPath &f, u32 l, int cur) {
         gemmBatched(L.w2, f.n, hipk::EPI_RES, {.xh = dHh_, .ldOut = dim(), .rf = {dX_[cur], dX_[cur ^ 1], nextNormW(l)}});
     else if (f.bat)
         gemmBatched(L.w2, f.n, hipk::EPI_STORE, {.xh = dHh_, .out = dY_, .ldOut = dim()});
-    else if (!q40_ || hQ80_)
+    else if (!blocks() || hQ80_)
         gemv(L.w2, f.n, hipk::PRO_GLOBAL, hipk::EPI_STORE,
-             {.in = q40_ ? nullptr : dH_, .ldIn = hidden0(), .aq = dHQ_, .as = dHS_, .out = dY_, .ldOut = dim(),
+             {.in = blocks() ? nullptr : dH_, .ldIn = hidden0(), .aq = dHQ_, .as = dHS_, .out = dY_, .ldOut = dim(),
               .tp = fusedTp(false)});
     else
         gemv(L.w2, f.n, hipk::PRO_RESNORM, hipk::EPI_STORE,
@@ -739,7 +744,7 @@ void HipEngineImpl::enqueueForward(int n, FwdKind k) {
     f.pre = prenormOn_ && row && kind != GraphKind::EMBED;
     // one greedy decode row: the logits GEMV ends in the row's argmax (EPI_ARGMAX: no logits
     // written, no argmax launch; under TP the winners trade over the fused exchange's region)
-    f.argTail = argTailOn_ && q40_ && !f.bat && !f.fz && n == 1 &&
+    f.argTail = argTailOn_ && q40() && !f.bat && !f.fz && n == 1 &&
                 (kind == GraphKind::ARGMAX || kind == GraphKind::CHAIN) &&
                 (plan_.nRanks == 1 || (tpFused_ && tpArg_.stride >= 2));
     {

@@ -34,8 +34,13 @@
 namespace dl {
 namespace engine_detail {
 
+// The weight type of a model: every matrix of an engine has the same one. Q80 weights follow the F32
+// weights' schedule (plain launches: no fused attention block, no fused exchange, no pre-normalized
+// hand-off, no argmax tail) on Q80 activations, with kernels of their own (q80w.hip, q80w_gemm.hip).
+enum class WeightKind { F32, Q40, Q80 };
+
 struct DevMat {
-    uint8_t *qs = nullptr;  // Q40: tiled for `lanes` lanes per row (hipk::Q40Tiling)
+    uint8_t *qs = nullptr;  // Q40 / Q80: tiled for `lanes` lanes per row (hipk::Q40Tiling / Q80Tiling)
     uint16_t *d = nullptr;
     float *f = nullptr;
     int rows = 0, n = 0, lanes = 0;
@@ -192,7 +197,7 @@ class HipEngineImpl : public HipEngine {
     size_t matStageBytes(u32 rows, u32 n) const;
     // lanes per row of a matrix's Q40 tiling (the GEMV's choice)
     static int lanesFor(int rows, int n) { return hipk::gemvLanesPerRow(n, rows, 1, true); }
-    void placeQ40(DevMat &m, const hipk::Q40Tiling &t, int mi, u32 l);
+    void placeTiled(DevMat &m, size_t qsBytes, size_t dBytes, int mi, u32 l);
     struct RowSrc {
         const TensorInfo *t;
         u32 r0, nr;
@@ -230,7 +235,7 @@ class HipEngineImpl : public HipEngine {
     int tpPasses(const DevMat &m, int bc) const;
     int batchChunk(const DevMat &m, int pro, int epi) const;
     int passesFor(const DevMat &m, int epi, int B) const {
-        return hipk::gemvDefaultPasses(m.n, m.rows, B, q40_, epi, q40_ ? m.lanes : 0);
+        return hipk::gemvDefaultPasses(m.n, m.rows, B, blocks(), epi, blocks() ? m.lanes : 0);
     }
     // rows one workgroup of a Q40 GEMV launch covers, and the launch's grid
     static int rowsPerWorkgroup(int lanes, int passes) { return (256 / lanes) * 2 * passes; }
@@ -286,7 +291,7 @@ class HipEngineImpl : public HipEngine {
     hipk::GemvArgs w13ConsumerArgs(const DevLayer &L) const;
     // Q80 hand-off of h needs one workgroup per 32 hidden units; for skinny TP shards the w13
     // epilogue emits f32 and w2 quantizes in its prologue instead.
-    int w13Epi() const { return q40_ && hQ80_ ? hipk::EPI_ACT_Q80 : hipk::EPI_ACT; }
+    int w13Epi() const { return blocks() && hQ80_ ? hipk::EPI_ACT_Q80 : hipk::EPI_ACT; }
     int w2Pro() const { return hQ80_ ? hipk::PRO_GLOBAL : hipk::PRO_RESNORM; }
     const float *nextNormW(u32 l) const { return l + 1 < h_.nLayers ? layers_[l + 1].rmsAtt : rmsFinal_; }
     hipk::AttnArgs attnArgs(const DevLayer &L, bool bat) const;
@@ -304,7 +309,7 @@ class HipEngineImpl : public HipEngine {
     bool fuseNorm(int n) const { return fuseNormEnv_ && (plan_.nRanks == 1 || tpBatchedOk(n)); }
     void gemmBatched(const DevMat &m, int n, int epi, const MatOperands &o);
     void allReduce(float *buf, size_t count);
-    bool fusedTp(bool bat) const { return tpFused_ && !bat && q40_; }
+    bool fusedTp(bool bat) const { return tpFused_ && !bat && q40(); }
     // The path a forward of n rows takes (enqueueForward): the per-matrix steps pick their launch from it.
     struct FwdPath {
         int n;
@@ -345,7 +350,12 @@ class HipEngineImpl : public HipEngine {
     std::unique_ptr<ModelFile> file_;
     ModelHeader h_;
     ShardPlan plan_;
-    bool q40_ = true, kvBf16_ = true, syncQ80_ = false, tpFused_ = false;
+    WeightKind wkind_ = WeightKind::Q40;
+    bool q40() const { return wkind_ == WeightKind::Q40; }    // the fused paths
+    bool q80w() const { return wkind_ == WeightKind::Q80; }
+    // block-quantized weights: tiled planes, Q80 activations, two rows per GEMV lane group
+    bool blocks() const { return wkind_ != WeightKind::F32; }
+    bool kvBf16_ = true, syncQ80_ = false, tpFused_ = false;
     bool tpTested_ = false;  // tpFusedSelfTest ran (first forward)
     int fusedGridMax_ = 0;  // largest grid of a fused-exchange GEMV launch (checked co-resident)
     hipk::TpXchg tpVec_, tpArg_;

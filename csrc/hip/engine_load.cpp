@@ -193,7 +193,7 @@ void HipEngineImpl::allocBuffers() {
         int cnt = 0;
         auto acc = [&](int rows, int n) {
             part = std::max(part, hipk::gemmPartFloats(rows, n, mt));
-            if (invariant_ && q40_) part = std::max(part, hipk::gemmPartFloatsFixed(rows, n));
+            if (invariant_ && blocks()) part = std::max(part, hipk::gemmPartFloatsFixed(rows, n));
             cnt = std::max(cnt, hipk::gemmCounterInts(rows, mt));
         };
         acc(p.q0 + 2 * p.kv0, h_.dim);
@@ -330,8 +330,9 @@ void HipEngineImpl::stageRelease(Loader &ld) {
 // Read the rows of every source (restricted to columns [c0, c0 + nc)) into ld.raw and point
 // ld.rowPtr at each output row (w1/w3 interleaved row by row when `interleave`).
 void HipEngineImpl::readRows(Loader &ld, const std::vector<RowSrc> &srcs, bool interleave, u32 c0, u32 nc) {
-    const u64 esz = q40_ ? 0 : 4;
-    auto rowBytes = [&](u32 cols) { return q40_ ? (u64)cols / kQBlock * kQ40BlockBytes : (u64)cols * esz; };
+    auto rowBytes = [&](u32 cols) {
+        return blocks() ? (u64)cols / kQBlock * (q40() ? kQ40BlockBytes : kQ80BlockBytes) : (u64)cols * 4;
+    };
     const u64 slice = rowBytes(nc);
     u64 total = 0;
     for (const auto &s : srcs) total += (u64)s.nr * slice;
@@ -366,27 +367,31 @@ void HipEngineImpl::readRows(Loader &ld, const std::vector<RowSrc> &srcs, bool i
 }
 
 size_t HipEngineImpl::matStageBytes(u32 rows, u32 n) const {
-    if (!q40_) return (size_t)rows * n * 4;
+    if (q80w()) {
+        const hipk::Q80Tiling t = hipk::q80Tiling((int)rows, (int)n, lanesFor((int)rows, (int)n));
+        return t.qBytes + t.dBytes;
+    }
+    if (!q40()) return (size_t)rows * n * 4;
     const hipk::Q40Tiling t = hipk::q40Tiling((int)rows, (int)n, lanesFor((int)rows, (int)n));
     return t.qsBytes + t.dBytes;
 }
 
-// Device storage of a Q40 matrix: layer matrix `mi` (0 qkv, 1 wo, 2 w13, 3 w2) of layer l lives in
+// Device storage of a tiled (Q40 / Q80) matrix of qsBytes + dBytes: layer matrix `mi` (0 qkv, 1 wo, 2 w13, 3 w2) of layer l lives in
 // one slab per matrix kind, all layers back to back (4 allocations instead of 4 x nLayers);
 // other matrices get their own allocation.
-void HipEngineImpl::placeQ40(DevMat &m, const hipk::Q40Tiling &t, int mi, u32 l) {
+void HipEngineImpl::placeTiled(DevMat &m, size_t qsBytes, size_t dBytes, int mi, u32 l) {
     if (mi < 0) {
-        m.qs = dalloc<uint8_t>(t.qsBytes);
-        m.d = dalloc<uint16_t>(t.dBytes / 2);
+        m.qs = dalloc<uint8_t>(qsBytes);
+        m.d = dalloc<uint16_t>(dBytes / 2);
         return;
     }
     if (!qsSlab_[mi]) {
-        qsStride_[mi] = t.qsBytes;
-        dStride_[mi] = t.dBytes;
-        qsSlab_[mi] = dalloc<uint8_t>(t.qsBytes * h_.nLayers);
-        dSlab_[mi] = dalloc<uint16_t>(t.dBytes / 2 * h_.nLayers);
+        qsStride_[mi] = qsBytes;
+        dStride_[mi] = dBytes;
+        qsSlab_[mi] = dalloc<uint8_t>(qsBytes * h_.nLayers);
+        dSlab_[mi] = dalloc<uint16_t>(dBytes / 2 * h_.nLayers);
     }
-    DL_CHECK(qsStride_[mi] == t.qsBytes && dStride_[mi] == t.dBytes, "layer matrices of one kind differ in size");
+    DL_CHECK(qsStride_[mi] == qsBytes && dStride_[mi] == dBytes, "layer matrices of one kind differ in size");
     m.qs = qsSlab_[mi] + (size_t)l * qsStride_[mi];
     m.d = dSlab_[mi] + (size_t)l * (dStride_[mi] / 2);
 }
@@ -398,14 +403,22 @@ void HipEngineImpl::buildMat(Loader &ld, DevMat &m, const std::vector<RowSrc> &s
     m.rows = rows;
     m.n = (int)nc;
     u8 *st = stageAcquire(ld);
-    if (q40_) {
+    if (q40()) {
         m.lanes = lanesFor(rows, (int)nc);
         const hipk::Q40Tiling t = hipk::q40Tiling(rows, (int)nc, m.lanes);
         DL_CHECK(t.qsBytes + t.dBytes <= ld.stageBytes, "staging buffer too small");
         hipk::tileQ40AoS(ld.rowPtr.data(), rows, (int)nc, m.lanes, st, reinterpret_cast<uint32_t *>(st + t.qsBytes));
-        placeQ40(m, t, mi, l);
+        placeTiled(m, t.qsBytes, t.dBytes, mi, l);
         stageCopy(ld, m.qs, st, t.qsBytes);
         stageCopy(ld, m.d, st + t.qsBytes, t.dBytes);
+    } else if (q80w()) {
+        m.lanes = lanesFor(rows, (int)nc);
+        const hipk::Q80Tiling t = hipk::q80Tiling(rows, (int)nc, m.lanes);
+        DL_CHECK(t.qBytes + t.dBytes <= ld.stageBytes, "staging buffer too small");
+        hipk::tileQ80AoS(ld.rowPtr.data(), rows, (int)nc, m.lanes, st, reinterpret_cast<uint32_t *>(st + t.qBytes));
+        placeTiled(m, t.qBytes, t.dBytes, mi, l);
+        stageCopy(ld, m.qs, st, t.qBytes);
+        stageCopy(ld, m.d, st + t.qBytes, t.dBytes);
     } else {
         const size_t rb = (size_t)nc * 4;
         DL_CHECK((size_t)rows * rb <= ld.stageBytes, "staging buffer too small");
@@ -488,12 +501,17 @@ void HipEngineImpl::synthMat(DevMat &m, int rows, int n, u64 seed, int mi, u32 l
     m.rows = rows;
     m.n = n;
     const float scale = 1.0f / std::sqrt(21.5f * (float)n);
-    if (q40_) {
+    if (q40()) {
         m.lanes = lanesFor(rows, n);
         const hipk::Q40Tiling t = hipk::q40Tiling(rows, n, m.lanes);
         const size_t nBlocks = t.qsBytes / 16;  // == t.dBytes / 2 f16 scales
-        placeQ40(m, t, mi, l);
+        placeTiled(m, t.qsBytes, t.dBytes, mi, l);
         hipk::launchFillQ40(m.qs, m.d, nBlocks, scale, seed, stream_);
+    } else if (q80w()) {  // uniform int8 codes (variance ~ 128^2 / 3): the Q40 fill's weight variance
+        m.lanes = lanesFor(rows, n);
+        const hipk::Q80Tiling t = hipk::q80Tiling(rows, n, m.lanes);
+        placeTiled(m, t.qBytes, t.dBytes, mi, l);
+        hipk::launchFillQ80w(m.qs, m.d, t.qBytes / 16, t.dBytes / 2, 1.0f / std::sqrt(5461.0f * (float)n), seed, stream_);
     } else {
         m.f = dalloc<float>((size_t)rows * n);
         hipk::launchFillF32Uniform(m.f, (size_t)rows * n, std::sqrt(3.0f / (float)n), seed, stream_);

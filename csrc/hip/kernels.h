@@ -75,6 +75,35 @@ void tileQ40(const uint8_t *qs, const uint16_t *d, int rows, int n, int L, uint8
 // at row r's first block of the column slice being tiled.
 void tileQ40AoS(const uint8_t *const *rowBlocks, int rows, int n, int L, uint8_t *qsOut, uint32_t *dOut);
 
+// Q80 weights (34-byte file blocks: f16 scale + 32 int8) live on the device as an int8 plane and an
+// f16 scale plane, TILED in the Q80-weight GEMV's consumption order with the Q40 tiling's geometry
+// (L lanes per row, NG = 256/L row pairs per workgroup pass, K = ceil(nb/L) steps, chunk c = g*K + k):
+//   q: [c][r in {0,1}][h in {0,1}][256 threads] x 16 B   thread tid = gi*L + li holds bytes
+//                                                        16h .. 16h+15 of block j = li + k*L of
+//                                                        row 2*(g*NG+gi) + r, in the file's order
+//   d: [c][256 threads] x u32                            {lo: f16 scale of the even row, hi: odd row}
+// so a workgroup streams one contiguous region (16 KB of int8 + 1 KB of scales per step) in 16-byte
+// loads, and the batched GEMM's lane (row, h8) finds the 8 bytes 8*h8 .. 8*h8+7 of a block at
+// q80Off(row, j, h8 >> 1) + 8 * (h8 & 1): its MFMA k order is the file's, matching f16 activations
+// read at the same offsets. Padding (rows past the end, j >= nb) is zero.
+struct Q80Tiling {
+    int L = 16, NG = 16, K = 0, groups = 0;
+    size_t chunks = 0, qBytes = 0, dBytes = 0;
+};
+Q80Tiling q80Tiling(int rows, int n, int L);
+// byte offset in the int8 plane of half h of block j of `row`; u32 index of the row pair's scales
+__host__ __device__ inline size_t q80Off(int L, int K, int row, int j, int h) {
+    const int NG = 256 / L, g = row / (2 * NG), gi = (row % (2 * NG)) >> 1;
+    return (((((size_t)g * K + j / L) * 2 + (row & 1)) * 2 + h) * 256 + gi * L + j % L) * 16;
+}
+__host__ __device__ inline size_t q80ScaleOff(int L, int K, int row, int j) {
+    const int NG = 256 / L, g = row / (2 * NG), gi = (row % (2 * NG)) >> 1;
+    return ((size_t)g * K + j / L) * 256 + gi * L + j % L;
+}
+// Host repack of the file's AoS blocks: rowBlocks[r] points at row r's first block of the column
+// slice being tiled (n columns), as tileQ40AoS.
+void tileQ80AoS(const uint8_t *const *rowBlocks, int rows, int n, int L, uint8_t *qOut, uint32_t *dOut);
+
 // Paged KV cache: with a page table the cache rows of (slot, pos) live at row
 // table[slot * pagesPerSlot + (pos >> pageShift)] * 2^pageShift + (pos & (2^pageShift - 1)) of a
 // per-layer pool of pages, so slots hold only the pages their sequences reached; without one the
@@ -204,7 +233,8 @@ struct ArgmaxTail {
 };
 
 struct GemvArgs {
-    // weights: Q40 tiled (see Q40Tiling; `lanes` must be the tiling's L) or F32 [rows][n]
+    // weights: Q40 tiled (see Q40Tiling; `lanes` must be the tiling's L), Q80 tiled (Q80Tiling: qs the
+    // int8 plane, wd the scale pairs; launchGemvQ80w / launchGemmQ80w) or F32 [rows][n]
     const uint8_t *qs = nullptr;
     const uint16_t *wd = nullptr;
     const float *wf = nullptr;
@@ -295,6 +325,10 @@ GemmKernel gemmKernelFor(int n, int M, int lanes, int splits, bool fixed);
 int gemmChunkTokens(int n, int M, bool q40, bool fixed);
 // Same contract for F32 weights (`e.wf` [rows][n] row-major; EPI_ACT_Q80 not supported).
 void launchGemmF32(const GemmArgs &a, int epi, hipStream_t s);
+// Same contract for Q80 weights (`e.qs` / `e.wd` tiled as Q80Tiling at `e.lanes`; <= kGemmF32MaxTokens
+// tokens per launch; EPI_STORE, EPI_ACT, EPI_ACT_F16, EPI_QKV, EPI_RES; no tile exchange).
+// fetch: 0 the default weight fetch, else 8 or 16 bytes per lane and load (measurements, q80w_gemm.hip).
+void launchGemmQ80w(const GemmArgs &a, int epi, hipStream_t s, int fetch = 0);
 // Tile / split-K plan of one matrix (rt = 16-row tiles per wave: 64 * rt rows per workgroup).
 struct GemmPlan {
     int rt = 1, tiles = 0, splits = 1;
@@ -333,6 +367,14 @@ void launchNormF16(const GemvArgs &a, _Float16 *out, int M, hipStream_t s);
 
 // B = batch rows in this launch (1, 2 or 4); q40 = weight format.
 void launchGemv(const GemvArgs &a, int B, int pro, int epi, bool q40, hipStream_t s);
+// Decode GEMV on Q80 weights (q80w.hip), B = 1, 2 or 4: y[b][r] = sum_j f32(dw[r][j]) * dx[b][j] *
+// (sum_i qw * qx), the inner sum an exact int32 (v_dot4_i32_i8), accumulated in f32. Activations are
+// Q80 blocks staged once per workgroup in LDS: PRO_GLOBAL copies the producer's (aq / as), PRO_RESNORM
+// quantizes (in + addIn) through the RMS norm. Epilogues EPI_STORE, EPI_ACT, EPI_ACT_Q80, EPI_QKV.
+// Lanes, passes and the LDS footprint follow the Q40 GEMV's rules (gemvLanesPerRow / gemvDefaultPasses
+// / gemvLdsBytes with q40 = true: two rows per lane group, the same activation image).
+// depth > 0 (measurements only; B = 1, PRO_GLOBAL, EPI_STORE): the instance with `depth` steps per register group.
+void launchGemvQ80w(const GemvArgs &a, int B, int pro, int epi, hipStream_t s, int depth = 0);
 // Co-residency of one GEMV launch on the current device: its grid and the most workgroups of that
 // kernel (at its LDS size) the device holds at once (occupancy per CU x CUs). A kernel whose
 // workgroups spin on peers (EPI_STORE_TP) is deadlock-free only if grid <= maxResident.
@@ -773,6 +815,8 @@ void launchUnshardLogits(const float *in, float *out, int nRanks, int B, int voc
 
 // Synthetic weights: random Q40 nibbles with scale ~ scale*(0.5..1.5), f32 uniform(-a,a), or constant.
 void launchFillQ40(uint8_t *qs, uint16_t *d, size_t nBlocks, float scale, uint64_t seed, hipStream_t s);
+// Q80 planes of `nUnits` 16-byte units and `nScales` f16 scales: random int8 codes, scales as above.
+void launchFillQ80w(uint8_t *q, uint16_t *d, size_t nUnits, size_t nScales, float scale, uint64_t seed, hipStream_t s);
 void launchFillF32Uniform(float *p, size_t n, float amp, uint64_t seed, hipStream_t s);
 void launchFillF32Const(float *p, size_t n, float v, hipStream_t s);
 

@@ -294,6 +294,212 @@ std::vector<float> gemvF32(const std::vector<float> &w, int rows, int n, const s
     return sc.downloadRows(a.out, B, outRows, a.ldOut);
 }
 
+// ---- Q80 weights (q80w.hip, q80w_gemm.hip) --------------------------------------------------------
+void tileQ80Host(const std::vector<uint8_t> &blocks, int rows, int n, int lanes, int c0, int nc, std::vector<uint8_t> &q,
+                 std::vector<uint32_t> &d) {
+    DL_CHECK(n > 0 && n % 32 == 0 && rows > 0, "Q80 shape");
+    DL_CHECK(lanes == 16 || lanes == 32 || lanes == 64, "tiling lanes must be 16, 32 or 64");
+    DL_CHECK(c0 >= 0 && nc > 0 && c0 % 32 == 0 && nc % 32 == 0 && c0 + nc <= n, "Q80 column slice");
+    const size_t nb = (size_t)n / 32;
+    DL_CHECK(blocks.size() == (size_t)rows * nb * sizeof(BlockQ80), "Q80 blocks size");
+    const hipk::Q80Tiling t = hipk::q80Tiling(rows, nc, lanes);
+    // preset to a pattern the tiler never writes as padding: every byte of the image must be written
+    q.assign(t.qBytes, 0xEE);
+    d.assign(t.dBytes / 4, 0xEEEEEEEEu);
+    std::vector<const uint8_t *> rowPtr(rows);
+    for (int r = 0; r < rows; r++) rowPtr[r] = blocks.data() + ((size_t)r * nb + c0 / 32) * sizeof(BlockQ80);
+    hipk::tileQ80AoS(rowPtr.data(), rows, nc, lanes, q.data(), d.data());
+}
+
+namespace {
+// the tiled planes of `blocks` on the device, into a.qs / a.wd / a.lanes
+void uploadQ80w(Scratch &sc, const std::vector<uint8_t> &blocks, int rows, int n, int lanes, hipk::GemvArgs &a) {
+    std::vector<uint8_t> q;
+    std::vector<uint32_t> d;
+    tileQ80Host(blocks, rows, n, lanes, 0, n, q, d);
+    a.qs = sc.upload(q);
+    a.wd = reinterpret_cast<const uint16_t *>(sc.upload(d));
+    a.lanes = lanes;
+    a.rows = rows;
+    a.n = n;
+}
+}  // namespace
+
+GemvQ80wResult gemvQ80w(const GemvQ80wArgs &p) {
+    const int B = p.B, rows = p.rows, n = p.n;
+    DL_CHECK(B == 1 || B == 2 || B == 4, "gemv batch must be 1, 2 or 4");
+    DL_CHECK(p.pro == hipk::PRO_GLOBAL || p.pro == hipk::PRO_RESNORM, "gemv_q80w prologue: 0 global, 1 residual + norm");
+    DL_CHECK(p.epi == hipk::EPI_STORE || p.epi == hipk::EPI_ACT || p.epi == hipk::EPI_ACT_Q80 || p.epi == hipk::EPI_QKV,
+             "gemv_q80w epilogue: 0 store, 1 SwiGLU, 2 QKV, 3 SwiGLU -> Q80");
+    DL_CHECK(p.pro == hipk::PRO_RESNORM || p.epi == hipk::EPI_STORE, "gemv_q80w: the global prologue stores only");
+    DL_CHECK(p.pro == hipk::PRO_RESNORM || (p.residual.empty() && p.normW.empty()),
+             "gemv_q80w: the global prologue takes no residual or norm");
+    DL_CHECK(p.epi == hipk::EPI_STORE || rows % 2 == 0, "gemv_q80w: row-pair epilogues need an even row count");
+    DL_CHECK(p.epi != hipk::EPI_ACT_Q80 || rows % 64 == 0, "gemv_q80w SwiGLU -> Q80: rows must be whole 64-row blocks");
+    DL_CHECK(p.in.size() == (size_t)B * n, "gemv input size");
+    checkRows(p.residual, (size_t)B * n, "residual");
+    checkRows(p.normW, (size_t)n, "norm weights");
+    const Q40Geom g = q40Geom(rows, n, B, p.epi, p.lanes, p.passes);  // the Q40 GEMV's geometry rules
+    DL_CHECK(B == 1 || hipk::gemvLdsBytes(n, B, true, g.wgRows, hipk::PRO_RESNORM) <= 64 * 1024,
+             "gemv LDS footprint too large for this batch");
+    Scratch sc;
+    hipk::GemvArgs a;
+    uploadQ80w(sc, p.blocks, rows, n, g.lanes, a);
+    a.passes = g.passes;
+    a.eps = p.eps;
+    a.act = 1;
+    a.ldIn = n;
+    if (p.pro == hipk::PRO_RESNORM) {
+        a.in = sc.upload(p.in);
+        a.addIn = sc.upload(p.residual);
+        a.xNext = p.residual.empty() ? nullptr : sc.allocGuarded<float>(1, (size_t)B * n, (size_t)B * n + 256, "xNext");
+        a.normW = sc.upload(p.normW);
+    } else {  // host Q80 (the reference quantizer) -> codes + (d, sum of codes), as the producers hand them over
+        const int nb = n / 32;
+        std::vector<BlockQ80> q((size_t)B * nb);
+        quantizeQ80(p.in.data(), q.data(), (u64)B * n);
+        std::vector<int8_t> codes((size_t)B * n);
+        std::vector<float> scales((size_t)B * nb * 2);
+        for (size_t i = 0; i < q.size(); i++) {
+            int s = 0;
+            for (int j = 0; j < 32; j++) s += (codes[i * 32 + j] = q[i].qs[j]);
+            scales[2 * i] = f16ToF32(q[i].d);
+            scales[2 * i + 1] = (float)s;
+        }
+        a.aq = sc.upload(codes);
+        a.as = reinterpret_cast<const float2 *>(sc.upload(scales));
+    }
+    GemvQ80wResult res;
+    float *os = nullptr;
+    uint8_t *kc = nullptr, *vc = nullptr;
+    std::vector<int> slots(B);
+    const size_t cacheElems = (size_t)B * p.seqLen * p.kv0;
+    int outRows = rows;
+    if (p.epi == hipk::EPI_ACT_Q80) {
+        outRows = rows / 2;
+        a.ldOut = outRows + g.wgRows;  // a multiple of 32: the scale pairs are [B][ldOut / 32]
+        a.oq = sc.allocGuarded<int8_t>(B, outRows, a.ldOut, "the Q80 codes");
+        os = sc.allocGuarded<float>(B, (size_t)outRows / 32 * 2, (size_t)a.ldOut / 32 * 2, "the Q80 scales");
+        a.os = reinterpret_cast<float2 *>(os);
+    } else {
+        if (p.epi == hipk::EPI_ACT) outRows = rows / 2;
+        if (p.epi == hipk::EPI_QKV) {
+            DL_CHECK(rows == p.q0 + 2 * p.kv0 && p.hs % 2 == 0 && p.hs <= 128 && (p.hs & (p.hs - 1)) == 0 &&
+                         p.q0 % p.hs == 0 && p.kv0 % p.hs == 0 && p.kv0 > 0,
+                     "qkv head layout");
+            DL_CHECK((int)p.pos.size() == B && p.rope.size() == (size_t)p.seqLen * p.hs, "qkv operand sizes");
+            for (int q : p.pos) DL_CHECK(q >= 0 && q < p.seqLen, "qkv position out of range");
+            outRows = p.q0;
+            for (int b = 0; b < B; b++) slots[b] = b;
+            const size_t eb = p.kvBf16 ? 2 : 4, cacheGuard = (size_t)g.wgRows * p.seqLen;
+            kc = sc.allocGuarded<uint8_t>(1, cacheElems * eb, (cacheElems + cacheGuard) * eb, "the K cache");
+            vc = sc.allocGuarded<uint8_t>(1, cacheElems * eb, (cacheElems + cacheGuard) * eb, "the V cache");
+            a.q0 = p.q0;
+            a.kv0 = p.kv0;
+            a.hs = p.hs;
+            a.seqLen = p.seqLen;
+            a.rope = reinterpret_cast<const float2 *>(sc.upload(p.rope));
+            a.pos = sc.upload(p.pos);
+            a.slot = sc.upload(slots);
+            a.kcache = kc;
+            a.vcache = vc;
+            a.kvBf16 = p.kvBf16 ? 1 : 0;
+        }
+        a.ldOut = outRows + g.wgRows;
+        a.out = sc.allocGuarded<float>(B, outRows, a.ldOut, "the GEMV output");
+    }
+    hipk::launchGemvQ80w(a, B, p.pro, p.epi, sc.s);
+    sc.sync();
+    sc.checkGuards();
+    if (a.xNext) res.xNext = sc.download(a.xNext, (size_t)B * n);
+    if (a.out) res.out = sc.downloadRows(a.out, B, outRows, a.ldOut);
+    if (a.oq) {
+        res.codes = sc.downloadRows(a.oq, B, outRows, a.ldOut);
+        res.scales = sc.downloadRows(os, B, (size_t)outRows / 32 * 2, (size_t)a.ldOut / 32 * 2);
+    }
+    if (kc) {
+        appendedRows(sc, kc, cacheElems, p.seqLen, p.kv0, p.hs, p.pos, slots, p.kvBf16, "the K cache", &res.k);
+        appendedRows(sc, vc, cacheElems, p.seqLen, p.kv0, p.hs, p.pos, slots, p.kvBf16, "the V cache", &res.v);
+    }
+    return res;
+}
+
+GemmQ80wResult gemmQ80w(const GemmQ80wArgs &p) {
+    const int rows = p.rows, n = p.n, M = p.M;
+    DL_CHECK(M >= 1 && M <= 256, "gemm tokens must be 1..256");
+    DL_CHECK(hipk::gemmSupported(n) && p.in.size() == (size_t)M * n, "gemm operand sizes");
+    DL_CHECK(p.splits == 0 || (p.splits > 0 && (n / 32) % p.splits == 0), "gemm splits must divide n / 32");
+    DL_CHECK(p.epi == hipk::EPI_STORE || p.epi == hipk::EPI_RES, "gemm_q80w epilogue: 0 store, 6 residual + norm hand-off");
+    const bool res = p.epi == hipk::EPI_RES;
+    DL_CHECK(!res || (rows % 2 == 0 && p.resIn.size() == (size_t)M * rows && p.resW.size() == (size_t)rows),
+             "gemm_q80w: EPI_RES takes resIn [M][rows] and resW [rows], rows even");
+    checkLanes(p.lanes);
+    Scratch sc;
+    hipk::GemmArgs g;
+    uploadQ80w(sc, p.blocks, rows, n, p.lanes > 0 ? p.lanes : hipk::gemvLanesPerRow(n, rows, 1, true), g.e);
+    // the activation operand: `in` rounded to f16, rows past M (read by the last launch) zero
+    const int chunk = hipk::kGemmF32MaxTokens, rowsPad = (M + chunk - 1) / chunk * chunk;
+    std::vector<uint16_t> xh((size_t)rowsPad * n, 0);
+    for (size_t i = 0; i < p.in.size(); i++) xh[i] = f32ToF16(p.in[i]);
+    const _Float16 *x = reinterpret_cast<const _Float16 *>(sc.upload(xh));
+    const int tiles = (rows + 63) / 64, ld = rows + 64, ldSS = M + 16;
+    float *out = sc.allocGuardedTail<float>(M, rows, ld, 1, res ? "the residual output" : "the GEMM output");
+    uint16_t *resX = res ? sc.allocGuardedTail<uint16_t>(M, rows, ld, 1, "the f16 hand-off rows") : nullptr;
+    float *ss = res ? sc.allocGuardedTail<float>(tiles, M, ldSS, 1, "the sums of squares") : nullptr;
+    std::vector<float> resInLd;
+    if (res) {  // resIn at the outputs' leading dimension
+        resInLd.assign((size_t)M * ld, 0.f);
+        for (int t = 0; t < M; t++) std::copy(p.resIn.begin() + (size_t)t * rows, p.resIn.begin() + (size_t)(t + 1) * rows, resInLd.begin() + (size_t)t * ld);
+    }
+    const float *resIn = sc.upload(resInLd), *resW = sc.upload(p.resW);
+    DL_CHECK(p.ss.empty() || (p.ssTiles > 0 && p.ss.size() == (size_t)p.ssTiles * M), "gemm_q80w: ss is [ssTiles][M]");
+    const float *ssIn = sc.upload(p.ss);
+    g.e.eps = p.eps;
+    const int S = p.splits > 0 ? p.splits : 0;
+    size_t part = (size_t)std::max(S, 8) * tiles * chunk * 64;
+    float *partBuf = sc.alloc<float>(part);
+    int *counters = sc.alloc<int>((size_t)tiles + 1);
+    GemmQ80wResult r;
+    for (int c0 = 0; c0 < M; c0 += chunk) {
+        const int bc = std::min(chunk, M - c0);
+        hipk::GemmArgs a = g;
+        a.e.ldOut = ld;
+        a.x = x + (size_t)c0 * n;
+        a.M = bc;
+        a.splits = S > 0 ? S : hipk::gemmSplits(rows, n, bc);
+        a.part = partBuf;
+        a.partFloats = part;
+        a.counters = counters;
+        if (ssIn) {
+            a.ssIn = ssIn + c0;
+            a.ssTiles = p.ssTiles;
+            a.ldSS = M;
+        }
+        if (res) {
+            a.resIn = resIn + (size_t)c0 * ld;
+            a.resOut = out + (size_t)c0 * ld;
+            a.resW = resW;
+            a.resX = reinterpret_cast<_Float16 *>(resX) + (size_t)c0 * ld;
+            a.ssOut = ss + c0;
+            a.ldSS = ldSS;
+        } else {
+            a.e.out = out + (size_t)c0 * ld;
+        }
+        r.splits.push_back(a.splits);
+        hipk::launchGemmQ80w(a, p.epi, sc.s, p.fetch);
+    }
+    sc.sync();
+    sc.checkGuards();
+    r.out = sc.downloadRows(out, M, rows, ld);
+    if (res) {
+        const std::vector<uint16_t> xr = sc.downloadRows(resX, M, rows, ld);
+        r.resX.resize(xr.size());
+        for (size_t i = 0; i < xr.size(); i++) r.resX[i] = f16ToF32(xr[i]);
+        r.ssOut = sc.downloadRows(ss, tiles, M, ldSS);
+    }
+    return r;
+}
+
 void gemvDefaults(int rows, int n, int B, bool q40, int epi, int &lanes, int &passes) {
     lanes = hipk::gemvLanesPerRow(n, rows, q40 ? 1 : B, q40);
     passes = hipk::gemvDefaultPasses(n, rows, B, q40, epi, q40 ? lanes : 0);

@@ -70,6 +70,53 @@ void gemvDefaults(int rows, int n, int B, bool q40, int epi, int &lanes, int &pa
 void tileQ40Host(const std::vector<uint8_t> &blocks, int rows, int n, int lanes, bool aos, std::vector<uint8_t> &qs,
                  std::vector<uint32_t> &d);
 
+// Q80 weights: `blocks` = [rows][n/32] blocks in file layout (34 bytes: f16 d + 32 int8).
+// tileQ80Host: the tiled device image (Q80Tiling, kernels.h) of columns [c0, c0 + nc) written by
+// tileQ80AoS (a tensor-parallel column slice when nc < n); no device needed.
+void tileQ80Host(const std::vector<uint8_t> &blocks, int rows, int n, int lanes, int c0, int nc, std::vector<uint8_t> &q,
+                 std::vector<uint32_t> &d);
+// gemvQ80w: one gemvQ80wKernel launch, B = 1, 2 or 4. pro 0 (PRO_GLOBAL): `in` is quantized to Q80
+// on the host with the reference quantizer, store epilogue only; pro 1 (PRO_RESNORM): in (+ residual)
+// -> RMS norm with normW (if given) -> Q80 in LDS. epi 0 store, 1 SwiGLU of interleaved (w1, w3)
+// rows, 2 QKV (rows = q0 + 2 kv0; rope / pos as qkvRope, row b appends to cache slot b; k / v = the
+// appended rows), 3 SwiGLU -> Q80 (codes [B][rows/2], scales [B][rows/64][2]). lanes / passes and the
+// guards as the Q40 GEMV ops.
+struct GemvQ80wArgs {
+    std::vector<uint8_t> blocks;
+    int rows = 0, n = 0;
+    std::vector<float> in, residual, normW;
+    float eps = 1e-5f;
+    int B = 1, pro = 1, epi = 0, lanes = 0, passes = 0;
+    int q0 = 0, kv0 = 0, hs = 0, seqLen = 0;
+    std::vector<float> rope;
+    std::vector<int> pos;
+    bool kvBf16 = true;
+};
+struct GemvQ80wResult {
+    std::vector<float> out, xNext, k, v, scales;
+    std::vector<int8_t> codes;
+};
+GemvQ80wResult gemvQ80w(const GemvQ80wArgs &a);
+// gemmQ80w: gemmQ80wKernel over M tokens in launches of <= 64, `in` rounded to f16 on the host. epi 0
+// (EPI_STORE): out [M][rows]; epi 6 (EPI_RES): resIn [M][rows], resW [rows] -> out = resOut, resX (the
+// f16 hand-off rows as f32), ssOut [ceil(rows / 64)][M]. splits 0 = gemmSplits per launch. Outputs are
+// guarded as gemmBatched's.
+struct GemmQ80wArgs {
+    std::vector<uint8_t> blocks;
+    int rows = 0, n = 0, lanes = 0, M = 0, epi = 0, splits = 0;
+    int fetch = 0;  // 0 the launcher's default, 8 or 16: weight bytes per lane and load
+    std::vector<float> in, resIn, resW;
+    // consumer of an EPI_RES producer: `in` = its resX rows, ss = its ssOut [ssTiles][M] (else empty)
+    std::vector<float> ss;
+    int ssTiles = 0;
+    float eps = 1e-5f;
+};
+struct GemmQ80wResult {
+    std::vector<float> out, resX, ssOut;
+    std::vector<int> splits;
+};
+GemmQ80wResult gemmQ80w(const GemmQ80wArgs &a);
+
 // Batched F32 matmul on MFMA: norm kernel -> f16 -> gemmF32Kernel (store epilogue).
 std::vector<float> gemmF32(const std::vector<float> &w, int rows, int n, const std::vector<float> &in,
                            const std::vector<float> &normW, float eps, int M);

@@ -442,6 +442,94 @@ void bindOps(py::module_ &m) {
           },
           py::arg("blocks"), py::arg("rows"), py::arg("n"), py::arg("lanes"), py::arg("aos") = false,
           "the tiled device image (nibble bytes, u32 scale pairs) written by tileQ40 / tileQ40AoS; no device needed");
+    o.def("tile_q80",
+          [](py::object blocks, int rows, int n, int lanes, int c0, int nc) {
+              const std::vector<uint8_t> w = vec<uint8_t>(blocks);
+              std::vector<uint8_t> q;
+              std::vector<uint32_t> d;
+              ops::tileQ80Host(w, rows, n, lanes, c0, nc > 0 ? nc : n - c0, q, d);
+              return py::make_tuple(arr(q, {(py::ssize_t)q.size()}), arr(d, {(py::ssize_t)d.size()}));
+          },
+          py::arg("blocks"), py::arg("rows"), py::arg("n"), py::arg("lanes"), py::arg("c0") = 0, py::arg("nc") = 0,
+          "the tiled device image (int8 plane, u32 scale pairs) of columns [c0, c0 + nc) written by tileQ80AoS; no device needed");
+    o.def("gemv_q80w",
+          [](py::object blocks, int rows, int n, py::object x, py::object residual, py::object normW, float eps, int pro,
+             int epi, int lanes, int passes, int q0, int kv0, int hs, py::object rope, int seqLen, std::vector<int> pos,
+             bool kvBf16) {
+              ops::GemvQ80wArgs a;
+              a.blocks = vec<uint8_t>(blocks);
+              a.rows = rows;
+              a.n = n;
+              a.in = vec<float>(x);
+              a.residual = vec<float>(residual);
+              a.normW = vec<float>(normW);
+              a.eps = eps;
+              a.B = (int)(a.in.size() / n);
+              a.pro = pro;
+              a.epi = epi;
+              a.lanes = lanes;
+              a.passes = passes;
+              a.q0 = q0;
+              a.kv0 = kv0;
+              a.hs = hs;
+              a.rope = vec<float>(rope);
+              a.seqLen = seqLen;
+              a.pos = pos;
+              a.kvBf16 = kvBf16;
+              ops::GemvQ80wResult r;
+              {
+                  py::gil_scoped_release rel;
+                  r = ops::gemvQ80w(a);
+              }
+              const py::ssize_t B = a.B;
+              py::dict d;
+              if (!r.out.empty()) d["out"] = arr(r.out, {B, (py::ssize_t)r.out.size() / B});
+              if (!r.xNext.empty()) d["x_next"] = arr(r.xNext, {B, (py::ssize_t)n});
+              if (!r.codes.empty()) d["codes"] = arr(r.codes, {B, (py::ssize_t)r.codes.size() / B});
+              if (!r.scales.empty()) d["scales"] = arr(r.scales, {B, (py::ssize_t)r.scales.size() / B / 2, (py::ssize_t)2});
+              if (!r.k.empty()) d["k"] = arr(r.k, {B, (py::ssize_t)kv0});
+              if (!r.v.empty()) d["v"] = arr(r.v, {B, (py::ssize_t)kv0});
+              return d;
+          },
+          py::arg("blocks"), py::arg("rows"), py::arg("n"), py::arg("x"), py::arg("residual") = py::none(),
+          py::arg("norm_w") = py::none(), py::arg("eps") = 1e-5f, py::arg("pro") = 1, py::arg("epi") = 0,
+          py::arg("lanes") = 0, py::arg("passes") = 0, py::arg("q0") = 0, py::arg("kv0") = 0, py::arg("hs") = 0,
+          py::arg("rope") = py::none(), py::arg("seq_len") = 0, py::arg("pos") = std::vector<int>(),
+          py::arg("kv_bf16") = true);
+    o.def("gemm_q80w",
+          [](py::object blocks, int rows, int n, py::object x, int lanes, int splits, int epi, py::object resIn,
+             py::object resW, py::object ss, int ssTiles, float eps, int fetch) {
+              ops::GemmQ80wArgs a;
+              a.fetch = fetch;
+              a.blocks = vec<uint8_t>(blocks);
+              a.rows = rows;
+              a.n = n;
+              a.in = vec<float>(x);
+              a.M = (int)(a.in.size() / n);
+              a.lanes = lanes;
+              a.splits = splits;
+              a.epi = epi;
+              a.resIn = vec<float>(resIn);
+              a.resW = vec<float>(resW);
+              a.ss = vec<float>(ss);
+              a.ssTiles = ssTiles;
+              a.eps = eps;
+              ops::GemmQ80wResult r;
+              {
+                  py::gil_scoped_release rel;
+                  r = ops::gemmQ80w(a);
+              }
+              const py::ssize_t M = a.M;
+              py::dict d;
+              d["out"] = arr(r.out, {M, (py::ssize_t)rows});
+              d["splits"] = r.splits;
+              if (!r.resX.empty()) d["res_x"] = arr(r.resX, {M, (py::ssize_t)rows});
+              if (!r.ssOut.empty()) d["ss"] = arr(r.ssOut, {(py::ssize_t)r.ssOut.size() / M, M});
+              return d;
+          },
+          py::arg("blocks"), py::arg("rows"), py::arg("n"), py::arg("x"), py::arg("lanes") = 0, py::arg("splits") = 0,
+          py::arg("epi") = 0, py::arg("res_in") = py::none(), py::arg("res_w") = py::none(), py::arg("ss") = py::none(),
+          py::arg("ss_tiles") = 0, py::arg("eps") = 1e-5f, py::arg("fetch") = 0);
     o.def("gemm_q40",
           [](py::object blocks, int rows, int n, py::object x, py::object residual, py::object normW, float eps,
              int splits) {
@@ -1070,6 +1158,26 @@ PYBIND11_MODULE(_C, m) {
         cpu::matmulQ40Q80(reinterpret_cast<const BlockQ40 *>(blocks.data()), rows, cols, xs.data(), B, ys.data(), pool);
         return out;
     }, py::arg("blocks"), py::arg("rows"), py::arg("cols"), py::arg("x"), py::arg("nthreads") = 4);
+    // the same for Q80 weight blocks [rows][cols/32] (34 bytes): sum_j f32(dw) * dx * (sum_i qw * qx)
+    co.def("matmul_q80_q80", [](py::array_t<uint8_t, py::array::c_style> blocks, int rows, int cols,
+                                py::array_t<float, py::array::c_style | py::array::forcecast> x, int nThreads) {
+        DL_CHECK(cols % kQBlock == 0 && (size_t)blocks.size() == (size_t)rows * cols / kQBlock * kQ80BlockBytes &&
+                     x.size() % cols == 0, "matmul_q80_q80 shapes");
+        const int B = (int)(x.size() / cols);
+        std::vector<BlockQ80> xq((size_t)B * cols / kQBlock);
+        quantizeQ80(x.data(), xq.data(), (u64)B * cols);
+        std::vector<const BlockQ80 *> xs(B);
+        py::array_t<float> out({(py::ssize_t)B, (py::ssize_t)rows});
+        std::vector<float *> ys(B);
+        for (int b = 0; b < B; b++) {
+            xs[b] = xq.data() + (size_t)b * cols / kQBlock;
+            ys[b] = out.mutable_data() + (size_t)b * rows;
+        }
+        ThreadPool pool(nThreads);
+        py::gil_scoped_release rel;
+        cpu::matmulQ80Q80(reinterpret_cast<const BlockQ80 *>(blocks.data()), rows, cols, xs.data(), B, ys.data(), pool);
+        return out;
+    }, py::arg("blocks"), py::arg("rows"), py::arg("cols"), py::arg("x"), py::arg("nthreads") = 4);
 
     m.def("load_header", [](const std::string &path, u32 maxSeqLen) { return headerToDict(loadModelHeader(path, maxSeqLen)); },
           py::arg("path"), py::arg("max_seq_len") = 0);
@@ -1439,6 +1547,17 @@ PYBIND11_MODULE(_C, m) {
     m.def("bench_gemm_q40", [](int rows, int n, int M, int epi, int copies, int iters) {
               return benchGemmQ40(rows, n, M, epi, copies, iters);
           }, py::arg("rows"), py::arg("n"), py::arg("tokens"), py::arg("epi") = 0,
+          py::arg("copies") = 8, py::arg("iters") = 100, py::call_guard<py::gil_scoped_release>());
+    m.def("bench_gemv_q80w",
+          [](int rows, int n, int pro, int epi, int B, int lanes, int passes, int depth, int copies, int iters) {
+              return benchGemvQ80w(rows, n, pro, epi, B, lanes, passes, depth, copies, iters);
+          },
+          py::arg("rows"), py::arg("n"), py::arg("pro") = 0, py::arg("epi") = 0, py::arg("batch") = 1, py::arg("lanes") = 0,
+          py::arg("passes") = 0, py::arg("depth") = 0, py::arg("copies") = 8, py::arg("iters") = 200,
+          py::call_guard<py::gil_scoped_release>());
+    m.def("bench_gemm_q80w", [](int rows, int n, int M, bool f32, int fetch, int copies, int iters) {
+              return benchGemmQ80w(rows, n, M, f32, fetch, copies, iters);
+          }, py::arg("rows"), py::arg("n"), py::arg("tokens"), py::arg("f32") = false, py::arg("fetch") = 0,
           py::arg("copies") = 8, py::arg("iters") = 100, py::call_guard<py::gil_scoped_release>());
     m.def("bench_attention",
           [](int nh, int kvm, int hs, int seq, int pos, int B, int copies, int iters, bool kvBf16) {

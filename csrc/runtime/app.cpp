@@ -76,6 +76,11 @@ AppArgs AppArgs::parse(int argc, char **argv, bool requireMode) {
         else if (name == "--graph") a.graphs = std::atoi(value) != 0;
         else if (name == "--log-level") a.logLevel = std::atoi(value);
         else if (name == "--synthetic") a.synthetic = value;
+        else if (name == "--synthetic-weights") {
+            a.syntheticWeights = parseFloatType(value);
+            if (a.syntheticWeights != FloatType::Q40 && a.syntheticWeights != FloatType::Q80)
+                throw Error("Invalid --synthetic-weights (q40|q80): " + std::string(value));
+        }
         else if (name == "--web-ui") a.webUi = value;
         else if (name == "--stream-weights") a.streamWeights = std::atoi(value) != 0;
         else if (name == "--weights-cache") a.weightsCache = value;
@@ -89,9 +94,9 @@ AppArgs AppArgs::parse(int argc, char **argv, bool requireMode) {
     return a;
 }
 
-ModelHeader syntheticHeader(const std::string &name, u32 seqLen) {
+ModelHeader syntheticHeader(const std::string &name, u32 seqLen, FloatType weights) {
     ModelHeader h;
-    h.weightType = FloatType::Q40;
+    h.weightType = weights;
     h.vocabSize = 128256;
     h.nKvHeads = 8;
     h.ropeTheta = 500000.f;
@@ -137,7 +142,7 @@ static EngineConfig engineConfigFrom(const AppArgs &a, int nSlots) {
     c.batchInvariant = a.batchInvariant;
     if (!a.synthetic.empty()) {
         c.synthetic = true;
-        c.syntheticHeader = syntheticHeader(a.synthetic, a.maxSeqLen);
+        c.syntheticHeader = syntheticHeader(a.synthetic, a.maxSeqLen, a.syntheticWeights);
         c.bufferType = FloatType::Q80;
     }
     return c;
@@ -162,7 +167,7 @@ InferenceSession::InferenceSession(const AppArgs &args, int nSlots) : args_(args
         ModelHeader h = loadModelHeader(args.modelPath, args.maxSeqLen);
         if ((u32)world > h.nKvHeads)
             throw Error("This version does not support more nodes than the number of KV heads in the model");
-        if (h.weightType == FloatType::Q40 && args.bufferType != FloatType::Q80)
+        if ((h.weightType == FloatType::Q40 || h.weightType == FloatType::Q80) && args.bufferType != FloatType::Q80)
             throw Error("This version supports only Q40 weights with Q80 sync type");
     }
 
@@ -175,7 +180,7 @@ InferenceSession::InferenceSession(const AppArgs &args, int nSlots) : args_(args
             const char *dcEnv = std::getenv("DL_TP_COMM");
             wc.devComm = dcEnv && *dcEnv ? dcEnv : "xgmi";
             const ModelHeader h = args.synthetic.empty() ? loadModelHeader(args.modelPath, args.maxSeqLen)
-                                                         : syntheticHeader(args.synthetic, args.maxSeqLen);
+                                                         : syntheticHeader(args.synthetic, args.maxSeqLen, args.syntheticWeights);
             const u64 vocab0 = (h.vocabSize + world - 1) / world;
             wc.xgmiMaxFloats = (u64)ec.maxBatch * std::max<u64>(h.dim, vocab0);
             if (wc.devComm == "rccl") wc.rcclUid = rcclGetUniqueId();

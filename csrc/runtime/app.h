@@ -54,6 +54,7 @@ struct AppArgs {
     bool graphs = true;
     int logLevel = 1;
     std::string synthetic;                       // "llama3_1_8b" etc: random-init weights on device
+    FloatType syntheticWeights = FloatType::Q40; // --synthetic-weights q40|q80: their weight type
     std::string webUi;                           // dllama-api: directory served at GET /
     bool streamWeights = false;                  // worker: always fetch slices from the root
     std::string weightsCache = "/tmp";           // worker: directory for streamed weight files
@@ -157,6 +158,6 @@ class InferenceSession {
 void runWorker(const AppArgs &args);
 
 // Builds the synthetic header for a named shape (see --synthetic).
-ModelHeader syntheticHeader(const std::string &name, u32 seqLen);
+ModelHeader syntheticHeader(const std::string &name, u32 seqLen, FloatType weights = FloatType::Q40);
 
 }  // namespace dl

@@ -4,7 +4,7 @@ HIP kernels (SURVEY §4 "HIP-vs-PyTorch oracle tests").
 Semantics follow the reference graph (src/llm.cpp:184-434): pre-norm blocks, RoPE over adjacent
 pairs (Q/K rows are pre-permuted in the .m file, convert-hf.py:11-14), GQA attention, SwiGLU
 (or GELU·up when hidden_act = 0), final norm, vocab projection. With `q80=True` every matmul input
-is rounded through Q80 exactly like the Q40/Q80 runtime path.
+is rounded through Q80 exactly like the runtime path of Q40 and Q80 weights.
 """
 from __future__ import annotations
 
@@ -56,7 +56,7 @@ def q80_round(x: torch.Tensor) -> torch.Tensor:
 class TorchLlama:
     def __init__(self, path: str, device: str = "cpu", q80: Optional[bool] = None):
         self.header, self.spec, w = read_model(path)
-        self.q80 = (self.spec.weights_float_type == 2) if q80 is None else q80
+        self.q80 = (self.spec.weights_float_type in (2, 3)) if q80 is None else q80
         self.device = device
         self.w: Dict[tuple, torch.Tensor] = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device) for k, v in w.items()}
         self.rope = rope_table(self.spec, self.spec.max_seq_len).to(device)

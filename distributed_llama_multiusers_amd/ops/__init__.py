@@ -114,6 +114,42 @@ def gemm_f32(w, x, norm_w=None, eps: float = 1e-5) -> torch.Tensor:
     return torch.from_numpy(native().ops.gemm_f32(_np(w), rows, n, _np(x), _np(norm_w), eps))
 
 
+def tile_q80(blocks, rows: int, n: int, lanes: int, c0: int = 0, nc: int = 0):
+    """Tiled device image of file-layout Q80 weight blocks [rows][n/32] (34 bytes each), host only:
+    (int8 plane as uint8, uint32 scale pairs) of columns [c0, c0 + nc) (nc = 0: to the end)."""
+    return native().ops.tile_q80(_np(blocks, np.uint8), rows, n, lanes, c0, nc)
+
+
+def gemv_q80w(blocks, rows: int, n: int, x, residual=None, norm_w=None, eps: float = 1e-5, prologue: str = "resnorm",
+              epilogue: str = "store", lanes: int = 0, passes: int = 0, q0: int = 0, kv0: int = 0, hs: int = 0,
+              rope=None, pos=None, kv_bf16: bool = True):
+    """Q80-weight decode GEMV (1, 2 or 4 rows) over file-layout blocks. prologue "resnorm": (x +
+    residual) -> RMS norm (norm_w) -> Q80 in LDS; "global": x quantized to Q80 on the host and read
+    as the producer's blocks (store only). epilogue "store", "swiglu" (interleaved (w1, w3) rows),
+    "swiglu_q80" (-> codes, scales) or "qkv" (rows = q0 + 2 kv0: RoPE from `rope` [seq_len, hs/2, 2]
+    at `pos`, K / V appended to a cache, row b in slot b). Returns a dict of torch tensors: out,
+    x_next, codes, scales, k, v as the launch produced them."""
+    epi = {"store": 0, "swiglu": 1, "qkv": 2, "swiglu_q80": 3}[epilogue]
+    seq_len = 0 if rope is None else int(np.asarray(rope).shape[0])
+    r = native().ops.gemv_q80w(_np(blocks, np.uint8), rows, n, _np(x), _np(residual), _np(norm_w), eps,
+                               {"global": 0, "resnorm": 1}[prologue], epi, lanes, passes, q0, kv0, hs, _np(rope),
+                               seq_len, [int(p) for p in (pos if pos is not None else [])], kv_bf16)
+    return {k: torch.from_numpy(v) for k, v in r.items()}
+
+
+def gemm_q80w(blocks, rows: int, n: int, x, lanes: int = 0, splits: int = 0, epilogue: str = "store", res_in=None,
+              res_w=None, ss=None, eps: float = 1e-5, fetch: int = 0):
+    """Batched (MFMA) matmul for Q80 weights, 1..256 tokens in launches of <= 64: x rounded to f16,
+    weights exact (int8 -> f16 into a per-block accumulator, scaled in f32). epilogue "store", or
+    "res": out = res_in + W.x, res_x = the f16 hand-off rows out * res_w / 32, ss = per-64-row-tile
+    sums of squares. `fetch` 8 / 16 picks the kernel's weight bytes per lane and load (0: the default). `ss` given: x is a producer's res_x and each token's output is scaled by its RMS
+    factor. `splits` > 0 forces the K split. Returns a dict: out, splits (per launch), res_x, ss."""
+    ss_tiles = 0 if ss is None else int(np.asarray(ss).shape[0])
+    r = native().ops.gemm_q80w(_np(blocks, np.uint8), rows, n, _np(x), lanes, splits, {"store": 0, "res": 6}[epilogue],
+                               _np(res_in), _np(res_w), _np(ss), ss_tiles, eps, fetch)
+    return {k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()}
+
+
 GEMM_INPUTS = {"norm": 0, "f16": 1, "prenorm": 2}
 GEMM_EPILOGUES = {"store": 0, "qkv": 2, "swiglu_f16": 4, "res": 6}
 
