@@ -99,7 +99,8 @@ double benchGemvQ40(int rows, int n, int pro, int epi, int B, int lanes, int pas
 }
 
 double benchGemmQ40(int rows, int n, int M, int epi, int copies, int iters, std::vector<unsigned long long> *trace) {
-    DL_CHECK(M >= 1 && M <= hipk::kGemmMaxTokens && hipk::gemmSupported(n) && rows % 64 == 0, "bad gemm bench shape");
+    DL_CHECK(M >= 1 && (M <= hipk::kGemmMaxTokens || (M <= 2048 && hipk::gemmUsesWide(M))) && hipk::gemmSupported(n) &&
+                 rows % 64 == 0, "bad gemm bench shape");
     Scratch sc;
     hipStream_t s = sc.s;
     const int L = hipk::gemvLanesPerRow(n, rows, 1, true);
@@ -185,9 +186,13 @@ double benchGemvQ80w(int rows, int n, int pro, int epi, int B, int lanes, int pa
 }
 
 // Batched GEMM on Q80 (fetch 0 / 8 / 16: launchGemmQ80w) or F32 (f32 = true: gemmF32Kernel) weights, EPI_STORE.
-double benchGemmQ80w(int rows, int n, int M, bool f32, int fetch, int copies, int iters) {
-    DL_CHECK(M >= 1 && M <= hipk::kGemmF32MaxTokens && hipk::gemmSupported(n) && rows % 64 == 0 && copies >= 1,
-             "bad gemm bench shape");
+// M > 64: one pass over the M tokens per timed iteration, as one launchGemmQ80wWide (wide) or as
+// ceil(M / 64) narrow launches (the chunking of an engine without the wide kernel).
+double benchGemmQ80w(int rows, int n, int M, bool f32, int fetch, int copies, int iters, bool wide) {
+    const int C = hipk::kGemmF32MaxTokens;
+    DL_CHECK(M >= 1 && M <= 2048 && hipk::gemmSupported(n) && rows % 64 == 0 && copies >= 1, "bad gemm bench shape");
+    wide = wide && !f32 && M > C;
+    DL_CHECK(!wide || hipk::gemmWideAccepts(n, 1), "the wide kernel takes widths of whole two-block stages");
     Scratch sc;
     hipStream_t s = sc.s;
     const int L = hipk::gemvLanesPerRow(n, rows, 1, true);
@@ -205,27 +210,33 @@ double benchGemmQ80w(int rows, int n, int M, bool f32, int fetch, int copies, in
             hipk::launchFillQ80w(q[c], d[c], t.qBytes / 16, t.dBytes / 2, 1e-3f, 77 + c, s);
         }
     }
-    const int MP = hipk::gemmTokenPad(M);
+    const int MP = (M + 127) / 128 * 128;  // covers the narrow launches' 16 / 32 / 64-row pads too
     _Float16 *x = sc.alloc<_Float16>((size_t)MP * n);
     hipk::launchFillF32Uniform((float *)x, (size_t)MP * n / 2, 1e-3f, 3, s);  // small finite f16 pairs
-    const size_t part = hipk::gemmPartFloats(rows, n, M);
+    const int chunk = wide ? M : C;
+    const size_t part = wide ? hipk::gemmWidePartFloats(rows, n, M) : hipk::gemmPartFloats(rows, n, std::min(M, C));
     hipk::GemmArgs g;
     g.e.rows = rows;
     g.e.n = n;
     g.e.lanes = L;
-    g.e.out = sc.alloc<float>((size_t)M * rows);
+    float *out = sc.alloc<float>((size_t)M * rows);
     g.e.ldOut = rows;
-    g.x = x;
-    g.M = M;
-    g.splits = hipk::gemmSplits(rows, n, M);
     g.part = part ? sc.alloc<float>(part) : nullptr;
-    g.counters = sc.alloc<int>((size_t)rows / 64 + 1);
+    g.partFloats = part;
+    g.counters = sc.alloc<int>((size_t)std::max(rows / 64 + 1, hipk::gemmWideCounters(rows, M)));
     return timeGraphUs(s, iters, [&](int c) {
         g.e.qs = q[c % copies];
         g.e.wd = d[c % copies];
         g.e.wf = wf[c % copies];
-        if (f32) hipk::launchGemmF32(g, hipk::EPI_STORE, s);
-        else hipk::launchGemmQ80w(g, hipk::EPI_STORE, s, fetch);
+        for (int c0 = 0; c0 < M; c0 += chunk) {
+            g.M = std::min(chunk, M - c0);
+            g.splits = wide ? hipk::gemmWideSplits(rows, n, M) : hipk::gemmSplits(rows, n, g.M);
+            g.x = x + (size_t)c0 * n;
+            g.e.out = out + (size_t)c0 * rows;
+            if (f32) hipk::launchGemmF32(g, hipk::EPI_STORE, s);
+            else if (wide) hipk::launchGemmQ80wWide(g, hipk::EPI_STORE, s);
+            else hipk::launchGemmQ80w(g, hipk::EPI_STORE, s, fetch);
+        }
     });
 }
 

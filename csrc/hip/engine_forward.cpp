@@ -453,11 +453,12 @@ bool HipEngineImpl::tpBatchedOk(int n) const {
 
 void HipEngineImpl::gemmBatched(const DevMat &m, int n, int epi, const MatOperands &o) {
     DL_CHECK(!o.aq && !o.as && !o.oq && !o.os && !o.tp, "GEMV operand on a GEMM launch");
-    // tokens per launch: the wide Q40 kernel takes the whole forward in one launch (one weight
-    // pass per token tile, all tiles of a row tile on one XCD), the narrow one <= 128
+    // tokens per launch: the wide Q40 / Q80 kernels take the whole forward in one launch (one weight
+    // pass per token tile, all tiles of a row tile on one XCD), the narrow ones <= 128 (Q40) / 64
     // (batch-invariant engines: narrow launches only, the split count of a 16-token launch for all)
-    // (a width the wide kernel cannot split into its two-block stages: narrow launches too)
-    const int chunk = hipk::gemmChunkTokens(m.n, n, q40(), invariant_);
+    // (a width the wide kernels cannot split into their two-block stages: narrow launches too)
+    const hipk::GemmWeights kind = q40() ? hipk::GEMM_W_Q40 : q80w() ? hipk::GEMM_W_Q80 : hipk::GEMM_W_F32;
+    const int chunk = hipk::gemmChunkTokens(m.n, n, kind, invariant_);
     for (int c0 = 0; c0 < n; c0 += chunk) {
         const int bc = std::min(chunk, n - c0);
         xChunk_ = c0 / chunk;  // each launch's tile exchange waits in a measured-sync slot of its own
@@ -514,6 +515,8 @@ void HipEngineImpl::gemmBatched(const DevMat &m, int n, int epi, const MatOperan
         g.counters = dGemmCnt_;
         if (q40())
             hipk::launchGemmQ40(g, epi, stream_);
+        else if (q80w() && !invariant_ && hipk::gemmUsesWide(bc))
+            hipk::launchGemmQ80wWide(g, epi, stream_);
         else if (q80w())
             hipk::launchGemmQ80w(g, epi, stream_);
         else

@@ -437,10 +437,11 @@ GemmKernel gemmKernelFor(int n, int M, int lanes, int splits, bool fixed) {
     return gemmL16Eligible(n, M, lanes) && splits > 0 && (n / 32 / kG16Ch) % splits == 0 ? GEMM_L16 : GEMM_NARROW;
 }
 
-int gemmChunkTokens(int n, int M, bool q40, bool fixed) {
-    if (!q40) return kGemmF32MaxTokens;
-    if (!gemmUsesWide(M) || fixed) return kGemmMaxTokens;
-    return gemmWideAccepts(n, 1) ? M : std::min(kGemmMaxTokens, gemmWideMin() - 1);
+int gemmChunkTokens(int n, int M, GemmWeights kind, bool fixed) {
+    if (kind == GEMM_W_F32) return kGemmF32MaxTokens;
+    const int narrow = kind == GEMM_W_Q40 ? kGemmMaxTokens : kGemmF32MaxTokens;
+    if (!gemmUsesWide(M) || fixed) return narrow;
+    return gemmWideAccepts(n, 1) ? M : std::min(narrow, gemmWideMin() - 1);
 }
 
 void launchGemmQ40(const GemmArgs &ga, int epi, hipStream_t s) {

@@ -319,22 +319,31 @@ void launchGemmQ40(const GemmArgs &a, int epi, hipStream_t s);
 enum GemmKernel : int { GEMM_NARROW = 0, GEMM_L16 = 1, GEMM_WIDE = 2 };
 GemmKernel gemmKernelFor(int n, int M, int lanes, int splits, bool fixed);
 // Tokens per launch of a forward of M tokens over a matrix of input width n: the whole forward in
-// one wide launch where the wide kernel takes it, else <= 128 (Q40) / <= 64 (F32) per narrow launch.
-// The wide kernel streams two Q40 blocks per stage, so a width that is no multiple of 64 stays on
-// narrow launches below its token threshold.
-int gemmChunkTokens(int n, int M, bool q40, bool fixed);
+// one wide launch where a wide kernel (Q40: gemm_wide.hip, Q80: q80w_gemm_wide.hip) takes it, else
+// <= 128 (Q40) / <= 64 (Q80, F32) per narrow launch. The wide kernels stream two blocks per stage, so
+// a width that is no multiple of 64 stays on narrow launches below the token threshold.
+enum GemmWeights : int { GEMM_W_F32 = 0, GEMM_W_Q40 = 1, GEMM_W_Q80 = 2 };
+int gemmChunkTokens(int n, int M, GemmWeights kind, bool fixed);
 // Same contract for F32 weights (`e.wf` [rows][n] row-major; EPI_ACT_Q80 not supported).
 void launchGemmF32(const GemmArgs &a, int epi, hipStream_t s);
-// Same contract for Q80 weights (`e.qs` / `e.wd` tiled as Q80Tiling at `e.lanes`; <= kGemmF32MaxTokens
-// tokens per launch; EPI_STORE, EPI_ACT, EPI_ACT_F16, EPI_QKV, EPI_RES; no tile exchange).
-// fetch: 0 the default weight fetch, else 8 or 16 bytes per lane and load (measurements, q80w_gemm.hip).
+// Same contract for Q80 weights (`e.qs` / `e.wd` tiled as Q80Tiling at `e.lanes`; EPI_STORE, EPI_ACT,
+// EPI_ACT_F16, EPI_QKV, EPI_RES; no tile exchange), two launchers with one numerics contract (int8 ->
+// f16 exact, one zeroed MFMA accumulator per block, acc += f32(dw) * blockAcc):
+//   launchGemmQ80w      <= kGemmF32MaxTokens tokens per launch, weights straight to VGPRs (q80w_gemm.hip).
+//                       fetch: 0 the default weight fetch, else 8 or 16 bytes per lane and load.
+//   launchGemmQ80wWide  any token count in one launch (q80w_gemm_wide.hip): 128 x 128 tiles staged in
+//                       LDS, grid = row tiles x token tiles x K splits. `x` padded to whole 128-token
+//                       tiles; splits must satisfy gemmWideAccepts (whole two-block stages); split-K
+//                       buffers sized by gemmWidePartFloats / gemmWideCounters. The engine uses it for
+//                       launches of gemmUsesWide(M) tokens (gemmChunkTokens).
 void launchGemmQ80w(const GemmArgs &a, int epi, hipStream_t s, int fetch = 0);
+void launchGemmQ80wWide(const GemmArgs &a, int epi, hipStream_t s);
 // Tile / split-K plan of one matrix (rt = 16-row tiles per wave: 64 * rt rows per workgroup).
 struct GemmPlan {
     int rt = 1, tiles = 0, splits = 1;
 };
 constexpr int kGemmMaxTokens = 128;    // tokens per narrow Q40 GEMM launch (16, 32, 64 or 128 padded)
-// Wide Q40 GEMM (gemm_wide.hip): launches of >= gemmWideMin() tokens (default 65; DL_GEMM_WIDE=0
+// Wide GEMMs (Q40: gemm_wide.hip, Q80: q80w_gemm_wide.hip): launches of >= gemmWideMin() tokens (default 65; DL_GEMM_WIDE=0
 // disables) run 128 x 128 tiles over every token tile of the launch; any token count per launch
 // (activation operand padded to whole 128-token tiles).
 bool gemmWideOn();

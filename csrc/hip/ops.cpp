@@ -426,9 +426,16 @@ GemvQ80wResult gemvQ80w(const GemvQ80wArgs &p) {
 
 GemmQ80wResult gemmQ80w(const GemmQ80wArgs &p) {
     const int rows = p.rows, n = p.n, M = p.M;
-    DL_CHECK(M >= 1 && M <= 256, "gemm tokens must be 1..256");
+    DL_CHECK(M >= 1 && M <= 2048, "gemm tokens must be 1..2048");
     DL_CHECK(hipk::gemmSupported(n) && p.in.size() == (size_t)M * n, "gemm operand sizes");
     DL_CHECK(p.splits == 0 || (p.splits > 0 && (n / 32) % p.splits == 0), "gemm splits must divide n / 32");
+    // tokens per launch: the engine's rule, one wide launch, or narrow launches of <= 64
+    const int narrowChunk = hipk::kGemmF32MaxTokens;
+    const int chunk = p.wide < 0 ? hipk::gemmChunkTokens(n, M, hipk::GEMM_W_Q80, false) : p.wide ? M : narrowChunk;
+    const bool wide = p.wide < 0 ? hipk::gemmUsesWide(std::min(chunk, M)) : p.wide != 0;
+    DL_CHECK(wide || M <= 256, "gemm_q80w: narrow launches take 1..256 tokens");
+    DL_CHECK(!wide || hipk::gemmWideAccepts(n, std::max(p.splits, 1)),
+             "gemm_q80w: the wide kernel splits K into whole two-block stages");
     DL_CHECK(p.epi == hipk::EPI_STORE || p.epi == hipk::EPI_RES, "gemm_q80w epilogue: 0 store, 6 residual + norm hand-off");
     const bool res = p.epi == hipk::EPI_RES;
     DL_CHECK(!res || (rows % 2 == 0 && p.resIn.size() == (size_t)M * rows && p.resW.size() == (size_t)rows),
@@ -437,8 +444,9 @@ GemmQ80wResult gemmQ80w(const GemmQ80wArgs &p) {
     Scratch sc;
     hipk::GemmArgs g;
     uploadQ80w(sc, p.blocks, rows, n, p.lanes > 0 ? p.lanes : hipk::gemvLanesPerRow(n, rows, 1, true), g.e);
-    // the activation operand: `in` rounded to f16, rows past M (read by the last launch) zero
-    const int chunk = hipk::kGemmF32MaxTokens, rowsPad = (M + chunk - 1) / chunk * chunk;
+    // the activation operand: `in` rounded to f16, rows past M (read by the last launch: 64-token
+    // pads, or the wide kernel's whole 128-token tiles) zero
+    const int pad = wide ? 128 : narrowChunk, rowsPad = (M + pad - 1) / pad * pad;
     std::vector<uint16_t> xh((size_t)rowsPad * n, 0);
     for (size_t i = 0; i < p.in.size(); i++) xh[i] = f32ToF16(p.in[i]);
     const _Float16 *x = reinterpret_cast<const _Float16 *>(sc.upload(xh));
@@ -456,9 +464,12 @@ GemmQ80wResult gemmQ80w(const GemmQ80wArgs &p) {
     const float *ssIn = sc.upload(p.ss);
     g.e.eps = p.eps;
     const int S = p.splits > 0 ? p.splits : 0;
-    size_t part = (size_t)std::max(S, 8) * tiles * chunk * 64;
+    // split-K partials and counters: 64-row x 64-token tiles, or the wide kernel's 128 x 128
+    const size_t wideTiles = (size_t)((rows + 127) / 128) * (rowsPad / 128);
+    size_t part = (size_t)std::max(S, 8) * tiles * narrowChunk * 64;
+    if (wide) part = (size_t)std::max(S, 4) * wideTiles * 128 * 128;
     float *partBuf = sc.alloc<float>(part);
-    int *counters = sc.alloc<int>((size_t)tiles + 1);
+    int *counters = sc.alloc<int>(std::max((size_t)tiles, wideTiles) + 1);
     GemmQ80wResult r;
     for (int c0 = 0; c0 < M; c0 += chunk) {
         const int bc = std::min(chunk, M - c0);
@@ -466,7 +477,7 @@ GemmQ80wResult gemmQ80w(const GemmQ80wArgs &p) {
         a.e.ldOut = ld;
         a.x = x + (size_t)c0 * n;
         a.M = bc;
-        a.splits = S > 0 ? S : hipk::gemmSplits(rows, n, bc);
+        a.splits = S > 0 ? S : wide ? hipk::gemmWideSplits(rows, n, bc) : hipk::gemmSplits(rows, n, bc);
         a.part = partBuf;
         a.partFloats = part;
         a.counters = counters;
@@ -486,7 +497,11 @@ GemmQ80wResult gemmQ80w(const GemmQ80wArgs &p) {
             a.e.out = out + (size_t)c0 * ld;
         }
         r.splits.push_back(a.splits);
-        hipk::launchGemmQ80w(a, p.epi, sc.s, p.fetch);
+        r.kernels.push_back(wide ? "wide" : "narrow");
+        if (wide)
+            hipk::launchGemmQ80wWide(a, p.epi, sc.s);
+        else
+            hipk::launchGemmQ80w(a, p.epi, sc.s, p.fetch);
     }
     sc.sync();
     sc.checkGuards();
@@ -665,7 +680,7 @@ std::vector<GemmLaunch> gemmBatchedPlan(const GemmBatchedArgs &a) {
     }
     DL_CHECK(a.splits >= 0 && a.chunk >= 0 && (a.fixed == 0 || a.fixed == 1), "gemm launch controls");
     const int L = q40 ? (a.lanes > 0 ? a.lanes : hipk::gemvLanesPerRow(n, rows, 1, true)) : 0;
-    const int chunk = a.chunk > 0 ? a.chunk : hipk::gemmChunkTokens(n, M, q40, a.fixed != 0);
+    const int chunk = a.chunk > 0 ? a.chunk : hipk::gemmChunkTokens(n, M, q40 ? hipk::GEMM_W_Q40 : hipk::GEMM_W_F32, a.fixed != 0);
     const int tiles = (rows + 63) / 64;
     std::vector<GemmLaunch> plan;
     for (int c0 = 0; c0 < M; c0 += chunk) {

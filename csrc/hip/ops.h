@@ -97,7 +97,9 @@ struct GemvQ80wResult {
     std::vector<int8_t> codes;
 };
 GemvQ80wResult gemvQ80w(const GemvQ80wArgs &a);
-// gemmQ80w: gemmQ80wKernel over M tokens in launches of <= 64, `in` rounded to f16 on the host. epi 0
+// gemmQ80w: M tokens over Q80 weights, `in` rounded to f16 on the host. wide < 0: the engine's chunking
+// (gemmChunkTokens: one gemmQ80wWideKernel launch from the wide threshold up, else gemmQ80wKernel
+// launches of <= 64); 1: one wide launch whatever M; 0: narrow launches (M <= 256). epi 0
 // (EPI_STORE): out [M][rows]; epi 6 (EPI_RES): resIn [M][rows], resW [rows] -> out = resOut, resX (the
 // f16 hand-off rows as f32), ssOut [ceil(rows / 64)][M]. splits 0 = gemmSplits per launch. Outputs are
 // guarded as gemmBatched's.
@@ -105,6 +107,7 @@ struct GemmQ80wArgs {
     std::vector<uint8_t> blocks;
     int rows = 0, n = 0, lanes = 0, M = 0, epi = 0, splits = 0;
     int fetch = 0;  // 0 the launcher's default, 8 or 16: weight bytes per lane and load
+    int wide = -1;
     std::vector<float> in, resIn, resW;
     // consumer of an EPI_RES producer: `in` = its resX rows, ss = its ssOut [ssTiles][M] (else empty)
     std::vector<float> ss;
@@ -114,6 +117,7 @@ struct GemmQ80wArgs {
 struct GemmQ80wResult {
     std::vector<float> out, resX, ssOut;
     std::vector<int> splits;
+    std::vector<std::string> kernels;  // per launch: "narrow" / "wide"
 };
 GemmQ80wResult gemmQ80w(const GemmQ80wArgs &a);
 

@@ -24,24 +24,7 @@ static constexpr int kQ80wGemmU = 4;
 static constexpr int kQ80wGemmFetch = DL_Q80W_GEMM_FETCH;
 static constexpr int kGemmScaleFloats = 128 + 256;  // gemmFinish: per-token RMS scales + per-thread slices
 
-// 8 int8 -> 8 f16, exact.
-__device__ __forceinline__ half8 q80ToF16x8(u32x2 wv) {
-    const uint32_t lo = wv.x ^ 0x80808080u, hi = wv.y ^ 0x80808080u;  // q + 128 in 0..255
-    const uint32_t magic = 0x64646464u;                               // f16 0x64bb = 1024 + bb
-    const uint32_t p0 = __builtin_amdgcn_perm(magic, lo, 0x07010700u);
-    const uint32_t p1 = __builtin_amdgcn_perm(magic, lo, 0x07030702u);
-    const uint32_t p2 = __builtin_amdgcn_perm(magic, hi, 0x07010700u);
-    const uint32_t p3 = __builtin_amdgcn_perm(magic, hi, 0x07030702u);
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    const h2 off = {(_Float16)-1152.0f, (_Float16)-1152.0f};
-    const h2 r0 = __builtin_bit_cast(h2, p0) + off, r1 = __builtin_bit_cast(h2, p1) + off;
-    const h2 r2 = __builtin_bit_cast(h2, p2) + off, r3 = __builtin_bit_cast(h2, p3) + off;
-    half8 out;
-    out[0] = r0[0]; out[1] = r0[1]; out[2] = r1[0]; out[3] = r1[1];
-    out[4] = r2[0]; out[5] = r2[1]; out[6] = r3[0]; out[7] = r3[1];
-    return out;
-}
-
+// (int8 -> f16: q80ToF16x8, gemm_dev.h.)
 // FETCH = 16: the same product with one 16-byte weight load per lane and block pair. Lane (col, h)
 // loads the whole unit (block j + (h & 1), half h >> 1) of its row and the matching 2 x 16 B of
 // activations; each block of the pair takes two MFMAs (the unit's first and second 8 bytes) in which

@@ -498,9 +498,10 @@ void bindOps(py::module_ &m) {
           py::arg("kv_bf16") = true);
     o.def("gemm_q80w",
           [](py::object blocks, int rows, int n, py::object x, int lanes, int splits, int epi, py::object resIn,
-             py::object resW, py::object ss, int ssTiles, float eps, int fetch) {
+             py::object resW, py::object ss, int ssTiles, float eps, int fetch, py::object wide) {
               ops::GemmQ80wArgs a;
               a.fetch = fetch;
+              a.wide = wide.is_none() ? -1 : (wide.cast<bool>() ? 1 : 0);
               a.blocks = vec<uint8_t>(blocks);
               a.rows = rows;
               a.n = n;
@@ -523,13 +524,14 @@ void bindOps(py::module_ &m) {
               py::dict d;
               d["out"] = arr(r.out, {M, (py::ssize_t)rows});
               d["splits"] = r.splits;
+              d["kernels"] = r.kernels;
               if (!r.resX.empty()) d["res_x"] = arr(r.resX, {M, (py::ssize_t)rows});
               if (!r.ssOut.empty()) d["ss"] = arr(r.ssOut, {(py::ssize_t)r.ssOut.size() / M, M});
               return d;
           },
           py::arg("blocks"), py::arg("rows"), py::arg("n"), py::arg("x"), py::arg("lanes") = 0, py::arg("splits") = 0,
           py::arg("epi") = 0, py::arg("res_in") = py::none(), py::arg("res_w") = py::none(), py::arg("ss") = py::none(),
-          py::arg("ss_tiles") = 0, py::arg("eps") = 1e-5f, py::arg("fetch") = 0);
+          py::arg("ss_tiles") = 0, py::arg("eps") = 1e-5f, py::arg("fetch") = 0, py::arg("wide") = py::none());
     o.def("gemm_q40",
           [](py::object blocks, int rows, int n, py::object x, py::object residual, py::object normW, float eps,
              int splits) {
@@ -1555,10 +1557,12 @@ PYBIND11_MODULE(_C, m) {
           py::arg("rows"), py::arg("n"), py::arg("pro") = 0, py::arg("epi") = 0, py::arg("batch") = 1, py::arg("lanes") = 0,
           py::arg("passes") = 0, py::arg("depth") = 0, py::arg("copies") = 8, py::arg("iters") = 200,
           py::call_guard<py::gil_scoped_release>());
-    m.def("bench_gemm_q80w", [](int rows, int n, int M, bool f32, int fetch, int copies, int iters) {
-              return benchGemmQ80w(rows, n, M, f32, fetch, copies, iters);
+    m.def("bench_gemm_q80w", [](int rows, int n, int M, bool f32, int fetch, int copies, int iters, bool wide) {
+              return benchGemmQ80w(rows, n, M, f32, fetch, copies, iters, wide);
           }, py::arg("rows"), py::arg("n"), py::arg("tokens"), py::arg("f32") = false, py::arg("fetch") = 0,
-          py::arg("copies") = 8, py::arg("iters") = 100, py::call_guard<py::gil_scoped_release>());
+          py::arg("copies") = 8, py::arg("iters") = 100, py::arg("wide") = true, py::call_guard<py::gil_scoped_release>(),
+          "us per pass over `tokens` rows: above 64 tokens one gemmQ80wWideKernel launch (wide) or the chunked "
+          "narrow launches of <= 64 (wide = false)");
     m.def("bench_attention",
           [](int nh, int kvm, int hs, int seq, int pos, int B, int copies, int iters, bool kvBf16) {
               return benchAttention(nh, kvm, hs, seq, pos, B, copies, iters, nullptr, kvBf16);

@@ -11,6 +11,8 @@ with GQA (nn-cpu-ops.cpp:749-784), SiLU (nn-cpu-ops.cpp:453-491), embedding (nn-
 """
 from __future__ import annotations
 
+from typing import Optional
+
 import numpy as np
 import torch
 
@@ -138,15 +140,19 @@ def gemv_q80w(blocks, rows: int, n: int, x, residual=None, norm_w=None, eps: flo
 
 
 def gemm_q80w(blocks, rows: int, n: int, x, lanes: int = 0, splits: int = 0, epilogue: str = "store", res_in=None,
-              res_w=None, ss=None, eps: float = 1e-5, fetch: int = 0):
-    """Batched (MFMA) matmul for Q80 weights, 1..256 tokens in launches of <= 64: x rounded to f16,
-    weights exact (int8 -> f16 into a per-block accumulator, scaled in f32). epilogue "store", or
+              res_w=None, ss=None, eps: float = 1e-5, fetch: int = 0, wide: Optional[bool] = None):
+    """Batched (MFMA) matmul for Q80 weights: x rounded to f16, weights exact (int8 -> f16 into a
+    per-block accumulator, scaled in f32). `wide` None: the engine's chunking (one gemmQ80wWideKernel
+    launch for the whole of x from the wide threshold, 65 rows, up; else gemmQ80wKernel launches of
+    <= 64); True: one wide launch whatever the row count; False: narrow launches (1..256 rows).
+    epilogue "store", or
     "res": out = res_in + W.x, res_x = the f16 hand-off rows out * res_w / 32, ss = per-64-row-tile
     sums of squares. `fetch` 8 / 16 picks the kernel's weight bytes per lane and load (0: the default). `ss` given: x is a producer's res_x and each token's output is scaled by its RMS
-    factor. `splits` > 0 forces the K split. Returns a dict: out, splits (per launch), res_x, ss."""
+    factor. `splits` > 0 forces the K split. Returns a dict: out, splits and kernels ("narrow" / "wide")
+    per launch, res_x, ss."""
     ss_tiles = 0 if ss is None else int(np.asarray(ss).shape[0])
     r = native().ops.gemm_q80w(_np(blocks, np.uint8), rows, n, _np(x), lanes, splits, {"store": 0, "res": 6}[epilogue],
-                               _np(res_in), _np(res_w), _np(ss), ss_tiles, eps, fetch)
+                               _np(res_in), _np(res_w), _np(ss), ss_tiles, eps, fetch, wide)
     return {k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()}
 
 
