@@ -545,25 +545,31 @@ void launchAttentionPrefillDma(const AttnArgs &a, int nRows, hipStream_t s) {
 }
 
 bool attnMfmaSupported(const AttnArgs &a) {
-    return a.kvBf16 && a.hs == kAmHS && (a.kvMul == 1 || a.kvMul == 2 || a.kvMul == 4 || a.kvMul == 8) &&
-           a.nHeads0 % a.kvMul == 0;
+    if (!a.kvBf16) return attnF32MfmaSupported(a);  // attn_mfma_f32.hip
+    return a.hs == kAmHS && (a.kvMul == 1 || a.kvMul == 2 || a.kvMul == 4 || a.kvMul == 8) && a.nHeads0 % a.kvMul == 0;
 }
 
-// DL_ATTN_MFMA: 0 = the VALU kernel everywhere, 1 = this kernel for every supported launch,
-// default (-1) = this kernel when the cache is long enough for it to matter (seqLen >= 1024).
+// DL_ATTN_MFMA: 0 = the VALU kernel everywhere, 1 = the MFMA kernel for every supported launch,
+// default (-1) = the MFMA kernel when the launch asks for it (AttnArgs::mfma, the engine's rule);
+// a launch that leaves the choice open (mfma -1) takes it for bf16 caches long enough for it to
+// matter (seqLen >= 1024) and keeps the VALU kernel on f32 caches.
+// Read at every launch decision (host side, a few per forward; a captured graph keeps its kernels),
+// so an engine built after the variable changed follows the new value.
 static int attnMfmaMode() {
-    static const int v = [] {
-        const char *e = std::getenv("DL_ATTN_MFMA");
-        return e ? std::atoi(e) : -1;
-    }();
-    return v;
+    const char *e = std::getenv("DL_ATTN_MFMA");
+    return e ? std::atoi(e) : -1;
 }
 
 bool attnUsesMfma(const AttnArgs &a) {
     const int mode = attnMfmaMode();
     if (mode == 0 || !attnMfmaSupported(a)) return false;
     if (mode == 1) return true;
-    return a.mfma >= 0 ? a.mfma == 1 : a.seqLen >= 1024;
+    return a.mfma >= 0 ? a.mfma == 1 : a.kvBf16 && a.seqLen >= 1024;
+}
+
+std::string attnMfmaKernelName(const AttnArgs &a) {
+    const std::string km = std::to_string(a.kvMul);
+    return a.kvBf16 ? "attnDecodeMfmaKernel<" + km + ">" : "attnDecodeF32MfmaKernel<" + km + "," + std::to_string(a.hs) + ">";
 }
 
 
@@ -571,6 +577,7 @@ bool attnUsesMfma(const AttnArgs &a) {
 const void *attnMfmaModuleKernel() { return (const void *)attnDecodeMfmaKernel<4>; }
 
 const char *attnMfmaRefusal(const AttnArgs &a) {
+    if (!a.kvBf16) return attnF32MfmaRefusal(a);
     if (!attnMfmaSupported(a)) return "launchAttentionMfma: unsupported kvMul";
     if (2 * a.kvMul * a.splitGrid * 4 + 4096 > (int)kAmLds) return "attention split grid too large";
     if (a.kvMap.table && (a.chunkMax >> a.kvMap.pageShift) + 2 > 64)
@@ -579,6 +586,10 @@ const char *attnMfmaRefusal(const AttnArgs &a) {
 }
 
 void launchAttentionMfma(const AttnArgs &a, int B, hipStream_t s) {
+    if (!a.kvBf16) {
+        launchAttentionF32Mfma(a, B, s);
+        return;
+    }
     const dim3 grid(a.nHeads0 / a.kvMul, a.splitGrid, B);
     if (const char *why = attnMfmaRefusal(a)) throw Error(why);
 #define DL_AM_CASE(K)                                                                             \

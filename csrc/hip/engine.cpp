@@ -517,7 +517,7 @@ void HipEngineImpl::chainLaunch(int token, int pos, int slot) {
     } else {  // dTok_ / dPos_ hold the previous step's id and position + 1 (written on the device)
         DL_CHECK(chainHead_ > 0, "chainLaunch: no chain started");
         mapPages(1, &pos, &chainSlot_, 0);
-        attnLong_ = !invariant_ && pos >= kAttnMfmaMinPos;
+        attnLong_ = attnLongFor(1, pos);
         bucket_ = (int)(&bucketFor(pos) - buckets_.data());
     }
     const int k = (int)(chainHead_ % kChainDepth);

@@ -45,6 +45,13 @@ class HipEngine : public Backend {
         (void)token, (void)pos, (void)slot, (void)layer;
         return {};
     }
+    // The decode attention kernel of a forward of `rows` decode rows (one slot each) whose longest
+    // row is at position maxPos: the instance name ops::attentionPlan reports ("attnKernel" for the
+    // VALU kernel whatever its head group), or "attnBlock" when the row runs the fused block.
+    virtual std::string decodeAttnKernel(int rows, int maxPos) const {
+        (void)rows, (void)maxPos;
+        return "";
+    }
     virtual int fusedGridMax() const { return 0; }
     // Tensor parallel: a batched forward of n rows all-reduces its wo / w2 tiles inside the GEMM
     // epilogues (no separate all-reduce / norm kernels).

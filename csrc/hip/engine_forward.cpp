@@ -53,10 +53,11 @@ void HipEngineImpl::setInputs(int n, const int *tokens, const int *positions, co
     // row's context reaches kAttnMfmaMinPos keys (measured faster from ~1.5K keys, slower on
     // short contexts: profiles/r3_prefill_attention.md) or the forward has kAttnMfmaMinRows rows
     // (batch 16 / 64 at 150 keys: 8.2 / 17.2 us vs 9.5 / 22.8 on the VALU kernel, which stays
-    // ahead up to batch 8: profiles/r5_batched_attention.md), else the VALU kernel
+    // ahead up to batch 8: profiles/r5_batched_attention.md), else the VALU kernel; f32 caches have
+    // their own pair of thresholds (attnLongFor)
     int maxPos = 0;
     for (int b = 0; b < n; b++) maxPos = std::max(maxPos, positions[b] + ahead);
-    attnLong_ = !invariant_ && (maxPos >= kAttnMfmaMinPos || n >= kAttnMfmaMinRows);
+    attnLong_ = attnLongFor(n, maxPos);
     bucket_ = (int)(&bucketFor(maxPos) - buckets_.data());
     const u32 MB = cfg_.maxBatch;
     // keep the pinned staging buffer stable while a previous copy may still read it (every
@@ -243,6 +244,20 @@ hipk::AttnArgs HipEngineImpl::attnArgs(const DevLayer &L, bool bat) const {
     a.headGroup = invariant_ ? 1 : 0;
     a.counters = dAttCnt_;
     return a;
+}
+
+std::string HipEngineImpl::decodeAttnKernel(int rows, int maxPos) const {
+    DL_CHECK(rows >= 1 && (u32)rows <= cfg_.maxBatch && maxPos >= 0 && (u32)maxPos < h_.seqLen, "decodeAttnKernel: rows / position");
+    const int bucket = (int)(&bucketFor(maxPos) - buckets_.data());
+    if (rows == 1 && !batchedPath(1) && blockOn_ && buckets_[bucket].block) return "attnBlock";
+    hipk::AttnArgs a;
+    a.nHeads0 = plan_.nHeads0;
+    a.kvMul = plan_.kvMul;
+    a.hs = plan_.headSize;
+    a.seqLen = h_.seqLen;
+    a.kvBf16 = kvBf16_ ? 1 : 0;
+    a.mfma = attnLongFor(rows, maxPos) ? 1 : 0;
+    return hipk::attnUsesMfma(a) ? hipk::attnMfmaKernelName(a) : "attnKernel";
 }
 
 // The fused attention block of a single decode row (kernels.h AttnBlockArgs): qkv GEMV +

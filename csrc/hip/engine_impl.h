@@ -107,6 +107,7 @@ class HipEngineImpl : public HipEngine {
     bool attnBlock() const override { return blockOn_; }
     bool prenorm() const override { return prenormOn_; }
     std::vector<unsigned long long> traceAttnBlock(int token, int pos, int slot, int layer) override;
+    std::string decodeAttnKernel(int rows, int maxPos) const override;
     int fusedGridMax() const override { return fusedGridMax_; }
     bool tpBatchedFused(int n) const override { return plan_.nRanks > 1 && batchedPath(n) && fuseNorm(n); }
 
@@ -342,6 +343,18 @@ class HipEngineImpl : public HipEngine {
     static constexpr int kBlockCntWords = kMaxKvGroups * 64 + 64 + 8 * 64 + 64 + 8 * 64 + 64;
     static constexpr int kAttnMfmaMinPos = 1024;
     static constexpr int kAttnMfmaMinRows = 16;
+    // f32 caches (attnDecodeF32MfmaKernel): never. It measured slower than the VALU kernel at every
+    // long-context and batched point but one (50 keys x 64 rows: 15.9 vs 17.5 us; 1500 keys 16.6 vs
+    // 13.9 us, 150 keys x 16 rows 12.8 vs 11.5 us: profiles/attn_f32_mfma.md), so no forward selects
+    // it; DL_ATTN_MFMA=1 and the ops' "mfma" switch still run it.
+    static constexpr int kAttnF32MfmaMinPos = 1 << 30;
+    static constexpr int kAttnF32MfmaMinRows = 1 << 30;
+    // the decode attention of a forward of n rows, the longest at maxPos, runs the MFMA kernel
+    bool attnLongFor(int n, int maxPos) const {
+        const int minPos = kvBf16_ ? kAttnMfmaMinPos : kAttnF32MfmaMinPos;
+        const int minRows = kvBf16_ ? kAttnMfmaMinRows : kAttnF32MfmaMinRows;
+        return !invariant_ && (maxPos >= minPos || n >= minRows);
+    }
 
     EngineConfig cfg_;
     DeviceComm *comm_;

@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string>
 
 #include <vector>
 
@@ -407,8 +408,10 @@ size_t gemvLdsBytes(int n, int B, bool q40, int rowsPerWg, int pro);
 int gemvDefaultPasses(int n, int rows, int B, bool q40, int epi, int lanes = 0);
 
 void launchAttention(const AttnArgs &a, int B, hipStream_t s);
-// MFMA decode attention (attn_mfma.hip): bf16 cache, head size 128, kvMul 1/2/4/8; launchAttention
-// takes it for caches of >= 1024 positions (DL_ATTN_MFMA=1: always, 0: never).
+// MFMA decode attention, kvMul 1/2/4/8: bf16 caches of head size 128 (attn_mfma.hip), f32 caches of
+// head size 128 / 64 (attn_mfma_f32.hip). launchAttention takes it when AttnArgs::mfma asks for it
+// (the engine's rule), for bf16 caches of >= 1024 positions when mfma is -1, with DL_ATTN_MFMA=1 for
+// every supported launch and with DL_ATTN_MFMA=0 never.
 bool attnMfmaSupported(const AttnArgs &a);
 bool attnUsesMfma(const AttnArgs &a);
 void launchAttentionMfma(const AttnArgs &a, int B, hipStream_t s);
@@ -418,6 +421,12 @@ int attnValuHeadGroup(const AttnArgs &a, int B);
 // Why a launcher refuses these arguments (the message it throws), or null when it launches them;
 // host only, no device needed.
 const char *attnMfmaRefusal(const AttnArgs &a);
+// the instance launchAttentionMfma runs: "attnDecodeMfmaKernel<KM>" or "attnDecodeF32MfmaKernel<KM,HS>"
+std::string attnMfmaKernelName(const AttnArgs &a);
+// the f32-cache kernel behind launchAttentionMfma / attnMfmaRefusal (attn_mfma_f32.hip)
+bool attnF32MfmaSupported(const AttnArgs &a);
+const char *attnF32MfmaRefusal(const AttnArgs &a);
+void launchAttentionF32Mfma(const AttnArgs &a, int B, hipStream_t s);
 const char *attnPrefillRefusal(const AttnArgs &a);     // launchAttentionPrefill, either kernel family
 // Prefill rows with LDS-DMA staged K / V (attn_mfma.hip; other shapes take the register-staged
 // kernels.hip kernel): bf16 cache, head size 128, kvMul 1..16.

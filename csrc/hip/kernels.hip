@@ -203,7 +203,7 @@ static void attnDispatchHG(const AttnArgs &a, int B, int HG, hipStream_t s) {
 }
 
 void launchAttention(const AttnArgs &a, int B, hipStream_t s) {
-    if (attnUsesMfma(a))  // bf16 cache, long context: MFMA kernel (attn_mfma.hip)
+    if (attnUsesMfma(a))  // long contexts, many rows: the MFMA kernels (attn_mfma.hip, attn_mfma_f32.hip)
         launchAttentionMfma(a, B, s);
     else
         launchAttentionValu(a, B, s);
@@ -429,6 +429,7 @@ const void *gemmModuleKernel();
 const void *gemmWideModuleKernel();
 const void *gemmQ80wWideModuleKernel();
 const void *attnMfmaModuleKernel();
+const void *attnF32MfmaModuleKernel();
 const void *xgmiModuleKernel();
 const void *sampleModuleKernel();
 const void *logitProcModuleKernel();
@@ -454,7 +455,7 @@ void preloadModules() {
     const BlockFn blocks[] = {attnBlockFn_16_16_128, attnBlockFn_16_32_128, attnBlockFn_32_32_128, attnBlockFn_64_32_128, attnBlockFn_64_16_128,
                               attnBlockFn_64_64_128, attnBlockFn_32_64_128, attnBlockFn_64_64_64};
     std::vector<const void *> fns = {sampleModuleKernel(), logitProcModuleKernel(), logitFilterModuleKernel(), jsonMaskModuleKernel(), grammarMaskModuleKernel(), attnPrefillModuleKernel(), tpCheckModuleKernel(),
-                                     gemmModuleKernel(),   gemmWideModuleKernel(),    gemmQ80wWideModuleKernel(), attnMfmaModuleKernel(),
+                                     gemmModuleKernel(),   gemmWideModuleKernel(),    gemmQ80wWideModuleKernel(), attnMfmaModuleKernel(), attnF32MfmaModuleKernel(),
                                      xgmiModuleKernel(),   gemvFnL16(true, 1, 0, 0),
                                      gemvFnL32(true, 1, 0, 0), gemvFnL64(true, 1, 0, 0)};
     for (BlockFn b : blocks) {  // any instance of the unit will do

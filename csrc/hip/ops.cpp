@@ -989,7 +989,7 @@ std::vector<float> attention(const std::vector<float> &q, const std::vector<floa
     else if (impl == 2)
         hipk::launchAttentionValu(a, B, sc.s);
     else if (impl == 3) {
-        DL_CHECK(hipk::attnMfmaSupported(a), "MFMA decode attention: bf16 cache, head size 128, kvMul 1/2/4/8");
+        DL_CHECK(hipk::attnMfmaSupported(a), "MFMA decode attention: head size 128 (f32 caches: 128 or 64), kvMul 1/2/4/8");
         hipk::launchAttentionMfma(a, B, sc.s);
     } else
         hipk::launchAttention(a, B, sc.s);
@@ -1109,14 +1109,14 @@ AttnLaunchPlan attentionPlan(const AttnLaunchArgs &l) {
     }
     bool mfma;
     if (l.kernel == ATTN_MFMA) {
-        DL_CHECK(hipk::attnMfmaSupported(a), "MFMA decode attention: bf16 cache, head size 128, kvMul 1/2/4/8");
+        DL_CHECK(hipk::attnMfmaSupported(a), "MFMA decode attention: head size 128 (f32 caches: 128 or 64), kvMul 1/2/4/8");
         mfma = true;
     } else {
         mfma = l.kernel == ATTN_AUTO && hipk::attnUsesMfma(a);
     }
     if (mfma) {
         if (const char *why = hipk::attnMfmaRefusal(a)) throw Error(why);
-        p.kernel = "attnDecodeMfmaKernel<" + kmS + ">";
+        p.kernel = hipk::attnMfmaKernelName(a);
         p.grid[0] = g.nKv;
     } else {
         p.hg = hipk::attnValuHeadGroup(a, g.B);

@@ -1795,7 +1795,9 @@ PYBIND11_MODULE(_C, m) {
                  return e.engine->traceAttnBlock(token, pos, slot, layer);
              },
              py::arg("token"), py::arg("pos"), py::arg("slot") = 0, py::arg("layer") = 1)
-        .def_property_readonly("fused_grid_max", [](const PyHipEngine &e) { return e.engine->fusedGridMax(); })
+        .def("decode_attn_kernel", [](const PyHipEngine &e, int rows, int maxPos) { return e.engine->decodeAttnKernel(rows, maxPos); },
+             py::arg("rows"), py::arg("max_pos"))
+        .def_property_readonly("fused_grid_max",[](const PyHipEngine &e) { return e.engine->fusedGridMax(); })
         .def_property_readonly("kv_pages_free", [](const PyHipEngine &e) { return e.engine->kvPagesFree(); })
         .def("tp_batched_fused", [](const PyHipEngine &e, int n) { return e.engine->tpBatchedFused(n); }, py::arg("n"))
         .def_property_readonly("load_stats",

@@ -206,7 +206,8 @@ def attention(q, k_cache, v_cache, n_heads0: int, kv_mul: int, head_size: int, p
     """Decode attention. k_cache / v_cache: [slots, seq_len, kv0]; q: [B, n_heads0 * head_size].
     prefill=True (impl "prefill"): the MFMA prefill kernel (bf16 MFMAs for a bf16 cache, f32 MFMAs
     for an f32 one; row blocks of 64 / kv_mul rows share a slot). impl "valu" / "mfma": force the VALU or the MFMA decode kernel ("auto": the
-    engine's choice, MFMA for bf16 caches of >= 1024 positions)."""
+    launcher's choice, MFMA for bf16 caches of >= 1024 positions). "mfma" takes kv_mul 1/2/4/8 and
+    head size 128 on a bf16 cache, head size 128 or 64 on an f32 cache (attnDecodeF32MfmaKernel)."""
     n_slots, seq_len, _ = k_cache.shape
     code = {"auto": 0, "prefill": 1, "valu": 2, "mfma": 3}["prefill" if prefill else impl]
     return torch.from_numpy(native().ops.attention(_np(q), _np(k_cache), _np(v_cache), n_slots, seq_len, n_heads0,
@@ -225,7 +226,8 @@ def attention_launch(q, k_cache, v_cache, n_heads0: int, kv_mul: int, head_size:
                      warm_pos=None, plan_only: bool = False) -> dict:
     """One attention launch set up as the engine sets it up (ops::attentionLaunch, csrc/hip/ops.h).
     q [B, ldq or q0], k_cache / v_cache [slots, seq_len, kv0]. kernel "auto" / "valu" / "mfma" /
-    "prefill"; prefill: prefill rows (row blocks share a slot). single: the engine's single-row split
+    "prefill" ("mfma": attnDecodeMfmaKernel<KM> on a bf16 cache, attnDecodeF32MfmaKernel<KM,HS> on an
+    f32 one; "auto" never picks the latter); prefill: prefill rows (row blocks share a slot). single: the engine's single-row split
     geometry; split_grid > 0 forces the grid. head_group 0 / 1 / 2 / 4 / 8. out "f32" / "f16" / "q80".
     page_size > 0: a paged cache, page_of [slots, ceil(seq_len / page_size)] pool pages (-1: not mapped:
     the poison page, which holds poison_k / poison_v [kv0] at every position). repeat: launches on
