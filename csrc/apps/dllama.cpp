@@ -210,7 +210,7 @@ static void usage() {
                  "  --temperature <t> --topp <p> --seed <s>\n"
                  "  --chat-template {llama2|llama3|deepSeek3}\n"
                  "  --max-seq-len <n> --max-batch <n> --prefill-chunk <n> --slots <n>\n"
-                 "  --kv-dtype {bf16|f32} --graph {0|1} --log-level {0|1|2}\n"
+                 "  --kv-dtype {f32|bf16|fp8} --graph {0|1} --log-level {0|1|2}\n"
                  "  --kv-pages <n> --kv-page-size <p>   (GPU paged KV cache: pool of n pages of p positions)\n"
                  "  --prefix-cache {0|1} --prefix-cache-min <n>  (dllama-api: reuse the KV of shared prompt prefixes;\n"
                  "                                      chat keeps its one session's KV across turns either way)\n"

@@ -516,7 +516,7 @@ __global__ __launch_bounds__(kAmThreads) void attnPrefillDmaKernel(AttnArgs a, i
 }
 
 bool attnPrefillDmaSupported(const AttnArgs &a) {
-    return a.kvBf16 && a.hs == kAmHS && (a.kvMul == 1 || a.kvMul == 2 || a.kvMul == 4 || a.kvMul == 8 ||
+    return !a.kvFp8 && a.kvBf16 && a.hs == kAmHS && (a.kvMul == 1 || a.kvMul == 2 || a.kvMul == 4 || a.kvMul == 8 ||
                                                 a.kvMul == 16);
 }
 
@@ -545,6 +545,7 @@ void launchAttentionPrefillDma(const AttnArgs &a, int nRows, hipStream_t s) {
 }
 
 bool attnMfmaSupported(const AttnArgs &a) {
+    if (a.kvFp8) return false;  // fp8 caches: launchAttentionFp8 (attn_fp8.hip)
     if (!a.kvBf16) return attnF32MfmaSupported(a);  // attn_mfma_f32.hip
     return a.hs == kAmHS && (a.kvMul == 1 || a.kvMul == 2 || a.kvMul == 4 || a.kvMul == 8) && a.nHeads0 % a.kvMul == 0;
 }
@@ -577,6 +578,7 @@ std::string attnMfmaKernelName(const AttnArgs &a) {
 const void *attnMfmaModuleKernel() { return (const void *)attnDecodeMfmaKernel<4>; }
 
 const char *attnMfmaRefusal(const AttnArgs &a) {
+    if (a.kvFp8) return "launchAttentionMfma: fp8 KV caches take launchAttentionFp8";
     if (!a.kvBf16) return attnF32MfmaRefusal(a);
     if (!attnMfmaSupported(a)) return "launchAttentionMfma: unsupported kvMul";
     if (2 * a.kvMul * a.splitGrid * 4 + 4096 > (int)kAmLds) return "attention split grid too large";
@@ -586,6 +588,7 @@ const char *attnMfmaRefusal(const AttnArgs &a) {
 }
 
 void launchAttentionMfma(const AttnArgs &a, int B, hipStream_t s) {
+    if (a.kvFp8) throw Error(attnMfmaRefusal(a));
     if (!a.kvBf16) {
         launchAttentionF32Mfma(a, B, s);
         return;

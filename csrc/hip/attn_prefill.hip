@@ -44,8 +44,9 @@ __device__ __forceinline__ void pfPages(const AttnArgs &a, int sl, int k0, int k
 }
 
 int attnPrefillRowsPerBlock(int kvMul) { return kPfWaves * (16 / kvMul); }
-bool attnPrefillSupported(int hs, int kvMul, bool kvBf16) {
+bool attnPrefillSupported(int hs, int kvMul, bool kvBf16, bool kvFp8) {
     (void)kvBf16;  // bf16: attnPrefillKernel (or the LDS-DMA kernel), f32: attnPrefillF32Kernel
+    if (kvFp8) return false;  // fp8: no prefill kernel, prompt rows take attnDecodeFp8Kernel
     return (hs == 64 || hs == 128) && kvMul >= 1 && kvMul <= 16 && (kvMul & (kvMul - 1)) == 0;
 }
 
@@ -426,6 +427,7 @@ int attnPrefillChunkKeys(const AttnArgs &a, int gridX) {  // as attnPrefillF32Ke
 }
 
 const char *attnPrefillRefusal(const AttnArgs &a) {
+    if (a.kvFp8) return "launchAttentionPrefill: no prefill kernel for fp8 KV caches (prompt rows take launchAttentionFp8)";
     if (attnPrefillDmaSupported(a)) return attnPrefillDmaRefusal(a);
     if (!attnPrefillSupported(a.hs, a.kvMul, a.kvBf16 != 0) || a.nHeads0 % a.kvMul)
         return "launchAttentionPrefill: head size 64 / 128 and a power-of-two GQA group <= 16";
@@ -437,6 +439,7 @@ const char *attnPrefillRefusal(const AttnArgs &a) {
 }
 
 void launchAttentionPrefill(const AttnArgs &a, int nRows, hipStream_t s) {
+    if (a.kvFp8) throw Error(attnPrefillRefusal(a));
     if (attnPrefillDmaSupported(a)) {  // LDS-DMA staged kernel (attn_mfma.hip)
         launchAttentionPrefillDma(a, nRows, s);
         return;

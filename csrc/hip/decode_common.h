@@ -244,6 +244,11 @@ __device__ __forceinline__ void st32(void *p, uint32_t v) {
     else *reinterpret_cast<uint32_t *>(p) = v;
 }
 template <bool WT>
+__device__ __forceinline__ void st16(void *p, uint16_t v) {
+    if constexpr (WT) __hip_atomic_store(reinterpret_cast<uint16_t *>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else *reinterpret_cast<uint16_t *>(p) = v;
+}
+template <bool WT>
 __device__ __forceinline__ void st64(void *p, uint64_t v) {
     if constexpr (WT) __hip_atomic_store(reinterpret_cast<uint64_t *>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else *reinterpret_cast<uint64_t *>(p) = v;
@@ -299,6 +304,15 @@ __device__ __forceinline__ bool splitArrive(int *counter, int S, int *flag) {
     return last;
 }
 
+// fp8 KV caches (kvFp8): a pair of values as two OCP e4m3fn bytes, e4m3fn(clamp(x, -448, 448)), round to
+// nearest even, subnormals kept (v_cvt_pk_fp8_f32). The clamp comes first, so overflow saturates and
+// never becomes NaN; zero is byte 0x00, so a zero-filled cache holds zeros.
+__device__ __forceinline__ uint16_t f32x2ToFp8(float x0, float x1) {
+    x0 = fminf(fmaxf(x0, -448.f), 448.f);
+    x1 = fminf(fmaxf(x1, -448.f), 448.f);
+    return (uint16_t)__builtin_amdgcn_cvt_pk_fp8_f32(x0, x1, 0, false);
+}
+
 // Rows [0, q0) are Q, [q0, q0+kv0) K, then V. Q and K pairs are rotated (RoPE at this row's
 // position); K and V are appended to the KV cache at [slot][pos]. WT: write-through (the fused
 // attention block's attention workgroups read them in the same launch).
@@ -315,7 +329,9 @@ __device__ __forceinline__ void qkvPairStore(const GemvArgs &a, int r0, float v0
             const int x = r0 - a.q0;  // K row: head x / hs, dim x % hs (a row pair stays in one head)
             const int lg = __builtin_ctz(a.hs);  // hs is a power of two (64 / 128)
             const size_t off = kvOff(a.kvMap, a.seqLen, a.kv0 >> lg, a.hs, sl, p, x >> lg) + (x & (a.hs - 1));
-            if (a.kvBf16) {
+            if (a.kvFp8) {
+                st16<WT>(reinterpret_cast<uint8_t *>(a.kcache) + off, f32x2ToFp8(o0, o1));
+            } else if (a.kvBf16) {
                 const uint32_t pk = (uint32_t)f32ToBf16(o0) | ((uint32_t)f32ToBf16(o1) << 16);
                 st32<WT>(reinterpret_cast<uint16_t *>(a.kcache) + off, pk);
             } else {
@@ -325,7 +341,9 @@ __device__ __forceinline__ void qkvPairStore(const GemvArgs &a, int r0, float v0
     } else {
         const int x = r0 - a.q0 - a.kv0, lg = __builtin_ctz(a.hs);
         const size_t off = kvOff(a.kvMap, a.seqLen, a.kv0 >> lg, a.hs, sl, p, x >> lg) + (x & (a.hs - 1));
-        if (a.kvBf16) {
+        if (a.kvFp8) {
+            st16<WT>(reinterpret_cast<uint8_t *>(a.vcache) + off, f32x2ToFp8(v0, v1));
+        } else if (a.kvBf16) {
             const uint32_t pk = (uint32_t)f32ToBf16(v0) | ((uint32_t)f32ToBf16(v1) << 16);
             st32<WT>(reinterpret_cast<uint16_t *>(a.vcache) + off, pk);
         } else {

@@ -47,7 +47,21 @@ HipEngineImpl::HipEngineImpl(const EngineConfig &cfg, DeviceComm *comm) : cfg_(c
     DL_CHECK(h_.headSize() == 64 || h_.headSize() == 128, "GPU kernels support head size 64 or 128");
     DL_CHECK(cfg.maxBatch >= 1 && cfg.nSlots >= 1, "maxBatch/nSlots");
     DL_CHECK(cfg.maxBatch <= kKeyMaxRows, "maxBatch: more rows than a graph key holds");
-    kvBf16_ = cfg.kvBf16;
+    kv_ = cfg.kvType();
+    if (kvFp8()) {  // refused here, with the reason, not at the first forward
+        if (cfg.batchInvariant)
+            throw Error("--kv-dtype fp8 cannot be combined with --batch-invariant: the batch-invariant decode path is "
+                        "the VALU attention kernel, which has no fp8 instance (use f32 or bf16)");
+        hipk::AttnArgs a;
+        a.kvFp8 = 1;
+        a.hs = (int)plan_.headSize;
+        a.kvMul = (int)plan_.kvMul;
+        a.nHeads0 = (int)plan_.nHeads0;
+        if (!hipk::attnFp8Supported(a))
+            throw Error("--kv-dtype fp8: the fp8 attention kernel covers head size 64 / 128 and 1, 2, 4 or 8 query heads "
+                        "per KV head; this model has head size " + std::to_string(plan_.headSize) + " and " +
+                        std::to_string(plan_.kvMul) + " (use f32 or bf16)");
+    }
     syncQ80_ = cfg.syncType == FloatType::Q80;
     decodeRows_ = (int)(cfg.maxDecode ? std::min(cfg.maxDecode, cfg.maxBatch) : cfg.maxBatch);
     if (comm_ && plan_.nRanks > 1) {

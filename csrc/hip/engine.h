@@ -24,6 +24,7 @@ class HipEngine : public Backend {
                                      int *outTokens) = 0;
     virtual void synchronize() = 0;
     virtual size_t deviceBytes() const = 0;
+    virtual size_t kvBytes() const = 0;  // the KV caches: layers x (K + V) x pool rows x kv0 x element bytes
     // Run one forward eagerly with a per-kernel-class timing breakdown (ms) printed to stdout.
     virtual void profileForward(int n, const int *tokens, const int *positions, const int *slots) = 0;
     // The same eager forward, returned as device ms per kernel class. specs null: host logits; else
@@ -84,7 +85,8 @@ double benchGemmQ40(int rows, int n, int M, int epi, int copies, int iters,
 // cycled through a graph of `iters` launches, every row at position `pos`. Returns microseconds per
 // launch.
 double benchAttention(int nHeads0, int kvMul, int hs, int seqLen, int pos, int B, int copies, int iters,
-                      std::vector<unsigned long long> *trace = nullptr, bool kvBf16 = true);
+                      std::vector<unsigned long long> *trace = nullptr, bool kvBf16 = true,
+                      bool kvFp8 = false);
 // Microseconds per device-to-device hipMemcpyAsync of `bytes` (the prefix copy's yardstick).
 double benchMemcpyD2D(size_t bytes, int iters);
 // Check a transport on the engine's separate-collective schedule (per layer Q80-rounded

@@ -241,17 +241,23 @@ double benchGemmQ80w(int rows, int n, int M, bool f32, int fetch, int copies, in
 }
 
 double benchAttention(int nHeads0, int kvMul, int hs, int seqLen, int pos, int B, int copies, int iters,
-                      std::vector<unsigned long long> *trace, bool kvBf16) {
+                      std::vector<unsigned long long> *trace, bool kvBf16, bool kvFp8) {
     DL_CHECK(kvMul >= 1 && nHeads0 % kvMul == 0 && pos >= 0 && pos < seqLen && B >= 1, "bad attention bench shape");
     Scratch sc;
     hipStream_t s = sc.s;
     const int kv0 = nHeads0 / kvMul * hs, q0 = nHeads0 * hs;
     const size_t kvElems = (size_t)B * seqLen * kv0;  // one slot per row
     std::vector<float *> kc(copies), vc(copies);
-    const size_t kvWords = kvBf16 ? kvElems / 2 : kvElems;  // bf16 pairs of small values, or f32
+    // bf16 pairs of small values, f32, or four e4m3 bytes per word
+    const size_t kvWords = kvElems * hipk::kvElemBytes(kvBf16, kvFp8) / 4;
     for (int c = 0; c < copies; c++) {
         kc[c] = sc.alloc<float>(kvWords);
         vc[c] = sc.alloc<float>(kvWords);
+        if (kvFp8) {  // one finite e4m3 value everywhere (random bytes would include NaN codes)
+            DL_HIP(hipMemset(kc[c], 0x30 + c % 8, kvWords * 4));
+            DL_HIP(hipMemset(vc[c], 0x38 + c % 8, kvWords * 4));
+            continue;
+        }
         hipk::launchFillF32Uniform(kc[c], kvWords, 1.f, 5 + c, s);
         hipk::launchFillF32Uniform(vc[c], kvWords, 1.f, 9 + c, s);
     }
@@ -278,6 +284,7 @@ double benchAttention(int nHeads0, int kvMul, int hs, int seqLen, int pos, int B
     a.outS = sc.alloc<float2>((size_t)B * q0 / 32);
     a.ldOut = q0;
     a.kvBf16 = kvBf16 ? 1 : 0;
+    a.kvFp8 = kvFp8 ? 1 : 0;
     a.counters = sc.alloc<int>((size_t)B * nHeads0);
     DL_HIP(hipStreamSynchronize(s));
     auto launch = [&](int c) {

@@ -68,13 +68,13 @@ void HipEngineImpl::setInputs(int n, const int *tokens, const int *positions, co
     std::memcpy(hIn_ + 2 * MB, slots, n * sizeof(int));
     size_t words = 2 * (size_t)MB + n;
     // prefill attention on MFMA: every block of rows it assigns to one workgroup is one slot
-    prefillOk_ = !invariant_ && hipk::attnPrefillSupported(plan_.headSize, plan_.kvMul, kvBf16_);
+    prefillOk_ = !invariant_ && hipk::attnPrefillSupported(plan_.headSize, plan_.kvMul, kvBf16(), kvFp8());
     const int rpb = prefillOk_ ? hipk::attnPrefillRowsPerBlock(plan_.kvMul) : 1;
     for (int b = 0; prefillOk_ && b < n; b++) prefillOk_ = slots[b] == slots[b - b % rpb];
     // f32 caches: the f32 MFMA prefill kernel from 128 keys on; below, the per-row decode attention
     // is faster (a 32-row chunk at positions 0-63: eval 0.0957 vs 0.0993 ms/token; crossover ~135
     // keys from the 4k-prompt slopes, profiles/r6_decode.md). DL_PREFILL_F32_MIN overrides.
-    if (prefillOk_ && !kvBf16_) {
+    if (prefillOk_ && kv_ == KvDtype::F32) {
         static const int f32Min = [] {
             const char *e = std::getenv("DL_PREFILL_F32_MIN");
             return e ? std::atoi(e) : 128;
@@ -136,7 +136,8 @@ void HipEngineImpl::fillLayerKv(hipk::GemvArgs &a, const DevLayer &L, int c0) co
     a.kcache = L.k;
     a.kvMap = kvMap();
     a.vcache = L.v;
-    a.kvBf16 = kvBf16_ ? 1 : 0;
+    a.kvBf16 = kvBf16() ? 1 : 0;
+    a.kvFp8 = kvFp8() ? 1 : 0;
 }
 
 // Arguments of one GEMV launch over rows [c0, c0 + bc) of the batch (see gemv()).
@@ -236,7 +237,8 @@ hipk::AttnArgs HipEngineImpl::attnArgs(const DevLayer &L, bool bat) const {
     a.outS = blocks() && !bat ? dAttS_ : nullptr;
     a.outH = bat ? dAttH_ : nullptr;
     a.ldOut = p.q0;
-    a.kvBf16 = kvBf16_ ? 1 : 0;
+    a.kvBf16 = kvBf16() ? 1 : 0;
+    a.kvFp8 = kvFp8() ? 1 : 0;
     a.mfma = attnLong_ ? 1 : 0;
     // batch-invariant engines: one query head per workgroup whatever the rows of the launch (the
     // launch would group 2+ heads from 33 rows x 8 heads on, which reorders a row's sums: a prompt
@@ -255,8 +257,10 @@ std::string HipEngineImpl::decodeAttnKernel(int rows, int maxPos) const {
     a.kvMul = plan_.kvMul;
     a.hs = plan_.headSize;
     a.seqLen = h_.seqLen;
-    a.kvBf16 = kvBf16_ ? 1 : 0;
+    a.kvBf16 = kvBf16() ? 1 : 0;
+    a.kvFp8 = kvFp8() ? 1 : 0;
     a.mfma = attnLongFor(rows, maxPos) ? 1 : 0;
+    if (kvFp8()) return hipk::attnFp8KernelName(a);  // every context length
     return hipk::attnUsesMfma(a) ? hipk::attnMfmaKernelName(a) : "attnKernel";
 }
 
@@ -287,7 +291,8 @@ hipk::AttnBlockArgs HipEngineImpl::attnBlockArgs(const DevLayer &L, u32 l, int c
 // DL_ATTN_BLOCK=0 keeps the three separate launches.
 void HipEngineImpl::setupAttnBlock() {
     const char *e = std::getenv("DL_ATTN_BLOCK");
-    if ((e && *e == '0') || !q40() || plan_.nKvHeads0 > kMaxKvGroups) return;
+    // fp8 caches: the block's attention role has no fp8 instance, decode rows take attnDecodeFp8Kernel
+    if ((e && *e == '0') || !q40() || plan_.nKvHeads0 > kMaxKvGroups || kvFp8()) return;
     // one KV group per rank (8 KV heads at TP8): the attention role is a handful of workgroups
     // the whole wo role waits on - measured 2x the three launches (8B TP8 rank: 38 vs ~18 us per
     // layer, profiles/r5_tp_rank.md); DL_ATTN_BLOCK=1 forces it

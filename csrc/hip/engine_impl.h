@@ -100,6 +100,7 @@ class HipEngineImpl : public HipEngine {
                              int *outTokens) override;
     void synchronize() override { DL_HIP(hipStreamSynchronize(stream_)); }
     size_t deviceBytes() const override { return deviceBytes_; }
+    size_t kvBytes() const override { return (size_t)h_.nLayers * 2 * kvPoolRows() * plan_.kv0 * kvEb(); }
     void profileForward(int n, const int *tokens, const int *positions, const int *slots) override;
     std::map<std::string, double> profileClasses(int n, const int *tokens, const int *positions, const int *slots,
                                                  const SampleSpec *specs, const PoolSpec *pool) override;
@@ -351,8 +352,8 @@ class HipEngineImpl : public HipEngine {
     static constexpr int kAttnF32MfmaMinRows = 1 << 30;
     // the decode attention of a forward of n rows, the longest at maxPos, runs the MFMA kernel
     bool attnLongFor(int n, int maxPos) const {
-        const int minPos = kvBf16_ ? kAttnMfmaMinPos : kAttnF32MfmaMinPos;
-        const int minRows = kvBf16_ ? kAttnMfmaMinRows : kAttnF32MfmaMinRows;
+        const int minPos = kvBf16() ? kAttnMfmaMinPos : kAttnF32MfmaMinPos;
+        const int minRows = kvBf16() ? kAttnMfmaMinRows : kAttnF32MfmaMinRows;
         return !invariant_ && (maxPos >= minPos || n >= minRows);
     }
 
@@ -368,7 +369,11 @@ class HipEngineImpl : public HipEngine {
     bool q80w() const { return wkind_ == WeightKind::Q80; }
     // block-quantized weights: tiled planes, Q80 activations, two rows per GEMV lane group
     bool blocks() const { return wkind_ != WeightKind::F32; }
-    bool kvBf16_ = true, syncQ80_ = false, tpFused_ = false;
+    KvDtype kv_ = KvDtype::Bf16;  // EngineConfig::kvType()
+    bool kvBf16() const { return kv_ == KvDtype::Bf16; }
+    bool kvFp8() const { return kv_ == KvDtype::Fp8; }
+    size_t kvEb() const { return (size_t)hipk::kvElemBytes(kvBf16(), kvFp8()); }  // bytes per cache element
+    bool syncQ80_ = false, tpFused_ = false;
     bool tpTested_ = false;  // tpFusedSelfTest ran (first forward)
     int fusedGridMax_ = 0;  // largest grid of a fused-exchange GEMV launch (checked co-resident)
     hipk::TpXchg tpVec_, tpArg_;

@@ -139,7 +139,7 @@ void HipEngineImpl::copyPrefix(int src, int dst, int n) {
     a.nKv = (int)(plan_.kv0 / plan_.headSize);
     a.hs = (int)plan_.headSize;
     a.seqLen = (int)h_.seqLen;
-    a.elemBytes = kvBf16_ ? 2 : 4;
+    a.elemBytes = (int)kvEb();
     a.srcSlot = src;
     a.dstSlot = dst;
     a.n = n;
@@ -191,7 +191,7 @@ void HipEngineImpl::forkPrefix(int src, const int *dsts, int m, int n) {
     a.nKv = (int)(plan_.kv0 / plan_.headSize);
     a.hs = (int)plan_.headSize;
     a.seqLen = (int)h_.seqLen;
-    a.elemBytes = kvBf16_ ? 2 : 4;
+    a.elemBytes = (int)kvEb();
     a.srcSlot = src;
     a.n = n;
     a.chunkPos = hipk::kvCopyChunkPos(a.hs, a.elemBytes, paged() ? pageShift_ : 0);

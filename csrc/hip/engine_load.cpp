@@ -18,14 +18,14 @@ void HipEngineImpl::checkFits() {
     DL_HIP(hipMemGetInfo(&freeB, &totalB));
     const ShardPlan &p = plan_;
     const double GB = 1e9;
-    const size_t kv = (size_t)h_.nLayers * 2 * kvPoolRows() * p.kv0 * (kvBf16_ ? 2 : 4);
+    const size_t kv = kvBytes();
     size_t w = (size_t)h_.nLayers * (matStageBytes(p.q0 + 2 * p.kv0, h_.dim) + matStageBytes(h_.dim, p.q0) +
                                      matStageBytes(2 * p.hidden0, h_.dim) + matStageBytes(h_.dim, p.hidden0));
     w += matStageBytes(p.vocab0, h_.dim) + (size_t)h_.vocabSize * h_.dim * 4;
     const size_t act = (size_t)cfg_.maxBatch * h_.vocabSize * 4 * 3 + ((size_t)256 << 20) + procBytes() + poolBytes();
     if (kv + w + act > freeB) {
         // the page pool that would fit (positions shared by all slots), as a hint
-        const size_t perPos = (size_t)h_.nLayers * 2 * p.kv0 * (kvBf16_ ? 2 : 4);
+        const size_t perPos = (size_t)h_.nLayers * 2 * p.kv0 * kvEb();
         const long long spare = (long long)freeB - (long long)(w + act);
         const long long pages = spare > 0 ? spare / (long long)(perPos * cfg_.kvPageSize) : 0;
         char msg[768];
@@ -37,7 +37,7 @@ void HipEngineImpl::checkFits() {
                               paged() ? (std::to_string(cfg_.kvPages) + " pages").c_str()
                                       : (std::to_string(cfg_.nSlots) + " slots x " + std::to_string(h_.seqLen) +
                                          " positions").c_str(),
-                              h_.nLayers, kvBf16_ ? "bf16" : "f32", act / GB, freeB / GB, totalB / GB, pages,
+                              h_.nLayers, kvDtypeName(kv_), act / GB, freeB / GB, totalB / GB, pages,
                               pages * (long long)cfg_.kvPageSize);
         throw Error(msg);
     }
@@ -272,15 +272,18 @@ void HipEngineImpl::allocBuffers() {
     const size_t kvElems = kvPoolRows() * p.kv0;
     setupPages();
     for (auto &L : layers_) {
-        if (kvBf16_) {
+        if (kvFp8()) {
+            L.k = dalloc<uint8_t>(kvElems);
+            L.v = dalloc<uint8_t>(kvElems);
+        } else if (kvBf16()) {
             L.k = dalloc<uint16_t>(kvElems);
             L.v = dalloc<uint16_t>(kvElems);
         } else {
             L.k = dalloc<float>(kvElems);
             L.v = dalloc<float>(kvElems);
         }
-        DL_HIP(hipMemsetAsync(L.k, 0, kvElems * (kvBf16_ ? 2 : 4), stream_));
-        DL_HIP(hipMemsetAsync(L.v, 0, kvElems * (kvBf16_ ? 2 : 4), stream_));
+        DL_HIP(hipMemsetAsync(L.k, 0, kvElems * kvEb(), stream_));
+        DL_HIP(hipMemsetAsync(L.v, 0, kvElems * kvEb(), stream_));
     }
     setupKvCopy();
 }

@@ -131,10 +131,13 @@ __host__ __device__ inline size_t kvOff(const KvMap &m, int seqLen, int nKv, int
     return kvOffAt(m, seqLen, nKv, hs, m.table ? kvPageOf(m, slot, pos) : (size_t)slot, pos, kvh);
 }
 
+// Bytes of one KV cache element: 1 (fp8 e4m3), 2 (bf16) or 4 (f32); kvFp8 overrides kvBf16.
+__host__ __device__ constexpr int kvElemBytes(bool kvBf16, bool kvFp8) { return kvFp8 ? 1 : kvBf16 ? 2 : 4; }
+
 // Prefix copy between KV slots (kv_copy.hip): positions [0, n) of srcSlot to dstSlot, K and V of
 // every layer and every local KV head, in one launch. Source and destination both go through
 // kvOff (contiguous cache or page pool; the destination's pages must be mapped). A plain byte
-// copy: elemBytes 2 (bf16) or 4 (f32).
+// copy: elemBytes 1 (fp8), 2 (bf16) or 4 (f32).
 struct KvCopyArgs {
     void *const *bases = nullptr;  // device array [nLayers * 2]: layer l's K base at 2l, V base at 2l + 1
     KvMap kvMap;
@@ -179,6 +182,7 @@ struct AttnArgs {
     float2 *outS = nullptr;
     int ldOut = 0;
     int kvBf16 = 1;
+    int kvFp8 = 0;              // e4m3 cache (1 byte per element; overrides kvBf16): launchAttentionFp8
     int mfma = -1;              // decode kernel: 1 MFMA, 0 VALU, -1 by cache length (attnUsesMfma)
     int headGroup = 0;          // VALU kernel: query heads per workgroup; 0 = chosen from the launch's rows
                                 // (the grouping changes a row's summation order: batch-invariant engines pin it)
@@ -268,6 +272,7 @@ struct GemvArgs {
     void *vcache = nullptr;
     KvMap kvMap;
     int kvBf16 = 1;
+    int kvFp8 = 0;                // e4m3 cache (1 byte per element; overrides kvBf16): qkvPairStore
     // EPI_STORE_TP (Q40 GEMV): the partial rows are all-reduced over the tensor-parallel ranks in
     // the kernel tail before `out` is written (exchange element = b * ldOut + row)
     TpXchg tp;
@@ -427,6 +432,14 @@ std::string attnMfmaKernelName(const AttnArgs &a);
 bool attnF32MfmaSupported(const AttnArgs &a);
 const char *attnF32MfmaRefusal(const AttnArgs &a);
 void launchAttentionF32Mfma(const AttnArgs &a, int B, hipStream_t s);
+// Decode attention over fp8 (e4m3) caches (attn_fp8.hip): head size 128 / 64, kvMul 1/2/4/8, every
+// context length. launchAttention routes kvFp8 launches here; there is no VALU kernel, no fused
+// attention block and no prefill kernel for fp8 caches (attnPrefillSupported is false: prompt rows take
+// this kernel row by row).
+bool attnFp8Supported(const AttnArgs &a);
+const char *attnFp8Refusal(const AttnArgs &a);
+std::string attnFp8KernelName(const AttnArgs &a);  // "attnDecodeFp8Kernel<KM,HS>"
+void launchAttentionFp8(const AttnArgs &a, int B, hipStream_t s);
 const char *attnPrefillRefusal(const AttnArgs &a);     // launchAttentionPrefill, either kernel family
 // Prefill rows with LDS-DMA staged K / V (attn_mfma.hip; other shapes take the register-staged
 // kernels.hip kernel): bf16 cache, head size 128, kvMul 1..16.
@@ -479,7 +492,7 @@ void launchTpSelfTest(const TpXchg &x, float *out, int n, float val, hipStream_t
 // must share one slot (positions arbitrary, causal per row); counters >= blocks x KV heads.
 void launchAttentionPrefill(const AttnArgs &a, int nRows, hipStream_t s);
 int attnPrefillRowsPerBlock(int kvMul);
-bool attnPrefillSupported(int hs, int kvMul, bool kvBf16);
+bool attnPrefillSupported(int hs, int kvMul, bool kvBf16, bool kvFp8 = false);
 int attnSplitGrid(int seqLen, bool shortChunks = false);
 // single decode rows of at most kAttnShortLen keys split into chunks of kAttnShortChunk (attnSplit)
 constexpr int kAttnShortLen = 512, kAttnShortChunk = 128;

@@ -203,7 +203,9 @@ static void attnDispatchHG(const AttnArgs &a, int B, int HG, hipStream_t s) {
 }
 
 void launchAttention(const AttnArgs &a, int B, hipStream_t s) {
-    if (attnUsesMfma(a))  // long contexts, many rows: the MFMA kernels (attn_mfma.hip, attn_mfma_f32.hip)
+    if (a.kvFp8)  // fp8 caches: one kernel for every context length (attn_fp8.hip)
+        launchAttentionFp8(a, B, s);
+    else if (attnUsesMfma(a))  // long contexts, many rows: the MFMA kernels (attn_mfma.hip, attn_mfma_f32.hip)
         launchAttentionMfma(a, B, s);
     else
         launchAttentionValu(a, B, s);
@@ -227,6 +229,7 @@ int attnValuHeadGroup(const AttnArgs &a, int B) {
 }
 
 void launchAttentionValu(const AttnArgs &a, int B, hipStream_t s) {
+    if (a.kvFp8) throw Error("launchAttentionValu: no VALU kernel for fp8 KV caches (launchAttentionFp8)");
     const int HG = attnValuHeadGroup(a, B);
     if (a.hs == 128) {
         if (a.kvBf16) attnDispatchHG<128, true>(a, B, HG, s);
@@ -430,6 +433,7 @@ const void *gemmWideModuleKernel();
 const void *gemmQ80wWideModuleKernel();
 const void *attnMfmaModuleKernel();
 const void *attnF32MfmaModuleKernel();
+const void *attnFp8ModuleKernel();
 const void *xgmiModuleKernel();
 const void *sampleModuleKernel();
 const void *logitProcModuleKernel();
@@ -455,7 +459,7 @@ void preloadModules() {
     const BlockFn blocks[] = {attnBlockFn_16_16_128, attnBlockFn_16_32_128, attnBlockFn_32_32_128, attnBlockFn_64_32_128, attnBlockFn_64_16_128,
                               attnBlockFn_64_64_128, attnBlockFn_32_64_128, attnBlockFn_64_64_64};
     std::vector<const void *> fns = {sampleModuleKernel(), logitProcModuleKernel(), logitFilterModuleKernel(), jsonMaskModuleKernel(), grammarMaskModuleKernel(), attnPrefillModuleKernel(), tpCheckModuleKernel(),
-                                     gemmModuleKernel(),   gemmWideModuleKernel(),    gemmQ80wWideModuleKernel(), attnMfmaModuleKernel(), attnF32MfmaModuleKernel(),
+                                     gemmModuleKernel(),   gemmWideModuleKernel(),    gemmQ80wWideModuleKernel(), attnMfmaModuleKernel(), attnF32MfmaModuleKernel(), attnFp8ModuleKernel(),
                                      xgmiModuleKernel(),   gemvFnL16(true, 1, 0, 0),
                                      gemvFnL32(true, 1, 0, 0), gemvFnL64(true, 1, 0, 0)};
     for (BlockFn b : blocks) {  // any instance of the unit will do

@@ -81,6 +81,9 @@ void launchKvForkPrefix(const KvForkArgs &a, hipStream_t s) {
     const dim3 grid((a.n + a.chunkPos - 1) / a.chunkPos, a.nLayers * 2 * a.nKv);
     DL_CHECK(grid.y <= 65535, "kvForkPrefix: too many (layer, head) runs for one launch");
     const int rowBytes = a.hs * a.elemBytes;
+    // 1-byte (fp8) elements: a head row of 64 / 128 bytes is whole 16-byte pieces; there is no narrower access
+    DL_CHECK(a.elemBytes == 2 || a.elemBytes == 4 || (a.elemBytes == 1 && rowBytes % 16 == 0),
+             "kvForkPrefix: element size 1 (whole 16-byte head rows), 2 or 4");
     if (rowBytes % 16 == 0)
         hipLaunchKernelGGL(kvForkPrefixKernel<Vec16>, grid, dim3(kCopyThreads), 0, s, a);
     else if (a.elemBytes == 4)

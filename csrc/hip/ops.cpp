@@ -74,12 +74,39 @@ DevQ40 uploadQ40(Scratch &sc, const std::vector<uint8_t> &blocks, int rows, int 
     return m;
 }
 
+// Host side of the fp8 cache rule (qkvPairStore): e4m3fn(clamp(x, -448, 448)), round to nearest
+// even, subnormals kept, and its exact inverse.
+uint8_t f32ToE4m3(float x) {
+    if (x != x) return 0x7F;
+    const uint8_t sign = std::signbit(x) ? 0x80 : 0;
+    const float a = std::fmin(std::fabs(x), 448.f);
+    if (a < 0.015625f) return sign | (uint8_t)std::nearbyint(a * 512.f);  // steps of 2^-9; 8 = the smallest normal
+    int e;
+    (void)std::frexp(a, &e);
+    int E = e - 1, mant = (int)std::nearbyint((std::ldexp(a, -E) - 1.f) * 8.f);
+    if (mant == 8) {
+        mant = 0;
+        E++;
+    }
+    return sign | (uint8_t)(((E + 7) << 3) | mant);
+}
+float e4m3ToF32(uint8_t c) {
+    const int e = (c >> 3) & 15, m = c & 7;
+    const float a = e == 0 ? std::ldexp((float)m, -9) : (e == 15 && m == 7) ? NAN : std::ldexp(1.f + m / 8.f, e - 7);
+    return c & 0x80 ? -a : a;
+}
+std::vector<uint8_t> toE4m3(const std::vector<float> &x) {
+    std::vector<uint8_t> h(x.size());
+    for (size_t i = 0; i < x.size(); i++) h[i] = f32ToE4m3(x[i]);
+    return h;
+}
+
 // The [kv0] cache row of (slot[b], pos[b]) for every b from a head-major cache preset to the guard
-// pattern as a whole (f32 view of the bf16 or f32 elements); throws when any other element changed.
+// pattern as a whole (f32 view of the fp8, bf16 or f32 elements); throws when any other element changed.
 void appendedRows(Scratch &sc, const uint8_t *cache, size_t cacheElems, int seqLen, int kv0, int hs,
                   const std::vector<int> &pos, const std::vector<int> &slot, bool kvBf16, const char *what,
-                  std::vector<float> *out) {
-    const size_t eb = kvBf16 ? 2 : 4;
+                  std::vector<float> *out, bool kvFp8 = false) {
+    const size_t eb = (size_t)hipk::kvElemBytes(kvBf16, kvFp8);
     const int B = (int)pos.size();
     std::vector<uint8_t> all = sc.download(cache, cacheElems * eb);
     out->assign((size_t)B * kv0, 0.f);
@@ -88,7 +115,10 @@ void appendedRows(Scratch &sc, const uint8_t *cache, size_t cacheElems, int seqL
             const size_t off = hipk::kvOff(hipk::KvMap{}, seqLen, kv0 / hs, hs, slot[b], pos[b], kh);
             for (int i = 0; i < hs; i++) {
                 uint32_t u = 0;
-                if (kvBf16) {
+                if (kvFp8) {
+                    const float f = e4m3ToF32(all[off + i]);
+                    std::memcpy(&u, &f, 4);
+                } else if (kvBf16) {
                     uint16_t h;
                     std::memcpy(&h, &all[(off + i) * 2], 2);
                     u = (uint32_t)h << 16;
@@ -391,7 +421,7 @@ GemvQ80wResult gemvQ80w(const GemvQ80wArgs &p) {
             for (int q : p.pos) DL_CHECK(q >= 0 && q < p.seqLen, "qkv position out of range");
             outRows = p.q0;
             for (int b = 0; b < B; b++) slots[b] = b;
-            const size_t eb = p.kvBf16 ? 2 : 4, cacheGuard = (size_t)g.wgRows * p.seqLen;
+            const size_t eb = (size_t)hipk::kvElemBytes(p.kvBf16, false), cacheGuard = (size_t)g.wgRows * p.seqLen;
             kc = sc.allocGuarded<uint8_t>(1, cacheElems * eb, (cacheElems + cacheGuard) * eb, "the K cache");
             vc = sc.allocGuarded<uint8_t>(1, cacheElems * eb, (cacheElems + cacheGuard) * eb, "the V cache");
             a.q0 = p.q0;
@@ -769,7 +799,7 @@ GemmBatchedResult gemmBatched(const GemmBatchedArgs &a) {
         // the caches are preset to the guard pattern as a whole (plus a guard after the last slot):
         // only the appended rows may change
         cacheElems = (size_t)a.nSlots * a.seqLen * a.kv0;
-        const size_t eb = a.kvBf16 ? 2 : 4, cacheGuard = (size_t)128 * a.seqLen;
+        const size_t eb = (size_t)hipk::kvElemBytes(a.kvBf16, a.kvFp8), cacheGuard = (size_t)128 * a.seqLen;
         kc = sc.allocGuarded<uint8_t>(1, cacheElems * eb, (cacheElems + cacheGuard) * eb, "the K cache");
         vc = sc.allocGuarded<uint8_t>(1, cacheElems * eb, (cacheElems + cacheGuard) * eb, "the V cache");
         rope = reinterpret_cast<const float2 *>(sc.upload(a.rope));
@@ -828,6 +858,7 @@ GemmBatchedResult gemmBatched(const GemmBatchedArgs &a) {
             e.kcache = kc;
             e.vcache = vc;
             e.kvBf16 = a.kvBf16 ? 1 : 0;
+            e.kvFp8 = a.kvFp8 ? 1 : 0;
         }
         if (epi == hipk::EPI_RES) {
             g.resIn = resIn + (size_t)c0 * ldOut;
@@ -866,8 +897,8 @@ GemmBatchedResult gemmBatched(const GemmBatchedArgs &a) {
         r.ssOut = sc.download(ssOut, (size_t)ssRows * a.ldSS);
     }
     if (epi == hipk::EPI_QKV) {
-        appendedRows(sc, kc, cacheElems, a.seqLen, a.kv0, a.hs, a.pos, a.slot, a.kvBf16, "the K cache", &r.k);
-        appendedRows(sc, vc, cacheElems, a.seqLen, a.kv0, a.hs, a.pos, a.slot, a.kvBf16, "the V cache", &r.v);
+        appendedRows(sc, kc, cacheElems, a.seqLen, a.kv0, a.hs, a.pos, a.slot, a.kvBf16, "the K cache", &r.k, a.kvFp8);
+        appendedRows(sc, vc, cacheElems, a.seqLen, a.kv0, a.hs, a.pos, a.slot, a.kvBf16, "the V cache", &r.v, a.kvFp8);
     }
     return r;
 }
@@ -875,7 +906,7 @@ GemmBatchedResult gemmBatched(const GemmBatchedArgs &a) {
 std::vector<float> qkvRope(const std::vector<uint8_t> &blocks, int q0, int kv0, int hs, int n,
                            const std::vector<float> &in, const std::vector<float> &normW, float eps,
                            const std::vector<float> &rope, int seqLen, const std::vector<int> &pos, bool kvBf16,
-                           std::vector<float> *kOut, std::vector<float> *vOut, int lanes, int passes) {
+                           std::vector<float> *kOut, std::vector<float> *vOut, int lanes, int passes, bool kvFp8) {
     const int B = (int)pos.size(), rows = q0 + 2 * kv0;
     DL_CHECK(B == 1 || B == 2 || B == 4, "qkv batch must be 1, 2 or 4");
     DL_CHECK(hs % 2 == 0 && hs <= 128 && q0 % hs == 0 && kv0 % hs == 0, "qkv head layout");
@@ -890,7 +921,7 @@ std::vector<float> qkvRope(const std::vector<uint8_t> &blocks, int q0, int kv0, 
     // the caches are preset to the guard pattern as a whole (plus a guard after the last slot):
     // only the B appended rows may change
     const size_t cacheElems = (size_t)B * seqLen * kv0, cacheGuard = (size_t)g.wgRows * seqLen;
-    const size_t eb = kvBf16 ? 2 : 4;
+    const size_t eb = (size_t)hipk::kvElemBytes(kvBf16, kvFp8);
     uint8_t *kc = sc.allocGuarded<uint8_t>(1, cacheElems * eb, (cacheElems + cacheGuard) * eb, "the K cache");
     uint8_t *vc = sc.allocGuarded<uint8_t>(1, cacheElems * eb, (cacheElems + cacheGuard) * eb, "the V cache");
     hipk::GemvArgs a;
@@ -916,12 +947,13 @@ std::vector<float> qkvRope(const std::vector<uint8_t> &blocks, int q0, int kv0, 
     a.kcache = kc;
     a.vcache = vc;
     a.kvBf16 = kvBf16 ? 1 : 0;
+    a.kvFp8 = kvFp8 ? 1 : 0;
     hipk::launchGemv(a, B, hipk::PRO_RESNORM, hipk::EPI_QKV, true, sc.s);
     sc.sync();
     sc.checkGuards();
     std::vector<float> k, v;
-    appendedRows(sc, kc, cacheElems, seqLen, kv0, hs, pos, slots, kvBf16, "the K cache", &k);
-    appendedRows(sc, vc, cacheElems, seqLen, kv0, hs, pos, slots, kvBf16, "the V cache", &v);
+    appendedRows(sc, kc, cacheElems, seqLen, kv0, hs, pos, slots, kvBf16, "the K cache", &k, kvFp8);
+    appendedRows(sc, vc, cacheElems, seqLen, kv0, hs, pos, slots, kvBf16, "the V cache", &v, kvFp8);
     if (kOut) *kOut = k;
     if (vOut) *vOut = v;
     return sc.downloadRows(a.out, B, q0, a.ldOut);
@@ -929,9 +961,11 @@ std::vector<float> qkvRope(const std::vector<uint8_t> &blocks, int q0, int kv0, 
 
 std::vector<float> attention(const std::vector<float> &q, const std::vector<float> &k, const std::vector<float> &v,
                              int nSlots, int seqLen, int nHeads0, int kvMul, int hs, const std::vector<int> &pos,
-                             const std::vector<int> &slot, bool kvBf16, int impl) {
+                             const std::vector<int> &slot, bool kvBf16, int impl, bool kvFp8) {
     const int B = (int)pos.size();
     DL_CHECK(B >= 1 && slot.size() == pos.size(), "attention rows");
+    DL_CHECK(!kvFp8 || impl == 0 || impl == 4, "attention: fp8 caches take impl \"auto\" or \"fp8\" (one kernel)");
+    DL_CHECK(impl != 4 || kvFp8, "attention: impl \"fp8\" needs kv_dtype=\"fp8\"");
     if (impl == 1) {
         DL_CHECK(hipk::attnPrefillSupported(hs, kvMul, kvBf16), "prefill attention: head size 64 / 128, power-of-two GQA group");
         const int rpb = hipk::attnPrefillRowsPerBlock(kvMul);
@@ -953,6 +987,7 @@ std::vector<float> attention(const std::vector<float> &q, const std::vector<floa
                 for (int kh = 0; kh < nKv; kh++)
                     std::memcpy(&x[hipk::kvOff(hipk::KvMap{}, seqLen, nKv, hs, sl, p, kh)],
                                 &xs[((size_t)sl * seqLen + p) * kv0 + (size_t)kh * hs], hs * sizeof(float));
+        if (kvFp8) return sc.upload(toE4m3(x));
         if (!kvBf16) return sc.upload(x);
         std::vector<uint16_t> h(x.size());
         for (size_t i = 0; i < x.size(); i++) {  // round to nearest even, as the QKV epilogue stores
@@ -982,6 +1017,7 @@ std::vector<float> attention(const std::vector<float> &q, const std::vector<floa
     a.out = sc.alloc<float>((size_t)B * q0);
     a.ldOut = q0;
     a.kvBf16 = kvBf16 ? 1 : 0;
+    a.kvFp8 = kvFp8 ? 1 : 0;
     a.counters = sc.alloc<int>((size_t)B * nHeads0);
     DL_HIP(hipMemsetAsync(a.counters, 0, sizeof(int) * (size_t)B * nHeads0, sc.s));
     if (impl == 1)
@@ -991,7 +1027,7 @@ std::vector<float> attention(const std::vector<float> &q, const std::vector<floa
     else if (impl == 3) {
         DL_CHECK(hipk::attnMfmaSupported(a), "MFMA decode attention: head size 128 (f32 caches: 128 or 64), kvMul 1/2/4/8");
         hipk::launchAttentionMfma(a, B, sc.s);
-    } else
+    } else  // 0, 4: launchAttention routes fp8 caches to launchAttentionFp8
         hipk::launchAttention(a, B, sc.s);
     sc.sync();
     return sc.download(a.out, (size_t)B * q0);
@@ -1013,7 +1049,7 @@ AttnGeom attnGeom(const AttnLaunchArgs &l) {
     AttnGeom g;
     const int B = g.B = (int)l.pos.size();
     DL_CHECK(B >= 1 && l.slot.size() == l.pos.size(), "attention rows");
-    DL_CHECK(l.kvMul >= 1 && l.nHeads0 >= 1 && l.nHeads0 % l.kvMul == 0 && (l.hs == 64 || l.hs == 128), "attention head layout");
+    DL_CHECK(l.kvMul >= 1 && l.nHeads0 >= 1 && l.nHeads0 % l.kvMul == 0 && (l.hs == 64 || l.hs == 128 || l.kvFp8), "attention head layout");
     DL_CHECK(l.nSlots >= 1 && l.seqLen >= 1, "attention cache shape");
     g.q0 = l.nHeads0 * l.hs;
     g.nKv = l.nHeads0 / l.kvMul;
@@ -1026,7 +1062,9 @@ AttnGeom attnGeom(const AttnLaunchArgs &l) {
     DL_CHECK(l.q.size() == (size_t)B * g.ldq && l.k.size() == cacheElems && l.v.size() == cacheElems, "attention sizes");
     for (int b = 0; b < B; b++)
         DL_CHECK(l.pos[b] >= 0 && l.pos[b] < l.seqLen && l.slot[b] >= 0 && l.slot[b] < l.nSlots, "attention row out of range");
-    DL_CHECK(l.kernel >= ATTN_AUTO && l.kernel <= ATTN_PREFILL && (l.mode == ATTN_DECODE || l.mode == ATTN_PREFILL_ROWS),
+    DL_CHECK(l.kvFp8 ? (l.kernel == ATTN_AUTO || l.kernel == ATTN_FP8) : l.kernel != ATTN_FP8,
+             "attention: fp8 caches take kernel \"auto\" or \"fp8\", other caches any kernel but \"fp8\"");
+    DL_CHECK(l.kernel >= ATTN_AUTO && l.kernel <= ATTN_FP8 && (l.mode == ATTN_DECODE || l.mode == ATTN_PREFILL_ROWS),
              "attention kernel / mode");
     g.prefill = l.mode == ATTN_PREFILL_ROWS;
     DL_CHECK(g.prefill ? (l.kernel == ATTN_AUTO || l.kernel == ATTN_PREFILL) : l.kernel != ATTN_PREFILL,
@@ -1072,6 +1110,7 @@ AttnGeom attnGeom(const AttnLaunchArgs &l) {
     }
     a.ldOut = g.ldOut;
     a.kvBf16 = l.kvBf16 ? 1 : 0;
+    a.kvFp8 = l.kvFp8 ? 1 : 0;
     a.mfma = l.kernel == ATTN_MFMA ? 1 : l.kernel == ATTN_VALU ? 0 : -1;
     a.headGroup = l.headGroup;
     return g;
@@ -1107,14 +1146,18 @@ AttnLaunchPlan attentionPlan(const AttnLaunchArgs &l) {
         }
         return p;
     }
-    bool mfma;
+    bool mfma = false;
     if (l.kernel == ATTN_MFMA) {
         DL_CHECK(hipk::attnMfmaSupported(a), "MFMA decode attention: head size 128 (f32 caches: 128 or 64), kvMul 1/2/4/8");
         mfma = true;
-    } else {
+    } else if (!a.kvFp8) {
         mfma = l.kernel == ATTN_AUTO && hipk::attnUsesMfma(a);
     }
-    if (mfma) {
+    if (a.kvFp8) {  // one kernel, every context length (attn_fp8.hip)
+        if (const char *why = hipk::attnFp8Refusal(a)) throw Error(why);
+        p.kernel = hipk::attnFp8KernelName(a);
+        p.grid[0] = g.nKv;
+    } else if (mfma) {
         if (const char *why = hipk::attnMfmaRefusal(a)) throw Error(why);
         p.kernel = hipk::attnMfmaKernelName(a);
         p.grid[0] = g.nKv;
@@ -1172,6 +1215,7 @@ AttnLaunchResult attentionLaunch(const AttnLaunchArgs &l) {
                     std::memcpy(&x[hipk::kvOff(hostMap, seqLen, nKv, hs, sl, p, kh)],
                                 &xs[((size_t)sl * seqLen + p) * kv0 + (size_t)kh * hs], hs * sizeof(float));
             }
+        if (l.kvFp8) return sc.upload(toE4m3(x));
         if (!l.kvBf16) return sc.upload(x);
         std::vector<uint16_t> h(x.size());
         for (size_t i = 0; i < x.size(); i++) {  // round to nearest even, as the QKV epilogue stores

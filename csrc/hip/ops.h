@@ -169,6 +169,7 @@ struct GemmBatchedArgs {
     std::vector<float> rope;
     std::vector<int> pos, slot;
     bool kvBf16 = true;
+    bool kvFp8 = false;  // e4m3 caches (overrides kvBf16): k / v come back dequantised
     int splits = 0, fixed = 0, chunk = 0;
 };
 struct GemmLaunch {
@@ -190,15 +191,17 @@ int gemmSplitsFor(int rows, int n, int M, int lanes);
 std::vector<float> qkvRope(const std::vector<uint8_t> &blocks, int q0, int kv0, int hs, int n,
                            const std::vector<float> &in, const std::vector<float> &normW, float eps,
                            const std::vector<float> &rope, int seqLen, const std::vector<int> &pos, bool kvBf16,
-                           std::vector<float> *kOut, std::vector<float> *vOut, int lanes = 0, int passes = 0);
+                           std::vector<float> *kOut, std::vector<float> *vOut, int lanes = 0, int passes = 0,
+                           bool kvFp8 = false);  // kvFp8: e4m3 caches (overrides kvBf16), rows dequantised
 
 // Decode attention over caches k/v [nSlots][seqLen][kv0] (f32 values, stored bf16 when kvBf16),
 // q [B][nHeads0*hs] (already rotated), row b at position pos[b] in slot slot[b]. Returns f32 [B][q0].
 std::vector<float> attention(const std::vector<float> &q, const std::vector<float> &k, const std::vector<float> &v,
                              int nSlots, int seqLen, int nHeads0, int kvMul, int hs, const std::vector<int> &pos,
-                             const std::vector<int> &slot, bool kvBf16, int impl = 0);
+                             const std::vector<int> &slot, bool kvBf16, int impl = 0, bool kvFp8 = false);
 // attention impl: 0 = launchAttention's choice, 1 = MFMA prefill kernel, 2 = VALU decode kernel,
-// 3 = MFMA decode kernel
+// 3 = MFMA decode kernel, 4 = the fp8 decode kernel. kvFp8: the caches are quantised on the host by
+// the append rule, e4m3fn(clamp(x, -448, 448)); only impl 0 and 4 apply (fp8 caches have one kernel)
 
 // One attention launch as the engine's attnArgs / enqueueAttention set it up (engine_forward.cpp),
 // which ops::attention above cannot: a page table, the single-row split geometry, the f16 and Q80
@@ -225,7 +228,7 @@ std::vector<float> attention(const std::vector<float> &q, const std::vector<floa
 // the last row, behind partO, partML and counters; for f16 / Q80 around the code and scale arrays
 // separately. The op throws when a launch changed one. A launch the launchers refuse, or whose
 // operands are outside their contract, throws before any device work (attentionPlan).
-enum AttnKernelSel : int { ATTN_AUTO = 0, ATTN_VALU = 1, ATTN_MFMA = 2, ATTN_PREFILL = 3 };
+enum AttnKernelSel : int { ATTN_AUTO = 0, ATTN_VALU = 1, ATTN_MFMA = 2, ATTN_PREFILL = 3, ATTN_FP8 = 4 };
 enum AttnMode : int { ATTN_DECODE = 0, ATTN_PREFILL_ROWS = 1 };
 enum AttnOut : int { ATTN_OUT_F32 = 0, ATTN_OUT_F16 = 1, ATTN_OUT_Q80 = 2 };
 struct AttnLaunchArgs {
@@ -233,6 +236,7 @@ struct AttnLaunchArgs {
     int nSlots = 0, seqLen = 0, nHeads0 = 0, kvMul = 1, hs = 0;
     std::vector<int> pos, slot;
     bool kvBf16 = true;
+    bool kvFp8 = false;  // e4m3 caches (overrides kvBf16), quantised on the host by the append rule
     int kernel = ATTN_AUTO, mode = ATTN_DECODE;
     bool single = false;
     int splitGrid = 0, headGroup = 0;

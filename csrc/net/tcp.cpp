@@ -242,7 +242,7 @@ std::string encodeWorkerConfig(const WorkerConfig &c) {
       << "\ngpu=" << (c.gpu ? 1 : 0) << "\nmodel=" << e.modelPath << "\nmax_seq_len=" << e.maxSeqLen
       << "\nmax_batch=" << e.maxBatch << "\nmax_decode=" << e.maxDecode << "\nn_slots=" << e.nSlots << "\nbuffer=" << (int)e.bufferType
       << "\nsync=" << (int)e.syncType
-      << "\ngraphs=" << (e.useGraphs ? 1 : 0) << "\nkv_bf16=" << (e.kvBf16 ? 1 : 0) << "\nkv_pages=" << e.kvPages
+      << "\ngraphs=" << (e.useGraphs ? 1 : 0) << "\nkv_bf16=" << (e.kvBf16 ? 1 : 0) << "\nkv_dtype=" << kvDtypeName(e.kvDtype) << "\nkv_pages=" << e.kvPages
       << "\nkv_page_size=" << e.kvPageSize << "\nbatch_invariant=" << (e.batchInvariant ? 1 : 0)
       << "\nsynthetic=" << (e.synthetic ? 1 : 0) << "\nseed=" << e.seed << "\nh_dim=" << h.dim
       << "\nh_hidden=" << h.hiddenDim << "\nh_layers=" << h.nLayers << "\nh_heads=" << h.nHeads
@@ -280,6 +280,9 @@ WorkerConfig decodeWorkerConfig(const std::string &s) {
         else if (k == "sync") e.syncType = (FloatType)std::stoi(v);
         else if (k == "graphs") e.useGraphs = v == "1";
         else if (k == "kv_bf16") e.kvBf16 = v == "1";
+        else if (k == "kv_dtype") {
+            if (!parseKvDtype(v, e.kvDtype)) throw NetError("unknown kv_dtype in the worker config: " + v);
+        }
         else if (k == "kv_pages") e.kvPages = std::stoul(v);
         else if (k == "kv_page_size") e.kvPageSize = std::stoul(v);
         else if (k == "batch_invariant") e.batchInvariant = v == "1";

@@ -565,7 +565,7 @@ void bindOps(py::module_ &m) {
           [](py::object blocks, py::object wf, int rows, int n, int lanes, int input, py::object x, py::object residual,
              py::object normW, float eps, py::object ss, int ssTiles, int ldSS, int epi, py::object resIn,
              py::object resW, int q0, int kv0, int hs, py::object rope, int seqLen, int nSlots, std::vector<int> pos,
-             std::vector<int> slot, bool kvBf16, int splits, int fixed, int chunk, bool planOnly) {
+             std::vector<int> slot, bool kvBf16, int splits, int fixed, int chunk, bool planOnly, bool kvFp8) {
               ops::GemmBatchedArgs a;
               a.blocks = vec<uint8_t>(blocks);
               a.wf = vec<float>(wf);
@@ -593,6 +593,7 @@ void bindOps(py::module_ &m) {
               a.pos = pos;
               a.slot = slot;
               a.kvBf16 = kvBf16;
+              a.kvFp8 = kvFp8;
               a.splits = splits;
               a.fixed = fixed;
               a.chunk = chunk;
@@ -636,45 +637,46 @@ void bindOps(py::module_ &m) {
           py::arg("res_in") = py::none(), py::arg("res_w") = py::none(), py::arg("q0") = 0, py::arg("kv0") = 0,
           py::arg("head_size") = 0, py::arg("rope") = py::none(), py::arg("seq_len") = 0, py::arg("n_slots") = 0,
           py::arg("pos") = std::vector<int>(), py::arg("slot") = std::vector<int>(), py::arg("kv_bf16") = true,
-          py::arg("splits") = 0, py::arg("fixed") = 0, py::arg("chunk") = 0, py::arg("plan_only") = false);
+          py::arg("splits") = 0, py::arg("fixed") = 0, py::arg("chunk") = 0, py::arg("plan_only") = false,
+          py::arg("kv_fp8") = false);
     o.def("gemm_splits", &ops::gemmSplitsFor, py::arg("rows"), py::arg("n"), py::arg("tokens"), py::arg("lanes") = 0,
           "K splits the GEMM launcher takes for a launch of `tokens`; no device needed");
     o.def("qkv_rope",
           [](py::object blocks, int q0, int kv0, int hs, int n, py::object x, py::object normW, float eps, py::object rope,
-             int seqLen, std::vector<int> pos, bool kvBf16, int lanes, int passes) {
+             int seqLen, std::vector<int> pos, bool kvBf16, int lanes, int passes, bool kvFp8) {
               const std::vector<uint8_t> w = vec<uint8_t>(blocks);
               const std::vector<float> in = vec<float>(x), nw = vec<float>(normW), rp = vec<float>(rope);
               std::vector<float> k, v, q;
               {
                   py::gil_scoped_release rel;
-                  q = ops::qkvRope(w, q0, kv0, hs, n, in, nw, eps, rp, seqLen, pos, kvBf16, &k, &v, lanes, passes);
+                  q = ops::qkvRope(w, q0, kv0, hs, n, in, nw, eps, rp, seqLen, pos, kvBf16, &k, &v, lanes, passes, kvFp8);
               }
               const py::ssize_t B = (py::ssize_t)pos.size();
               return py::make_tuple(arr(q, {B, q0}), arr(k, {B, kv0}), arr(v, {B, kv0}));
           },
           py::arg("blocks"), py::arg("q0"), py::arg("kv0"), py::arg("head_size"), py::arg("n"), py::arg("x"),
           py::arg("norm_w"), py::arg("eps"), py::arg("rope"), py::arg("seq_len"), py::arg("pos"), py::arg("kv_bf16") = true,
-          py::arg("lanes") = 0, py::arg("passes") = 0);
+          py::arg("lanes") = 0, py::arg("passes") = 0, py::arg("kv_fp8") = false);
     o.def("attention",
           [](py::object q, py::object k, py::object v, int nSlots, int seqLen, int nHeads0, int kvMul, int hs,
-             std::vector<int> pos, std::vector<int> slot, bool kvBf16, int impl) {
+             std::vector<int> pos, std::vector<int> slot, bool kvBf16, int impl, bool kvFp8) {
               const std::vector<float> qv = vec<float>(q), kv = vec<float>(k), vv = vec<float>(v);
               std::vector<float> out;
               {
                   py::gil_scoped_release rel;
-                  out = ops::attention(qv, kv, vv, nSlots, seqLen, nHeads0, kvMul, hs, pos, slot, kvBf16, impl);
+                  out = ops::attention(qv, kv, vv, nSlots, seqLen, nHeads0, kvMul, hs, pos, slot, kvBf16, impl, kvFp8);
               }
               return arr(out, {(py::ssize_t)pos.size(), (py::ssize_t)nHeads0 * hs});
           },
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("n_slots"), py::arg("seq_len"), py::arg("n_heads0"),
           py::arg("kv_mul"), py::arg("head_size"), py::arg("pos"), py::arg("slot"), py::arg("kv_bf16") = true,
-          py::arg("impl") = 0);
+          py::arg("impl") = 0, py::arg("kv_fp8") = false);
     // ops::attentionLaunch: `plan_only` returns the plan (and raises the refusals) without a device
     o.def("attention_launch",
           [](py::object q, py::object k, py::object v, int nSlots, int seqLen, int nHeads0, int kvMul, int hs,
              std::vector<int> pos, std::vector<int> slot, bool kvBf16, int kernel, int mode, bool single, int splitGrid,
              int headGroup, int out, int ldq, int ldOut, int pageSize, std::vector<int> pageOf, py::object poisonK,
-             py::object poisonV, int repeat, std::vector<int> warmPos, bool planOnly) {
+             py::object poisonV, int repeat, std::vector<int> warmPos, bool planOnly, bool kvFp8) {
               ops::AttnLaunchArgs a;
               a.warmPos = warmPos;
               a.q = vec<float>(q);
@@ -688,6 +690,7 @@ void bindOps(py::module_ &m) {
               a.pos = pos;
               a.slot = slot;
               a.kvBf16 = kvBf16;
+              a.kvFp8 = kvFp8;
               a.kernel = kernel;
               a.mode = mode;
               a.single = single;
@@ -731,7 +734,7 @@ void bindOps(py::module_ &m) {
           py::arg("head_group") = 0, py::arg("out") = 0, py::arg("ldq") = 0, py::arg("ld_out") = 0,
           py::arg("page_size") = 0, py::arg("page_of") = std::vector<int>(), py::arg("poison_k") = py::none(),
           py::arg("poison_v") = py::none(), py::arg("repeat") = 1, py::arg("warm_pos") = std::vector<int>(),
-          py::arg("plan_only") = false);
+          py::arg("plan_only") = false, py::arg("kv_fp8") = false);
     o.def("sample",
           [](py::object logits, int B, py::object specs) {
               const std::vector<float> l = vec<float>(logits), sp = vec<float>(specs);
@@ -1564,11 +1567,12 @@ PYBIND11_MODULE(_C, m) {
           "us per pass over `tokens` rows: above 64 tokens one gemmQ80wWideKernel launch (wide) or the chunked "
           "narrow launches of <= 64 (wide = false)");
     m.def("bench_attention",
-          [](int nh, int kvm, int hs, int seq, int pos, int B, int copies, int iters, bool kvBf16) {
-              return benchAttention(nh, kvm, hs, seq, pos, B, copies, iters, nullptr, kvBf16);
+          [](int nh, int kvm, int hs, int seq, int pos, int B, int copies, int iters, bool kvBf16, bool kvFp8) {
+              return benchAttention(nh, kvm, hs, seq, pos, B, copies, iters, nullptr, kvBf16, kvFp8);
           },
           py::arg("n_heads0"), py::arg("kv_mul"), py::arg("head_size"), py::arg("seq_len"), py::arg("pos"),
           py::arg("batch") = 1, py::arg("copies") = 32, py::arg("iters") = 200, py::arg("kv_bf16") = true,
+          py::arg("kv_fp8") = false,
           py::call_guard<py::gil_scoped_release>());
     m.def("bench_memcpy_d2d", &benchMemcpyD2D, py::arg("bytes"), py::arg("iters") = 20,
           py::call_guard<py::gil_scoped_release>());
@@ -1755,9 +1759,10 @@ PYBIND11_MODULE(_C, m) {
         .def(py::init([](const std::string &model, const std::string &bufferType, u32 maxSeqLen, u32 maxBatch,
                          u32 nSlots, int gpuIndex, bool useGraphs, bool kvBf16, py::object synthetic, u64 seed,
                          int rank, int world, py::object uid, py::object comm, const std::string &syncType,
-                         u32 kvPages, u32 kvPageSize, bool batchInvariant) {
+                         u32 kvPages, u32 kvPageSize, bool batchInvariant, const std::string &kvDtype) {
                  EngineConfig c = makeConfig(model, bufferType, 1, maxSeqLen, maxBatch, nSlots, gpuIndex, useGraphs,
                                              kvBf16, synthetic, seed);
+                 DL_CHECK(parseKvDtype(kvDtype, c.kvDtype), "kv_dtype must be \"\" (follow kv_bf16), \"f32\", \"bf16\" or \"fp8\"");
                  c.syncType = parseFloatType(syncType);
                  c.kvPages = kvPages;
                  c.kvPageSize = kvPageSize;
@@ -1783,9 +1788,10 @@ PYBIND11_MODULE(_C, m) {
              py::arg("kv_bf16") = true, py::arg("synthetic") = py::none(), py::arg("seed") = 1234, py::arg("rank") = 0,
              py::arg("world") = 1, py::arg("uid") = py::none(), py::arg("comm") = py::none(),
              py::arg("sync_type") = "f32", py::arg("kv_pages") = 0, py::arg("kv_page_size") = 256,
-             py::arg("batch_invariant") = false)
+             py::arg("batch_invariant") = false, py::arg("kv_dtype") = "")
         .def_property_readonly("header", [](const PyHipEngine &e) { return headerToDict(e.engine->header()); })
         .def_property_readonly("device_bytes", [](const PyHipEngine &e) { return e.engine->deviceBytes(); })
+        .def_property_readonly("kv_bytes", [](const PyHipEngine &e) { return e.engine->kvBytes(); })
         .def_property_readonly("tp_fused", [](const PyHipEngine &e) { return e.engine->tpFused(); })
         .def_property_readonly("attn_block", [](const PyHipEngine &e) { return e.engine->attnBlock(); })
         .def_property_readonly("prenorm", [](const PyHipEngine &e) { return e.engine->prenorm(); })

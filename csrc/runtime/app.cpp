@@ -65,9 +65,11 @@ AppArgs AppArgs::parse(int argc, char **argv, bool requireMode) {
         else if (name == "--slots") a.slots = std::atoi(value);
         else if (name == "--kv-dtype") {
             const std::string v = value;
+            a.kvDtype = KvDtype::Auto;
             if (v == "bf16") a.kvBf16 = true;
             else if (v == "f32") a.kvBf16 = false;
-            else throw Error("Invalid --kv-dtype (bf16|f32): " + v);
+            else if (v == "fp8") a.kvDtype = KvDtype::Fp8;
+            else throw Error("Invalid --kv-dtype (f32|bf16|fp8): " + v);
         } else if (name == "--kv-pages") a.kvPages = std::atoi(value);
         else if (name == "--kv-page-size") a.kvPageSize = std::atoi(value);
         else if (name == "--batch-invariant") a.batchInvariant = std::atoi(value) != 0;
@@ -137,6 +139,7 @@ static EngineConfig engineConfigFrom(const AppArgs &a, int nSlots) {
     c.gpuIndex = a.gpuIndex;
     c.useGraphs = a.graphs;
     c.kvBf16 = a.kvBf16;
+    c.kvDtype = a.kvDtype;
     c.kvPages = (u32)std::max(0, a.kvPages);
     c.kvPageSize = (u32)std::max(32, a.kvPageSize);
     c.batchInvariant = a.batchInvariant;

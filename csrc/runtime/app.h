@@ -42,6 +42,7 @@ struct AppArgs {
     int gpuIndex = -1;
     int gpuSegmentFrom = -1, gpuSegmentTo = -1;  // accepted for CLI compatibility (no effect)
     int slots = 0;                               // KV slots (0 = 1 for CLI modes, 8 for the API)
+    KvDtype kvDtype = KvDtype::Auto;  // --kv-dtype fp8 (f32 / bf16 set kvBf16 and leave this Auto)
     bool kvBf16 = false;  // --kv-dtype: f32 by default (the reference's KV precision, llm.cpp:197-198)
     int kvPages = 0;       // --kv-pages: paged KV pool pages per layer (0 = contiguous per slot)
     bool batchInvariant = false;  // --batch-invariant 1: rows take the same kernels whatever the batch

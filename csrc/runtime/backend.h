@@ -18,6 +18,20 @@
 
 namespace dl {
 
+// GPU KV cache element type. Auto: EngineConfig::kvBf16 decides (bf16 or f32). Fp8: OCP e4m3fn,
+// e4m3fn(clamp(x, -448, 448)) at append, no scale factor (README "fp8 KV cache").
+enum class KvDtype : int { Auto = 0, F32 = 1, Bf16 = 2, Fp8 = 3 };
+inline const char *kvDtypeName(KvDtype t) { return t == KvDtype::Fp8 ? "fp8" : t == KvDtype::Bf16 ? "bf16" : t == KvDtype::F32 ? "f32" : ""; }
+// "" (Auto), "f32", "bf16" or "fp8"; false for anything else
+inline bool parseKvDtype(const std::string &s, KvDtype &t) {
+    if (s.empty()) t = KvDtype::Auto;
+    else if (s == "f32") t = KvDtype::F32;
+    else if (s == "bf16") t = KvDtype::Bf16;
+    else if (s == "fp8") t = KvDtype::Fp8;
+    else return false;
+    return true;
+}
+
 struct EngineConfig {
     std::string modelPath;          // .m file (ignored when synthetic)
     u32 maxSeqLen = 0;              // clamp of header seqLen (0 = model's)
@@ -34,6 +48,8 @@ struct EngineConfig {
     int gpuIndex = -1;              // HIP device ordinal (-1 = CPU backend)
     bool useGraphs = true;          // capture per-batch-size hipGraphs
     bool kvBf16 = true;             // GPU KV cache dtype (bf16 default, f32 when false)
+    KvDtype kvDtype = KvDtype::Auto;  // when not Auto, overrides kvBf16 (the only way to ask for fp8)
+    KvDtype kvType() const { return kvDtype != KvDtype::Auto ? kvDtype : kvBf16 ? KvDtype::Bf16 : KvDtype::F32; }
     u32 kvPages = 0;                // GPU paged KV cache: pool pages per layer (0 = contiguous
                                     // nSlots x seqLen, no page table)
     u32 kvPageSize = 256;           // positions per page (power of two, >= 32)

@@ -83,9 +83,11 @@ class TorchLlama:
         return torch.stack([o0, o1], dim=-1).reshape(T, n)
 
     @torch.no_grad()
-    def forward(self, tokens, start_pos: int = 0, kv: Optional[dict] = None) -> torch.Tensor:
+    def forward(self, tokens, start_pos: int = 0, kv: Optional[dict] = None, kv_round=None) -> torch.Tensor:
         """Full causal forward of `tokens` at positions start_pos.. ; returns logits [T, vocab].
-        `kv` (dict) carries the cache between calls for incremental decoding."""
+        `kv` (dict) carries the cache between calls for incremental decoding. `kv_round` (callable,
+        optional) is applied to the rotated K and to V as they are appended: the rounding of a reduced
+        precision KV cache (None: the values are kept as computed)."""
         sp = self.spec
         w = self.w
         tok = torch.as_tensor(tokens, dtype=torch.long, device=self.device)
@@ -100,6 +102,8 @@ class TorchLlama:
             q = self._rope(self._mm(w[("q", l)], xn), pos)
             k = self._rope(self._mm(w[("k", l)], xn), pos)
             v = self._mm(w[("v", l)], xn)
+            if kv_round is not None:
+                k, v = kv_round(k), kv_round(v)
             kc, vc = kv.get(l, (torch.zeros(0, sp.kv_dim, device=self.device), torch.zeros(0, sp.kv_dim, device=self.device)))
             kc = torch.cat([kc, k]) if kc.shape[0] == start_pos else torch.cat([kc[:start_pos], k])
             vc = torch.cat([vc, v]) if vc.shape[0] == start_pos else torch.cat([vc[:start_pos], v])

@@ -156,6 +156,13 @@ def gemm_q80w(blocks, rows: int, n: int, x, lanes: int = 0, splits: int = 0, epi
     return {k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()}
 
 
+def _kv(kv_bf16: bool, kv_dtype: str):
+    """(kv_bf16, kv_fp8) of a kv_dtype keyword: "" follows kv_bf16, else "f32" / "bf16" / "fp8"."""
+    if kv_dtype not in ("", "f32", "bf16", "fp8"):
+        raise ValueError('kv_dtype must be "", "f32", "bf16" or "fp8"')
+    return (kv_bf16 if kv_dtype in ("", "fp8") else kv_dtype == "bf16"), kv_dtype == "fp8"
+
+
 GEMM_INPUTS = {"norm": 0, "f16": 1, "prenorm": 2}
 GEMM_EPILOGUES = {"store": 0, "qkv": 2, "swiglu_f16": 4, "res": 6}
 
@@ -163,7 +170,8 @@ GEMM_EPILOGUES = {"store": 0, "qkv": 2, "swiglu_f16": 4, "res": 6}
 def gemm(x, blocks=None, w=None, rows: int = 0, n: int = 0, lanes: int = 0, input: str = "norm", residual=None,
          norm_w=None, eps: float = 1e-5, ss=None, ld_ss: int = 0, epilogue: str = "store", res_in=None, res_w=None,
          q0: int = 0, kv0: int = 0, head_size: int = 0, rope=None, n_slots: int = 0, pos=(), slot=(),
-         kv_bf16: bool = True, splits: int = 0, fixed: bool = False, chunk: int = 0, plan_only: bool = False) -> dict:
+         kv_bf16: bool = True, splits: int = 0, fixed: bool = False, chunk: int = 0, plan_only: bool = False,
+         kv_dtype: str = "") -> dict:
     """One batched GEMM of the forward schedule, launched as the engine launches it (ops::gemmBatched,
     csrc/hip/ops.h): Q40 `blocks` [rows][n/32] tiled at `lanes` (0: the GEMV's choice; 16 / 32 / 64) or
     F32 `w` [rows, n]; x [M, n].
@@ -175,7 +183,10 @@ def gemm(x, blocks=None, w=None, rows: int = 0, n: int = 0, lanes: int = 0, inpu
     splits 0: the launcher's choice; fixed: the batch-invariant narrow launch; chunk: tokens per launch
     (0: the engine's rule). Outputs are guarded: a store outside their valid part raises. Returns a
     dict with the outputs and "launches": [{c0, tokens, kernel, splits, grid}] ("narrow", "l16",
-    "wide", "f32"). plan_only: just the launches and the refusals, no device needed."""
+    "wide", "f32"). plan_only: just the launches and the refusals, no device needed.
+    kv_dtype "" (follow kv_bf16) / "f32" / "bf16" / "fp8": the cache type of the "qkv" epilogue; "fp8"
+    stores e4m3fn(clamp(x, -448, 448)) and k / v come back dequantised."""
+    kv_bf16, kv_fp8 = _kv(kv_bf16, kv_dtype)
     if w is not None:
         rows, n = w.shape
     ss_np = _np(ss)
@@ -184,7 +195,7 @@ def gemm(x, blocks=None, w=None, rows: int = 0, n: int = 0, lanes: int = 0, inpu
                           _np(norm_w), eps, ss_np, 0 if ss_np is None else ss_np.shape[0], ld_ss,
                           GEMM_EPILOGUES[epilogue], _np(res_in), _np(res_w), q0, kv0, head_size, rope_np,
                           0 if rope_np is None else rope_np.shape[0], n_slots, [int(p) for p in pos],
-                          [int(s) for s in slot], kv_bf16, splits, 1 if fixed else 0, chunk, plan_only)
+                          [int(s) for s in slot], kv_bf16, splits, 1 if fixed else 0, chunk, plan_only, kv_fp8)
     return {k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()}
 
 
@@ -194,28 +205,34 @@ def gemm_splits(rows: int, n: int, tokens: int, lanes: int = 0) -> int:
 
 
 def qkv_rope(blocks, q0: int, kv0: int, head_size: int, n: int, x, norm_w, eps: float, rope, seq_len: int,
-             pos, kv_bf16: bool = True, lanes: int = 0, passes: int = 0):
-    """QKV GEMV with the RoPE + KV-cache-append epilogue. Returns (q rotated, k row, v row)."""
+             pos, kv_bf16: bool = True, lanes: int = 0, passes: int = 0, kv_dtype: str = ""):
+    """QKV GEMV with the RoPE + KV-cache-append epilogue. Returns (q rotated, k row, v row).
+    kv_dtype "" (follow kv_bf16) / "f32" / "bf16" / "fp8"; "fp8": the rows are stored as
+    e4m3fn(clamp(x, -448, 448)) and returned dequantised."""
+    kv_bf16, kv_fp8 = _kv(kv_bf16, kv_dtype)
     q, k, v = native().ops.qkv_rope(_np(blocks, np.uint8), q0, kv0, head_size, n, _np(x), _np(norm_w), eps,
-                                    _np(rope), seq_len, [int(p) for p in pos], kv_bf16, lanes, passes)
+                                    _np(rope), seq_len, [int(p) for p in pos], kv_bf16, lanes, passes, kv_fp8)
     return torch.from_numpy(q), torch.from_numpy(k), torch.from_numpy(v)
 
 
 def attention(q, k_cache, v_cache, n_heads0: int, kv_mul: int, head_size: int, pos, slot,
-              kv_bf16: bool = True, prefill: bool = False, impl: str = "auto") -> torch.Tensor:
+              kv_bf16: bool = True, prefill: bool = False, impl: str = "auto", kv_dtype: str = "") -> torch.Tensor:
     """Decode attention. k_cache / v_cache: [slots, seq_len, kv0]; q: [B, n_heads0 * head_size].
     prefill=True (impl "prefill"): the MFMA prefill kernel (bf16 MFMAs for a bf16 cache, f32 MFMAs
     for an f32 one; row blocks of 64 / kv_mul rows share a slot). impl "valu" / "mfma": force the VALU or the MFMA decode kernel ("auto": the
     launcher's choice, MFMA for bf16 caches of >= 1024 positions). "mfma" takes kv_mul 1/2/4/8 and
-    head size 128 on a bf16 cache, head size 128 or 64 on an f32 cache (attnDecodeF32MfmaKernel)."""
+    head size 128 on a bf16 cache, head size 128 or 64 on an f32 cache (attnDecodeF32MfmaKernel).
+    kv_dtype "" (follow kv_bf16) / "f32" / "bf16" / "fp8"; "fp8": the caches are quantised on the host by
+    the append rule and attnDecodeFp8Kernel runs (impl "auto" or "fp8"; there is no other fp8 kernel)."""
+    kv_bf16, kv_fp8 = _kv(kv_bf16, kv_dtype)
     n_slots, seq_len, _ = k_cache.shape
-    code = {"auto": 0, "prefill": 1, "valu": 2, "mfma": 3}["prefill" if prefill else impl]
+    code = {"auto": 0, "prefill": 1, "valu": 2, "mfma": 3, "fp8": 4}["prefill" if prefill else impl]
     return torch.from_numpy(native().ops.attention(_np(q), _np(k_cache), _np(v_cache), n_slots, seq_len, n_heads0,
                                                    kv_mul, head_size, [int(p) for p in pos], [int(s) for s in slot],
-                                                   kv_bf16, code))
+                                                   kv_bf16, code, kv_fp8))
 
 
-ATTN_KERNELS = {"auto": 0, "valu": 1, "mfma": 2, "prefill": 3}
+ATTN_KERNELS = {"auto": 0, "valu": 1, "mfma": 2, "prefill": 3, "fp8": 4}
 ATTN_OUTPUTS = {"f32": 0, "f16": 1, "q80": 2}
 
 
@@ -223,7 +240,7 @@ def attention_launch(q, k_cache, v_cache, n_heads0: int, kv_mul: int, head_size:
                      kv_bf16: bool = True, kernel: str = "auto", prefill: bool = False, single: bool = False,
                      split_grid: int = 0, head_group: int = 0, out: str = "f32", ldq: int = 0, ld_out: int = 0,
                      page_size: int = 0, page_of=None, poison_k=None, poison_v=None, repeat: int = 1,
-                     warm_pos=None, plan_only: bool = False) -> dict:
+                     warm_pos=None, plan_only: bool = False, kv_dtype: str = "") -> dict:
     """One attention launch set up as the engine sets it up (ops::attentionLaunch, csrc/hip/ops.h).
     q [B, ldq or q0], k_cache / v_cache [slots, seq_len, kv0]. kernel "auto" / "valu" / "mfma" /
     "prefill" ("mfma": attnDecodeMfmaKernel<KM> on a bf16 cache, attnDecodeF32MfmaKernel<KM,HS> on an
@@ -236,7 +253,11 @@ def attention_launch(q, k_cache, v_cache, n_heads0: int, kv_mul: int, head_size:
     guarded: a store outside their valid part raises. Returns {"kernel", "hg", "grid", "split_grid",
     "chunk_max", "short_len", "splits": [(nSplit, ch) per decode row, or per prefill row block], "out" [B, q0] (f32, the f16
     values or the Q80 codes), "scales" [B, q0 / 32, 2] (Q80: d, sum of codes)}. plan_only: just the
-    plan and the refusals, no device needed."""
+    plan and the refusals, no device needed. kv_dtype "" (follow kv_bf16) / "f32" / "bf16" / "fp8";
+    "fp8": the caches (and the poison rows) are quantised on the host by the append rule,
+    e4m3fn(clamp(x, -448, 448)), and attnDecodeFp8Kernel<KM,HS> runs (kernel "auto" or "fp8"; decode
+    rows only: fp8 caches have no prefill kernel)."""
+    kv_bf16, kv_fp8 = _kv(kv_bf16, kv_dtype)
     n_slots, seq_len, _ = k_cache.shape
     po = [] if page_of is None else [int(p) for p in np.asarray(page_of).reshape(-1)]
     r = native().ops.attention_launch(_np(q), _np(k_cache), _np(v_cache), n_slots, seq_len, n_heads0, kv_mul,
@@ -244,7 +265,7 @@ def attention_launch(q, k_cache, v_cache, n_heads0: int, kv_mul: int, head_size:
                                       ATTN_KERNELS["prefill" if prefill and kernel == "auto" else kernel],
                                       1 if prefill else 0, single, split_grid, head_group, ATTN_OUTPUTS[out], ldq,
                                       ld_out, page_size, po, _np(poison_k), _np(poison_v), repeat,
-                                      [] if warm_pos is None else [int(p) for p in warm_pos], plan_only)
+                                      [] if warm_pos is None else [int(p) for p in warm_pos], plan_only, kv_fp8)
     return {k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()}
 
 
