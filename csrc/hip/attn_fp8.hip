@@ -1,5 +1,6 @@
-// Decode attention for fp8 (OCP e4m3fn) KV caches: every decode row of a --kv-dtype fp8 engine, from
-// a context of one key upward (there is no VALU kernel and no fused attention block for this type).
+// Attention for fp8 (OCP e4m3fn) KV caches: attnDecodeFp8Kernel for every decode row of a --kv-dtype
+// fp8 engine, from a context of one key upward (there is no VALU kernel and no fused attention block
+// for this type), and attnPrefillFp8Kernel (below it) for the row blocks of a prompt.
 //
 // Semantics: the cache holds e4m3fn(clamp(x, -448, 448)) of the rotated K and of V (qkvPairStore,
 // decode_common.h); attention over an fp8 cache is attention over those stored values. The kernel
@@ -46,7 +47,7 @@
 // Kept from attn_mfma.hip: page ids loaded once per workgroup, one per lane, and shuffled to rows;
 // LDS-DMA data ordered by a counted vmcnt followed by a workgroup barrier; keys past the chunk are
 // masked, never branched around (the DMA re-reads the chunk's last key); no scratch.
-#include "decode_dev.h"
+#include "attn_prefill_dev.h"
 
 namespace dl {
 namespace hipk {
@@ -285,6 +286,199 @@ __global__ __launch_bounds__(kF8Threads) void attnDecodeFp8Kernel(AttnArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Prefill attention over fp8 caches: the prompt rows of a batched forward. Semantics are the decode
+// kernel's (bytes widened to bf16 in registers, Q . scale and P rounded to bf16,
+// v_mfma_f32_16x16x32_bf16, f32 online softmax, no scale factor); the work split is the other prefill
+// kernels' (attn_prefill.hip, attn_mfma.hip): one workgroup owns one KV head and a block of 4 x 16 / KM
+// consecutive rows of one slot, a wave's 16 MFMA columns are (row, query head) pairs, all four waves
+// read every K / V tile of the chunk from LDS, long contexts split over grid.y by attnPrefillSplit and
+// finish through pfFinish. The decode kernel walked the context once per row: a 64-row chunk at
+// position p read 64 x p keys, here it reads p per row block.
+//
+// Tiles and LDS image are the decode kernel's: 64-key tiles of unpadded HS-byte rows, f8Swz source
+// pieces, fkKey key order, K by ds_read_b128 (two MFMAs each), V^T by ds_read_b64_tr_b8. Neither
+// fkKey nor f8Swz reads row bit 5, so a tile is two independent 32-key halves with the same bank
+// maps, and the half is the unit of everything that attnPrefillSplit's 32-key granularity touches:
+//   * a chunk starts at a multiple of 32, so a 64-key tile may straddle a page of a paged cache; a
+//     half never does. The page list (LDS, filled before any DMA) has one entry per half;
+//   * the DMA unit is the half: wave w copies half w of a round (K and V: HS / 32 + HS / 32
+//     wave-instructions of 1024 / HS rows), so a round is 4 halves = 2 tiles = 128 keys;
+//   * a chunk's last tile may own one half only. The other half is still copied (its keys clamp to
+//     the chunk's last key, as every row past the chunk does), because its V bytes enter the O^T MFMA
+//     with P = 0 and stale LDS could hold NaN codes.
+// Staging is attnPrefillDmaKernel's: rounds copied by LDS-DMA two ahead, a counted vmcnt (this wave's
+// copy of the round landed, the next round's may stay in flight), a workgroup barrier, every wave
+// consumes both tiles, a second barrier frees the buffer for round r + 2.
+//
+// What the halved bytes are spent on. Two rounds of 128 keys in flight are the bf16 kernel's keys in
+// flight (it holds 2 x 4 tiles of 32) in half its LDS: 64 KB at head size 128 (32 KB at 64) instead of
+// 128 KB, so two (four) workgroups share a CU where the bf16 kernel runs one. The alternatives were
+// twice the keys in flight per workgroup (four 64-key tiles a round) or a third round at the same
+// 128 KB. Per tile and wave this kernel issues 32 MFMAs but also 256 VALU conversions (8 per 8-byte
+// fragment, every wave converting the tiles for its own columns) before the softmax's VALU work, so a
+// lone workgroup leaves the CU idle at both barriers of a round and whenever its four waves sit in
+// the same conversion or exp stretch; deeper staging would only lengthen a queue that the DMA already
+// keeps full, while a second resident workgroup runs its MFMAs and conversions in those gaps. The
+// cost is none in keys in flight per CU (2 x 256 = the bf16 kernel's 512 at HS 128).
+// No non-temporal hint on the DMA (every row block of the prompt reads the same tiles); no scratch.
+// ------------------------------------------------------------------------------------------------
+static constexpr int kFpRound = 2;       // 64-key tiles per round (4 halves, one per wave)
+static constexpr int kFpMaxHalves = 256; // per-chunk page list (paged caches): one page per 32-key half
+__host__ __device__ constexpr size_t fpLds(int hs) { return (size_t)2 * kFpRound * 2 * f8TileBytes(hs) + 64; }
+
+template <int KM, int HS>
+__global__ __launch_bounds__(kF8Threads) void attnPrefillFp8Kernel(AttnArgs a, int nRows) {
+    constexpr int TILE = kF8Tile, HALF = TILE / 2, NU = TILE / 16, NH = TILE / 32, NT = HS / 16, DS = HS / 32, QD = HS / 4;
+    constexpr int PPR = HS / 16, RPI = 1024 / HS, NIH = HALF / RPI;  // pieces per row, rows per DMA instruction, instructions per half
+    constexpr int PPL = HS / 64;                                      // 16-byte K pieces per lane and key
+    constexpr int TB = f8TileBytes(HS), RPW = 16 / KM, RPB = kF8Waves * RPW;
+    static_assert(kF8Threads == kPfThreads && kF8Waves == kPfWaves && 2 * kFpRound == kF8Waves, "pfFinish's workgroup, one half per wave");
+    static_assert(HALF == kAttnPrefillTile && DS == 2 * PPL, "tile geometry");
+    static_assert(2 * kFpRound * 2 * TB >= 4 * (64 * (HS / 2) + 64), "combine weights must fit the tiles");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int pageL[kFpMaxHalves];
+    const int nKv = a.nHeads0 / KM;
+    const int g = blockIdx.x % nKv, rb = blockIdx.x / nKv, c = blockIdx.y;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 15, h = lane >> 4;
+    const int b0 = rb * RPB;
+    const int maxLen = rowsMaxLen(a.pos, b0, RPB, nRows);
+    int nSplit, ch;
+    attnPrefillSplit(maxLen, a.splitGrid, HS, kAttnPrefillChunk, nSplit, ch);
+    if (c >= nSplit) return;
+    const int k0 = c * ch, k1 = min(k0 + ch, maxLen);
+    const int sl = a.slot[b0];  // every row of the block (host-checked)
+    // this lane's column: a (row, query head) pair; its quarter QD h of the head for S^T
+    const int row = b0 + wave * RPW + col / KM, head = g * KM + col % KM;
+    const bool rowOk = row < nRows;
+    const int myLen = rowOk ? a.pos[row] + 1 : 0;
+    const float scale = 1.0f / sqrtf((float)HS);
+    bf16x8 qf[DS];  // qf[s]: dims QD h + 8 s .. + 7
+#pragma unroll
+    for (int s = 0; s < DS; s++) {
+        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (rowOk) {
+            const float *qp = a.q + (size_t)row * a.ldq + (size_t)head * HS + QD * h + 8 * s;
+            const float4 x0 = ld4(qp), x1 = ld4(qp + 4);
+            v[0] = x0.x * scale; v[1] = x0.y * scale; v[2] = x0.z * scale; v[3] = x0.w * scale;
+            v[4] = x1.x * scale; v[5] = x1.y * scale; v[6] = x1.z * scale; v[7] = x1.w * scale;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j++) qf[s][j] = (__bf16)v[j];
+    }
+    const uint8_t *kc = reinterpret_cast<const uint8_t *>(a.kcache);
+    const uint8_t *vc = reinterpret_cast<const uint8_t *>(a.vcache);
+    const int nHalves = (k1 - k0 + HALF - 1) / HALF, nTiles = (nHalves + 1) / 2;
+    const int nRounds = (nTiles + kFpRound - 1) / kFpRound;
+    // paged cache: the chunk's per-half pages in LDS before any DMA (a table load per key row would
+    // put a vmcnt(0) drain before every DMA pair, contiguous caches included)
+    if (a.kvMap.table)
+        for (int i = tid; i < nHalves; i += kF8Threads) pageL[i] = (int)kvPageOf(a.kvMap, sl, k0 + i * HALF);
+    __syncthreads();
+    auto tileBuf = [&](int bf, int tt) { return smem + (size_t)(bf * kFpRound + tt) * 2 * TB; };
+    // wave w copies half w of round r (half w & 1 of tile w >> 1) into buffer bf: NIH + NIH
+    // wave-instructions, or none when the tile is past the chunk
+    auto issue = [&](int r, int bf) {
+        const int hf = 2 * kFpRound * r + wave;
+        if ((hf >> 1) >= nTiles) return;
+        char *kb = tileBuf(bf, wave >> 1) + (wave & 1) * HALF * HS, *vb = kb + TB;
+        const size_t blk = a.kvMap.table ? (size_t)pageL[min(hf, nHalves - 1)] : (size_t)sl;
+#pragma unroll
+        for (int j = 0; j < NIH; j++) {
+            const int rr = RPI * j + lane / PPR, p = lane % PPR;
+            const int key = min(k0 + HALF * hf + rr, k1 - 1);  // past the chunk: masked below (in half nHalves - 1)
+            const size_t off = kvOffAt(a.kvMap, a.seqLen, nKv, HS, blk, key, g) + (size_t)(p ^ f8Swz<HS>(rr)) * 16;
+            __builtin_amdgcn_global_load_lds(const_cast<uint8_t *>(kc + off),
+                                             reinterpret_cast<__attribute__((address_space(3))) void *>(
+                                                 reinterpret_cast<uintptr_t>(kb + j * 1024)), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(const_cast<uint8_t *>(vc + off),
+                                             reinterpret_cast<__attribute__((address_space(3))) void *>(
+                                                 reinterpret_cast<uintptr_t>(vb + j * 1024)), 16, 0, 0);
+        }
+    };
+    f32x4 o[NT];
+#pragma unroll
+    for (int n = 0; n < NT; n++) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m = -INFINITY, lsum = 0.f;
+    // V: lane 2 q + p of group h addresses row 32 x + 8 h + q, bytes 8 p.. of piece n
+    const int vRow = 8 * h + (col >> 1), vHalf = 8 * (col & 1);
+    issue(0, 0);
+    if (nRounds > 1) issue(1, 1);
+    for (int r = 0; r < nRounds; r++) {
+        // this wave's copy of round r landed (round r + 1's may stay in flight), then every wave's
+        if (r + 1 < nRounds && ((2 * kFpRound * (r + 1) + wave) >> 1) < nTiles) {
+            if constexpr (HS == 128) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        __builtin_amdgcn_s_barrier();
+        for (int tt = 0; tt < kFpRound; tt++) {
+            const int t = kFpRound * r + tt;
+            if (t >= nTiles) break;  // uniform over the workgroup
+            const char *kb = tileBuf(r & 1, tt), *vb = kb + TB;
+            const int tb = k0 + TILE * t;
+            f32x4 st[NU];
+#pragma unroll
+            for (int u = 0; u < NU; u++) {
+                st[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+                const int rr = fkKey(u, col);
+#pragma unroll
+                for (int e = 0; e < PPL; e++) {
+                    const u32x4 kw = *reinterpret_cast<const u32x4 *>(kb + rr * HS + 16 * ((PPL * h + e) ^ f8Swz<HS>(rr)));
+                    st[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fp8x8ToBf16(kw.x, kw.y), qf[2 * e], st[u], 0, 0, 0);
+                    st[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fp8x8ToBf16(kw.z, kw.w), qf[2 * e + 1], st[u], 0, 0, 0);
+                }
+            }
+            float mx = -INFINITY;
+#pragma unroll
+            for (int u = 0; u < NU; u++)
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const int key = tb + fkKey(u, 4 * h + e);
+                    if (key >= k1 || key >= myLen) st[u][e] = -INFINITY;
+                    mx = fmaxf(mx, st[u][e]);
+                }
+            mx = fmaxf(mx, __shfl_xor(mx, 16));
+            mx = fmaxf(mx, __shfl_xor(mx, 32));
+            const float mn = fmaxf(m, mx);
+            const float corr = m == -INFINITY ? 0.f : __expf(m - mn);
+            bf16x8 pf[NH];  // pf[x][4 (u & 1) + e]: key 32 x + 8 h + 4 (u & 1) + e
+            float ps = 0.f;
+#pragma unroll
+            for (int u = 0; u < NU; u++)
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const float p = st[u][e] == -INFINITY ? 0.f : __expf(st[u][e] - mn);
+                    ps += p;
+                    pf[u >> 1][4 * (u & 1) + e] = (__bf16)p;
+                }
+            lsum = lsum * corr + ps;
+            m = mn;
+#pragma unroll
+            for (int n = 0; n < NT; n++) {
+                o[n] *= corr;
+#pragma unroll
+                for (int x = 0; x < NH; x++) {
+                    const int rr = 32 * x + vRow;
+                    const char *ad = vb + rr * HS + 16 * (n ^ f8Swz<HS>(rr)) + vHalf;
+                    const i32x2 vw = __builtin_amdgcn_ds_read_tr8_b64_v2i32(
+                        reinterpret_cast<__attribute__((address_space(3))) i32x2 *>(reinterpret_cast<uintptr_t>(ad)));
+                    o[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fp8x8ToBf16((uint32_t)vw.x, (uint32_t)vw.y), pf[x], o[n], 0, 0, 0);
+                }
+            }
+        }
+        // every wave's reads of buffer r & 1 retired before round r + 2 is copied into it
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        if (r + 2 < nRounds) issue(r + 2, r & 1);
+    }
+    // wts [64 columns][nSplit <= HS / 2] and tot [64] reuse the tiles; the flag sits behind them
+    float *wts = reinterpret_cast<float *>(smem);
+    pfFinish<HS>(a, nRows, o, m, lsum, nSplit, rb, g, c, b0, row, head, wts, wts + 64 * (HS / 2),
+                 *reinterpret_cast<int *>(smem + 2 * kFpRound * 2 * TB));
+}
+
 bool attnFp8Supported(const AttnArgs &a) {
     return a.kvFp8 && (a.hs == 128 || a.hs == 64) && (a.kvMul == 1 || a.kvMul == 2 || a.kvMul == 4 || a.kvMul == 8) &&
            a.nHeads0 % a.kvMul == 0;
@@ -321,6 +515,39 @@ void launchAttentionFp8(const AttnArgs &a, int B, hipStream_t s) {
     DL_F8_CASE(1, 64) DL_F8_CASE(2, 64) DL_F8_CASE(4, 64) DL_F8_CASE(8, 64)
 #undef DL_F8_CASE
     throw Error("launchAttentionFp8: fp8 KV caches need head size 64 or 128 and kvMul 1, 2, 4 or 8");
+}
+
+const char *attnPrefillFp8Refusal(const AttnArgs &a) {
+    if (!attnFp8Supported(a))
+        return "launchAttentionPrefillFp8: fp8 KV caches need head size 64 or 128 and kvMul 1, 2, 4 or 8";
+    // the combine's weights (64 columns x up to hs / 2 splits) and totals live in the tile buffers
+    const int maxSplits = std::max(1, std::min(a.splitGrid, a.hs / 2));
+    if ((size_t)4 * (64 * maxSplits + 64) + 64 > fpLds(a.hs))
+        return "launchAttentionPrefillFp8: attention split grid too large";
+    // the longest chunk's 32-key halves fit the kernel's LDS page list
+    if (a.kvMap.table && ((a.seqLen + maxSplits - 1) / maxSplits + kAttnPrefillTile - 1) / kAttnPrefillTile + 1 > kFpMaxHalves)
+        return "launchAttentionPrefillFp8: paged context too long for the per-chunk page list";
+    return nullptr;
+}
+
+std::string attnPrefillFp8KernelName(const AttnArgs &a) {
+    return "attnPrefillFp8Kernel<" + std::to_string(a.kvMul) + "," + std::to_string(a.hs) + ">";
+}
+
+void launchAttentionPrefillFp8(const AttnArgs &a, int nRows, hipStream_t s) {
+    if (const char *why = attnPrefillFp8Refusal(a)) throw Error(why);
+    const int nKv = a.nHeads0 / a.kvMul, rpb = kF8Waves * (16 / a.kvMul);
+    const dim3 grid(nKv * ((nRows + rpb - 1) / rpb), a.splitGrid);
+#define DL_FP_CASE(K, H)                                                                                      \
+    if (a.kvMul == K && a.hs == H) {                                                                          \
+        allowLds((const void *)attnPrefillFp8Kernel<K, H>, fpLds(H));                                         \
+        hipLaunchKernelGGL((attnPrefillFp8Kernel<K, H>), grid, dim3(kF8Threads), fpLds(H), s, a, nRows);      \
+        return;                                                                                               \
+    }
+    DL_FP_CASE(1, 128) DL_FP_CASE(2, 128) DL_FP_CASE(4, 128) DL_FP_CASE(8, 128)
+    DL_FP_CASE(1, 64) DL_FP_CASE(2, 64) DL_FP_CASE(4, 64) DL_FP_CASE(8, 64)
+#undef DL_FP_CASE
+    throw Error("launchAttentionPrefillFp8: fp8 KV caches need head size 64 or 128 and kvMul 1, 2, 4 or 8");
 }
 
 }  // namespace hipk

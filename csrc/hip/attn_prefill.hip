@@ -1,7 +1,8 @@
 // Prefill attention on MFMA for the batched path (split out of kernels.hip).
-#include "decode_dev.h"
+#include "attn_prefill_dev.h"
 
 #include <cstdlib>
+#include <string>
 #include <type_traits>
 
 namespace dl {
@@ -26,7 +27,7 @@ namespace hipk {
 // ------------------------------------------------------------------------------------------------
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-static constexpr int kPfThreads = 256, kPfWaves = 4, kPfChunk = kAttnPrefillChunk, kPfTile = kAttnPrefillTile;
+static constexpr int kPfChunk = kAttnPrefillChunk, kPfTile = kAttnPrefillTile;
 static constexpr int kPfVtStride = 40;  // bf16 per transposed-V row in LDS (32 keys + 8 pad)
 #ifndef DL_PF_F32_SMALL_CHUNK
 #define DL_PF_F32_SMALL_CHUNK 128
@@ -46,7 +47,7 @@ __device__ __forceinline__ void pfPages(const AttnArgs &a, int sl, int k0, int k
 int attnPrefillRowsPerBlock(int kvMul) { return kPfWaves * (16 / kvMul); }
 bool attnPrefillSupported(int hs, int kvMul, bool kvBf16, bool kvFp8) {
     (void)kvBf16;  // bf16: attnPrefillKernel (or the LDS-DMA kernel), f32: attnPrefillF32Kernel
-    if (kvFp8) return false;  // fp8: no prefill kernel, prompt rows take attnDecodeFp8Kernel
+    if (kvFp8) return (hs == 64 || hs == 128) && (kvMul == 1 || kvMul == 2 || kvMul == 4 || kvMul == 8);  // attnPrefillFp8Kernel
     return (hs == 64 || hs == 128) && kvMul >= 1 && kvMul <= 16 && (kvMul & (kvMul - 1)) == 0;
 }
 
@@ -55,98 +56,6 @@ __device__ __forceinline__ bf16x8 f32x8ToBf16(const float (&v)[8]) {
 #pragma unroll
     for (int j = 0; j < 8; j++) r[j] = (__bf16)v[j];
     return r;
-}
-
-// Shared tail of both prefill kernels: normalize and store (one chunk), or publish the chunk's
-// partials and let the last-arriving chunk combine them. wts ([64 columns][nSplit]) and tot ([64])
-// reuse the workgroup's K / V tile LDS.
-template <int HS>
-__device__ __forceinline__ void pfFinish(const AttnArgs &a, int nRows, const f32x4 (&o)[HS / 16], float m, float lsum,
-                                         int nSplit, int rb, int g, int c, int b0, int row, int head, float *wts,
-                                         float *tot, int &flagL) {
-    constexpr int NT = HS / 16;
-    const int tid = threadIdx.x, lane = tid & 63, h = lane >> 4;
-    const int kvMul = a.kvMul, rpb = kPfWaves * (16 / kvMul), nKv = a.nHeads0 / kvMul;
-    const bool rowOk = row < nRows;
-    lsum += __shfl_xor(lsum, 16);
-    lsum += __shfl_xor(lsum, 32);
-    // O^T accumulators: lane holds O[column][dim 16 n + 4 h + i]
-    auto writeOut = [&](int r, int hd, int d, const float (&v)[4]) {
-        const size_t at = (size_t)r * a.ldOut + (size_t)hd * HS + d;
-        if (a.outH) {
-            typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-            *reinterpret_cast<h4 *>(a.outH + at) = h4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-        } else {
-            *reinterpret_cast<float4 *>(a.out + at) = make_float4(v[0], v[1], v[2], v[3]);
-        }
-    };
-    if (nSplit == 1) {
-        if (rowOk) {
-            const float il = lsum > 0.f ? 1.0f / lsum : 0.f;
-#pragma unroll
-            for (int n = 0; n < NT; n++) {
-                const float v[4] = {o[n][0] * il, o[n][1] * il, o[n][2] * il, o[n][3] * il};
-                writeOut(row, head, 16 * n + 4 * h, v);
-            }
-        }
-        return;
-    }
-    // several chunks: publish (every column of the block, masked ones as (-inf, 0, 0)), count in,
-    // the last arriver combines
-    const int G = a.splitGrid;
-    // fence-free hand-off (splitArrive, decode_common.h)
-    if (rowOk) {
-        const size_t pb = ((size_t)row * a.nHeads0 + head) * G + c;
-#pragma unroll
-        for (int n = 0; n < NT; n++)
-#pragma unroll
-            for (int e = 0; e < 4; e++) wtStore(a.partO + pb * HS + 16 * n + 4 * h + e, o[n][e]);
-        if (h == 0) {
-            wtStore(a.partML + pb * 2, m);
-            wtStore(a.partML + pb * 2 + 1, lsum);
-        }
-    }
-    // splitArrive (decode_common.h), open-coded: the call compiles to other code in this kernel
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int *cnt = a.counters + (size_t)rb * nKv + g;
-    if (tid == 0) flagL = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nSplit - 1;
-    __syncthreads();
-    if (!flagL) return;
-    if (tid == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // per column: chunk weights exp(m_c - M) and the total sum (LDS: the tiles are free now)
-    const int nCol = rpb * kvMul;  // 64 columns
-    if (tid < nCol) {
-        const int r = b0 + tid / kvMul, hd = g * kvMul + tid % kvMul;
-        float M = -INFINITY, L = 0.f;
-        if (r < nRows) {
-            const float *ml = a.partML + ((size_t)r * a.nHeads0 + hd) * G * 2;
-            for (int cc = 0; cc < nSplit; cc++) M = fmaxf(M, wtLoad(ml + 2 * cc));
-            for (int cc = 0; cc < nSplit; cc++) {
-                const float mc = wtLoad(ml + 2 * cc);
-                const float w = (M == -INFINITY || mc == -INFINITY) ? 0.f : __expf(mc - M);
-                wts[tid * nSplit + cc] = w;
-                L += w * wtLoad(ml + 2 * cc + 1);
-            }
-        }
-        tot[tid] = L;
-    }
-    __syncthreads();
-    for (int i = tid; i < nCol * (HS / 4); i += kPfThreads) {
-        const int cl = i / (HS / 4), d = (i % (HS / 4)) * 4;
-        const int r = b0 + cl / kvMul, hd = g * kvMul + cl % kvMul;
-        if (r >= nRows) continue;
-        const float *po = a.partO + ((size_t)r * a.nHeads0 + hd) * G * HS + d;
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int cc = 0; cc < nSplit; cc++) {
-            const float w = wts[cl * nSplit + cc];
-            const float *x = po + (size_t)cc * HS;
-            acc[0] += w * wtLoad(x); acc[1] += w * wtLoad(x + 1); acc[2] += w * wtLoad(x + 2); acc[3] += w * wtLoad(x + 3);
-        }
-        const float il = tot[cl] > 0.f ? 1.0f / tot[cl] : 0.f;
-        const float v[4] = {acc[0] * il, acc[1] * il, acc[2] * il, acc[3] * il};
-        writeOut(r, hd, d, v);
-    }
 }
 
 template <int HS>
@@ -426,8 +335,14 @@ int attnPrefillChunkKeys(const AttnArgs &a, int gridX) {  // as attnPrefillF32Ke
     return !a.kvBf16 && gridX < 256 ? kPfChunkF32Small : kPfChunk;
 }
 
+std::string attnPrefillKernelName(const AttnArgs &a) {
+    if (a.kvFp8) return attnPrefillFp8KernelName(a);
+    if (attnPrefillDmaSupported(a)) return "attnPrefillDmaKernel<" + std::to_string(a.kvMul) + ">";
+    return (a.kvBf16 ? "attnPrefillKernel<" : "attnPrefillF32Kernel<") + std::to_string(a.hs) + ">";
+}
+
 const char *attnPrefillRefusal(const AttnArgs &a) {
-    if (a.kvFp8) return "launchAttentionPrefill: no prefill kernel for fp8 KV caches (prompt rows take launchAttentionFp8)";
+    if (a.kvFp8) return attnPrefillFp8Refusal(a);  // attn_fp8.hip
     if (attnPrefillDmaSupported(a)) return attnPrefillDmaRefusal(a);
     if (!attnPrefillSupported(a.hs, a.kvMul, a.kvBf16 != 0) || a.nHeads0 % a.kvMul)
         return "launchAttentionPrefill: head size 64 / 128 and a power-of-two GQA group <= 16";
@@ -439,7 +354,10 @@ const char *attnPrefillRefusal(const AttnArgs &a) {
 }
 
 void launchAttentionPrefill(const AttnArgs &a, int nRows, hipStream_t s) {
-    if (a.kvFp8) throw Error(attnPrefillRefusal(a));
+    if (a.kvFp8) {  // attn_fp8.hip
+        launchAttentionPrefillFp8(a, nRows, s);
+        return;
+    }
     if (attnPrefillDmaSupported(a)) {  // LDS-DMA staged kernel (attn_mfma.hip)
         launchAttentionPrefillDma(a, nRows, s);
         return;

@@ -53,6 +53,10 @@ class HipEngine : public Backend {
         (void)rows, (void)maxPos;
         return "";
     }
+    // The attention kernel of a batched forward of `rows` rows of one slot whose longest row is at
+    // position maxPos: the prefill kernel's instance name when the forward takes one (the cache
+    // type's minimum context included), else what decodeAttnKernel returns.
+    virtual std::string prefillAttnKernel(int rows, int maxPos) const { return decodeAttnKernel(rows, maxPos); }
     virtual int fusedGridMax() const { return 0; }
     // Tensor parallel: a batched forward of n rows all-reduces its wo / w2 tiles inside the GEMM
     // epilogues (no separate all-reduce / norm kernels).
@@ -83,10 +87,11 @@ double benchGemmQ40(int rows, int n, int M, int epi, int copies, int iters,
                     std::vector<unsigned long long> *trace = nullptr);
 // Micro-benchmark of the decode attention kernel (bf16 or f32 KV, Q80 output): `copies` KV caches
 // cycled through a graph of `iters` launches, every row at position `pos`. Returns microseconds per
-// launch.
+// launch. rowBlock 1 / 2: the B rows are one prompt block instead, positions pos - B + 1 .. pos of one
+// slot with f16 output, through launchAttentionPrefill (1) or row by row through launchAttention (2).
 double benchAttention(int nHeads0, int kvMul, int hs, int seqLen, int pos, int B, int copies, int iters,
                       std::vector<unsigned long long> *trace = nullptr, bool kvBf16 = true,
-                      bool kvFp8 = false);
+                      bool kvFp8 = false, int rowBlock = 0);
 // Microseconds per device-to-device hipMemcpyAsync of `bytes` (the prefix copy's yardstick).
 double benchMemcpyD2D(size_t bytes, int iters);
 // Check a transport on the engine's separate-collective schedule (per layer Q80-rounded

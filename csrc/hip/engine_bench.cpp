@@ -241,12 +241,13 @@ double benchGemmQ80w(int rows, int n, int M, bool f32, int fetch, int copies, in
 }
 
 double benchAttention(int nHeads0, int kvMul, int hs, int seqLen, int pos, int B, int copies, int iters,
-                      std::vector<unsigned long long> *trace, bool kvBf16, bool kvFp8) {
+                      std::vector<unsigned long long> *trace, bool kvBf16, bool kvFp8, int rowBlock) {
     DL_CHECK(kvMul >= 1 && nHeads0 % kvMul == 0 && pos >= 0 && pos < seqLen && B >= 1, "bad attention bench shape");
+    DL_CHECK(rowBlock >= 0 && rowBlock <= 2 && (!rowBlock || (pos + 1 >= B && !trace)), "bad attention bench row block");
     Scratch sc;
     hipStream_t s = sc.s;
     const int kv0 = nHeads0 / kvMul * hs, q0 = nHeads0 * hs;
-    const size_t kvElems = (size_t)B * seqLen * kv0;  // one slot per row
+    const size_t kvElems = (size_t)(rowBlock ? 1 : B) * seqLen * kv0;  // one slot per row, or one for the block
     std::vector<float *> kc(copies), vc(copies);
     // bf16 pairs of small values, f32, or four e4m3 bytes per word
     const size_t kvWords = kvElems * hipk::kvElemBytes(kvBf16, kvFp8) / 4;
@@ -264,7 +265,7 @@ double benchAttention(int nHeads0, int kvMul, int hs, int seqLen, int pos, int B
     float *q = sc.alloc<float>((size_t)B * q0);
     hipk::launchFillF32Uniform(q, (size_t)B * q0, 1.f, 3, s);
     std::vector<int> hp(B), hsl(B);
-    for (int b = 0; b < B; b++) hp[b] = pos, hsl[b] = b;
+    for (int b = 0; b < B; b++) hp[b] = rowBlock ? pos - B + 1 + b : pos, hsl[b] = rowBlock ? 0 : b;
     hipk::AttnArgs a;
     a.q = q;
     a.ldq = q0;
@@ -280,8 +281,12 @@ double benchAttention(int nHeads0, int kvMul, int hs, int seqLen, int pos, int B
     a.chunkMin = hipk::attnChunkMin();
     a.partO = sc.alloc<float>((size_t)B * nHeads0 * a.splitGrid * hs);
     a.partML = sc.alloc<float>((size_t)B * nHeads0 * a.splitGrid * 2);
-    a.outQ = sc.alloc<int8_t>((size_t)B * q0);
-    a.outS = sc.alloc<float2>((size_t)B * q0 / 32);
+    if (rowBlock) {  // a batched forward's output
+        a.outH = reinterpret_cast<_Float16 *>(sc.alloc<uint16_t>((size_t)B * q0));
+    } else {
+        a.outQ = sc.alloc<int8_t>((size_t)B * q0);
+        a.outS = sc.alloc<float2>((size_t)B * q0 / 32);
+    }
     a.ldOut = q0;
     a.kvBf16 = kvBf16 ? 1 : 0;
     a.kvFp8 = kvFp8 ? 1 : 0;
@@ -290,7 +295,8 @@ double benchAttention(int nHeads0, int kvMul, int hs, int seqLen, int pos, int B
     auto launch = [&](int c) {
         a.kcache = kc[c % copies];
         a.vcache = vc[c % copies];
-        hipk::launchAttention(a, B, s);
+        if (rowBlock == 1) hipk::launchAttentionPrefill(a, B, s);
+        else hipk::launchAttention(a, B, s);
     };
     const double us = timeGraphUs(s, iters, launch);
     if (trace) {  // one more (eager) launch with per-workgroup stamps (MFMA decode kernel)

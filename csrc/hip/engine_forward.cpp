@@ -39,6 +39,26 @@ const CtxBucket &HipEngineImpl::bucketFor(int maxPos) const {
     return buckets_.back();
 }
 
+// f32 caches: the f32 MFMA prefill kernel from 128 keys on; below, the per-row decode attention
+// is faster (a 32-row chunk at positions 0-63: eval 0.0957 vs 0.0993 ms/token; crossover ~135
+// keys from the 4k-prompt slopes, profiles/r6_decode.md). DL_PREFILL_F32_MIN overrides.
+// fp8 caches: no floor. attnPrefillFp8Kernel beats the row-by-row decode kernel from 64 keys up (64 rows
+// ending at 64 / 128 / 320 / 1024 keys: 7.3 / 9.9 / 25.5 / 34.7 us vs 12.9 / 13.0 / 33.0 / 63.7) except for
+// 64-row blocks whose one unsplit chunk has 193-256 keys (15.4 vs 13.1 us at 256, a tie at 192; 256 rows
+// at 256 keys: 15.6 vs 48.2), which a minimum length cannot single out (profiles/kv_fp8.md).
+// DL_PREFILL_FP8_MIN is the A/B switch: a value above the context keeps prompt rows on the decode kernel.
+bool HipEngineImpl::prefillLongEnough(int maxLen) const {
+    static const int f32Min = [] {
+        const char *e = std::getenv("DL_PREFILL_F32_MIN");
+        return e ? std::atoi(e) : 128;
+    }();
+    static const int fp8Min = [] {
+        const char *e = std::getenv("DL_PREFILL_FP8_MIN");
+        return e ? std::atoi(e) : 0;
+    }();
+    return maxLen >= (kv_ == KvDtype::F32 ? f32Min : kvFp8() ? fp8Min : 0);
+}
+
 void HipEngineImpl::setInputs(int n, const int *tokens, const int *positions, const int *slots, const SampleSpec *specs,
                               int ahead, const float *procRows, const hipk::LogitFilterRow *filterRows) {
     DL_CHECK(n >= 1 && (u32)n <= cfg_.maxBatch, "batch size out of range");
@@ -71,17 +91,10 @@ void HipEngineImpl::setInputs(int n, const int *tokens, const int *positions, co
     prefillOk_ = !invariant_ && hipk::attnPrefillSupported(plan_.headSize, plan_.kvMul, kvBf16(), kvFp8());
     const int rpb = prefillOk_ ? hipk::attnPrefillRowsPerBlock(plan_.kvMul) : 1;
     for (int b = 0; prefillOk_ && b < n; b++) prefillOk_ = slots[b] == slots[b - b % rpb];
-    // f32 caches: the f32 MFMA prefill kernel from 128 keys on; below, the per-row decode attention
-    // is faster (a 32-row chunk at positions 0-63: eval 0.0957 vs 0.0993 ms/token; crossover ~135
-    // keys from the 4k-prompt slopes, profiles/r6_decode.md). DL_PREFILL_F32_MIN overrides.
-    if (prefillOk_ && kv_ == KvDtype::F32) {
-        static const int f32Min = [] {
-            const char *e = std::getenv("DL_PREFILL_F32_MIN");
-            return e ? std::atoi(e) : 128;
-        }();
+    if (prefillOk_) {
         int mx = 0;
         for (int b = 0; b < n; b++) mx = std::max(mx, positions[b] + 1);
-        prefillOk_ = mx >= f32Min;
+        prefillOk_ = prefillLongEnough(mx);
     }
     if (specs) {
         static_assert(sizeof(SampleSpec) == 4 * sizeof(float), "spec layout");
@@ -262,6 +275,22 @@ std::string HipEngineImpl::decodeAttnKernel(int rows, int maxPos) const {
     a.mfma = attnLongFor(rows, maxPos) ? 1 : 0;
     if (kvFp8()) return hipk::attnFp8KernelName(a);  // every context length
     return hipk::attnUsesMfma(a) ? hipk::attnMfmaKernelName(a) : "attnKernel";
+}
+
+std::string HipEngineImpl::prefillAttnKernel(int rows, int maxPos) const {
+    DL_CHECK(rows >= 1 && (u32)rows <= cfg_.maxBatch && maxPos >= 0 && (u32)maxPos < h_.seqLen, "prefillAttnKernel: rows / position");
+    // setInputs' rule for rows of one slot, and enqueueAttention's (batched forwards only)
+    if (invariant_ || !batchedPath(rows) || !hipk::attnPrefillSupported(plan_.headSize, plan_.kvMul, kvBf16(), kvFp8()) ||
+        !prefillLongEnough(maxPos + 1))
+        return decodeAttnKernel(rows, maxPos);
+    hipk::AttnArgs a;
+    a.nHeads0 = plan_.nHeads0;
+    a.kvMul = plan_.kvMul;
+    a.hs = plan_.headSize;
+    a.seqLen = h_.seqLen;
+    a.kvBf16 = kvBf16() ? 1 : 0;
+    a.kvFp8 = kvFp8() ? 1 : 0;
+    return hipk::attnPrefillKernelName(a);
 }
 
 // The fused attention block of a single decode row (kernels.h AttnBlockArgs): qkv GEMV +

@@ -109,6 +109,7 @@ class HipEngineImpl : public HipEngine {
     bool prenorm() const override { return prenormOn_; }
     std::vector<unsigned long long> traceAttnBlock(int token, int pos, int slot, int layer) override;
     std::string decodeAttnKernel(int rows, int maxPos) const override;
+    std::string prefillAttnKernel(int rows, int maxPos) const override;
     int fusedGridMax() const override { return fusedGridMax_; }
     bool tpBatchedFused(int n) const override { return plan_.nRanks > 1 && batchedPath(n) && fuseNorm(n); }
 
@@ -297,6 +298,8 @@ class HipEngineImpl : public HipEngine {
     int w2Pro() const { return hQ80_ ? hipk::PRO_GLOBAL : hipk::PRO_RESNORM; }
     const float *nextNormW(u32 l) const { return l + 1 < h_.nLayers ? layers_[l + 1].rmsAtt : rmsFinal_; }
     hipk::AttnArgs attnArgs(const DevLayer &L, bool bat) const;
+    // a forward whose longest row has maxLen keys is long enough for this cache type's prefill kernel
+    bool prefillLongEnough(int maxLen) const;
     hipk::AttnBlockArgs attnBlockArgs(const DevLayer &L, u32 l, int cur) const;
     void setupAttnBlock();
     void resetAttnBlockState();

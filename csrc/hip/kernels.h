@@ -432,15 +432,22 @@ std::string attnMfmaKernelName(const AttnArgs &a);
 bool attnF32MfmaSupported(const AttnArgs &a);
 const char *attnF32MfmaRefusal(const AttnArgs &a);
 void launchAttentionF32Mfma(const AttnArgs &a, int B, hipStream_t s);
-// Decode attention over fp8 (e4m3) caches (attn_fp8.hip): head size 128 / 64, kvMul 1/2/4/8, every
-// context length. launchAttention routes kvFp8 launches here; there is no VALU kernel, no fused
-// attention block and no prefill kernel for fp8 caches (attnPrefillSupported is false: prompt rows take
-// this kernel row by row).
+// Attention over fp8 (e4m3) caches (attn_fp8.hip): head size 128 / 64, kvMul 1/2/4/8, every context
+// length. launchAttention routes kvFp8 launches to the decode kernel; there is no VALU kernel and no
+// fused attention block for fp8 caches.
 bool attnFp8Supported(const AttnArgs &a);
 const char *attnFp8Refusal(const AttnArgs &a);
 std::string attnFp8KernelName(const AttnArgs &a);  // "attnDecodeFp8Kernel<KM,HS>"
 void launchAttentionFp8(const AttnArgs &a, int B, hipStream_t s);
-const char *attnPrefillRefusal(const AttnArgs &a);     // launchAttentionPrefill, either kernel family
+// Prefill rows of fp8 caches (attnPrefillFp8Kernel, the row-block split of the other prefill kernels):
+// launchAttentionPrefill routes kvFp8 launches here.
+const char *attnPrefillFp8Refusal(const AttnArgs &a);
+std::string attnPrefillFp8KernelName(const AttnArgs &a);  // "attnPrefillFp8Kernel<KM,HS>"
+void launchAttentionPrefillFp8(const AttnArgs &a, int nRows, hipStream_t s);
+const char *attnPrefillRefusal(const AttnArgs &a);     // launchAttentionPrefill, every kernel family
+// the instance launchAttentionPrefill runs: "attnPrefillDmaKernel<KM>", "attnPrefillKernel<HS>",
+// "attnPrefillF32Kernel<HS>" or "attnPrefillFp8Kernel<KM,HS>"
+std::string attnPrefillKernelName(const AttnArgs &a);
 // Prefill rows with LDS-DMA staged K / V (attn_mfma.hip; other shapes take the register-staged
 // kernels.hip kernel): bf16 cache, head size 128, kvMul 1..16.
 bool attnPrefillDmaSupported(const AttnArgs &a);
@@ -488,8 +495,8 @@ void launchAttnBlock(const AttnBlockArgs &a, bool tp, hipStream_t s);
 // el < n (n <= x.stride), through the transport of the fused exchange; every rank must call it.
 void launchTpSelfTest(const TpXchg &x, float *out, int n, float val, hipStream_t s);
 
-// Prefill rows on MFMA (bf16 caches): blocks of attnPrefillRowsPerBlock(kvMul) consecutive rows
-// must share one slot (positions arbitrary, causal per row); counters >= blocks x KV heads.
+// Prefill rows on MFMA (bf16, f32 and fp8 caches): blocks of attnPrefillRowsPerBlock(kvMul) consecutive
+// rows must share one slot (positions arbitrary, causal per row); counters >= blocks x KV heads.
 void launchAttentionPrefill(const AttnArgs &a, int nRows, hipStream_t s);
 int attnPrefillRowsPerBlock(int kvMul);
 bool attnPrefillSupported(int hs, int kvMul, bool kvBf16, bool kvFp8 = false);
@@ -515,7 +522,7 @@ __host__ __device__ __forceinline__ void attnSplit(int len, int splitGrid, int &
 }
 // Key split of a prefill row block whose longest row has maxLen keys: chunks of ~chunkKeys keys, at
 // most splitGrid and hs / 2 of them (the combine keeps 64 columns x nSplit weights in LDS), ch a whole
-// number of 32-key tiles. The three prefill kernels and the host's plan of a launch share this rule.
+// number of 32-key tiles. The prefill kernels and the host's plan of a launch share this rule.
 constexpr int kAttnPrefillChunk = 256, kAttnPrefillTile = 32;
 __host__ __device__ __forceinline__ void attnPrefillSplit(int maxLen, int splitGrid, int hs, int chunkKeys, int &nSplit,
                                                           int &ch) {

@@ -964,10 +964,11 @@ std::vector<float> attention(const std::vector<float> &q, const std::vector<floa
                              const std::vector<int> &slot, bool kvBf16, int impl, bool kvFp8) {
     const int B = (int)pos.size();
     DL_CHECK(B >= 1 && slot.size() == pos.size(), "attention rows");
-    DL_CHECK(!kvFp8 || impl == 0 || impl == 4, "attention: fp8 caches take impl \"auto\" or \"fp8\" (one kernel)");
+    DL_CHECK(!kvFp8 || impl == 0 || impl == 1 || impl == 4, "attention: fp8 caches take impl \"auto\", \"prefill\" or \"fp8\"");
     DL_CHECK(impl != 4 || kvFp8, "attention: impl \"fp8\" needs kv_dtype=\"fp8\"");
     if (impl == 1) {
-        DL_CHECK(hipk::attnPrefillSupported(hs, kvMul, kvBf16), "prefill attention: head size 64 / 128, power-of-two GQA group");
+        DL_CHECK(hipk::attnPrefillSupported(hs, kvMul, kvBf16, kvFp8),
+                 "prefill attention: head size 64 / 128, power-of-two GQA group (fp8 caches: kvMul 1, 2, 4 or 8)");
         const int rpb = hipk::attnPrefillRowsPerBlock(kvMul);
         for (int b = 0; b < B; b++) DL_CHECK(slot[b] == slot[b - b % rpb], "prefill row blocks must share a slot");
     }
@@ -1062,8 +1063,9 @@ AttnGeom attnGeom(const AttnLaunchArgs &l) {
     DL_CHECK(l.q.size() == (size_t)B * g.ldq && l.k.size() == cacheElems && l.v.size() == cacheElems, "attention sizes");
     for (int b = 0; b < B; b++)
         DL_CHECK(l.pos[b] >= 0 && l.pos[b] < l.seqLen && l.slot[b] >= 0 && l.slot[b] < l.nSlots, "attention row out of range");
-    DL_CHECK(l.kvFp8 ? (l.kernel == ATTN_AUTO || l.kernel == ATTN_FP8) : l.kernel != ATTN_FP8,
-             "attention: fp8 caches take kernel \"auto\" or \"fp8\", other caches any kernel but \"fp8\"");
+    DL_CHECK(l.kvFp8 ? (l.kernel == ATTN_AUTO || l.kernel == ATTN_FP8 || (l.kernel == ATTN_PREFILL && l.mode == ATTN_PREFILL_ROWS))
+                     : l.kernel != ATTN_FP8,
+             "attention: fp8 caches take kernel \"auto\", \"fp8\" or (prefill rows) \"prefill\", other caches any kernel but \"fp8\"");
     DL_CHECK(l.kernel >= ATTN_AUTO && l.kernel <= ATTN_FP8 && (l.mode == ATTN_DECODE || l.mode == ATTN_PREFILL_ROWS),
              "attention kernel / mode");
     g.prefill = l.mode == ATTN_PREFILL_ROWS;
@@ -1125,14 +1127,12 @@ AttnLaunchPlan attentionPlan(const AttnLaunchArgs &l) {
     p.splitGrid = a.splitGrid;
     p.chunkMax = a.chunkMax;
     p.shortLen = a.shortLen;
-    const std::string hsS = std::to_string(a.hs), kmS = std::to_string(a.kvMul);
+    const std::string hsS = std::to_string(a.hs);
     if (g.prefill) {
         if (const char *why = hipk::attnPrefillRefusal(a)) throw Error(why);
         const int rpb = hipk::attnPrefillRowsPerBlock(a.kvMul);
         for (int b = 0; b < g.B; b++) DL_CHECK(l.slot[b] == l.slot[b - b % rpb], "prefill row blocks must share a slot");
-        p.kernel = hipk::attnPrefillDmaSupported(a) ? "attnPrefillDmaKernel<" + kmS + ">"
-                   : a.kvBf16                       ? "attnPrefillKernel<" + hsS + ">"
-                                                    : "attnPrefillF32Kernel<" + hsS + ">";
+        p.kernel = hipk::attnPrefillKernelName(a);
         p.grid[0] = g.nKv * ((g.B + rpb - 1) / rpb);
         p.grid[1] = a.splitGrid;
         p.grid[2] = 1;

@@ -201,7 +201,7 @@ std::vector<float> attention(const std::vector<float> &q, const std::vector<floa
                              const std::vector<int> &slot, bool kvBf16, int impl = 0, bool kvFp8 = false);
 // attention impl: 0 = launchAttention's choice, 1 = MFMA prefill kernel, 2 = VALU decode kernel,
 // 3 = MFMA decode kernel, 4 = the fp8 decode kernel. kvFp8: the caches are quantised on the host by
-// the append rule, e4m3fn(clamp(x, -448, 448)); only impl 0 and 4 apply (fp8 caches have one kernel)
+// the append rule, e4m3fn(clamp(x, -448, 448)); impl 0, 1 and 4 apply (one decode and one prefill kernel)
 
 // One attention launch as the engine's attnArgs / enqueueAttention set it up (engine_forward.cpp),
 // which ops::attention above cannot: a page table, the single-row split geometry, the f16 and Q80

@@ -1567,13 +1567,15 @@ PYBIND11_MODULE(_C, m) {
           "us per pass over `tokens` rows: above 64 tokens one gemmQ80wWideKernel launch (wide) or the chunked "
           "narrow launches of <= 64 (wide = false)");
     m.def("bench_attention",
-          [](int nh, int kvm, int hs, int seq, int pos, int B, int copies, int iters, bool kvBf16, bool kvFp8) {
-              return benchAttention(nh, kvm, hs, seq, pos, B, copies, iters, nullptr, kvBf16, kvFp8);
+          [](int nh, int kvm, int hs, int seq, int pos, int B, int copies, int iters, bool kvBf16, bool kvFp8, int rowBlock) {
+              return benchAttention(nh, kvm, hs, seq, pos, B, copies, iters, nullptr, kvBf16, kvFp8, rowBlock);
           },
           py::arg("n_heads0"), py::arg("kv_mul"), py::arg("head_size"), py::arg("seq_len"), py::arg("pos"),
           py::arg("batch") = 1, py::arg("copies") = 32, py::arg("iters") = 200, py::arg("kv_bf16") = true,
-          py::arg("kv_fp8") = false,
-          py::call_guard<py::gil_scoped_release>());
+          py::arg("kv_fp8") = false, py::arg("row_block") = 0,
+          py::call_guard<py::gil_scoped_release>(),
+          "row_block 1 / 2: the rows are one prompt block (positions pos - batch + 1 .. pos of one slot, f16 output) "
+          "through the prefill launcher (1) or row by row through the decode launcher (2)");
     m.def("bench_memcpy_d2d", &benchMemcpyD2D, py::arg("bytes"), py::arg("iters") = 20,
           py::call_guard<py::gil_scoped_release>());
     m.def("trace_gemm_q40",
@@ -1802,6 +1804,8 @@ PYBIND11_MODULE(_C, m) {
              },
              py::arg("token"), py::arg("pos"), py::arg("slot") = 0, py::arg("layer") = 1)
         .def("decode_attn_kernel", [](const PyHipEngine &e, int rows, int maxPos) { return e.engine->decodeAttnKernel(rows, maxPos); },
+             py::arg("rows"), py::arg("max_pos"))
+        .def("prefill_attn_kernel", [](const PyHipEngine &e, int rows, int maxPos) { return e.engine->prefillAttnKernel(rows, maxPos); },
              py::arg("rows"), py::arg("max_pos"))
         .def_property_readonly("fused_grid_max",[](const PyHipEngine &e) { return e.engine->fusedGridMax(); })
         .def_property_readonly("kv_pages_free", [](const PyHipEngine &e) { return e.engine->kvPagesFree(); })

@@ -223,7 +223,8 @@ def attention(q, k_cache, v_cache, n_heads0: int, kv_mul: int, head_size: int, p
     launcher's choice, MFMA for bf16 caches of >= 1024 positions). "mfma" takes kv_mul 1/2/4/8 and
     head size 128 on a bf16 cache, head size 128 or 64 on an f32 cache (attnDecodeF32MfmaKernel).
     kv_dtype "" (follow kv_bf16) / "f32" / "bf16" / "fp8"; "fp8": the caches are quantised on the host by
-    the append rule and attnDecodeFp8Kernel runs (impl "auto" or "fp8"; there is no other fp8 kernel)."""
+    the append rule and attnDecodeFp8Kernel runs (impl "auto" or "fp8"), or attnPrefillFp8Kernel with
+    prefill=True (impl "prefill")."""
     kv_bf16, kv_fp8 = _kv(kv_bf16, kv_dtype)
     n_slots, seq_len, _ = k_cache.shape
     code = {"auto": 0, "prefill": 1, "valu": 2, "mfma": 3, "fp8": 4}["prefill" if prefill else impl]
@@ -255,8 +256,8 @@ def attention_launch(q, k_cache, v_cache, n_heads0: int, kv_mul: int, head_size:
     values or the Q80 codes), "scales" [B, q0 / 32, 2] (Q80: d, sum of codes)}. plan_only: just the
     plan and the refusals, no device needed. kv_dtype "" (follow kv_bf16) / "f32" / "bf16" / "fp8";
     "fp8": the caches (and the poison rows) are quantised on the host by the append rule,
-    e4m3fn(clamp(x, -448, 448)), and attnDecodeFp8Kernel<KM,HS> runs (kernel "auto" or "fp8"; decode
-    rows only: fp8 caches have no prefill kernel)."""
+    e4m3fn(clamp(x, -448, 448)), and attnDecodeFp8Kernel<KM,HS> runs on decode rows (kernel "auto" or
+    "fp8"), attnPrefillFp8Kernel<KM,HS> on prefill rows (kernel "auto" or "prefill")."""
     kv_bf16, kv_fp8 = _kv(kv_bf16, kv_dtype)
     n_slots, seq_len, _ = k_cache.shape
     po = [] if page_of is None else [int(p) for p in np.asarray(page_of).reshape(-1)]
