@@ -216,7 +216,7 @@ static void usage() {
                  "                                      chat keeps its one session's KV across turns either way)\n"
                  "  --metrics <file|->                  (JSON line per forward)  --profile 1  (GPU kernel table)\n"
                  "  --synthetic {llama3_2_1b|llama3_1_8b|llama3_3_70b|llama3_1_405b}  (random-init weights)\n"
-                 "  --synthetic-weights {q40|q80}  (weight type of --synthetic, default q40)\n"
+                 "  --synthetic-weights {q40|q80|f16}  (weight type of --synthetic, default q40; f16 runs on f32 buffers)\n"
                  "  --net-turbo {0|1} --gpu-segments <a:b>  (accepted for compatibility)\n");
 }
 

@@ -164,7 +164,8 @@ const char *tensorKindName(TensorKind k) {
 
 std::vector<TensorInfo> buildTensorTable(const ModelHeader &h) {
     if (h.nExperts > 0) throw Error("Mixture-of-experts models are not supported by this runtime");
-    if (h.weightType != FloatType::F32 && h.weightType != FloatType::Q40 && h.weightType != FloatType::Q80)
+    if (h.weightType != FloatType::F32 && h.weightType != FloatType::F16 && h.weightType != FloatType::Q40 &&
+        h.weightType != FloatType::Q80)
         throw Error(std::string("Unsupported weight type: ") + floatTypeName(h.weightType));
     std::vector<TensorInfo> t;
     u64 off = (u64)h.headerSize;

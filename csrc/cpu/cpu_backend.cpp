@@ -137,6 +137,8 @@ class CpuBackend : public Backend {
             throw Error("This version supports only Q40 weights with Q80 sync type");
         if (h_.weightType == FloatType::F32 && q80_)
             throw Error("F32 weights require --buffer-float-type f32");
+        if (h_.weightType == FloatType::F16 && q80_)
+            throw Error("F16 weights require --buffer-float-type f32");
         load();
         rope_ = buildRopeTable(h_);
         const u64 kvPerLayer = (u64)cfg_.nSlots * h_.seqLen * plan_.kv0;
@@ -217,6 +219,19 @@ class CpuBackend : public Backend {
         m.data = m.owned.data();
     }
 
+    // F16 weights are widened to f32 once at load (exact): from here on the matrix is an F32 one.
+    void widenF16(Mat &m) {
+        if (m.type != FloatType::F16) return;
+        const u64 count = (u64)m.rows * m.cols;
+        std::vector<u8> wide(count * 4);
+        const u16 *src = (const u16 *)m.data;
+        float *dst = (float *)wide.data();
+        for (u64 i = 0; i < count; i++) dst[i] = f16ToF32(src[i]);
+        m.owned.swap(wide);
+        m.data = m.owned.data();
+        m.type = FloatType::F32;
+    }
+
     void load() {
         const ShardPlan &p = plan_;
         layers_.resize(h_.nLayers);
@@ -229,12 +244,14 @@ class CpuBackend : public Backend {
             makeMat(L.w1, file_->find(TensorKind::W1, l), true, p.hiddenStart(), p.hidden0);
             makeMat(L.w2, file_->find(TensorKind::W2, l), false, p.hiddenStart(), p.hidden0);
             makeMat(L.w3, file_->find(TensorKind::W3, l), true, p.hiddenStart(), p.hidden0);
+            for (Mat *m : {&L.wq, &L.wk, &L.wv, &L.wo, &L.w1, &L.w2, &L.w3}) widenF16(*m);
             L.rmsAtt = (const float *)file_->ptr(file_->find(TensorKind::RMS_ATT, l));
             L.rmsFfn = (const float *)file_->ptr(file_->find(TensorKind::RMS_FFN, l));
         }
         emb_ = (const float *)file_->ptr(file_->find(TensorKind::EMBEDDING, -1));
         rmsFinal_ = (const float *)file_->ptr(file_->find(TensorKind::RMS_FINAL, -1));
         makeMat(wcls_, file_->find(TensorKind::WCLS, -1), true, p.vocabStart(), p.vocab0);
+        widenF16(wcls_);
     }
 
     void setAct(Act &a, const float *x, u32 n) {

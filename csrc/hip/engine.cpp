@@ -40,10 +40,12 @@ HipEngineImpl::HipEngineImpl(const EngineConfig &cfg, DeviceComm *comm) : cfg_(c
         case FloatType::Q40: wkind_ = WeightKind::Q40; break;
         case FloatType::Q80: wkind_ = WeightKind::Q80; break;
         case FloatType::F32: wkind_ = WeightKind::F32; break;
+        case FloatType::F16: wkind_ = WeightKind::F16; break;
         default: throw Error("unsupported weight type");
     }
     if (blocks() && cfg.bufferType != FloatType::Q80)
         throw Error("This version supports only Q40 weights with Q80 sync type");
+    if (f16w() && cfg.bufferType == FloatType::Q80) throw Error("F16 weights require --buffer-float-type f32");
     DL_CHECK(h_.headSize() == 64 || h_.headSize() == 128, "GPU kernels support head size 64 or 128");
     DL_CHECK(cfg.maxBatch >= 1 && cfg.nSlots >= 1, "maxBatch/nSlots");
     DL_CHECK(cfg.maxBatch <= kKeyMaxRows, "maxBatch: more rows than a graph key holds");

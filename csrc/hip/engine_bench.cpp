@@ -240,6 +240,88 @@ double benchGemmQ80w(int rows, int n, int M, bool f32, int fetch, int copies, in
     });
 }
 
+// F16-weight GEMV (gemvF16wKernel), or with f32 = true the F32 GEMV (gemvKernel) on the same shape and
+// harness, on synthetic weights: `copies` matrices cycled through a graph of `iters` launches.
+double benchGemvF16w(int rows, int n, int pro, int epi, int B, int lanes, int passes, bool f32, int copies, int iters) {
+    DL_CHECK(epi == hipk::EPI_STORE && rows > 0 && n % 32 == 0 && copies >= 1, "bad F16 gemv bench shape");
+    Scratch sc;
+    hipStream_t s = sc.s;
+    std::vector<void *> w(copies);
+    for (int c = 0; c < copies; c++) {
+        if (f32) {
+            w[c] = sc.allocRaw<float>((size_t)rows * n);
+            hipk::launchFillF32Uniform((float *)w[c], (size_t)rows * n, 1e-2f, 77 + c, s);
+        } else {
+            w[c] = sc.allocRaw<_Float16>((size_t)rows * n);
+            hipk::launchFillF16Uniform((_Float16 *)w[c], (size_t)rows * n, 1e-2f, 77 + c, s);
+        }
+    }
+    float *x = sc.allocRaw<float>((size_t)B * n), *nw = sc.allocRaw<float>(n);
+    hipk::launchFillF32Uniform(x, (size_t)B * n, 1.f, 1, s);
+    hipk::launchFillF32Const(nw, n, 1.f, s);
+    hipk::GemvArgs a;
+    a.rows = rows;
+    a.n = n;
+    a.lanes = lanes;  // 0: each kernel's own rule
+    a.passes = passes > 0 ? passes : hipk::gemvDefaultPasses(n, rows, B, false, epi);
+    a.in = x;
+    a.ldIn = n;
+    a.normW = nw;
+    a.out = sc.allocRaw<float>((size_t)B * rows);
+    a.ldOut = rows;
+    return timeGraphUs(s, iters, [&](int c) {
+        if (f32) {
+            a.wf = (const float *)w[c % copies];
+            hipk::launchGemv(a, B, pro, epi, false, s);
+        } else {
+            a.wh = (const _Float16 *)w[c % copies];
+            hipk::launchGemvF16w(a, B, pro, epi, s);
+        }
+    });
+}
+
+// Batched GEMM (1..64 tokens, EPI_STORE) on F16 weights (gemmF16wKernel) or, f32 = true, on F32 weights
+// (gemmF32Kernel), same shape and harness.
+double benchGemmF16w(int rows, int n, int M, bool f32, int copies, int iters) {
+    DL_CHECK(M >= 1 && M <= hipk::kGemmF32MaxTokens && hipk::gemmSupported(n) && rows % 64 == 0 && copies >= 1,
+             "bad gemm bench shape");
+    Scratch sc;
+    hipStream_t s = sc.s;
+    std::vector<void *> w(copies);
+    for (int c = 0; c < copies; c++) {
+        if (f32) {
+            w[c] = sc.allocRaw<float>((size_t)rows * n);
+            hipk::launchFillF32Uniform((float *)w[c], (size_t)rows * n, 1e-2f, 77 + c, s);
+        } else {
+            w[c] = sc.allocRaw<_Float16>((size_t)rows * n);
+            hipk::launchFillF16Uniform((_Float16 *)w[c], (size_t)rows * n, 1e-2f, 77 + c, s);
+        }
+    }
+    _Float16 *x = sc.alloc<_Float16>((size_t)hipk::kGemmF32MaxTokens * n);
+    hipk::launchFillF16Uniform(x, (size_t)hipk::kGemmF32MaxTokens * n, 1.f, 3, s);
+    const size_t part = hipk::gemmPartFloats(rows, n, M);
+    hipk::GemmArgs g;
+    g.e.rows = rows;
+    g.e.n = n;
+    g.e.out = sc.alloc<float>((size_t)M * rows);
+    g.e.ldOut = rows;
+    g.x = x;
+    g.M = M;
+    g.splits = hipk::gemmSplits(rows, n, M);
+    g.part = part ? sc.alloc<float>(part) : nullptr;
+    g.partFloats = part;
+    g.counters = sc.alloc<int>((size_t)rows / 64 + 1);
+    return timeGraphUs(s, iters, [&](int c) {
+        if (f32) {
+            g.e.wf = (const float *)w[c % copies];
+            hipk::launchGemmF32(g, hipk::EPI_STORE, s);
+        } else {
+            g.e.wh = (const _Float16 *)w[c % copies];
+            hipk::launchGemmF16w(g, hipk::EPI_STORE, s);
+        }
+    });
+}
+
 double benchAttention(int nHeads0, int kvMul, int hs, int seqLen, int pos, int B, int copies, int iters,
                       std::vector<unsigned long long> *trace, bool kvBf16, bool kvFp8, int rowBlock) {
     DL_CHECK(kvMul >= 1 && nHeads0 % kvMul == 0 && pos >= 0 && pos < seqLen && B >= 1, "bad attention bench shape");

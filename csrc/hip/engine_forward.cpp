@@ -160,6 +160,7 @@ hipk::GemvArgs HipEngineImpl::gemvArgs(const DevMat &m, int c0, int bc, int epi,
     a.qs = m.qs;
     a.wd = m.d;
     a.wf = m.f;
+    a.wh = m.h;
     a.rows = m.rows;
     a.n = m.n;
     a.passes = o.tp ? tpPasses(m, bc) : passesFor(m, epi, bc);
@@ -194,6 +195,8 @@ void HipEngineImpl::gemv(const DevMat &m, int n, int pro, int epi, const MatOper
         while (bc & (bc - 1)) bc &= bc - 1;  // 1, 2 or 4 rows per launch
         if (q80w())
             hipk::launchGemvQ80w(gemvArgs(m, c0, bc, epi, o), bc, pro, epi, stream_);
+        else if (f16w())
+            hipk::launchGemvF16w(gemvArgs(m, c0, bc, epi, o), bc, pro, epi, stream_);
         else
             hipk::launchGemv(gemvArgs(m, c0, bc, epi, o), bc, pro, epi, q40(), stream_);
         c0 += bc;
@@ -506,7 +509,7 @@ void HipEngineImpl::gemmBatched(const DevMat &m, int n, int epi, const MatOperan
     // pass per token tile, all tiles of a row tile on one XCD), the narrow ones <= 128 (Q40) / 64
     // (batch-invariant engines: narrow launches only, the split count of a 16-token launch for all)
     // (a width the wide kernels cannot split into their two-block stages: narrow launches too)
-    const hipk::GemmWeights kind = q40() ? hipk::GEMM_W_Q40 : q80w() ? hipk::GEMM_W_Q80 : hipk::GEMM_W_F32;
+    const hipk::GemmWeights kind = q40() ? hipk::GEMM_W_Q40 : q80w() ? hipk::GEMM_W_Q80 : f16w() ? hipk::GEMM_W_F16 : hipk::GEMM_W_F32;
     const int chunk = hipk::gemmChunkTokens(m.n, n, kind, invariant_);
     for (int c0 = 0; c0 < n; c0 += chunk) {
         const int bc = std::min(chunk, n - c0);
@@ -516,6 +519,7 @@ void HipEngineImpl::gemmBatched(const DevMat &m, int n, int epi, const MatOperan
         a.qs = m.qs;
         a.wd = m.d;
         a.wf = m.f;
+        a.wh = m.h;
         a.rows = m.rows;
         a.n = m.n;
         a.lanes = m.lanes;
@@ -568,6 +572,8 @@ void HipEngineImpl::gemmBatched(const DevMat &m, int n, int epi, const MatOperan
             hipk::launchGemmQ80wWide(g, epi, stream_);
         else if (q80w())
             hipk::launchGemmQ80w(g, epi, stream_);
+        else if (f16w())
+            hipk::launchGemmF16w(g, epi, stream_);
         else
             hipk::launchGemmF32(g, epi, stream_);
     }

@@ -37,12 +37,15 @@ namespace engine_detail {
 // The weight type of a model: every matrix of an engine has the same one. Q80 weights follow the F32
 // weights' schedule (plain launches: no fused attention block, no fused exchange, no pre-normalized
 // hand-off, no argmax tail) on Q80 activations, with kernels of their own (q80w.hip, q80w_gemm.hip).
-enum class WeightKind { F32, Q40, Q80 };
+// F16 weights follow the F32 weights' schedule unchanged (f32 activations) with the kernels of
+// f16w_inst.h and f16w_gemm.hip.
+enum class WeightKind { F32, Q40, Q80, F16 };
 
 struct DevMat {
     uint8_t *qs = nullptr;  // Q40 / Q80: tiled for `lanes` lanes per row (hipk::Q40Tiling / Q80Tiling)
     uint16_t *d = nullptr;
-    float *f = nullptr;
+    float *f = nullptr;      // F32: [rows][n] row-major
+    _Float16 *h = nullptr;   // F16: [rows][n] row-major, the file's values
     int rows = 0, n = 0, lanes = 0;
 };
 
@@ -370,8 +373,9 @@ class HipEngineImpl : public HipEngine {
     WeightKind wkind_ = WeightKind::Q40;
     bool q40() const { return wkind_ == WeightKind::Q40; }    // the fused paths
     bool q80w() const { return wkind_ == WeightKind::Q80; }
+    bool f16w() const { return wkind_ == WeightKind::F16; }
     // block-quantized weights: tiled planes, Q80 activations, two rows per GEMV lane group
-    bool blocks() const { return wkind_ != WeightKind::F32; }
+    bool blocks() const { return q40() || q80w(); }
     KvDtype kv_ = KvDtype::Bf16;  // EngineConfig::kvType()
     bool kvBf16() const { return kv_ == KvDtype::Bf16; }
     bool kvFp8() const { return kv_ == KvDtype::Fp8; }

@@ -334,7 +334,7 @@ void HipEngineImpl::stageRelease(Loader &ld) {
 // ld.rowPtr at each output row (w1/w3 interleaved row by row when `interleave`).
 void HipEngineImpl::readRows(Loader &ld, const std::vector<RowSrc> &srcs, bool interleave, u32 c0, u32 nc) {
     auto rowBytes = [&](u32 cols) {
-        return blocks() ? (u64)cols / kQBlock * (q40() ? kQ40BlockBytes : kQ80BlockBytes) : (u64)cols * 4;
+        return blocks() ? (u64)cols / kQBlock * (q40() ? kQ40BlockBytes : kQ80BlockBytes) : (u64)cols * (f16w() ? 2 : 4);
     };
     const u64 slice = rowBytes(nc);
     u64 total = 0;
@@ -374,7 +374,7 @@ size_t HipEngineImpl::matStageBytes(u32 rows, u32 n) const {
         const hipk::Q80Tiling t = hipk::q80Tiling((int)rows, (int)n, lanesFor((int)rows, (int)n));
         return t.qBytes + t.dBytes;
     }
-    if (!q40()) return (size_t)rows * n * 4;
+    if (!q40()) return (size_t)rows * n * (f16w() ? 2 : 4);
     const hipk::Q40Tiling t = hipk::q40Tiling((int)rows, (int)n, lanesFor((int)rows, (int)n));
     return t.qsBytes + t.dBytes;
 }
@@ -423,11 +423,13 @@ void HipEngineImpl::buildMat(Loader &ld, DevMat &m, const std::vector<RowSrc> &s
         stageCopy(ld, m.qs, st, t.qBytes);
         stageCopy(ld, m.d, st + t.qBytes, t.dBytes);
     } else {
-        const size_t rb = (size_t)nc * 4;
+        const size_t rb = (size_t)nc * (f16w() ? 2 : 4);  // row-major as in the file, 2- or 4-byte elements
         DL_CHECK((size_t)rows * rb <= ld.stageBytes, "staging buffer too small");
         for (int r = 0; r < rows; r++) std::memcpy(st + (size_t)r * rb, ld.rowPtr[r], rb);
-        m.f = dalloc<float>((size_t)rows * nc);
-        stageCopy(ld, m.f, st, (size_t)rows * rb);
+        void *dst;
+        if (f16w()) dst = m.h = dalloc<_Float16>((size_t)rows * nc);
+        else dst = m.f = dalloc<float>((size_t)rows * nc);
+        stageCopy(ld, dst, st, (size_t)rows * rb);
     }
     stageRelease(ld);
 }
@@ -515,6 +517,9 @@ void HipEngineImpl::synthMat(DevMat &m, int rows, int n, u64 seed, int mi, u32 l
         const hipk::Q80Tiling t = hipk::q80Tiling(rows, n, m.lanes);
         placeTiled(m, t.qBytes, t.dBytes, mi, l);
         hipk::launchFillQ80w(m.qs, m.d, t.qBytes / 16, t.dBytes / 2, 1.0f / std::sqrt(5461.0f * (float)n), seed, stream_);
+    } else if (f16w()) {  // the F32 fill's values (and variance), rounded to f16
+        m.h = dalloc<_Float16>((size_t)rows * n);
+        hipk::launchFillF16Uniform(m.h, (size_t)rows * n, std::sqrt(3.0f / (float)n), seed, stream_);
     } else {
         m.f = dalloc<float>((size_t)rows * n);
         hipk::launchFillF32Uniform(m.f, (size_t)rows * n, std::sqrt(3.0f / (float)n), seed, stream_);

@@ -243,6 +243,7 @@ struct GemvArgs {
     const uint8_t *qs = nullptr;
     const uint16_t *wd = nullptr;
     const float *wf = nullptr;
+    const _Float16 *wh = nullptr;  // F16 [rows][n] row-major (launchGemvF16w / launchGemmF16w)
     int rows = 0, n = 0;
     int passes = 1;  // row passes per workgroup (rows per WG = passes * 256 / L)
     int lanes = 0;   // lanes per row (0 = auto from n)
@@ -326,9 +327,9 @@ enum GemmKernel : int { GEMM_NARROW = 0, GEMM_L16 = 1, GEMM_WIDE = 2 };
 GemmKernel gemmKernelFor(int n, int M, int lanes, int splits, bool fixed);
 // Tokens per launch of a forward of M tokens over a matrix of input width n: the whole forward in
 // one wide launch where a wide kernel (Q40: gemm_wide.hip, Q80: q80w_gemm_wide.hip) takes it, else
-// <= 128 (Q40) / <= 64 (Q80, F32) per narrow launch. The wide kernels stream two blocks per stage, so
+// <= 128 (Q40) / <= 64 (Q80, F32, F16) per narrow launch. The wide kernels stream two blocks per stage, so
 // a width that is no multiple of 64 stays on narrow launches below the token threshold.
-enum GemmWeights : int { GEMM_W_F32 = 0, GEMM_W_Q40 = 1, GEMM_W_Q80 = 2 };
+enum GemmWeights : int { GEMM_W_F32 = 0, GEMM_W_Q40 = 1, GEMM_W_Q80 = 2, GEMM_W_F16 = 3 };
 int gemmChunkTokens(int n, int M, GemmWeights kind, bool fixed);
 // Same contract for F32 weights (`e.wf` [rows][n] row-major; EPI_ACT_Q80 not supported).
 void launchGemmF32(const GemmArgs &a, int epi, hipStream_t s);
@@ -343,6 +344,10 @@ void launchGemmF32(const GemmArgs &a, int epi, hipStream_t s);
 //                       buffers sized by gemmWidePartFloats / gemmWideCounters. The engine uses it for
 //                       launches of gemmUsesWide(M) tokens (gemmChunkTokens).
 void launchGemmQ80w(const GemmArgs &a, int epi, hipStream_t s, int fetch = 0);
+// Same contract as launchGemmF32 for F16 weights (`e.wh` [rows][n] row-major, n % 32 == 0, splits
+// dividing n / 32): the f16 weights are the MFMA's B operand as they sit in memory
+// (v_mfma_f32_16x16x32_f16), x rounded once to f16 is the only rounding (f16w_gemm.hip).
+void launchGemmF16w(const GemmArgs &a, int epi, hipStream_t s);
 void launchGemmQ80wWide(const GemmArgs &a, int epi, hipStream_t s);
 // Tile / split-K plan of one matrix (rt = 16-row tiles per wave: 64 * rt rows per workgroup).
 struct GemmPlan {
@@ -390,6 +395,13 @@ void launchGemv(const GemvArgs &a, int B, int pro, int epi, bool q40, hipStream_
 // / gemvLdsBytes with q40 = true: two rows per lane group, the same activation image).
 // depth > 0 (measurements only; B = 1, PRO_GLOBAL, EPI_STORE): the instance with `depth` steps per register group.
 void launchGemvQ80w(const GemvArgs &a, int B, int pro, int epi, hipStream_t s, int depth = 0);
+// Decode GEMV on F16 weights (f16w_inst.h), B = 1, 2 or 4: out[b][r] = sum_k f32(w[r][k]) * x[b][k],
+// one f32 FMA per term, x f32: PRO_GLOBAL reads `in`, PRO_RESNORM stages (in + addIn) through the RMS
+// norm in LDS. Epilogues (PRO_GLOBAL, EPI_STORE) and (PRO_RESNORM, EPI_STORE | EPI_QKV | EPI_ACT).
+// A workgroup owns passes * gemvF16wRowsPerPass(lanes) rows; lanes 0 = gemvF16wLanes.
+void launchGemvF16w(const GemvArgs &a, int B, int pro, int epi, hipStream_t s);
+int gemvF16wLanes(int n, int rows, int B);  // the F32 lane rule, skinny matrices widened for the row group
+int gemvF16wRowsPerPass(int lanes);
 // Co-residency of one GEMV launch on the current device: its grid and the most workgroups of that
 // kernel (at its LDS size) the device holds at once (occupancy per CU x CUs). A kernel whose
 // workgroups spin on peers (EPI_STORE_TP) is deadlock-free only if grid <= maxResident.
@@ -856,6 +868,7 @@ void launchFillQ40(uint8_t *qs, uint16_t *d, size_t nBlocks, float scale, uint64
 // Q80 planes of `nUnits` 16-byte units and `nScales` f16 scales: random int8 codes, scales as above.
 void launchFillQ80w(uint8_t *q, uint16_t *d, size_t nUnits, size_t nScales, float scale, uint64_t seed, hipStream_t s);
 void launchFillF32Uniform(float *p, size_t n, float amp, uint64_t seed, hipStream_t s);
+void launchFillF16Uniform(_Float16 *p, size_t n, float amp, uint64_t seed, hipStream_t s);  // the same values, rounded
 void launchFillF32Const(float *p, size_t n, float v, hipStream_t s);
 
 // Load every code object of this library onto the current device now. HIP loads a translation

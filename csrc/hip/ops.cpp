@@ -545,6 +545,164 @@ GemmQ80wResult gemmQ80w(const GemmQ80wArgs &p) {
     return r;
 }
 
+// ---- F16 weights (f16w_inst.h, f16w_gemm.hip) ------------------------------------------------------
+GemvF16wResult gemvF16w(const GemvF16wArgs &p) {
+    const int B = p.B, rows = p.rows, n = p.n;
+    DL_CHECK(B == 1 || B == 2 || B == 4, "gemv batch must be 1, 2 or 4");
+    DL_CHECK(rows > 0 && hipk::gemmSupported(n) && p.w.size() == (size_t)rows * n, "gemv_f16w: w is [rows][n] f16, n % 32 == 0");
+    DL_CHECK(p.pro == hipk::PRO_GLOBAL || p.pro == hipk::PRO_RESNORM, "gemv_f16w prologue: 0 global, 1 residual + norm");
+    DL_CHECK(p.epi == hipk::EPI_STORE || p.epi == hipk::EPI_ACT || p.epi == hipk::EPI_QKV,
+             "gemv_f16w epilogue: 0 store, 1 SwiGLU, 2 QKV");
+    DL_CHECK(p.pro == hipk::PRO_RESNORM || p.epi == hipk::EPI_STORE, "gemv_f16w: the global prologue stores only");
+    DL_CHECK(p.pro == hipk::PRO_RESNORM || (p.residual.empty() && p.normW.empty()),
+             "gemv_f16w: the global prologue takes no residual or norm");
+    DL_CHECK(p.epi == hipk::EPI_STORE || rows % 2 == 0, "gemv_f16w: row-pair epilogues need an even row count");
+    DL_CHECK(p.in.size() == (size_t)B * n, "gemv input size");
+    checkRows(p.residual, (size_t)B * n, "residual");
+    checkRows(p.normW, (size_t)n, "norm weights");
+    checkLanes(p.lanes);
+    const int lanes = p.lanes > 0 ? p.lanes : hipk::gemvF16wLanes(n, rows, B);
+    const int passes = p.passes > 0 ? p.passes : hipk::gemvDefaultPasses(n, rows, B, false, p.epi);
+    DL_CHECK(passes <= 64, "gemv passes out of range");
+    const int wgRows = hipk::gemvF16wRowsPerPass(lanes) * passes;
+    DL_CHECK(hipk::gemvLdsBytes(n, B, false, wgRows, p.pro) <= kLdsLimit, "gemv LDS footprint beyond the device limit");
+    Scratch sc;
+    hipk::GemvArgs a;
+    a.wh = reinterpret_cast<const _Float16 *>(sc.upload(p.w));
+    a.rows = rows;
+    a.n = n;
+    a.lanes = lanes;
+    a.passes = passes;
+    a.eps = p.eps;
+    a.act = 1;
+    a.ldIn = n;
+    a.in = sc.upload(p.in);
+    if (p.pro == hipk::PRO_RESNORM) {
+        a.addIn = sc.upload(p.residual);
+        a.xNext = p.residual.empty() ? nullptr : sc.allocGuarded<float>(1, (size_t)B * n, (size_t)B * n + 256, "xNext");
+        a.normW = sc.upload(p.normW);
+    }
+    GemvF16wResult res;
+    uint8_t *kc = nullptr, *vc = nullptr;
+    std::vector<int> slots(B);
+    const size_t cacheElems = (size_t)B * p.seqLen * p.kv0;
+    int outRows = rows;
+    if (p.epi == hipk::EPI_ACT) outRows = rows / 2;
+    if (p.epi == hipk::EPI_QKV) {
+        DL_CHECK(rows == p.q0 + 2 * p.kv0 && p.hs % 2 == 0 && p.hs <= 128 && (p.hs & (p.hs - 1)) == 0 &&
+                     p.q0 % p.hs == 0 && p.kv0 % p.hs == 0 && p.kv0 > 0,
+                 "qkv head layout");
+        DL_CHECK((int)p.pos.size() == B && p.rope.size() == (size_t)p.seqLen * p.hs, "qkv operand sizes");
+        for (int q : p.pos) DL_CHECK(q >= 0 && q < p.seqLen, "qkv position out of range");
+        outRows = p.q0;
+        for (int b = 0; b < B; b++) slots[b] = b;
+        const size_t eb = (size_t)hipk::kvElemBytes(p.kvBf16, p.kvFp8), cacheGuard = (size_t)wgRows * p.seqLen;
+        kc = sc.allocGuarded<uint8_t>(1, cacheElems * eb, (cacheElems + cacheGuard) * eb, "the K cache");
+        vc = sc.allocGuarded<uint8_t>(1, cacheElems * eb, (cacheElems + cacheGuard) * eb, "the V cache");
+        a.q0 = p.q0;
+        a.kv0 = p.kv0;
+        a.hs = p.hs;
+        a.seqLen = p.seqLen;
+        a.rope = reinterpret_cast<const float2 *>(sc.upload(p.rope));
+        a.pos = sc.upload(p.pos);
+        a.slot = sc.upload(slots);
+        a.kcache = kc;
+        a.vcache = vc;
+        a.kvBf16 = p.kvBf16 ? 1 : 0;
+        a.kvFp8 = p.kvFp8 ? 1 : 0;
+    }
+    a.ldOut = outRows + wgRows;
+    a.out = sc.allocGuarded<float>(B, outRows, a.ldOut, "the GEMV output");
+    hipk::launchGemvF16w(a, B, p.pro, p.epi, sc.s);
+    sc.sync();
+    sc.checkGuards();
+    if (a.xNext) res.xNext = sc.download(a.xNext, (size_t)B * n);
+    res.out = sc.downloadRows(a.out, B, outRows, a.ldOut);
+    if (kc) {
+        appendedRows(sc, kc, cacheElems, p.seqLen, p.kv0, p.hs, p.pos, slots, p.kvBf16, "the K cache", &res.k, p.kvFp8);
+        appendedRows(sc, vc, cacheElems, p.seqLen, p.kv0, p.hs, p.pos, slots, p.kvBf16, "the V cache", &res.v, p.kvFp8);
+    }
+    return res;
+}
+
+GemmF16wResult gemmF16w(const GemmF16wArgs &p) {
+    const int rows = p.rows, n = p.n, M = p.M;
+    DL_CHECK(M >= 1 && M <= 256, "gemm_f16w: 1..256 tokens");
+    DL_CHECK(rows > 0 && hipk::gemmSupported(n) && p.in.size() == (size_t)M * n && p.w.size() == (size_t)rows * n,
+             "gemm operand sizes");
+    DL_CHECK(p.splits == 0 || (p.splits > 0 && (n / 32) % p.splits == 0), "gemm splits must divide n / 32");
+    DL_CHECK(p.epi == hipk::EPI_STORE || p.epi == hipk::EPI_RES, "gemm_f16w epilogue: 0 store, 6 residual + norm hand-off");
+    const bool res = p.epi == hipk::EPI_RES;
+    DL_CHECK(!res || (rows % 2 == 0 && p.resIn.size() == (size_t)M * rows && p.resW.size() == (size_t)rows),
+             "gemm_f16w: EPI_RES takes resIn [M][rows] and resW [rows], rows even");
+    Scratch sc;
+    hipk::GemmArgs g;
+    g.e.wh = reinterpret_cast<const _Float16 *>(sc.upload(p.w));
+    g.e.rows = rows;
+    g.e.n = n;
+    g.e.eps = p.eps;
+    // the activation operand: `in` rounded to f16, rows past M (read by the last launch's 64-token pad) zero
+    const int chunk = hipk::kGemmF32MaxTokens, rowsPad = (M + chunk - 1) / chunk * chunk;
+    std::vector<uint16_t> xh((size_t)rowsPad * n, 0);
+    for (size_t i = 0; i < p.in.size(); i++) xh[i] = f32ToF16(p.in[i]);
+    const _Float16 *x = reinterpret_cast<const _Float16 *>(sc.upload(xh));
+    const int tiles = (rows + 63) / 64, ld = rows + 64, ldSS = M + 16;
+    float *out = sc.allocGuardedTail<float>(M, rows, ld, 1, res ? "the residual output" : "the GEMM output");
+    uint16_t *resX = res ? sc.allocGuardedTail<uint16_t>(M, rows, ld, 1, "the f16 hand-off rows") : nullptr;
+    float *ss = res ? sc.allocGuardedTail<float>(tiles, M, ldSS, 1, "the sums of squares") : nullptr;
+    std::vector<float> resInLd;
+    if (res) {  // resIn at the outputs' leading dimension
+        resInLd.assign((size_t)M * ld, 0.f);
+        for (int t = 0; t < M; t++)
+            std::copy(p.resIn.begin() + (size_t)t * rows, p.resIn.begin() + (size_t)(t + 1) * rows, resInLd.begin() + (size_t)t * ld);
+    }
+    const float *resIn = sc.upload(resInLd), *resW = sc.upload(p.resW);
+    DL_CHECK(p.ss.empty() || (p.ssTiles > 0 && p.ss.size() == (size_t)p.ssTiles * M), "gemm_f16w: ss is [ssTiles][M]");
+    const float *ssIn = sc.upload(p.ss);
+    const size_t part = (size_t)std::max(p.splits, 8) * tiles * chunk * 64;
+    float *partBuf = sc.alloc<float>(part);
+    int *counters = sc.alloc<int>((size_t)tiles + 1);
+    GemmF16wResult r;
+    for (int c0 = 0; c0 < M; c0 += chunk) {
+        const int bc = std::min(chunk, M - c0);
+        hipk::GemmArgs a = g;
+        a.e.ldOut = ld;
+        a.x = x + (size_t)c0 * n;
+        a.M = bc;
+        a.splits = p.splits > 0 ? p.splits : hipk::gemmSplits(rows, n, bc);
+        a.part = partBuf;
+        a.partFloats = part;
+        a.counters = counters;
+        if (ssIn) {
+            a.ssIn = ssIn + c0;
+            a.ssTiles = p.ssTiles;
+            a.ldSS = M;
+        }
+        if (res) {
+            a.resIn = resIn + (size_t)c0 * ld;
+            a.resOut = out + (size_t)c0 * ld;
+            a.resW = resW;
+            a.resX = reinterpret_cast<_Float16 *>(resX) + (size_t)c0 * ld;
+            a.ssOut = ss + c0;
+            a.ldSS = ldSS;
+        } else {
+            a.e.out = out + (size_t)c0 * ld;
+        }
+        r.splits.push_back(a.splits);
+        hipk::launchGemmF16w(a, p.epi, sc.s);
+    }
+    sc.sync();
+    sc.checkGuards();
+    r.out = sc.downloadRows(out, M, rows, ld);
+    if (res) {
+        const std::vector<uint16_t> xr = sc.downloadRows(resX, M, rows, ld);
+        r.resX.resize(xr.size());
+        for (size_t i = 0; i < xr.size(); i++) r.resX[i] = f16ToF32(xr[i]);
+        r.ssOut = sc.downloadRows(ss, tiles, M, ldSS);
+    }
+    return r;
+}
+
 void gemvDefaults(int rows, int n, int B, bool q40, int epi, int &lanes, int &passes) {
     lanes = hipk::gemvLanesPerRow(n, rows, q40 ? 1 : B, q40);
     passes = hipk::gemvDefaultPasses(n, rows, B, q40, epi, q40 ? lanes : 0);

@@ -121,6 +121,41 @@ struct GemmQ80wResult {
 };
 GemmQ80wResult gemmQ80w(const GemmQ80wArgs &a);
 
+// F16 weights (f16w_inst.h, f16w_gemm.hip): `w` is [rows][n] f16 bit patterns, row-major.
+// gemvF16w: one gemvF16wKernel launch, B = 1, 2 or 4. pro 0 (PRO_GLOBAL): the kernel reads `in`, store
+// epilogue only; pro 1 (PRO_RESNORM): in (+ residual) -> RMS norm with normW (if given) -> f32 in LDS.
+// epi 0 store, 1 SwiGLU of interleaved (w1, w3) rows, 2 QKV (as gemvQ80w's; kvFp8: an e4m3 cache).
+// lanes 0 = gemvF16wLanes, passes 0 = the F32 GEMV's rule. Outputs are guarded as the other GEMV ops'.
+struct GemvF16wArgs {
+    std::vector<uint16_t> w;
+    int rows = 0, n = 0;
+    std::vector<float> in, residual, normW;
+    float eps = 1e-5f;
+    int B = 1, pro = 1, epi = 0, lanes = 0, passes = 0;
+    int q0 = 0, kv0 = 0, hs = 0, seqLen = 0;
+    std::vector<float> rope;
+    std::vector<int> pos;
+    bool kvBf16 = true, kvFp8 = false;
+};
+struct GemvF16wResult {
+    std::vector<float> out, xNext, k, v;
+};
+GemvF16wResult gemvF16w(const GemvF16wArgs &a);
+// gemmF16w: M (1..256) tokens over F16 weights in gemmF16wKernel launches of <= 64, `in` rounded to f16
+// on the host. Epilogues, the consumer side (ss) and the results as gemmQ80w's.
+struct GemmF16wArgs {
+    std::vector<uint16_t> w;
+    int rows = 0, n = 0, M = 0, epi = 0, splits = 0;
+    std::vector<float> in, resIn, resW, ss;
+    int ssTiles = 0;
+    float eps = 1e-5f;
+};
+struct GemmF16wResult {
+    std::vector<float> out, resX, ssOut;
+    std::vector<int> splits;
+};
+GemmF16wResult gemmF16w(const GemmF16wArgs &a);
+
 // Batched F32 matmul on MFMA: norm kernel -> f16 -> gemmF32Kernel (store epilogue).
 std::vector<float> gemmF32(const std::vector<float> &w, int rows, int n, const std::vector<float> &in,
                            const std::vector<float> &normW, float eps, int M);

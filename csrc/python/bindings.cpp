@@ -532,6 +532,83 @@ void bindOps(py::module_ &m) {
           py::arg("blocks"), py::arg("rows"), py::arg("n"), py::arg("x"), py::arg("lanes") = 0, py::arg("splits") = 0,
           py::arg("epi") = 0, py::arg("res_in") = py::none(), py::arg("res_w") = py::none(), py::arg("ss") = py::none(),
           py::arg("ss_tiles") = 0, py::arg("eps") = 1e-5f, py::arg("fetch") = 0, py::arg("wide") = py::none());
+    o.def("gemv_f16w",
+          [](py::object w, int rows, int n, py::object x, py::object residual, py::object normW, float eps, int pro, int epi,
+             int lanes, int passes, int q0, int kv0, int hs, py::object rope, int seqLen, std::vector<int> pos, bool kvBf16,
+             bool kvFp8) {
+              ops::GemvF16wArgs a;
+              a.w = vec<uint16_t>(w);
+              a.rows = rows;
+              a.n = n;
+              a.in = vec<float>(x);
+              a.residual = vec<float>(residual);
+              a.normW = vec<float>(normW);
+              a.eps = eps;
+              a.B = (int)(a.in.size() / n);
+              a.pro = pro;
+              a.epi = epi;
+              a.lanes = lanes;
+              a.passes = passes;
+              a.q0 = q0;
+              a.kv0 = kv0;
+              a.hs = hs;
+              a.rope = vec<float>(rope);
+              a.seqLen = seqLen;
+              a.pos = pos;
+              a.kvBf16 = kvBf16;
+              a.kvFp8 = kvFp8;
+              ops::GemvF16wResult r;
+              {
+                  py::gil_scoped_release rel;
+                  r = ops::gemvF16w(a);
+              }
+              const py::ssize_t B = a.B;
+              py::dict d;
+              d["out"] = arr(r.out, {B, (py::ssize_t)r.out.size() / B});
+              if (!r.xNext.empty()) d["x_next"] = arr(r.xNext, {B, (py::ssize_t)n});
+              if (!r.k.empty()) d["k"] = arr(r.k, {B, (py::ssize_t)kv0});
+              if (!r.v.empty()) d["v"] = arr(r.v, {B, (py::ssize_t)kv0});
+              return d;
+          },
+          py::arg("w"), py::arg("rows"), py::arg("n"), py::arg("x"), py::arg("residual") = py::none(),
+          py::arg("norm_w") = py::none(), py::arg("eps") = 1e-5f, py::arg("pro") = 1, py::arg("epi") = 0,
+          py::arg("lanes") = 0, py::arg("passes") = 0, py::arg("q0") = 0, py::arg("kv0") = 0, py::arg("hs") = 0,
+          py::arg("rope") = py::none(), py::arg("seq_len") = 0, py::arg("pos") = std::vector<int>(),
+          py::arg("kv_bf16") = true, py::arg("kv_fp8") = false,
+          "F16-weight decode GEMV: w [rows][n] f16 bit patterns (uint16)");
+    o.def("gemm_f16w",
+          [](py::object w, int rows, int n, py::object x, int splits, int epi, py::object resIn, py::object resW,
+             py::object ss, int ssTiles, float eps) {
+              ops::GemmF16wArgs a;
+              a.w = vec<uint16_t>(w);
+              a.rows = rows;
+              a.n = n;
+              a.in = vec<float>(x);
+              a.M = (int)(a.in.size() / n);
+              a.splits = splits;
+              a.epi = epi;
+              a.resIn = vec<float>(resIn);
+              a.resW = vec<float>(resW);
+              a.ss = vec<float>(ss);
+              a.ssTiles = ssTiles;
+              a.eps = eps;
+              ops::GemmF16wResult r;
+              {
+                  py::gil_scoped_release rel;
+                  r = ops::gemmF16w(a);
+              }
+              const py::ssize_t M = a.M;
+              py::dict d;
+              d["out"] = arr(r.out, {M, (py::ssize_t)rows});
+              d["splits"] = r.splits;
+              if (!r.resX.empty()) d["res_x"] = arr(r.resX, {M, (py::ssize_t)rows});
+              if (!r.ssOut.empty()) d["ss"] = arr(r.ssOut, {(py::ssize_t)r.ssOut.size() / M, M});
+              return d;
+          },
+          py::arg("w"), py::arg("rows"), py::arg("n"), py::arg("x"), py::arg("splits") = 0, py::arg("epi") = 0,
+          py::arg("res_in") = py::none(), py::arg("res_w") = py::none(), py::arg("ss") = py::none(),
+          py::arg("ss_tiles") = 0, py::arg("eps") = 1e-5f,
+          "F16-weight batched MFMA GEMM: w [rows][n] f16 bit patterns (uint16)");
     o.def("gemm_q40",
           [](py::object blocks, int rows, int n, py::object x, py::object residual, py::object normW, float eps,
              int splits) {
@@ -1566,6 +1643,13 @@ PYBIND11_MODULE(_C, m) {
           py::arg("copies") = 8, py::arg("iters") = 100, py::arg("wide") = true, py::call_guard<py::gil_scoped_release>(),
           "us per pass over `tokens` rows: above 64 tokens one gemmQ80wWideKernel launch (wide) or the chunked "
           "narrow launches of <= 64 (wide = false)");
+    m.def("bench_gemv_f16w", &benchGemvF16w, py::arg("rows"), py::arg("n"), py::arg("pro") = 0, py::arg("epi") = 0,
+          py::arg("batch") = 1, py::arg("lanes") = 0, py::arg("passes") = 0, py::arg("f32") = false, py::arg("copies") = 8,
+          py::arg("iters") = 200, py::call_guard<py::gil_scoped_release>(),
+          "us per gemvF16wKernel launch (f32 = true: the F32 GEMV on the same shape)");
+    m.def("bench_gemm_f16w", &benchGemmF16w, py::arg("rows"), py::arg("n"), py::arg("tokens"), py::arg("f32") = false,
+          py::arg("copies") = 8, py::arg("iters") = 100, py::call_guard<py::gil_scoped_release>(),
+          "us per gemmF16wKernel launch of 1..64 tokens (f32 = true: gemmF32Kernel on the same shape)");
     m.def("bench_attention",
           [](int nh, int kvm, int hs, int seq, int pos, int B, int copies, int iters, bool kvBf16, bool kvFp8, int rowBlock) {
               return benchAttention(nh, kvm, hs, seq, pos, B, copies, iters, nullptr, kvBf16, kvFp8, rowBlock);

@@ -80,8 +80,9 @@ AppArgs AppArgs::parse(int argc, char **argv, bool requireMode) {
         else if (name == "--synthetic") a.synthetic = value;
         else if (name == "--synthetic-weights") {
             a.syntheticWeights = parseFloatType(value);
-            if (a.syntheticWeights != FloatType::Q40 && a.syntheticWeights != FloatType::Q80)
-                throw Error("Invalid --synthetic-weights (q40|q80): " + std::string(value));
+            if (a.syntheticWeights != FloatType::Q40 && a.syntheticWeights != FloatType::Q80 &&
+                a.syntheticWeights != FloatType::F16)
+                throw Error("Invalid --synthetic-weights (q40|q80|f16): " + std::string(value));
         }
         else if (name == "--web-ui") a.webUi = value;
         else if (name == "--stream-weights") a.streamWeights = std::atoi(value) != 0;
@@ -146,7 +147,7 @@ static EngineConfig engineConfigFrom(const AppArgs &a, int nSlots) {
     if (!a.synthetic.empty()) {
         c.synthetic = true;
         c.syntheticHeader = syntheticHeader(a.synthetic, a.maxSeqLen, a.syntheticWeights);
-        c.bufferType = FloatType::Q80;
+        c.bufferType = a.syntheticWeights == FloatType::F16 ? FloatType::F32 : FloatType::Q80;
     }
     return c;
 }

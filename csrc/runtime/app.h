@@ -55,7 +55,7 @@ struct AppArgs {
     bool graphs = true;
     int logLevel = 1;
     std::string synthetic;                       // "llama3_1_8b" etc: random-init weights on device
-    FloatType syntheticWeights = FloatType::Q40; // --synthetic-weights q40|q80: their weight type
+    FloatType syntheticWeights = FloatType::Q40; // --synthetic-weights q40|q80|f16: their weight type
     std::string webUi;                           // dllama-api: directory served at GET /
     bool streamWeights = false;                  // worker: always fetch slices from the root
     std::string weightsCache = "/tmp";           // worker: directory for streamed weight files

@@ -112,7 +112,7 @@ def make_test_assets(directory: str, name: str = "tiny", weights: int = FloatTyp
                      seed: int = 0, **overrides) -> tuple:
     os.makedirs(directory, exist_ok=True)
     spec = make_spec(name, weights, seq_len, **overrides)
-    wt = {FloatType.Q40: "q40", FloatType.Q80: "q80"}.get(weights, "f32")
+    wt = {FloatType.Q40: "q40", FloatType.Q80: "q80", FloatType.F16: "f16"}.get(weights, "f32")
     mpath = os.path.join(directory, f"{name}_{wt}.m")
     tpath = os.path.join(directory, f"{name}.t")
     if not os.path.exists(mpath):

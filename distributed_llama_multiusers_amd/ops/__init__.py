@@ -156,6 +156,49 @@ def gemm_q80w(blocks, rows: int, n: int, x, lanes: int = 0, splits: int = 0, epi
     return {k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()}
 
 
+def _f16_bits(w) -> np.ndarray:
+    """[rows, n] float16 weights (array or tensor) as their uint16 bit patterns."""
+    if isinstance(w, torch.Tensor):
+        w = w.detach().cpu().numpy()
+    w = np.ascontiguousarray(w)
+    if w.dtype != np.float16 or w.ndim != 2:
+        raise ValueError("w must be a [rows, n] float16 array")
+    return w.view(np.uint16)
+
+
+def gemv_f16w(w, x, residual=None, norm_w=None, eps: float = 1e-5, prologue: str = "resnorm", epilogue: str = "store",
+              lanes: int = 0, passes: int = 0, q0: int = 0, kv0: int = 0, hs: int = 0, rope=None, pos=None,
+              kv_bf16: bool = True, kv_dtype: str = ""):
+    """F16-weight decode GEMV (1, 2 or 4 rows): out[b][r] = sum_k f32(w[r][k]) * x[b][k], one f32 FMA per
+    term. `w` is a [rows, n] float16 array. prologue "resnorm": (x + residual) -> RMS norm (norm_w) -> f32
+    in LDS; "global": the kernel reads x (store only). epilogue "store", "swiglu" (interleaved (w1, w3)
+    rows) or "qkv" (rows = q0 + 2 kv0: RoPE from `rope` [seq_len, hs/2, 2] at `pos`, K / V appended to an
+    f32, bf16 or fp8 cache, row b in slot b). Returns a dict of torch tensors: out, x_next, k, v."""
+    bits = _f16_bits(w)
+    rows, n = bits.shape
+    epi = {"store": 0, "swiglu": 1, "qkv": 2}[epilogue]
+    seq_len = 0 if rope is None else int(np.asarray(rope).shape[0])
+    bf16, fp8 = _kv(kv_bf16, kv_dtype)
+    r = native().ops.gemv_f16w(bits, rows, n, _np(x), _np(residual), _np(norm_w), eps, {"global": 0, "resnorm": 1}[prologue],
+                               epi, lanes, passes, q0, kv0, hs, _np(rope), seq_len,
+                               [int(p) for p in (pos if pos is not None else [])], bf16, fp8)
+    return {k: torch.from_numpy(v) for k, v in r.items()}
+
+
+def gemm_f16w(w, x, splits: int = 0, epilogue: str = "store", res_in=None, res_w=None, ss=None, eps: float = 1e-5):
+    """Batched (MFMA) matmul for F16 weights (1..256 rows of x, launches of <= 64): x rounded to f16 once,
+    the [rows, n] float16 weights exact, f32 accumulation. epilogue "store", or "res": out = res_in + W.x,
+    res_x = the f16 hand-off rows, ss = per-64-row-tile sums of squares. `ss` given: x is a producer's res_x
+    and each token's output is scaled by its RMS factor. `splits` > 0 forces the K split. Returns a dict:
+    out, splits per launch, res_x, ss."""
+    bits = _f16_bits(w)
+    rows, n = bits.shape
+    ss_tiles = 0 if ss is None else int(np.asarray(ss).shape[0])
+    r = native().ops.gemm_f16w(bits, rows, n, _np(x), splits, {"store": 0, "res": 6}[epilogue], _np(res_in), _np(res_w),
+                               _np(ss), ss_tiles, eps)
+    return {k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()}
+
+
 def _kv(kv_bf16: bool, kv_dtype: str):
     """(kv_bf16, kv_fp8) of a kv_dtype keyword: "" follows kv_bf16, else "f32" / "bf16" / "fp8"."""
     if kv_dtype not in ("", "f32", "bf16", "fp8"):
