@@ -85,7 +85,7 @@ double benchGemvQ80w(int rows, int n, int pro, int epi, int B, int lanes, int pa
 double benchGemmQ80w(int rows, int n, int M, bool f32, int fetch, int copies, int iters, bool wide = true);
 // The F16-weight kernels, or with f32 = true the F32-weight ones on the same shape (engine_bench.cpp).
 double benchGemvF16w(int rows, int n, int pro, int epi, int B, int lanes, int passes, bool f32, int copies, int iters);
-double benchGemmF16w(int rows, int n, int M, bool f32, int copies, int iters);
+double benchGemmF16w(int rows, int n, int M, bool f32, int copies, int iters, bool wide = false);
 double benchGemmQ40(int rows, int n, int M, int epi, int copies, int iters,
                     std::vector<unsigned long long> *trace = nullptr);
 // Micro-benchmark of the decode attention kernel (bf16 or f32 KV, Q80 output): `copies` KV caches

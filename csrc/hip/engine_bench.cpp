@@ -280,11 +280,15 @@ double benchGemvF16w(int rows, int n, int pro, int epi, int B, int lanes, int pa
     });
 }
 
-// Batched GEMM (1..64 tokens, EPI_STORE) on F16 weights (gemmF16wKernel) or, f32 = true, on F32 weights
-// (gemmF32Kernel), same shape and harness.
-double benchGemmF16w(int rows, int n, int M, bool f32, int copies, int iters) {
-    DL_CHECK(M >= 1 && M <= hipk::kGemmF32MaxTokens && hipk::gemmSupported(n) && rows % 64 == 0 && copies >= 1,
-             "bad gemm bench shape");
+// Batched GEMM (EPI_STORE) on F16 weights (gemmF16wKernel) or, f32 = true, on F32 weights (gemmF32Kernel),
+// same shape and harness. M > 64: one pass over the M tokens per timed iteration, as one
+// launchGemmF16wWide (wide) or as ceil(M / 64) narrow launches (the chunking of an engine without the
+// wide kernel).
+double benchGemmF16w(int rows, int n, int M, bool f32, int copies, int iters, bool wide) {
+    const int C = hipk::kGemmF32MaxTokens;
+    DL_CHECK(M >= 1 && M <= 2048 && hipk::gemmSupported(n) && rows % 64 == 0 && copies >= 1, "bad gemm bench shape");
+    wide = wide && !f32 && M > C;
+    DL_CHECK(!wide || hipk::gemmWideAccepts(n, 1), "the wide kernel takes widths of whole 64-k stages");
     Scratch sc;
     hipStream_t s = sc.s;
     std::vector<void *> w(copies);
@@ -297,27 +301,30 @@ double benchGemmF16w(int rows, int n, int M, bool f32, int copies, int iters) {
             hipk::launchFillF16Uniform((_Float16 *)w[c], (size_t)rows * n, 1e-2f, 77 + c, s);
         }
     }
-    _Float16 *x = sc.alloc<_Float16>((size_t)hipk::kGemmF32MaxTokens * n);
-    hipk::launchFillF16Uniform(x, (size_t)hipk::kGemmF32MaxTokens * n, 1.f, 3, s);
-    const size_t part = hipk::gemmPartFloats(rows, n, M);
+    const int MP = (M + 127) / 128 * 128;  // covers the narrow launches' 16 / 32 / 64-row pads too
+    _Float16 *x = sc.alloc<_Float16>((size_t)MP * n);
+    hipk::launchFillF16Uniform(x, (size_t)MP * n, 1.f, 3, s);
+    const int chunk = wide ? M : C;
+    const size_t part = wide ? hipk::gemmWidePartFloats(rows, n, M) : hipk::gemmPartFloats(rows, n, std::min(M, C));
     hipk::GemmArgs g;
     g.e.rows = rows;
     g.e.n = n;
-    g.e.out = sc.alloc<float>((size_t)M * rows);
+    float *out = sc.alloc<float>((size_t)M * rows);
     g.e.ldOut = rows;
-    g.x = x;
-    g.M = M;
-    g.splits = hipk::gemmSplits(rows, n, M);
     g.part = part ? sc.alloc<float>(part) : nullptr;
     g.partFloats = part;
-    g.counters = sc.alloc<int>((size_t)rows / 64 + 1);
+    g.counters = sc.alloc<int>((size_t)std::max(rows / 64 + 1, hipk::gemmWideCounters(rows, M)));
     return timeGraphUs(s, iters, [&](int c) {
-        if (f32) {
-            g.e.wf = (const float *)w[c % copies];
-            hipk::launchGemmF32(g, hipk::EPI_STORE, s);
-        } else {
-            g.e.wh = (const _Float16 *)w[c % copies];
-            hipk::launchGemmF16w(g, hipk::EPI_STORE, s);
+        g.e.wf = f32 ? (const float *)w[c % copies] : nullptr;
+        g.e.wh = f32 ? nullptr : (const _Float16 *)w[c % copies];
+        for (int c0 = 0; c0 < M; c0 += chunk) {
+            g.M = std::min(chunk, M - c0);
+            g.splits = wide ? hipk::gemmWideSplits(rows, n, M) : hipk::gemmSplits(rows, n, g.M);
+            g.x = x + (size_t)c0 * n;
+            g.e.out = out + (size_t)c0 * rows;
+            if (f32) hipk::launchGemmF32(g, hipk::EPI_STORE, s);
+            else if (wide) hipk::launchGemmF16wWide(g, hipk::EPI_STORE, s);
+            else hipk::launchGemmF16w(g, hipk::EPI_STORE, s);
         }
     });
 }

@@ -505,7 +505,7 @@ bool HipEngineImpl::tpBatchedOk(int n) const {
 
 void HipEngineImpl::gemmBatched(const DevMat &m, int n, int epi, const MatOperands &o) {
     DL_CHECK(!o.aq && !o.as && !o.oq && !o.os && !o.tp, "GEMV operand on a GEMM launch");
-    // tokens per launch: the wide Q40 / Q80 kernels take the whole forward in one launch (one weight
+    // tokens per launch: the wide Q40 / Q80 / F16 kernels take the whole forward in one launch (one weight
     // pass per token tile, all tiles of a row tile on one XCD), the narrow ones <= 128 (Q40) / 64
     // (batch-invariant engines: narrow launches only, the split count of a 16-token launch for all)
     // (a width the wide kernels cannot split into their two-block stages: narrow launches too)
@@ -572,6 +572,8 @@ void HipEngineImpl::gemmBatched(const DevMat &m, int n, int epi, const MatOperan
             hipk::launchGemmQ80wWide(g, epi, stream_);
         else if (q80w())
             hipk::launchGemmQ80w(g, epi, stream_);
+        else if (f16w() && !invariant_ && hipk::gemmUsesWide(bc))
+            hipk::launchGemmF16wWide(g, epi, stream_);
         else if (f16w())
             hipk::launchGemmF16w(g, epi, stream_);
         else

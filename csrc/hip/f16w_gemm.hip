@@ -1,5 +1,6 @@
-// F16 weights on gfx950: the batched MFMA GEMM (1..64 tokens per launch), the decode GEMV's launcher
-// (kernel: f16w_inst.h, instances: f16w_l16/32/64.hip) and the synthetic fill.
+// F16 weights on gfx950: the narrow batched MFMA GEMM (1..64 tokens per launch; forwards of >= 65
+// tokens take the wide LDS-staged kernel of f16w_gemm_wide.hip, gemmChunkTokens), the decode GEMV's
+// launcher (kernel: f16w_inst.h, instances: f16w_l16/32/64.hip) and the synthetic fill.
 //
 //   out[t][row] = sum_k w[row][k] * x[t][k]      w f16 row-major [rows][n], x f16
 //

@@ -438,7 +438,7 @@ GemmKernel gemmKernelFor(int n, int M, int lanes, int splits, bool fixed) {
 }
 
 int gemmChunkTokens(int n, int M, GemmWeights kind, bool fixed) {
-    if (kind == GEMM_W_F32 || kind == GEMM_W_F16) return kGemmF32MaxTokens;
+    if (kind == GEMM_W_F32) return kGemmF32MaxTokens;
     const int narrow = kind == GEMM_W_Q40 ? kGemmMaxTokens : kGemmF32MaxTokens;
     if (!gemmUsesWide(M) || fixed) return narrow;
     return gemmWideAccepts(n, 1) ? M : std::min(narrow, gemmWideMin() - 1);

@@ -326,9 +326,10 @@ void launchGemmQ40(const GemmArgs &a, int epi, hipStream_t s);
 enum GemmKernel : int { GEMM_NARROW = 0, GEMM_L16 = 1, GEMM_WIDE = 2 };
 GemmKernel gemmKernelFor(int n, int M, int lanes, int splits, bool fixed);
 // Tokens per launch of a forward of M tokens over a matrix of input width n: the whole forward in
-// one wide launch where a wide kernel (Q40: gemm_wide.hip, Q80: q80w_gemm_wide.hip) takes it, else
-// <= 128 (Q40) / <= 64 (Q80, F32, F16) per narrow launch. The wide kernels stream two blocks per stage, so
-// a width that is no multiple of 64 stays on narrow launches below the token threshold.
+// one wide launch where a wide kernel (Q40: gemm_wide.hip, Q80: q80w_gemm_wide.hip, F16:
+// f16w_gemm_wide.hip) takes it, else <= 128 (Q40) / <= 64 (Q80, F16, F32: always) per narrow launch.
+// The wide kernels stream 64 k (two blocks) per stage, so a width that is no multiple of 64 stays on
+// narrow launches below the token threshold.
 enum GemmWeights : int { GEMM_W_F32 = 0, GEMM_W_Q40 = 1, GEMM_W_Q80 = 2, GEMM_W_F16 = 3 };
 int gemmChunkTokens(int n, int M, GemmWeights kind, bool fixed);
 // Same contract for F32 weights (`e.wf` [rows][n] row-major; EPI_ACT_Q80 not supported).
@@ -346,15 +347,21 @@ void launchGemmF32(const GemmArgs &a, int epi, hipStream_t s);
 void launchGemmQ80w(const GemmArgs &a, int epi, hipStream_t s, int fetch = 0);
 // Same contract as launchGemmF32 for F16 weights (`e.wh` [rows][n] row-major, n % 32 == 0, splits
 // dividing n / 32): the f16 weights are the MFMA's B operand as they sit in memory
-// (v_mfma_f32_16x16x32_f16), x rounded once to f16 is the only rounding (f16w_gemm.hip).
+// (v_mfma_f32_16x16x32_f16), x rounded once to f16 is the only rounding. Two launchers, one product:
+//   launchGemmF16w      <= kGemmF32MaxTokens tokens per launch, weights straight to VGPRs (f16w_gemm.hip).
+//   launchGemmF16wWide  any token count in one launch (f16w_gemm_wide.hip): 128 x 128 tiles, weight
+//                       and activation panels staged in LDS as one swizzled image. `x` padded to
+//                       whole 128-token tiles; EPI_STORE, EPI_ACT, EPI_ACT_F16, EPI_QKV, EPI_RES; no
+//                       tile exchange; splits, split-K buffers and the engine's use as launchGemmQ80wWide's.
 void launchGemmF16w(const GemmArgs &a, int epi, hipStream_t s);
+void launchGemmF16wWide(const GemmArgs &a, int epi, hipStream_t s);
 void launchGemmQ80wWide(const GemmArgs &a, int epi, hipStream_t s);
 // Tile / split-K plan of one matrix (rt = 16-row tiles per wave: 64 * rt rows per workgroup).
 struct GemmPlan {
     int rt = 1, tiles = 0, splits = 1;
 };
 constexpr int kGemmMaxTokens = 128;    // tokens per narrow Q40 GEMM launch (16, 32, 64 or 128 padded)
-// Wide GEMMs (Q40: gemm_wide.hip, Q80: q80w_gemm_wide.hip): launches of >= gemmWideMin() tokens (default 65; DL_GEMM_WIDE=0
+// Wide GEMMs (Q40: gemm_wide.hip, Q80: q80w_gemm_wide.hip, F16: f16w_gemm_wide.hip): launches of >= gemmWideMin() tokens (default 65; DL_GEMM_WIDE=0
 // disables) run 128 x 128 tiles over every token tile of the launch; any token count per launch
 // (activation operand padded to whole 128-token tiles).
 bool gemmWideOn();

@@ -627,10 +627,16 @@ GemvF16wResult gemvF16w(const GemvF16wArgs &p) {
 
 GemmF16wResult gemmF16w(const GemmF16wArgs &p) {
     const int rows = p.rows, n = p.n, M = p.M;
-    DL_CHECK(M >= 1 && M <= 256, "gemm_f16w: 1..256 tokens");
+    DL_CHECK(M >= 1 && M <= 2048, "gemm_f16w: 1..2048 tokens");
     DL_CHECK(rows > 0 && hipk::gemmSupported(n) && p.in.size() == (size_t)M * n && p.w.size() == (size_t)rows * n,
              "gemm operand sizes");
     DL_CHECK(p.splits == 0 || (p.splits > 0 && (n / 32) % p.splits == 0), "gemm splits must divide n / 32");
+    // tokens per launch: the engine's rule, one wide launch, or narrow launches of <= 64
+    const int narrowChunk = hipk::kGemmF32MaxTokens;
+    const int chunk = p.wide < 0 ? hipk::gemmChunkTokens(n, M, hipk::GEMM_W_F16, false) : p.wide ? M : narrowChunk;
+    const bool wide = p.wide < 0 ? hipk::gemmUsesWide(std::min(chunk, M)) : p.wide != 0;
+    DL_CHECK(wide || M <= 256, "gemm_f16w: narrow launches take 1..256 tokens");
+    DL_CHECK(!wide || hipk::gemmWideAccepts(n, std::max(p.splits, 1)), "gemm_f16w: the wide kernel splits K into whole 64-k stages");
     DL_CHECK(p.epi == hipk::EPI_STORE || p.epi == hipk::EPI_RES, "gemm_f16w epilogue: 0 store, 6 residual + norm hand-off");
     const bool res = p.epi == hipk::EPI_RES;
     DL_CHECK(!res || (rows % 2 == 0 && p.resIn.size() == (size_t)M * rows && p.resW.size() == (size_t)rows),
@@ -641,8 +647,9 @@ GemmF16wResult gemmF16w(const GemmF16wArgs &p) {
     g.e.rows = rows;
     g.e.n = n;
     g.e.eps = p.eps;
-    // the activation operand: `in` rounded to f16, rows past M (read by the last launch's 64-token pad) zero
-    const int chunk = hipk::kGemmF32MaxTokens, rowsPad = (M + chunk - 1) / chunk * chunk;
+    // the activation operand: `in` rounded to f16, rows past M (read by the last launch: 64-token
+    // pads, or the wide kernel's whole 128-token tiles) zero
+    const int pad = wide ? 128 : narrowChunk, rowsPad = (M + pad - 1) / pad * pad;
     std::vector<uint16_t> xh((size_t)rowsPad * n, 0);
     for (size_t i = 0; i < p.in.size(); i++) xh[i] = f32ToF16(p.in[i]);
     const _Float16 *x = reinterpret_cast<const _Float16 *>(sc.upload(xh));
@@ -659,9 +666,12 @@ GemmF16wResult gemmF16w(const GemmF16wArgs &p) {
     const float *resIn = sc.upload(resInLd), *resW = sc.upload(p.resW);
     DL_CHECK(p.ss.empty() || (p.ssTiles > 0 && p.ss.size() == (size_t)p.ssTiles * M), "gemm_f16w: ss is [ssTiles][M]");
     const float *ssIn = sc.upload(p.ss);
-    const size_t part = (size_t)std::max(p.splits, 8) * tiles * chunk * 64;
+    // split-K partials and counters: 64-row x 64-token tiles, or the wide kernel's 128 x 128
+    const size_t wideTiles = (size_t)((rows + 127) / 128) * (rowsPad / 128);
+    size_t part = (size_t)std::max(p.splits, 8) * tiles * narrowChunk * 64;
+    if (wide) part = (size_t)std::max(p.splits, 4) * wideTiles * 128 * 128;
     float *partBuf = sc.alloc<float>(part);
-    int *counters = sc.alloc<int>((size_t)tiles + 1);
+    int *counters = sc.alloc<int>(std::max((size_t)tiles, wideTiles) + 1);
     GemmF16wResult r;
     for (int c0 = 0; c0 < M; c0 += chunk) {
         const int bc = std::min(chunk, M - c0);
@@ -669,7 +679,7 @@ GemmF16wResult gemmF16w(const GemmF16wArgs &p) {
         a.e.ldOut = ld;
         a.x = x + (size_t)c0 * n;
         a.M = bc;
-        a.splits = p.splits > 0 ? p.splits : hipk::gemmSplits(rows, n, bc);
+        a.splits = p.splits > 0 ? p.splits : wide ? hipk::gemmWideSplits(rows, n, bc) : hipk::gemmSplits(rows, n, bc);
         a.part = partBuf;
         a.partFloats = part;
         a.counters = counters;
@@ -689,7 +699,11 @@ GemmF16wResult gemmF16w(const GemmF16wArgs &p) {
             a.e.out = out + (size_t)c0 * ld;
         }
         r.splits.push_back(a.splits);
-        hipk::launchGemmF16w(a, p.epi, sc.s);
+        r.kernels.push_back(wide ? "wide" : "narrow");
+        if (wide)
+            hipk::launchGemmF16wWide(a, p.epi, sc.s);
+        else
+            hipk::launchGemmF16w(a, p.epi, sc.s);
     }
     sc.sync();
     sc.checkGuards();

@@ -141,11 +141,14 @@ struct GemvF16wResult {
     std::vector<float> out, xNext, k, v;
 };
 GemvF16wResult gemvF16w(const GemvF16wArgs &a);
-// gemmF16w: M (1..256) tokens over F16 weights in gemmF16wKernel launches of <= 64, `in` rounded to f16
-// on the host. Epilogues, the consumer side (ss) and the results as gemmQ80w's.
+// gemmF16w: M tokens over F16 weights, `in` rounded to f16 on the host. wide < 0: the engine's chunking
+// (gemmChunkTokens: one gemmF16wWideKernel launch from the wide threshold up, else gemmF16wKernel
+// launches of <= 64); 1: one wide launch whatever M (<= 2048); 0: narrow launches (M <= 256).
+// Epilogues, the consumer side (ss) and the results as gemmQ80w's.
 struct GemmF16wArgs {
     std::vector<uint16_t> w;
     int rows = 0, n = 0, M = 0, epi = 0, splits = 0;
+    int wide = -1;
     std::vector<float> in, resIn, resW, ss;
     int ssTiles = 0;
     float eps = 1e-5f;
@@ -153,6 +156,7 @@ struct GemmF16wArgs {
 struct GemmF16wResult {
     std::vector<float> out, resX, ssOut;
     std::vector<int> splits;
+    std::vector<std::string> kernels;  // per launch: "narrow" / "wide"
 };
 GemmF16wResult gemmF16w(const GemmF16wArgs &a);
 

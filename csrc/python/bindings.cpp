@@ -578,8 +578,9 @@ void bindOps(py::module_ &m) {
           "F16-weight decode GEMV: w [rows][n] f16 bit patterns (uint16)");
     o.def("gemm_f16w",
           [](py::object w, int rows, int n, py::object x, int splits, int epi, py::object resIn, py::object resW,
-             py::object ss, int ssTiles, float eps) {
+             py::object ss, int ssTiles, float eps, py::object wide) {
               ops::GemmF16wArgs a;
+              a.wide = wide.is_none() ? -1 : (wide.cast<bool>() ? 1 : 0);
               a.w = vec<uint16_t>(w);
               a.rows = rows;
               a.n = n;
@@ -601,14 +602,15 @@ void bindOps(py::module_ &m) {
               py::dict d;
               d["out"] = arr(r.out, {M, (py::ssize_t)rows});
               d["splits"] = r.splits;
+              d["kernels"] = r.kernels;
               if (!r.resX.empty()) d["res_x"] = arr(r.resX, {M, (py::ssize_t)rows});
               if (!r.ssOut.empty()) d["ss"] = arr(r.ssOut, {(py::ssize_t)r.ssOut.size() / M, M});
               return d;
           },
           py::arg("w"), py::arg("rows"), py::arg("n"), py::arg("x"), py::arg("splits") = 0, py::arg("epi") = 0,
           py::arg("res_in") = py::none(), py::arg("res_w") = py::none(), py::arg("ss") = py::none(),
-          py::arg("ss_tiles") = 0, py::arg("eps") = 1e-5f,
-          "F16-weight batched MFMA GEMM: w [rows][n] f16 bit patterns (uint16)");
+          py::arg("ss_tiles") = 0, py::arg("eps") = 1e-5f, py::arg("wide") = py::none(),
+          "F16-weight batched MFMA GEMM: w [rows][n] f16 bit patterns (uint16); wide None / True / False as gemm_q80w's");
     o.def("gemm_q40",
           [](py::object blocks, int rows, int n, py::object x, py::object residual, py::object normW, float eps,
              int splits) {
@@ -1648,8 +1650,9 @@ PYBIND11_MODULE(_C, m) {
           py::arg("iters") = 200, py::call_guard<py::gil_scoped_release>(),
           "us per gemvF16wKernel launch (f32 = true: the F32 GEMV on the same shape)");
     m.def("bench_gemm_f16w", &benchGemmF16w, py::arg("rows"), py::arg("n"), py::arg("tokens"), py::arg("f32") = false,
-          py::arg("copies") = 8, py::arg("iters") = 100, py::call_guard<py::gil_scoped_release>(),
-          "us per gemmF16wKernel launch of 1..64 tokens (f32 = true: gemmF32Kernel on the same shape)");
+          py::arg("copies") = 8, py::arg("iters") = 100, py::arg("wide") = false, py::call_guard<py::gil_scoped_release>(),
+          "us per pass over `tokens` rows in gemmF16wKernel launches of <= 64 (f32 = true: gemmF32Kernel on the same "
+          "shape), or, wide = true above 64 tokens, as one gemmF16wWideKernel launch");
     m.def("bench_attention",
           [](int nh, int kvm, int hs, int seq, int pos, int B, int copies, int iters, bool kvBf16, bool kvFp8, int rowBlock) {
               return benchAttention(nh, kvm, hs, seq, pos, B, copies, iters, nullptr, kvBf16, kvFp8, rowBlock);

@@ -185,17 +185,20 @@ def gemv_f16w(w, x, residual=None, norm_w=None, eps: float = 1e-5, prologue: str
     return {k: torch.from_numpy(v) for k, v in r.items()}
 
 
-def gemm_f16w(w, x, splits: int = 0, epilogue: str = "store", res_in=None, res_w=None, ss=None, eps: float = 1e-5):
-    """Batched (MFMA) matmul for F16 weights (1..256 rows of x, launches of <= 64): x rounded to f16 once,
-    the [rows, n] float16 weights exact, f32 accumulation. epilogue "store", or "res": out = res_in + W.x,
-    res_x = the f16 hand-off rows, ss = per-64-row-tile sums of squares. `ss` given: x is a producer's res_x
-    and each token's output is scaled by its RMS factor. `splits` > 0 forces the K split. Returns a dict:
-    out, splits per launch, res_x, ss."""
+def gemm_f16w(w, x, splits: int = 0, epilogue: str = "store", res_in=None, res_w=None, ss=None, eps: float = 1e-5,
+              wide: Optional[bool] = None):
+    """Batched (MFMA) matmul for F16 weights: x rounded to f16 once, the [rows, n] float16 weights exact,
+    f32 accumulation. `wide` None: the engine's chunking (one gemmF16wWideKernel launch for the whole of
+    x from the wide threshold, 65 rows, up; else gemmF16wKernel launches of <= 64); True: one wide launch
+    whatever the row count (up to 2048); False: narrow launches (1..256 rows). epilogue "store", or
+    "res": out = res_in + W.x, res_x = the f16 hand-off rows, ss = per-64-row-tile sums of squares. `ss`
+    given: x is a producer's res_x and each token's output is scaled by its RMS factor. `splits` > 0
+    forces the K split. Returns a dict: out, splits and kernels ("narrow" / "wide") per launch, res_x, ss."""
     bits = _f16_bits(w)
     rows, n = bits.shape
     ss_tiles = 0 if ss is None else int(np.asarray(ss).shape[0])
     r = native().ops.gemm_f16w(bits, rows, n, _np(x), splits, {"store": 0, "res": 6}[epilogue], _np(res_in), _np(res_w),
-                               _np(ss), ss_tiles, eps)
+                               _np(ss), ss_tiles, eps, wide)
     return {k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()}
 
 

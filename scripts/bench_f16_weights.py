@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """F16-weight kernels and model next to their F32 / Q80 counterparts on one GPU (profiles/f16_weights.md).
 
-  python scripts/bench_f16_weights.py [--out DIR] [--repeats 3] [--skip-model]
+  python scripts/bench_f16_weights.py [--out DIR] [--repeats 3] [--skip-model] [--wide-only]
 
 Kernels: us per launch (device events around a graph of back-to-back launches over rotating weight
 copies, engine_bench.cpp) of gemvF16wKernel vs the F32 GEMV and gemmF16wKernel vs gemmF32Kernel on the
 Llama-3.1-8B wcls / w13 / wo shapes, alternating, with the weight bytes per second of each.
+Wide: us per pass over 65..1024 tokens as one gemmF16wWideKernel launch vs 64-token narrow launches
+(profiles/f16_wide_gemm.md).
 Model: `dllama inference --synthetic llama3_1_8b` with f16 and q80 synthetic weights, alternating: a
 64-token prompt + 128 predicted (decode) and a 1025-token prompt + 63 predicted (prefill)."""
 import argparse
@@ -42,6 +44,24 @@ def kernels(C, repeats):
     return rows_out
 
 
+def wide_kernels(C, repeats):
+    """One pass over `tokens` rows as one gemmF16wWideKernel launch against the chunked narrow launches
+    of <= 64 (an engine without the wide kernel), alternating; TFLOP/s of the fastest wide repeat."""
+    rows_out = []
+    for name, (rows, n) in SHAPES.items():
+        copies = 64 if name == "wo" else 8
+        for tokens in (65, 128, 256, 512, 1024):
+            us = {"narrow": [], "wide": []}
+            for _ in range(repeats):
+                for kind in ("narrow", "wide"):
+                    us[kind].append(round(C.bench_gemm_f16w(rows, n, tokens, False, copies, 30, kind == "wide"), 1))
+            r = {"shape": name, "tokens": tokens, "us": us, "narrow_over_wide": round(min(us["narrow"]) / min(us["wide"]), 2),
+                 "wide_tflops": round(2.0 * rows * n * tokens / (min(us["wide"]) * 1e-6) / 1e12, 1)}
+            print(json.dumps(r), flush=True)
+            rows_out.append(r)
+    return rows_out
+
+
 def model_point(weights, prompt_tokens, steps, tok):
     exe = os.path.join(REPO, "build", "dllama")
     prompt = ("The quick brown fox jumps over the lazy dog " * 40)[:prompt_tokens]
@@ -60,10 +80,13 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--skip-model", action="store_true")
+    ap.add_argument("--wide-only", action="store_true", help="the wide GEMM section alone")
     a = ap.parse_args()
     import distributed_llama_multiusers_amd as dl
     from distributed_llama_multiusers_amd.models.synthetic import make_tokenizer
-    res = {"kernels": kernels(dl.native(), a.repeats), "model": []}
+    res = {"kernels": [] if a.wide_only else kernels(dl.native(), a.repeats), "wide": wide_kernels(dl.native(), a.repeats),
+           "model": []}
+    a.skip_model = a.skip_model or a.wide_only
     if not a.skip_model:
         with tempfile.TemporaryDirectory() as d:
             tok = os.path.join(d, "llama3_synth.t")
