@@ -89,6 +89,10 @@ HipEngineImpl::HipEngineImpl(const EngineConfig &cfg, DeviceComm *comm) : cfg_(c
         if (invariant_) gemmMin_ = 1;
         const char *f = std::getenv("DL_GEMM_FUSE_NORM");
         fuseNormEnv_ = !(f && *f == '0');
+        // ragged prefill attention for forwards whose row blocks are not aligned to one slot (setInputs).
+        // On unless DL_ATTN_RAGGED=0: faster on every mixed forward measured (profiles/attn_ragged.md)
+        const char *r = std::getenv("DL_ATTN_RAGGED");
+        raggedOn_ = !(r && *r == '0');
     }
     Timer timer;
     allocBuffers();
@@ -844,7 +848,7 @@ void HipEngineImpl::runGraph(int n, FwdKind kind, unsigned *syncDst) {
         return;
     }
     const GraphKey key = graphKey({.bucket = (unsigned)bucket_, .attnLong = attnLong_, .prefillOk = prefillOk_,
-                                   .stages = kind.stages, .kind = kind.kind, .rows = (unsigned)n});
+                                   .stages = kind.stages, .kind = kind.kind, .rows = (unsigned)n, .ragged = ragged_});
     auto it = graphs_.find(key);
     if (it == graphs_.end()) {
         // capture on the second use of a shape: a one-off row count (the tail chunk of a prompt,

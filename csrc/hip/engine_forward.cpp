@@ -90,11 +90,26 @@ void HipEngineImpl::setInputs(int n, const int *tokens, const int *positions, co
     // prefill attention on MFMA: every block of rows it assigns to one workgroup is one slot
     prefillOk_ = !invariant_ && hipk::attnPrefillSupported(plan_.headSize, plan_.kvMul, kvBf16(), kvFp8());
     const int rpb = prefillOk_ ? hipk::attnPrefillRowsPerBlock(plan_.kvMul) : 1;
+    const bool blocksOk = prefillOk_;  // before the alignment test
     for (int b = 0; prefillOk_ && b < n; b++) prefillOk_ = slots[b] == slots[b - b % rpb];
-    if (prefillOk_) {
-        int mx = 0;
-        for (int b = 0; b < n; b++) mx = std::max(mx, positions[b] + 1);
-        prefillOk_ = prefillLongEnough(mx);
+    int mx = 0;
+    for (int b = 0; b < n; b++) mx = std::max(mx, positions[b] + 1);
+    if (prefillOk_) prefillOk_ = prefillLongEnough(mx);
+    // ragged prefill attention: only the alignment kept an f32-cache forward off the prefill kernels,
+    // it has a segment of 2+ rows (a pure decode batch stays on the decode kernels) and is one
+    // attention launch. The table follows the row arrays through the same staging copy; every
+    // tensor-parallel rank builds it from the same rows.
+    ragged_ = false;
+    if (raggedOn_ && blocksOk && !prefillOk_ && kv_ == KvDtype::F32 && batchedPath(n) && n <= attRows_ && prefillLongEnough(mx)) {
+        hipk::AttnArgs probe;
+        probe.nHeads0 = plan_.nHeads0, probe.kvMul = plan_.kvMul, probe.hs = plan_.headSize, probe.seqLen = h_.seqLen;
+        probe.kvBf16 = 0, probe.kvMap = kvMap(), probe.splitGrid = buckets_[bucket_].splitGridBat;
+        int *segRow = hIn_ + 15 * MB + 1, *segRows = segRow + MB;
+        const int nSeg = hipk::attnRaggedSegments(slots, n, plan_.kvMul, segRow, segRows);
+        if (nSeg < n && !hipk::attnRaggedRefusal(probe)) {
+            hIn_[15 * MB] = nSeg;
+            ragged_ = true;
+        }
     }
     if (specs) {
         static_assert(sizeof(SampleSpec) == 4 * sizeof(float), "spec layout");
@@ -110,6 +125,7 @@ void HipEngineImpl::setInputs(int n, const int *tokens, const int *positions, co
         std::memcpy(hIn_ + 11 * MB, filterRows, (size_t)n * sizeof(hipk::LogitFilterRow));
         words = 11 * (size_t)MB + 4 * (size_t)n;
     }
+    if (ragged_) words = 16 * (size_t)MB + 1 + n;  // segRows[0 .. nSeg) ends the table
     // one copy of the row arrays (the unused tail of each is never read)
     DL_HIP(hipMemcpyAsync(dTok_, hIn_, words * sizeof(int), hipMemcpyHostToDevice, stream_));
     inputsInFlight_ = true;
@@ -618,9 +634,14 @@ void HipEngineImpl::enqueueAttention(const FwdPath &f, const DevLayer &L) {
         if (ar.outH) ar.outH += (size_t)r0 * a.ldOut;
         if (ar.outQ) ar.outQ += (size_t)r0 * a.ldOut;
         if (ar.outS) ar.outS += (size_t)r0 * (a.ldOut / 32);
-        if (f.bat && prefillOk_)
+        if (f.bat && prefillOk_) {
             hipk::launchAttentionPrefill(ar, nr, stream_);
-        else
+        } else if (f.bat && ragged_) {  // one launch (setInputs): the table's rows are the forward's
+            ar.nSeg = dSeg_;
+            ar.segRow = dSeg_ + 1;
+            ar.segRows = dSeg_ + 1 + cfg_.maxBatch;
+            hipk::launchAttentionRagged(ar, nr, stream_);
+        } else
             hipk::launchAttention(ar, nr, stream_);
     }
 }

@@ -528,6 +528,11 @@ class HipEngineImpl : public HipEngine {
     int bucket_ = 0;          // index into buckets_
     bool attnLong_ = false;   // decode attention runs the MFMA kernel
     bool prefillOk_ = false;  // the rows qualify for the MFMA prefill attention
+    // the rows take the ragged prefill attention (attn_ragged.hip): only the alignment of the row
+    // blocks kept them off the prefill kernels (setInputs); never together with prefillOk_
+    bool ragged_ = false;
+    bool raggedOn_ = false;   // DL_ATTN_RAGGED, read at construction
+    int *dSeg_ = nullptr;     // [nSeg | segRow[maxBatch] | segRows[maxBatch]] behind the row arrays of dTok_
 
     // fused attention block
     unsigned *dEpoch_ = nullptr, *dBlockCnt_ = nullptr, *dBlockExpect_ = nullptr;

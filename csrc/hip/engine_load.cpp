@@ -118,16 +118,17 @@ void HipEngineImpl::allocBuffers() {
     const ShardPlan &p = plan_;
     // [tokens | positions | slots | sample specs (4 floats per row) | logit processors (4 floats per
     // row) | candidate filters (4 words per row)]: one H2D copy per forward, up to the last array the
-    // forward uses
-    dTok_ = dalloc<int>(15 * (size_t)MB);
+    // forward uses; behind them the ragged attention's segment table [nSeg | segRow | segRows]
+    dTok_ = dalloc<int>(17 * (size_t)MB + 1);
     dPos_ = dTok_ + MB;
     dSlot_ = dTok_ + 2 * MB;
     dSpec_ = reinterpret_cast<float4 *>(dTok_ + 3 * MB);
     dProc_ = reinterpret_cast<float4 *>(dTok_ + 7 * MB);
     dFilter_ = reinterpret_cast<hipk::LogitFilterRow *>(dTok_ + 11 * MB);
+    dSeg_ = dTok_ + 15 * MB;
     dIds_ = dalloc<int>(MB);
     dHist_ = dalloc<int>((size_t)decodeRows_ * h_.seqLen);  // greedy chains only (decode rows)
-    hIn_ = halloc<int>(15 * MB);
+    hIn_ = halloc<int>(17 * MB + 1);
     if (rank() == 0) {  // logit processors: the root draws
         const size_t S = cfg_.nSlots, V = h_.vocabSize;
         dProcCounts_ = dalloc<uint32_t>(S * V);

@@ -35,13 +35,15 @@ struct GraphKeyFields {
     unsigned stages = 0;     // DrawStage bits
     GraphKind kind = GraphKind::LOGITS;
     unsigned rows = 0;
+    bool ragged = false;     // the rows take the ragged prefill attention (the key's top bit)
 };
 using GraphKey = uint32_t;
 constexpr unsigned kKeyBucketBits = 4, kKeyStageBits = 4, kKeyKindBits = 3, kKeyRowBits = 14;
 constexpr unsigned kKeyStageShift = kKeyBucketBits + 2, kKeyKindShift = kKeyStageShift + kKeyStageBits,
                    kKeyRowShift = kKeyKindShift + kKeyKindBits;
 constexpr unsigned kKeyMaxBucket = (1u << kKeyBucketBits) - 1, kKeyMaxRows = (1u << kKeyRowBits) - 1;
-static_assert(kKeyRowShift + kKeyRowBits <= 32, "the fields fit the key");
+constexpr unsigned kKeyRaggedShift = kKeyRowShift + kKeyRowBits;
+static_assert(kKeyRaggedShift + 1 <= 32, "the fields fit the key");
 static_assert(kGraphKinds <= 1u << kKeyKindBits && kDrawStageSets == 1u << kKeyStageBits, "kinds and stage sets fit their fields");
 
 // Throws when a value does not fit its field: a wider value would alias another forward's graph.
@@ -51,7 +53,8 @@ constexpr GraphKey graphKey(const GraphKeyFields &f) {
     DL_CHECK((unsigned)f.kind < kGraphKinds, "graph key: kind");
     DL_CHECK(f.rows <= kKeyMaxRows, "graph key: rows");
     return f.bucket | (f.attnLong ? 1u : 0u) << kKeyBucketBits | (f.prefillOk ? 1u : 0u) << (kKeyBucketBits + 1) |
-           f.stages << kKeyStageShift | (unsigned)f.kind << kKeyKindShift | f.rows << kKeyRowShift;
+           f.stages << kKeyStageShift | (unsigned)f.kind << kKeyKindShift | f.rows << kKeyRowShift |
+           (f.ragged ? 1u : 0u) << kKeyRaggedShift;
 }
 
 constexpr GraphKeyFields graphKeyFields(GraphKey k) {
@@ -61,7 +64,8 @@ constexpr GraphKeyFields graphKeyFields(GraphKey k) {
     f.prefillOk = (k >> (kKeyBucketBits + 1) & 1u) != 0;
     f.stages = k >> kKeyStageShift & (kDrawStageSets - 1);
     f.kind = (GraphKind)(k >> kKeyKindShift & ((1u << kKeyKindBits) - 1));
-    f.rows = k >> kKeyRowShift;
+    f.rows = k >> kKeyRowShift & kKeyMaxRows;
+    f.ragged = (k >> kKeyRaggedShift & 1u) != 0;
     return f;
 }
 

@@ -192,6 +192,9 @@ struct AttnArgs {
     // landed, [3] key loop done, [4] waves merged, [5] split hand-off / combine done, [6] 1 if
     // this workgroup combined the chunks (wave 0's view)
     unsigned long long *trace = nullptr;
+    // launchAttentionRagged only (null for every other launch): the forward's segment table on the
+    // device, segRow[s] the first row and segRows[s] the row count of segment s < nSeg[0]
+    const int *segRow = nullptr, *segRows = nullptr, *nSeg = nullptr;
 };
 
 // Tensor-parallel partial-sum exchange fused into the tail of the kernel that produces the partial
@@ -519,6 +522,21 @@ void launchTpSelfTest(const TpXchg &x, float *out, int n, float val, hipStream_t
 void launchAttentionPrefill(const AttnArgs &a, int nRows, hipStream_t s);
 int attnPrefillRowsPerBlock(int kvMul);
 bool attnPrefillSupported(int hs, int kvMul, bool kvBf16, bool kvFp8 = false);
+// Ragged prefill rows of f32 caches (attnRaggedF32Kernel<KM,HS>, attn_ragged.hip): the rows are cut
+// into segments, maximal runs of at most attnPrefillRowsPerBlock(kvMul) consecutive rows of one slot,
+// which may start at any row; AttnArgs::segRow / segRows / nSeg name the table on the device. Segments
+// of more than 16 / kvMul rows run the row-block schedule, narrower ones the key-split schedule
+// (attnRaggedRowBlock). Head size 64 / 128, kvMul 1 / 2 / 4 / 8, f32 or f16 output (no Q80 writer),
+// counters >= nRows x KV heads, partials as launchAttentionPrefill.
+// attnRaggedSegments writes the table of `slots` into segRow / segRows (room for nRows each), returns nSeg.
+int attnRaggedSegments(const int *slots, int nRows, int kvMul, int *segRow, int *segRows);
+bool attnRaggedRowBlock(int rows, int kvMul);
+bool attnRaggedSupported(const AttnArgs &a);
+const char *attnRaggedRefusal(const AttnArgs &a);  // the message launchAttentionRagged throws, or null
+// a host copy of a table: null when its segments tile [0, nRows), each within one slot and the row limit
+const char *attnRaggedTableRefusal(const int *segRow, const int *segRows, int nSeg, const int *slots, int nRows, int kvMul);
+std::string attnRaggedKernelName(const AttnArgs &a);  // "attnRaggedF32Kernel<KM,HS>"
+void launchAttentionRagged(const AttnArgs &a, int nRows, hipStream_t s);
 int attnSplitGrid(int seqLen, bool shortChunks = false);
 // single decode rows of at most kAttnShortLen keys split into chunks of kAttnShortChunk (attnSplit)
 constexpr int kAttnShortLen = 512, kAttnShortChunk = 128;

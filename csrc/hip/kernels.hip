@@ -434,6 +434,7 @@ const void *gemmQ80wWideModuleKernel();
 const void *gemmF16wWideModuleKernel();
 const void *attnMfmaModuleKernel();
 const void *attnF32MfmaModuleKernel();
+const void *attnRaggedModuleKernel();
 const void *attnFp8ModuleKernel();
 const void *xgmiModuleKernel();
 const void *sampleModuleKernel();
@@ -460,7 +461,7 @@ void preloadModules() {
     const BlockFn blocks[] = {attnBlockFn_16_16_128, attnBlockFn_16_32_128, attnBlockFn_32_32_128, attnBlockFn_64_32_128, attnBlockFn_64_16_128,
                               attnBlockFn_64_64_128, attnBlockFn_32_64_128, attnBlockFn_64_64_64};
     std::vector<const void *> fns = {sampleModuleKernel(), logitProcModuleKernel(), logitFilterModuleKernel(), jsonMaskModuleKernel(), grammarMaskModuleKernel(), attnPrefillModuleKernel(), tpCheckModuleKernel(),
-                                     gemmModuleKernel(),   gemmWideModuleKernel(),    gemmQ80wWideModuleKernel(), gemmF16wWideModuleKernel(), attnMfmaModuleKernel(), attnF32MfmaModuleKernel(), attnFp8ModuleKernel(),
+                                     gemmModuleKernel(),   gemmWideModuleKernel(),    gemmQ80wWideModuleKernel(), gemmF16wWideModuleKernel(), attnMfmaModuleKernel(), attnF32MfmaModuleKernel(), attnRaggedModuleKernel(), attnFp8ModuleKernel(),
                                      xgmiModuleKernel(),   gemvFnL16(true, 1, 0, 0),
                                      gemvFnL32(true, 1, 0, 0), gemvFnL64(true, 1, 0, 0)};
     for (BlockFn b : blocks) {  // any instance of the unit will do

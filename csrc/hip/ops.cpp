@@ -1235,10 +1235,11 @@ AttnGeom attnGeom(const AttnLaunchArgs &l) {
     DL_CHECK(l.q.size() == (size_t)B * g.ldq && l.k.size() == cacheElems && l.v.size() == cacheElems, "attention sizes");
     for (int b = 0; b < B; b++)
         DL_CHECK(l.pos[b] >= 0 && l.pos[b] < l.seqLen && l.slot[b] >= 0 && l.slot[b] < l.nSlots, "attention row out of range");
+    DL_CHECK(l.kernel != ATTN_RAGGED || (!l.kvBf16 && !l.kvFp8), "attention: kernel \"ragged\" takes f32 KV caches only");
     DL_CHECK(l.kvFp8 ? (l.kernel == ATTN_AUTO || l.kernel == ATTN_FP8 || (l.kernel == ATTN_PREFILL && l.mode == ATTN_PREFILL_ROWS))
                      : l.kernel != ATTN_FP8,
              "attention: fp8 caches take kernel \"auto\", \"fp8\" or (prefill rows) \"prefill\", other caches any kernel but \"fp8\"");
-    DL_CHECK(l.kernel >= ATTN_AUTO && l.kernel <= ATTN_FP8 && (l.mode == ATTN_DECODE || l.mode == ATTN_PREFILL_ROWS),
+    DL_CHECK(l.kernel >= ATTN_AUTO && l.kernel <= ATTN_RAGGED && (l.mode == ATTN_DECODE || l.mode == ATTN_PREFILL_ROWS),
              "attention kernel / mode");
     g.prefill = l.mode == ATTN_PREFILL_ROWS;
     DL_CHECK(g.prefill ? (l.kernel == ATTN_AUTO || l.kernel == ATTN_PREFILL) : l.kernel != ATTN_PREFILL,
@@ -1250,7 +1251,8 @@ AttnGeom attnGeom(const AttnLaunchArgs &l) {
     DL_CHECK(l.repeat >= 1, "attention repeat must be at least 1");
     DL_CHECK(l.warmPos.empty() || l.warmPos.size() == l.pos.size(), "attention warm positions: one per row");
     for (int p : l.warmPos) DL_CHECK(p >= 0 && p < l.seqLen, "attention warm position out of range");
-    DL_CHECK(!(g.prefill && l.out == ATTN_OUT_Q80), "attention: the prefill kernels ignore outQ (no Q80 output)");
+    DL_CHECK(!((g.prefill || l.kernel == ATTN_RAGGED) && l.out == ATTN_OUT_Q80), "attention: the prefill kernels ignore outQ (no Q80 output)");
+    DL_CHECK(l.kernel != ATTN_RAGGED || (!g.prefill && !l.single), "attention: kernel \"ragged\" takes any rows (no prefill / single flag)");
     DL_CHECK((l.poisonK.empty() || l.poisonK.size() == (size_t)g.kv0) && (l.poisonV.empty() || l.poisonV.size() == (size_t)g.kv0),
              "attention poison rows: [kv0]");
     hipk::AttnArgs &a = g.a;
@@ -1315,6 +1317,27 @@ AttnLaunchPlan attentionPlan(const AttnLaunchArgs &l) {
             hipk::attnPrefillSplit(maxLen, a.splitGrid, a.hs, chunkKeys, ns, ch);
             p.nSplit.push_back(ns);
             p.ch.push_back(ch);
+        }
+        return p;
+    }
+    if (l.kernel == ATTN_RAGGED) {  // the table the engine's setInputs would build for these slots
+        if (const char *why = hipk::attnRaggedRefusal(a)) throw Error(why);
+        p.segRow.resize(g.B);
+        p.segRows.resize(g.B);
+        const int nSeg = hipk::attnRaggedSegments(l.slot.data(), g.B, a.kvMul, p.segRow.data(), p.segRows.data());
+        p.segRow.resize(nSeg);
+        p.segRows.resize(nSeg);
+        p.kernel = hipk::attnRaggedKernelName(a);
+        p.grid[0] = g.nKv * g.B;
+        p.grid[1] = a.splitGrid;
+        p.grid[2] = 1;
+        for (int s = 0; s < nSeg; s++) {
+            int maxLen = 0, ns, ch;
+            for (int b = p.segRow[s]; b < p.segRow[s] + p.segRows[s]; b++) maxLen = std::max(maxLen, l.pos[b] + 1);
+            hipk::attnPrefillSplit(maxLen, a.splitGrid, a.hs, hipk::kAttnPrefillChunk, ns, ch);
+            p.nSplit.push_back(ns);
+            p.ch.push_back(ch);
+            p.segRowBlock.push_back(hipk::attnRaggedRowBlock(p.segRows[s], a.kvMul) ? 1 : 0);
         }
         return p;
     }
@@ -1403,6 +1426,15 @@ AttnLaunchResult attentionLaunch(const AttnLaunchArgs &l) {
     if (l.pageSize) a.kvMap.table = sc.upload(table);
     a.pos = sc.upload(l.pos);
     a.slot = sc.upload(l.slot);
+    if (l.kernel == ATTN_RAGGED) {  // the plan's table, checked as a launch argument before it is uploaded
+        const AttnLaunchPlan &p = res.plan;
+        const int nSeg = (int)p.segRow.size();
+        if (const char *why = hipk::attnRaggedTableRefusal(p.segRow.data(), p.segRows.data(), nSeg, l.slot.data(), B, a.kvMul))
+            throw Error(why);
+        a.segRow = sc.upload(p.segRow);
+        a.segRows = sc.upload(p.segRows);
+        a.nSeg = sc.upload(std::vector<int>{nSeg});
+    }
     // scratch of the engine's sizes (engine_load.cpp), each followed by a guard
     const size_t nPartO = (size_t)B * l.nHeads0 * a.splitGrid * hs, nPartML = (size_t)B * l.nHeads0 * a.splitGrid * 2;
     const size_t nCnt = (size_t)B * l.nHeads0, guard = 256;
@@ -1432,6 +1464,8 @@ AttnLaunchResult attentionLaunch(const AttnLaunchArgs &l) {
     auto run = [&] {
         if (g.prefill)
             hipk::launchAttentionPrefill(a, B, sc.s);
+        else if (l.kernel == ATTN_RAGGED)
+            hipk::launchAttentionRagged(a, B, sc.s);
         else if (l.kernel == ATTN_VALU)
             hipk::launchAttentionValu(a, B, sc.s);
         else if (l.kernel == ATTN_MFMA)

@@ -246,7 +246,9 @@ std::vector<float> attention(const std::vector<float> &q, const std::vector<floa
 // which ops::attention above cannot: a page table, the single-row split geometry, the f16 and Q80
 // writers, a pinned head group, strided rows and reused scratch.
 //   kernel   ATTN_AUTO: launchAttention's choice (decode) / launchAttentionPrefill's (prefill);
-//            ATTN_VALU / ATTN_MFMA: that decode kernel; ATTN_PREFILL: the prefill launcher
+//            ATTN_VALU / ATTN_MFMA: that decode kernel; ATTN_PREFILL: the prefill launcher;
+//            ATTN_RAGGED: launchAttentionRagged (f32 caches, any slot list, mode ATTN_DECODE, the
+//            batched split geometry): the segments are derived from `slot` as the engine derives them
 //   mode     ATTN_DECODE or ATTN_PREFILL_ROWS (blocks of attnPrefillRowsPerBlock rows share a slot)
 //   single   the engine's single-row setup: shortLen = kAttnShortLen, splitGrid =
 //            attnSplitGrid(seqLen, true), chunkMax from the *batched* grid attnSplitGrid(seqLen, false);
@@ -267,7 +269,7 @@ std::vector<float> attention(const std::vector<float> &q, const std::vector<floa
 // the last row, behind partO, partML and counters; for f16 / Q80 around the code and scale arrays
 // separately. The op throws when a launch changed one. A launch the launchers refuse, or whose
 // operands are outside their contract, throws before any device work (attentionPlan).
-enum AttnKernelSel : int { ATTN_AUTO = 0, ATTN_VALU = 1, ATTN_MFMA = 2, ATTN_PREFILL = 3, ATTN_FP8 = 4 };
+enum AttnKernelSel : int { ATTN_AUTO = 0, ATTN_VALU = 1, ATTN_MFMA = 2, ATTN_PREFILL = 3, ATTN_FP8 = 4, ATTN_RAGGED = 5 };
 enum AttnMode : int { ATTN_DECODE = 0, ATTN_PREFILL_ROWS = 1 };
 enum AttnOut : int { ATTN_OUT_F32 = 0, ATTN_OUT_F16 = 1, ATTN_OUT_Q80 = 2 };
 struct AttnLaunchArgs {
@@ -295,7 +297,8 @@ struct AttnLaunchPlan {
     int hg = 0;               // VALU decode: heads per workgroup (attnValuHeadGroup); else 0
     int grid[3] = {0, 0, 0};
     int splitGrid = 0, chunkMax = 0, shortLen = 0;
-    std::vector<int> nSplit, ch;  // decode: attnSplit of every row; prefill: attnPrefillSplit of every row block
+    std::vector<int> nSplit, ch;  // decode: attnSplit of every row; prefill: attnPrefillSplit of every row block (ragged: segment)
+    std::vector<int> segRow, segRows, segRowBlock;  // ragged: first row, rows, 1 = row-block / 0 = key-split schedule
 };
 struct AttnLaunchResult {
     std::vector<float> out;     // [B][q0]: f32, the f16 values, or the Q80 codes

@@ -801,6 +801,12 @@ void bindOps(py::module_ &m) {
               py::list splits;
               for (size_t b = 0; b < r.plan.nSplit.size(); b++) splits.append(py::make_tuple(r.plan.nSplit[b], r.plan.ch[b]));
               res["splits"] = splits;
+              if (!r.plan.segRow.empty()) {  // kernel "ragged": (first row, rows, schedule) per segment
+                  py::list segs;
+                  for (size_t i = 0; i < r.plan.segRow.size(); i++)
+                      segs.append(py::make_tuple(r.plan.segRow[i], r.plan.segRows[i], r.plan.segRowBlock[i] ? "row-block" : "key-split"));
+                  res["segments"] = segs;
+              }
               if (planOnly) return res;
               const py::ssize_t B = (py::ssize_t)pos.size(), q0 = (py::ssize_t)nHeads0 * hs;
               res["out"] = arr(r.out, {B, q0});

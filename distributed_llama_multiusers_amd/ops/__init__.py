@@ -279,7 +279,7 @@ def attention(q, k_cache, v_cache, n_heads0: int, kv_mul: int, head_size: int, p
                                                    kv_bf16, code, kv_fp8))
 
 
-ATTN_KERNELS = {"auto": 0, "valu": 1, "mfma": 2, "prefill": 3, "fp8": 4}
+ATTN_KERNELS = {"auto": 0, "valu": 1, "mfma": 2, "prefill": 3, "fp8": 4, "ragged": 5}
 ATTN_OUTPUTS = {"f32": 0, "f16": 1, "q80": 2}
 
 
@@ -303,7 +303,11 @@ def attention_launch(q, k_cache, v_cache, n_heads0: int, kv_mul: int, head_size:
     plan and the refusals, no device needed. kv_dtype "" (follow kv_bf16) / "f32" / "bf16" / "fp8";
     "fp8": the caches (and the poison rows) are quantised on the host by the append rule,
     e4m3fn(clamp(x, -448, 448)), and attnDecodeFp8Kernel<KM,HS> runs on decode rows (kernel "auto" or
-    "fp8"), attnPrefillFp8Kernel<KM,HS> on prefill rows (kernel "auto" or "prefill")."""
+    "fp8"), attnPrefillFp8Kernel<KM,HS> on prefill rows (kernel "auto" or "prefill").
+    kernel "ragged": attnRaggedF32Kernel<KM,HS> on an f32 cache and any slot list (decode rows and prompt
+    chunks in one launch, no prefill / single flag). The rows are cut into segments as the engine cuts
+    them, runs of at most 64 / kv_mul consecutive rows of one slot; the result adds "segments":
+    [(first_row, rows, "row-block" | "key-split")] and "splits" holds one (nSplit, ch) per segment."""
     kv_bf16, kv_fp8 = _kv(kv_bf16, kv_dtype)
     n_slots, seq_len, _ = k_cache.shape
     po = [] if page_of is None else [int(p) for p in np.asarray(page_of).reshape(-1)]
